@@ -1,15 +1,19 @@
 #!/usr/bin/env python
 """Headline benchmark: train patches/sec of the ResEncM 3-D residual-encoder U-Net (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One STEP = forward -> per-task loss -> backward -> (RCCL gradient all-reduce, overlapped) ->
 clip_grad_norm_(3) -> AdamW step -> zero_grad(set_to_none=True) on one synthetic batch that is already
 resident in HBM.  Workload at every N: BASELINE configs[1] = autoconfigured ResEncM,
 1-in / 1 seg head, patch 128^3, bf16, batch 2 per GPU (weak scaling: global batch 2N, configs[3] at N=8).
-Prints ONE JSON line (rank 0) with `roofline` (dominant MFMA kernel, algorithmic FLOPs / HIP-event time)
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line (`value`,
+`ms_per_step`, ...); the diagnostics that cost runs of their own stay null in it.  `--full` adds them: `with_h2d` (the
+same K steps fed from pinned host memory), `roofline` / `kernels` / `hbm` (HIP-event timing of every launch over a few
+further steps; live rocprofv3 --pmc child runs for the dominant kernel's traffic), `roofline_isolated`, `clock_probe`
 and `cpu_baseline` (the CPU oracle = pure-PyTorch restatement of the reference, timed on this host).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64; see dump_outputs).
 """
 import argparse
 import json
@@ -132,6 +136,45 @@ def pmc_traffic_live(workload, dtype, kernel_label, timeout_s=150):
     rd, wr = 2.0 * tot["FETCH_SIZE"][0] * 1024 / nf, tot["WRITE_SIZE"][0] * 1024 / nw
     return dict(bytes_per_launch=rd + wr, read=rd, write=wr, launches_sampled=nf,
                 source="live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child runs of this command (3 steps each)")
+
+
+DUMP_LOGIT_ELEMS = 8 << 20      # logits beyond this many elements in all are dumped as a fixed, seeded sample (32 MiB)
+DUMP_PARAM_ELEMS = 4 << 20      # parameters: a fixed, seeded sample of this many elements of all of them (16 MiB)
+
+
+def _sample_index(numel, k, seed):
+    """k fixed element positions (sorted, with repeats possible) of a flat tensor of `numel` elements, the same in every run"""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(numel, (k,), generator=g, dtype=torch.int64).sort().values
+
+
+def dump_outputs(path, out, loss, params):
+    """What a caller of the timed step holds after the last one: the network outputs of its forward (`logits.<task>`, fp32,
+    NCDHW), its loss (`loss`, fp64 scalar) and the parameters after its AdamW update (`params`, fp32: a fixed sample of
+    DUMP_PARAM_ELEMS elements of all parameters concatenated in `named_parameters()` order).  Logits of more than
+    DUMP_LOGIT_ELEMS elements in all are sampled the same way (flattened to 1-D).  Same arguments -> same inputs, same
+    positions, so two builds compare file for file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(v.numel() for v in out.values())
+    for i, (name, v) in enumerate(sorted(out.items())):
+        v = v.detach().float()
+        if total > DUMP_LOGIT_ELEMS:
+            k = max(1, DUMP_LOGIT_ELEMS * v.numel() // total)
+            v = v.flatten()[_sample_index(v.numel(), k, 1000 + i).to(v.device)]
+        np.save(os.path.join(path, f"logits.{name}.npy"), v.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "loss.npy"), np.float64(float(loss.detach())))
+    sizes = torch.tensor([p.numel() for p in params], dtype=torch.int64)
+    ends = sizes.cumsum(0)
+    idx = _sample_index(int(ends[-1]), min(DUMP_PARAM_ELEMS, int(ends[-1])), 2000)
+    cuts = torch.searchsorted(idx, ends).tolist()                # idx is sorted: parameter j owns idx[cuts[j-1]:cuts[j]]
+    vals, a = [], 0
+    for j, b in enumerate(cuts):
+        if b > a:
+            local = (idx[a:b] - (ends[j] - sizes[j])).to(params[j].device)
+            vals.append(params[j].detach().flatten()[local].float().cpu())
+        a = b
+    np.save(os.path.join(path, "params.npy"), torch.cat(vals).numpy())
 
 
 def make_mgr(w):
@@ -302,6 +345,11 @@ def main():
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--dtype", default="bf16", choices=sorted(DTYPES))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: with_h2d, per-kernel roofline / hbm / isolated "
+                         "timing, live PMC traffic, clock probe, CPU baseline (each can still be dropped with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (logits, loss, sampled updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="take roofline.traffic from the newest profiles/*pmc_hbm_traffic.json "
@@ -320,6 +368,8 @@ def main():
     if args.cpu_baseline_only:
         cpu_baseline_worker(args.workload, args.cpu_threads or host_threads())
         return
+    if not args.full:           # a plain run: the timed steps and nothing else
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_h2d = args.no_pmc = True
 
     rank = int(os.environ.get("RANK", 0))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -376,9 +426,11 @@ def main():
     stepper = StreamedOptimizerStep(opt, net) if os.environ.get("RX_STREAMED_STEP", "0") == "1" else None
     from mt3d_amd.training.optim import clip_and_step
     fused_clip = os.environ.get("RX_FUSED_CLIP", "1") != "0"   # same update as clip_grad_norm_(3) + step(), one gradient pass less
+    last = {}
 
     def step():
         out = net(x)
+        last["out"] = out
         if sync is not None:
             for plan in net._plans.values():
                 plan.grad_sync = sync
@@ -417,6 +469,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["out"], loss, params)
     ddp_block = None
     if sync is not None:
         # self-describing multi-GPU run: what the collectives were, and how much of them the backward did NOT hide

@@ -6,10 +6,10 @@ BASELINE train step uses.  Only `tests/`, `__graft_entry__.smoke()` and `bench.p
 `cpu_baseline` leg may import this file; the product package
 (`multi-task-3d-resencoder-unet_amd/`) never does and fails loudly without its HIP library.
 
-Parity status: PINNED.  `tests/test_oracle_vs_reference.py` (runs only where /root/reference
-exists) checks key-for-key `state_dict` equality and forward/backward equality against the real
-reference imported through `oracle/ref_shim.py`; `tests/golden/*.npz` (made by
-`oracle/make_golden.py` from the real reference) pin it everywhere else.  PARITY UNPINNED for two
+Parity status: PINNED.  `tests/test_oracle_vs_reference.py` checks key-for-key `state_dict` equality
+and forward/backward equality against what the real reference computed (`tests/golden/parity/<case>.npz`,
+made by `oracle/make_golden_parity.py` through `oracle/ref_shim.py`); `tests/golden/<case>.npz` (made by
+`oracle/make_golden.py` from the real reference) pin it further.  PARITY UNPINNED for two
 options: `squeeze_excitation=True` and `stochastic_depth_p>0`.  Their arithmetic lives in the
 un-vendored third-party `dynamic_network_architectures` (MIC-DKFZ; version unpinned by the reference,
 package absent from this image, no reference test or fixture covers it), so `SqueezeExcite` /

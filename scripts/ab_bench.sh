@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of environment knobs on the default bench step:  bash scripts/ab_bench.sh NAME "ENV=.. ENV=.." [NAME "ENV.."]...
-# prints ms/step and the hbm-block families named in $AB_FAMILIES (comma separated)
+# prints ms/step and the hbm-block families named in $AB_FAMILIES (comma separated; the hbm block needs AB_FLAGS=--full)
 mkdir -p gpurun_out
 while [ $# -gt 0 ]; do
   name=$1; envs=$2; shift 2

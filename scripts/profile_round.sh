@@ -8,7 +8,7 @@ set -o pipefail
 TAG=${1:-r03_a}
 OUT=gpurun_out
 export TMPDIR=/tmp
-python bench.py --steps 20 --warmup 5 --through-trainer > $OUT/${TAG}_bench_cfg2.json 2> $OUT/${TAG}_bench.err || exit 1
+python bench.py --full --steps 20 --warmup 5 --through-trainer > $OUT/${TAG}_bench_cfg2.json 2> $OUT/${TAG}_bench.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_kt -o kt -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-timing --no-h2d > $OUT/${TAG}_kt.log 2>&1 || exit 1
 cp $(find $OUT/${TAG}_kt -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_bench_cfg2_kernel_stats.csv
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_pmc_fetch -o f -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-h2d > $OUT/${TAG}_pmc_f.log 2>&1 || exit 1

@@ -10,7 +10,7 @@ mkdir -p $OUT
 for spec in "cfg2 bf16" "cfg1 bf16" "cfg3 bf16" "cfg5 fp16" "cfg2se bf16" "inkyaml bf16" "dumbyaml bf16"; do
   set -- $spec
   wl=$1; dt=$2
-  python bench.py --workload $wl --dtype $dt --steps 12 --warmup 5 --no-cpu-baseline --no-pmc --no-h2d > $OUT/${TAG}_wl_${wl}.json 2> $OUT/${TAG}_wl_${wl}.err || { echo "$wl FAILED" >> $OUT/${TAG}_workload_table.txt; continue; }
+  python bench.py --full --workload $wl --dtype $dt --steps 12 --warmup 5 --no-cpu-baseline --no-pmc --no-h2d > $OUT/${TAG}_wl_${wl}.json 2> $OUT/${TAG}_wl_${wl}.err || { echo "$wl FAILED" >> $OUT/${TAG}_workload_table.txt; continue; }
   if [ "$wl" != "cfg2" ]; then
     rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${TAG}_kt_$wl -o kt -- python3 bench.py --workload $wl --dtype $dt --steps 8 --warmup 4 --no-cpu-baseline --no-kernel-timing --no-h2d --no-pmc > $OUT/${TAG}_wl_${wl}_kt.log 2>&1 \
       && cp $(find /tmp/${TAG}_kt_$wl -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_wl_${wl}_kernel_stats.csv
