@@ -9,15 +9,20 @@
 
 #include "../../include/rxunet.h"
 
-// Host-side per-launch overhead: the dispatch code asks the environment for tuning knobs and (re)sets the dynamic-LDS limit of
-// the kernel it is about to launch on EVERY call (~700 launches per train step).  Both are answered from per-thread caches
-// after the first time (rx_prog.hip); the knobs are therefore read once per process, which is how they are used.
-const char* rx_getenv_cached(const char* name);
+// Host-side per-launch overhead: the dispatch code (re)sets the dynamic-LDS limit of the kernel it is about to launch on EVERY
+// call (~700 launches per train step).  That is answered from a per-thread cache keyed by (device, kernel) after the first time
+// (rx_prog.hip), so a second device of the same process still gets its own call.
 hipError_t rx_func_attr_once(const void* fn, hipFuncAttribute attr, int value);
 #ifndef RX_NO_HOST_MACROS
-#define getenv(name) rx_getenv_cached(name)
 #define hipFuncSetAttribute(fn, attr, value) rx_func_attr_once((fn), (attr), (value))
 #endif
+
+// The library's only environment reads: the ablation masks of the timing builds (RX_DBG -> geometry.dbg; RX_FAT_ABL under
+// RX_ABLATION).  0 unless set; call sites keep the value in a function-local static, so each is read once per process.
+inline int rx_env_mask(const char* name) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : 0;
+}
 
 #define RX_WAVE 64
 

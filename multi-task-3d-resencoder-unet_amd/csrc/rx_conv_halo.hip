@@ -54,7 +54,7 @@ __device__ inline int lane_voxel(int l /* lane & 31 */) {
 
 template <typename T, int BN>
 __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const T* __restrict__ in, const T* __restrict__ w, const float* __restrict__ bias,
-                                                           T* __restrict__ out, const ConvHaloGeom g, float* __restrict__ slab, int cps) {
+                                                           T* __restrict__ out, const ConvHaloGeom g) {
   constexpr int P = Elem<T>::PER16;
   constexpr int KB = 4 * P;             // input channels per 64-byte chunk
   constexpr int NB = BN / 32;
@@ -88,15 +88,11 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const T* __restrict__
       xoff[p] = ok ? (int)(((long)(z * g.Y + y) * g.X + x) * g.ldi) + chunk * P : -1;
     }
   }
-  // split-K (slab != nullptr; the 8^3 layers, whose 32 (tile, channel block) pairs cannot fill 256 CUs): blockIdx.z owns the
-  // 64-byte input-channel chunks [cbeg, cend) and leaves an fp32 partial tile in slab[split][n*V + v][co] (ch_splitk_reduce)
-  const int nchunks = g.Ci / KB;
-  const int cbeg = slab ? blockIdx.z * cps : 0, cend = slab ? min(nchunks, cbeg + cps) : nchunks;
-  const int nphase = (cend - cbeg) * 3;
+  const int nphase = (g.Ci / KB) * 3;
 
   u32x4 xr[RX_CH_XPIECES], wr[WPIECES];
   auto prefetch = [&](int ph) {
-    const int cc = cbeg + ph / 3, dzg = ph % 3;
+    const int cc = ph / 3, dzg = ph % 3;
     if (dzg == 0) {
 #pragma unroll
       for (int p = 0; p < RX_CH_XPIECES; ++p) {
@@ -192,16 +188,6 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const T* __restrict__
     int vx = v & (g.TX - 1), vy = (v >> g.lTX) & (g.TY - 1), vz = v >> (g.lTX + g.lTY);
     int z = z0 + vz, y = y0 + vy, x = x0 + vx;
     if (z >= g.Z || y >= g.Y || x >= g.X) continue;
-    if (slab) {
-      float* sp = slab + (((long)blockIdx.z * g.N + n) * ((long)g.Z * g.Y * g.X) + ((long)(z * g.Y + y) * g.X + x)) * g.Co + n0;
-#pragma unroll
-      for (int a = 0; a < NB; ++a)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4)
-          *reinterpret_cast<f32x4*>(sp + a * 32 + 8 * g4 + 4 * fh) =
-              f32x4{acc[a][b][4 * g4], acc[a][b][4 * g4 + 1], acc[a][b][4 * g4 + 2], acc[a][b][4 * g4 + 3]};
-      continue;
-    }
     T* op = out + (long)n * g.out_ss + ((long)(z * g.Y + y) * g.X + x) * g.ldo + n0;
     auto epi = [&](auto HB, auto RA) {
 #pragma unroll
@@ -230,33 +216,6 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const T* __restrict__
         }
     };
     RX_EPI_DISPATCH(bias != nullptr, g.accumulate != 0, epi);
-  }
-}
-
-// out[row][c] (+)= sum_s slab[s][row][c] (+ bias): fixed order, one thread per 4 channels of a voxel row (row = n*V + v)
-template <typename T>
-__global__ __launch_bounds__(256) void ch_splitk_reduce(const float* __restrict__ slab, int S, long rows, int Co, const float* __restrict__ bias,
-                                                        T* __restrict__ out, int ldo, int accumulate) {
-  const int CV = Co / 4;
-  const long total = rows * CV;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int cv = (int)(i % CV);
-    const long row = i / CV;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < S; ++k) a += *reinterpret_cast<const f32x4*>(slab + ((long)k * rows + row) * Co + cv * 4);
-    T* op = out + row * ldo + cv * 4;
-    T vals[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float f = a[j];
-      if (bias) f += bias[cv * 4 + j];
-      if (accumulate) f += Elem<T>::to_f(op[j]);
-      vals[j] = Elem<T>::from_f(f);
-    }
-    if (sizeof(T) == 2)
-      *reinterpret_cast<u32x2*>(op) = *reinterpret_cast<u32x2*>(vals);
-    else
-      *reinterpret_cast<u32x4*>(op) = *reinterpret_cast<u32x4*>(vals);
   }
 }
 
@@ -695,8 +654,9 @@ __global__ __launch_bounds__(512, 1) void conv_halo32p_kernel(const T* __restric
 // Wave-specialised, persistent variant of conv_halo_kernel<T,64> on the 4x4x16 tile (the 64/128-channel layers at 64^3
 // and 32^3 and the 64-channel data gradients at 128^3).  The generic kernel runs at 35 % MFMA / 36 % LDS utilisation: per
 // (chunk, dz) phase a workgroup stops twice at a barrier, commits 37-78 KB to LDS and only then issues the next phase's
-// loads.  Here 4 PRODUCER waves stream the next phase's weight plane (and, at a chunk boundary, the next halo) through
-// registers into the other LDS buffer while 4 CONSUMER waves run the phase's 72 MFMAs each from the current one:
+// loads.  Here 4 PRODUCER waves stream the next phase's weight plane (and, at a chunk boundary, the next halo) by LDS-DMA
+// into the other LDS buffer while 4 CONSUMER waves run the phase's 72 MFMAs each from the current one (XDMA = false: the
+// halo goes through registers, for inputs past the buffer-descriptor range):
 //   LDS = 2 x (9 x 64 weight rows + 648 halo rows) x 64 B = 156,672 B -> one workgroup per CU, one barrier per phase.
 // Rows stay 64 bytes, XOR-swizzled on (row>>2)&3; voxels are dealt to lanes by lane_voxel() (conflict-free lane groups) and
 // the swizzle term of (lane row + tap offset) comes out of a per-lane 32-bit table (one v_bfe per tap and voxel block).
@@ -716,14 +676,14 @@ __global__ __launch_bounds__(512, 1) void conv_halo32p_kernel(const T* __restric
 // NA: 32-channel output blocks per workgroup (2: the 64-channel block this kernel was written for; 1: layers whose (tile, 64-channel
 // block) pairs would leave CUs idle -- 256 channels at 16^3 -- run as (tile, 32-channel block) pairs: half the weight plane per phase,
 // half the MFMAs, the same halo; LDS-DMA variants only).
-template <typename T, bool FLIP, bool GLDS, bool XDMA = false, bool STATS = false, bool ACC = false, bool BSP = false, int NA = 2>
+template <typename T, bool FLIP, bool XDMA = false, bool STATS = false, bool ACC = false, bool BSP = false, int NA = 2>
 __global__ __launch_bounds__(512, 1) void conv_halo64ws_kernel(const T* __restrict__ in, const T* __restrict__ w, const float* __restrict__ bias,
                                                                T* __restrict__ out, const ConvHaloGeom g, int tiles_per_wg) {
   constexpr int P = Elem<T>::PER16;
   constexpr int KB = 4 * P;
   constexpr int TZ = 4, TY = 4, TX = 16, HY = TY + 2, HX = TX + 2, HV = 648;
   constexpr int XPIECES = (HV * 4 + 255) / 256;   // 11
-  static_assert(NA == 2 || (GLDS && XDMA && !BSP), "32-channel blocks: LDS-DMA variants without backward sums only");
+  static_assert(NA == 2 || (XDMA && !BSP), "32-channel blocks: LDS-DMA variants without backward sums only");
   constexpr int BNW = 32 * NA;                    // output channels per workgroup
   constexpr int W_BYTES = 9 * BNW * 64;           // one weight plane
   constexpr int WINSTR = 9 * BNW / 16;            // 1-KiB DMA pieces of a plane (18 / 9 per 4 producer waves)
@@ -762,15 +722,8 @@ __global__ __launch_bounds__(512, 1) void conv_halo64ws_kernel(const T* __restri
       const int hx = row % HX, t = row / HX;
       xh[p] = row < HV ? ((t / HY) << 16) | ((t % HY) << 8) | hx : -1;
     }
-    int woff[WPIECES];
-#pragma unroll
-    for (int p = 0; p < WPIECES; ++p) {
-      const int i = ptid + 256 * p;                  // piece ((tl*64 + r)*4 + c4)
-      const int c4 = i & 3, r = (i >> 2) % BNW, tl = (i >> 2) / BNW;
-      woff[p] = ((tl * g.Co + n0 + r) * g.Ci) + c4 * P;
-    }
     const long wplane = (long)9 * g.Co * g.Ci;
-    // GLDS: the weight plane goes global -> LDS directly (global_load_lds_dwordx4: no VGPRs, no ds_write).  One
+    // The weight plane goes global -> LDS directly (global_load_lds_dwordx4: no VGPRs, no ds_write).  One
     // wave-instruction writes 1 KiB = 16 rows x 64 B lane-linearly, so the XOR swizzle is applied to the SOURCE address:
     // lane l of piece j holds row (j*4 + pw)*16 + (l>>2), data chunk (l&3) ^ ((row>>2)&3).
     const int pw = wave - 4, pl = lane;
@@ -781,7 +734,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo64ws_kernel(const T* __restri
       const int tl = rr / BNW, r = rr % BNW, c4 = (pl & 3) ^ ((rr >> 2) & 3);
       goff[p] = ((tl * g.Co + n0 + r) * g.Ci) + c4 * P;
     }
-    u32x4 xr[XPIECES], wr[WPIECES];
+    u32x4 xr[XPIECES];
     auto dma_weights = [&](int ph) {
       if (RX_ABLATE(g, 2)) return;
       const int r = ph % ppt, cc = r / 3, dzg = r - cc * 3;
@@ -821,11 +774,6 @@ __global__ __launch_bounds__(512, 1) void conv_halo64ws_kernel(const T* __restri
     };
     auto load_phase = [&](int ph) {                  // ph relative to this workgroup
       const int tile = t_begin + ph / ppt, r = ph % ppt, cc = r / 3, dzg = r - cc * 3;
-      const T* wp = w + dzg * wplane + cc * KB;
-      if (!GLDS) {
-#pragma unroll
-        for (int p = 0; p < WPIECES; ++p) wr[p] = *reinterpret_cast<const u32x4*>(wp + woff[p]);
-      }
       if (dzg == 0) {
         int n, z0, y0, x0;
         tile_origin(tile, n, z0, y0, x0);
@@ -843,15 +791,6 @@ __global__ __launch_bounds__(512, 1) void conv_halo64ws_kernel(const T* __restri
       }
     };
     auto commit_phase = [&](int ph) {
-      unsigned char* sW = sWb + (ph & 1) * W_BYTES;
-      if (!GLDS) {
-#pragma unroll
-        for (int p = 0; p < WPIECES; ++p) {
-          const int i = ptid + 256 * p;
-          const int c4 = i & 3, rr = i >> 2;           // rr = tl*64 + r
-          *reinterpret_cast<u32x4*>(sW + rr * 64 + ((c4 ^ ((rr >> 2) & 3)) << 4)) = wr[p];
-        }
-      }
       if (ph % 3 == 0) {                              // (ppt is a multiple of 3: dz == 0 <=> ph % 3 == 0)
         unsigned char* sX = sXb + ((ph / 3) & 1) * CH64_X_BYTES;
 #pragma unroll
@@ -967,24 +906,23 @@ __global__ __launch_bounds__(512, 1) void conv_halo64ws_kernel(const T* __restri
       }
     } else {
     if (nphase > 0) {
-      if (GLDS) dma_weights(0);
+      dma_weights(0);
       load_phase(0);
       commit_phase(0);
       if (nphase > 1) load_phase(1);
-      if (GLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     lds_only_barrier();
     for (int ph = 0; ph < nphase; ++ph) {
       if (ph + 1 < nphase) {
-        if (GLDS) dma_weights(ph + 1);                // in flight behind the register-staged work of this iteration
+        dma_weights(ph + 1);                          // in flight behind the register-staged work of this iteration
         commit_phase(ph + 1);                         // buffers of phase ph+1 were last read in phase ph-1 / chunk-2
         if (ph + 2 < nphase) load_phase(ph + 2);
-        if (GLDS) {                                   // the DMAs must have landed; the halo loads issued after them may fly on
-          if (ph + 2 < nphase && (ph + 2) % 3 == 0)
-            asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-          else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        // the DMAs must have landed; the halo loads issued after them may fly on
+        if (ph + 2 < nphase && (ph + 2) % 3 == 0)
+          asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
+        else
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       lds_only_barrier();
     }
@@ -1162,14 +1100,6 @@ __global__ __launch_bounds__(512, 1) void conv_halo64ws_kernel(const T* __restri
 template <typename T>
 static void ch64ws_launch(hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
   const size_t lds = (size_t)2 * (CH64_W_BYTES + CH64_X_BYTES);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
   const int cob = g.Co / 64;
   int wgs = 256 / cob;                                   // one persistent workgroup per CU in total
   if (wgs < 1) wgs = 1;
@@ -1182,67 +1112,32 @@ static void ch64ws_launch(hipStream_t st, const void* in, const void* w, const f
   wgs = wgs_s * g.N;
   const_cast<ConvHaloGeom&>(g).wgs_s = wgs_s;
   dim3 grid(wgs, cob);
-  static int glds = -1;
-  if (glds < 0) {
-    const char* e = getenv("RX_CH64_GLDS");
-    glds = e ? atoi(e) : 1;   // default: weight planes by LDS-DMA (+2-4 % isolated, -0.1 ms per step, bit-identical)
-  }
-  static int xdma = -1;
-  if (xdma < 0) {
-    const char* e = getenv("RX_CH64_XDMA");
-    xdma = e ? atoi(e) : 1;   // default: the halo by LDS-DMA too
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  const bool dma_ok = glds && xdma && (long)g.N * g.in_ss * 2 < 0x7fffff00L;   // (out-of-range offsets must stay out of range of the descriptor)
+#define RX_64WS(...)                                                                                                                   \
+  do {                                                                                                                                 \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, __VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    hipLaunchKernelGGL((conv_halo64ws_kernel<T, __VA_ARGS__>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per); \
+  } while (0)
+  // the weight planes always go by LDS-DMA; the halo too unless the input is past the buffer-descriptor range (out-of-range
+  // offsets must stay out of range of the descriptor)
+  const bool dma_ok = (long)g.N * g.in_ss * 2 < 0x7fffff00L;
   if (dma_ok && g.stat_part && !g.flip && !g.bs_y) {
-    static bool attr_s = false;
-    if (!attr_s) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_s = true;
-    }
-    hipLaunchKernelGGL((conv_halo64ws_kernel<T, false, true, true, true>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
+    RX_64WS(false, true, true);
     return;
   }
   if (dma_ok && g.bs_y && g.stat_part && g.flip && !((uintptr_t)out & 15) && g.ldo % 8 == 0 && g.out_cs % 8 == 0 && !((uintptr_t)g.bs_y & 15) &&
       g.bs_ldy % 8 == 0) {     // backward sums on the producer waves (whole-row 16-byte stores / loads)
-    static bool attr_b = false;
-    if (!attr_b) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_b = true;
-    }
-    if (g.accumulate)
-      hipLaunchKernelGGL((conv_halo64ws_kernel<T, true, true, true, false, true, true>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
-    else
-      hipLaunchKernelGGL((conv_halo64ws_kernel<T, true, true, true, false, false, true>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
+    if (g.accumulate) RX_64WS(true, true, false, true, true);
+    else RX_64WS(true, true, false, false, true);
     return;
   }
   const_cast<ConvHaloGeom&>(g).bs_y = nullptr;                   // (not taken: the caller runs the separate reduce pass)
   const_cast<ConvHaloGeom&>(g).stat_part = nullptr;              // only the instantiations above accumulate statistics
-  if (glds && xdma && g.accumulate && g.flip && (long)g.N * g.in_ss * 2 < 0x7fffff00L) {     // dx +=: old values prefetched
-    static bool attr_a = false;
-    if (!attr_a) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_a = true;
-    }
-    hipLaunchKernelGGL((conv_halo64ws_kernel<T, true, true, true, false, true>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
-    return;
-  }
-  if (glds && xdma && (long)g.N * g.in_ss * 2 < 0x7fffff00L) {   // out-of-range offsets must stay out of range of the descriptor
-    if (g.flip)
-      hipLaunchKernelGGL((conv_halo64ws_kernel<T, true, true, true>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
-    else
-      hipLaunchKernelGGL((conv_halo64ws_kernel<T, false, true, true>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
-  } else if (glds) {
-    if (g.flip)
-      hipLaunchKernelGGL((conv_halo64ws_kernel<T, true, true>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
-    else
-      hipLaunchKernelGGL((conv_halo64ws_kernel<T, false, true>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
-  } else if (g.flip)
-    hipLaunchKernelGGL((conv_halo64ws_kernel<T, true, false>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
-  else
-    hipLaunchKernelGGL((conv_halo64ws_kernel<T, false, false>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per);
+  if (dma_ok && g.accumulate && g.flip) RX_64WS(true, true, false, true);     // dx +=: old values prefetched
+  else if (dma_ok && g.flip) RX_64WS(true, true);
+  else if (dma_ok) RX_64WS(false, true);
+  else if (g.flip) RX_64WS(true, false);
+  else RX_64WS(false, false);
+#undef RX_64WS
 }
 
 // the 32-channel-block instantiations (NA = 1) of conv_halo64ws: LDS-DMA only.  Returns false (nothing launched) when the DMA
@@ -1251,14 +1146,10 @@ template <typename T>
 static bool ch32ws_launch(hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
   const size_t lds = (size_t)2 * (9 * 32 * 64 + CH64_X_BYTES);
   if (!(((long)g.N * g.in_ss + (g.in_cs == 32 ? 0L : (long)(g.Ci / 32 - 1) * g.in_cs)) * 2 < 0x7fffff00L)) return false;   // (planar concat input: the planes lie in_cs apart)
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true, true, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true, true, true, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, true, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, true, false, true, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true, true, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, false, true, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int cob = g.Co / 32;
   int wgs = 256 / cob;                                   // one persistent workgroup per CU in total
   if (wgs < 1) wgs = 1;
@@ -1270,7 +1161,7 @@ static bool ch32ws_launch(hipStream_t st, const void* in, const void* w, const f
   wgs = wgs_s * g.N;
   const_cast<ConvHaloGeom&>(g).wgs_s = wgs_s;
   dim3 grid(wgs, cob);
-#define RX_32WS(F, S, A) hipLaunchKernelGGL((conv_halo64ws_kernel<T, F, true, true, S, A, false, 1>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per)
+#define RX_32WS(F, S, A) hipLaunchKernelGGL((conv_halo64ws_kernel<T, F, true, S, A, false, 1>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per)
   if (g.stat_part && !g.flip && !g.accumulate) {
     RX_32WS(false, true, false);
     return true;
@@ -1286,17 +1177,13 @@ static bool ch32ws_launch(hipStream_t st, const void* in, const void* w, const f
 template <typename T>
 static void ch32p_launch(hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
   const size_t lds = (size_t)CH32P_W_BYTES + 2 * (size_t)CH32P_HALO_BYTES;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int wgs = g.NT < 256 ? g.NT : 256;                    // one persistent workgroup per CU
   const int NTs = g.NT / g.N;                           // a workgroup's tile range never straddles samples
   int wgs_s = wgs / g.N > 0 ? wgs / g.N : 1;
@@ -1321,18 +1208,10 @@ static void ch32p_launch(hipStream_t st, const void* in, const void* w, const fl
 template <typename T>
 static void ch32_launch(dim3 grid, hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
   const size_t lds = (size_t)648 * 80 + (size_t)9 * 32 * 64;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (g.stat_part && !g.flip && !g.accumulate) {
-    static bool attr_s = false;
-    if (!attr_s) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_s = true;
-    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((conv_halo32_kernel<T, false, true>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
   } else if (g.flip)
     hipLaunchKernelGGL((conv_halo32_kernel<T, true>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
@@ -1352,24 +1231,15 @@ static int ch_ilog2(int v) {
 }
 
 template <typename T>
-static void ch_dispatch(int BN, dim3 grid, hipStream_t st, const void* in, const void* w, const float* bias, void* out,
-                        const ConvHaloGeom& g, float* slab = nullptr, int cps = 0) {
+static void ch_dispatch(int BN, dim3 grid, hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
   if (BN == 64) {
     const size_t lds = (size_t)(RX_CH_MAX_HV * 4 + 9 * 64 * 4) * 16;
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<T, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr = true;
-    }
-    hipLaunchKernelGGL((conv_halo_kernel<T, 64>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, slab, cps);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<T, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((conv_halo_kernel<T, 64>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
   } else {
     const size_t lds = (size_t)(RX_CH_MAX_HV * 4 + 9 * 32 * 4) * 16;
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<T, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr = true;
-    }
-    hipLaunchKernelGGL((conv_halo_kernel<T, 32>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, slab, cps);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<T, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((conv_halo_kernel<T, 32>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
   }
 }
 
@@ -1378,8 +1248,7 @@ static void ch_dispatch(int BN, dim3 grid, hipStream_t st, const void* in, const
 // stat_part / stat_chunks (forward only, optional): when the launch goes to a persistent kernel, per-wave partial sums of
 // y and y^2 are left in stat_part ([n][*stat_chunks][2][Co] floats) and *stat_chunks > 0; otherwise *stat_chunks = 0.
 int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip, int accumulate,
-                     void* ws, size_t ws_bytes, hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks,
-                     const RxBwdStat* bs) {
+                     hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks, const RxBwdStat* bs) {
   if (stat_chunks) *stat_chunks = 0;
   const int per16 = dt == RX_F32 ? 4 : 8;
   const int KB = 4 * per16;
@@ -1411,84 +1280,20 @@ int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* 
   g.tz_n = (g.Z + TZ - 1) / TZ, g.ty_n = (g.Y + TY - 1) / TY, g.tx_n = (g.X + TX - 1) / TX;
   g.NT = g.N * g.tz_n * g.ty_n * g.tx_n;
   g.accumulate = accumulate, g.flip = flip;
-  {
-    static int order = -1;   // RX_TILE_ORDER: 0 raster, 1 (default) locality-aware walk (rx_tile_coords), bit-identical results
-    if (order < 0) {
-      const char* e = getenv("RX_TILE_ORDER");
-      order = e ? atoi(e) : 1;
-    }
-    g.order = order;         // persistent kernels: z-fastest columns; one-tile grids: 4x4x4 bricks where the tile grid allows
-  }
-  {
-    static int dbg = -1;
-    if (dbg < 0) {
-      const char* e = getenv("RX_DBG");
-      dbg = e ? atoi(e) : 0;
-    }
-    g.dbg = dbg;
-  }
+  g.order = 1;               // persistent kernels: z-fastest columns; one-tile grids: 4x4x4 bricks where the tile grid allows
+  static const int dbg = rx_env_mask("RX_DBG");
+  g.dbg = dbg;
   int BN = (g.Co % 64 == 0) ? 64 : 32;
   if (BN == 64 && (long)g.NT * (g.Co / 64) < 256) BN = 32;  // under-filled grid: twice the workgroups, half the work each
   if ((in->cs || out->cs) && (long)g.NT * (g.Co / BN) < 192) RX_FAIL(RX_EUNSUPPORTED, "conv_halo: planar-concat operand on a layer too small for the halo kernels");
-  if ((long)g.NT * (g.Co / BN) < 192) {     // (128 pairs -- the 1024-channel data gradient of the first decoder conv at 8^3 -- measured 93 us here, ~60 us on igemm_fat)
-    // too few (tile, channel block) pairs to fill 256 CUs: split the input channels over blockIdx.z, fp32 slabs + a
-    // fixed-order reduce.  Against the split-K gather kernel (igemm_fat) the activations are staged ONCE per chunk with
-    // their halo instead of once per tap -- that kernel moves 340 MB through L2 for a 512->512 layer at 8^3 (216 MB of
-    // it re-gathered activations).  MEASURED (rocprofv3, inside the cfg2 step): 35.7 us + 5.5 us reduce against 36 us +
-    // 5 us for igemm_fat -- no gain: with 3-6 phases per workgroup the kernel is a chain of cold weight-slice fetches
-    // (64-byte pieces of 1 KB rows), not an L2-bandwidth problem.  Kept behind RX_CH_SPLITK=1 (off by default).
-    static int splitk = -1;
-    if (splitk < 0) {
-      const char* e = getenv("RX_CH_SPLITK");
-      splitk = e ? atoi(e) : 0;
-    }
-    const int nchunks = g.Ci / KB;
-    const long base = (long)g.NT * (g.Co / 64);      // the split path always runs the 64-channel-block kernel
-    if (!splitk || !ws || g.Co % 64 || nchunks < 4 || base < 8) return 0;
-    static int target = -1, minch = -1;
-    if (target < 0) {
-      const char* e = getenv("RX_CH_SPLITK_WGS");
-      target = e ? atoi(e) : 256;
-      const char* e2 = getenv("RX_CH_SPLITK_MINCH");
-      minch = e2 ? atoi(e2) : 2;
-    }
-    int S = (int)((target + base - 1) / base);
-    if (S > nchunks / minch) S = nchunks / minch;    // >= 2 chunks (6 phases) per workgroup
-    if (S > 16) S = 16;
-    const int cps = (nchunks + S - 1) / S;
-    S = (nchunks + cps - 1) / cps;
-    const long rows = (long)g.N * g.Z * g.Y * g.X;
-    if (S < 2 || (size_t)S * rows * g.Co * sizeof(float) > ws_bytes) return 0;
-    ConvHaloGeom gs = g;
-    gs.order = 0;
-    dim3 grid3(g.NT, g.Co / 64, S);
-    rx_note_kernel("conv_halo_kernel<64,splitk>");
-    const long total = rows * (g.Co / 4);
-    const int G = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-    switch (dt) {
-      case RX_F32:
-        ch_dispatch<float>(64, grid3, st, in->ptr, w, nullptr, out->ptr, gs, (float*)ws, cps);
-        hipLaunchKernelGGL((ch_splitk_reduce<float>), dim3(G), dim3(256), 0, st, (const float*)ws, S, rows, g.Co, bias, (float*)out->ptr, g.ldo, accumulate);
-        break;
-      case RX_BF16:
-        ch_dispatch<bf16_t>(64, grid3, st, in->ptr, w, nullptr, out->ptr, gs, (float*)ws, cps);
-        hipLaunchKernelGGL((ch_splitk_reduce<bf16_t>), dim3(G), dim3(256), 0, st, (const float*)ws, S, rows, g.Co, bias, (bf16_t*)out->ptr, g.ldo, accumulate);
-        break;
-      case RX_F16:
-        ch_dispatch<f16_t>(64, grid3, st, in->ptr, w, nullptr, out->ptr, gs, (float*)ws, cps);
-        hipLaunchKernelGGL((ch_splitk_reduce<f16_t>), dim3(G), dim3(256), 0, st, (const float*)ws, S, rows, g.Co, bias, (f16_t*)out->ptr, g.ldo, accumulate);
-        break;
-      default: return 0;
-    }
-    hipError_t e6 = hipGetLastError();
-    if (e6 != hipSuccess) {
-      rx_set_error("conv_halo split-K: %s", hipGetErrorString(e6));
-      return RX_ELAUNCH;
-    }
-    return 1;
-  }
+  // Too few (tile, channel block) pairs to fill 256 CUs (128 pairs -- the 1024-channel data gradient of the first decoder conv
+  // at 8^3 -- measured 93 us here, ~60 us on igemm_fat): the split-K gather kernel takes them.  A split-K variant of this kernel
+  // (input channels over blockIdx.z, fp32 slabs + a fixed-order reduce) measured no gain against it, 35.7 + 5.5 us against 36 +
+  // 5 us inside the cfg2 step: with 3-6 phases per workgroup it is a chain of cold weight-slice fetches, not an L2-bandwidth
+  // problem.
+  if ((long)g.NT * (g.Co / BN) < 192) return 0;
   dim3 grid(g.NT, g.Co / BN);
-  if (BN == 32 && TZ == 4 && TY == 4 && TX == 16 && dt != RX_F32 && g.Ci == 32 && g.Co == 32 && g.NT >= 512 && !getenv("RX_NO_CH32P")) {
+  if (BN == 32 && TZ == 4 && TY == 4 && TX == 16 && dt != RX_F32 && g.Ci == 32 && g.Co == 32 && g.NT >= 512) {
     rx_note_kernel("conv_halo32p_kernel");               // 32 -> 32 channels: persistent, weights stationary in LDS
     if (in->cs || out->cs) RX_FAIL(RX_EUNSUPPORTED, "conv_halo32p: planar-concat operand");
     const bool room = stat_part && stat_chunks && (size_t)g.N * 1024 * 2 * g.Co * sizeof(float) <= stat_bytes;
@@ -1512,32 +1317,25 @@ int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* 
     return 1;
   }
   ConvHaloGeom g1 = g;                                // one tile per workgroup: bricks of tiles where the tile grid allows
-  if (g.order && g.tx_n % 4 == 0 && g.ty_n % 4 == 0 && g.tz_n % 4 == 0) g1.order = 2;
+  if (g.tx_n % 4 == 0 && g.ty_n % 4 == 0 && g.tz_n % 4 == 0) g1.order = 2;
   if (BN == 32 && TZ == 4 && TY == 4 && TX == 16 && dt != RX_F32 && !out->cs && g.Ci >= 64 && (long)g.NT * (g.Co / 32) >= 256 &&
       !(accumulate && !flip)) {
     // 32-channel blocks on the wave-specialised DMA pipeline (the 256-channel layers at 16^3: 32 tiles x 8 blocks = one workgroup
     // per CU; alone 43 -> ~30 us against conv_halo32_kernel's one tile per workgroup)
-    static int ws32 = -1;     // RX_CH32WS=0: conv_halo32_kernel
-    if (ws32 < 0) {
-      const char* e = getenv("RX_CH32WS");
-      ws32 = e ? atoi(e) : 1;
-    }
-    if (ws32) {
-      const bool fuse = stat_part && stat_chunks && !flip && !accumulate && (size_t)g.N * 1024 * 2 * g.Co * sizeof(float) <= stat_bytes;
-      ConvHaloGeom g2 = g;
-      g2.stat_part = fuse ? stat_part : nullptr;
-      g2.bs_y = nullptr;
-      const bool launched = dt == RX_BF16 ? ch32ws_launch<bf16_t>(st, in->ptr, w, bias, out->ptr, g2) : ch32ws_launch<f16_t>(st, in->ptr, w, bias, out->ptr, g2);
-      if (launched) {
-        rx_note_kernel("conv_halo32ws_kernel");
-        hipError_t e7 = hipGetLastError();
-        if (e7 != hipSuccess) {
-          rx_set_error("conv_halo32ws: %s", hipGetErrorString(e7));
-          return RX_ELAUNCH;
-        }
-        if (fuse && g2.stat_part) *stat_chunks = g2.wgs_s * 4;
-        return 1;
+    const bool fuse = stat_part && stat_chunks && !flip && !accumulate && (size_t)g.N * 1024 * 2 * g.Co * sizeof(float) <= stat_bytes;
+    ConvHaloGeom g2 = g;
+    g2.stat_part = fuse ? stat_part : nullptr;
+    g2.bs_y = nullptr;
+    const bool launched = dt == RX_BF16 ? ch32ws_launch<bf16_t>(st, in->ptr, w, bias, out->ptr, g2) : ch32ws_launch<f16_t>(st, in->ptr, w, bias, out->ptr, g2);
+    if (launched) {
+      rx_note_kernel("conv_halo32ws_kernel");
+      hipError_t e7 = hipGetLastError();
+      if (e7 != hipSuccess) {
+        rx_set_error("conv_halo32ws: %s", hipGetErrorString(e7));
+        return RX_ELAUNCH;
       }
+      if (fuse && g2.stat_part) *stat_chunks = g2.wgs_s * 4;
+      return 1;
     }
   }
   if (BN == 32 && TZ == 4 && TY == 4 && TX == 16) {  // full-resolution layers: compile-time tile, padded rows
@@ -1563,28 +1361,12 @@ int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* 
     if (fuse32n) *stat_chunks = NTs32 * 4;
     return 1;
   }
-  static int ch64ws = -1;   // RX_CH64WS: 0 off, 1 (default) on for layers with >= 256 (tile, channel block) pairs, 2 always
-  if (ch64ws < 0) {
-    const char* e = getenv("RX_CH64WS");
-    ch64ws = e ? atoi(e) : 1;
-  }
-  if (g.Co % 64 == 0 && TZ == 4 && TY == 4 && TX == 16 && dt != RX_F32 && ch64ws &&
-      (ch64ws == 2 || (long)g.NT * (g.Co / 64) >= 256)) {
+  if (g.Co % 64 == 0 && TZ == 4 && TY == 4 && TX == 16 && dt != RX_F32 && (long)g.NT * (g.Co / 64) >= 256) {
     if (in->cs) RX_FAIL(RX_EUNSUPPORTED, "conv_halo64ws: planar-concat input");
     rx_note_kernel("conv_halo64ws_kernel");
-    static int st64 = -1;    // RX_CH64_STATS=0: statistics of the 64-channel-block layers by the separate pass
-    if (st64 < 0) {
-      const char* e = getenv("RX_CH64_STATS");
-      st64 = e ? atoi(e) : 1;
-    }
     const bool room64 = stat_part && stat_chunks && (size_t)g.N * 1024 * 2 * g.Co * sizeof(float) <= stat_bytes;
-    static int bs64 = -1;    // RX_CH64_BWD_STATS=0: no backward sums out of this kernel
-    if (bs64 < 0) {
-      const char* e = getenv("RX_CH64_BWD_STATS");
-      bs64 = e ? atoi(e) : 1;
-    }
-    const bool fuse64 = st64 && room64 && !flip && !accumulate && !bs;
-    const bool fuse64b = bs64 && room64 && flip && bs;
+    const bool fuse64 = room64 && !flip && !accumulate && !bs;
+    const bool fuse64b = room64 && flip && bs;
     g.stat_part = (fuse64 || fuse64b) ? stat_part : nullptr;
     if (fuse64b) {
       g.bs_y = bs->y->ptr, g.bs_ldy = bs->y->ld, g.bs_yss = rx_act_voxels(bs->y) * (long)bs->y->ld;

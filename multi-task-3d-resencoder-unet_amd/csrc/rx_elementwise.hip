@@ -674,19 +674,12 @@ __global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__
   }
 }
 
-// tuning knob (env RX_IN_SMALL_MAX, read once): largest per-sample voxel count that takes the single-launch path
-static long rx_in_small_max() {
-  static long v = [] { const char* e = getenv("RX_IN_SMALL_MAX"); return e ? atol(e) : 512L; }();
-  return v;
-}
-#define RX_IN_SMALL_MAX_VOXELS rx_in_small_max()
-// channels per workgroup of the single-launch kernels: 32, or 8 from RX_IN_SMALL_NARROW voxels per sample upwards (default 256:
-// the 8^3 stage; 80 workgroups instead of 20 for 320 channels x 2 samples, one 16-byte vector per voxel and thread.  Alone
-// 12.4 -> 7.6 us for the backward of a 320-channel 8^3 layer, 17.42 / 17.37 -> 17.32 / 17.30 ms per cfg2 step on one box)
-static long rx_in_small_narrow() {
-  static long v = [] { const char* e = getenv("RX_IN_SMALL_NARROW"); return e ? atol(e) : 256L; }();
-  return v;
-}
+// largest per-sample voxel count that takes the single-launch path
+constexpr long RX_IN_SMALL_MAX_VOXELS = 512;
+// channels per workgroup of the single-launch kernels: 32, or 8 from this many voxels per sample upwards (the 8^3 stage; 80
+// workgroups instead of 20 for 320 channels x 2 samples, one 16-byte vector per voxel and thread.  Alone 12.4 -> 7.6 us for
+// the backward of a 320-channel 8^3 layer, 17.42 / 17.37 -> 17.32 / 17.30 ms per cfg2 step on one box)
+constexpr long RX_IN_SMALL_NARROW_VOXELS = 256;
 
 extern "C" int rx_instnorm_act_bwd(rx_dtype dt, const rx_act* g, const rx_act* y, const float* stats, const rx_act* out,
                                    float slope, const rx_act* dy, const rx_act* d_residual, int accumulate_residual, void* ws,
@@ -713,7 +706,7 @@ extern "C" int rx_instnorm_act_bwd(rx_dtype dt, const rx_act* g, const rx_act* y
   if (V <= RX_IN_SMALL_MAX_VOXELS && C % 32 == 0) {   // low-resolution stages: one launch instead of three
     hipStream_t st1 = (hipStream_t)stream;
     const int mode = use_mask ? 1 : (mask_xhat ? 2 : 0);
-    const bool narrow = dt != RX_F32 && V >= rx_in_small_narrow();   // (fp32 = parity mode: the summation order the goldens' seeds were screened with)
+    const bool narrow = dt != RX_F32 && V >= RX_IN_SMALL_NARROW_VOXELS;   // (fp32 = parity mode: the summation order the goldens' seeds were screened with)
     dim3 grid1(narrow ? C / 8 : C / 32, N);
 #define RX_LAUNCH_IN_SMALL_BWD(G)                                                                                                     \
   hipLaunchKernelGGL((in_small_bwd_kernel<T, G>), grid1, dim3(256), 0, st1, (const T*)g->ptr, g->ld, V * g->ld, (const T*)y->ptr, y->ld, \
@@ -948,7 +941,7 @@ extern "C" int rx_instnorm_fwd(rx_dtype dt, const rx_act* y, float eps, float* s
     if (!same_geom(y, residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_fwd: residual geometry mismatch");
   }
   hipStream_t st = (hipStream_t)stream;
-  const bool narrow = dt != RX_F32 && V >= rx_in_small_narrow();   // (fp32 = parity mode: the summation order the goldens' seeds were screened with)
+  const bool narrow = dt != RX_F32 && V >= RX_IN_SMALL_NARROW_VOXELS;   // (fp32 = parity mode: the summation order the goldens' seeds were screened with)
   dim3 grid(narrow ? y->c / 8 : y->c / 32, y->n);
 #define RX_LAUNCH_IN_SMALL_FWD(G, RES)                                                                                              \
   hipLaunchKernelGGL((in_small_fwd_kernel<T, G, RES>), grid, dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld,                  \
@@ -1819,14 +1812,6 @@ static int check_kernel13(const int32_t k[3], const char* who) {
 
 int rx_stem_fwd_mfma_try(rx_dtype dt, const float* x, int n, int cin, int z, int y, int xx, const float* w, const float* bias,
                          const rx_act* out, const int32_t kernel[3], hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks);
-static int rx_stem_mfma_on() {
-  static int mf = -1;      // RX_STEM_MFMA=0: the VALU kernels
-  if (mf < 0) {
-    const char* e = getenv("RX_STEM_MFMA");
-    mf = e ? atoi(e) : 1;
-  }
-  return mf;
-}
 
 // the stem conv and the InstanceNorm statistics of its output (encoder.py:84 + simple_conv_blocks.py:58-72): one pass on the
 // MFMA kernel (the separate statistics pass read the 268 MB output of the cfg2 stem again: 109 us of a 17 ms step), the two
@@ -1840,14 +1825,8 @@ extern "C" int rx_stem_conv_fwd_stats(rx_dtype dt, const float* x_ncdhw, int n, 
   if ((rc = check_kernel13(kernel, "rx_stem_conv_fwd_stats"))) return rc;
   if (!x_ncdhw || !w || !stats || !ws || cin < 1 || cin > 16) RX_FAIL(RX_EINVAL, "rx_stem_conv_fwd_stats: bad arguments");
   if (out->n != n || out->z != z || out->y != y || out->x != x) RX_FAIL(RX_EINVAL, "rx_stem_conv_fwd_stats: geometry mismatch");
-  static int fuse = -1;
-  if (fuse < 0) {
-    const char* e = getenv("RX_FUSED_STATS");
-    fuse = e ? atoi(e) : 1;
-  }
   int chunks = 0;
-  if (fuse && rx_stem_mfma_on() &&
-      rx_stem_fwd_mfma_try(dt, x_ncdhw, n, cin, z, y, x, w, bias, out, kernel, (hipStream_t)stream, (float*)ws, ws_bytes, &chunks) == 1) {
+  if (rx_stem_fwd_mfma_try(dt, x_ncdhw, n, cin, z, y, x, w, bias, out, kernel, (hipStream_t)stream, (float*)ws, ws_bytes, &chunks) == 1) {
     if (chunks > 0) {
       rx_stats_finalize_launch((const float*)ws, n, chunks, out->c, (double)rx_act_voxels(out), eps, stats, (hipStream_t)stream);
       RX_CHECK_LAUNCH("rx_stem_conv_fwd_stats");
@@ -1881,11 +1860,11 @@ extern "C" int rx_stem_conv_fwd(rx_dtype dt, const float* x_ncdhw, int n, int ci
   if (out->n != n || out->z != z || out->y != y || out->x != x) RX_FAIL(RX_EINVAL, "rx_stem_conv_fwd: geometry mismatch");
   hipStream_t st = (hipStream_t)stream;
   const int TT = kernel[0] * kernel[1] * kernel[2];
-  if (rx_stem_mfma_on() && rx_stem_fwd_mfma_try(dt, x_ncdhw, n, cin, z, y, x, w, bias, out, kernel, st, nullptr, 0, nullptr) == 1) {
+  if (rx_stem_fwd_mfma_try(dt, x_ncdhw, n, cin, z, y, x, w, bias, out, kernel, st, nullptr, 0, nullptr) == 1) {
     RX_CHECK_LAUNCH("rx_stem_conv_fwd(mfma)");
     return RX_OK;
   }
-  if (dt != RX_F32 && out->c % 32 == 0 && (out->c * 4) % 16 == 0 && !getenv("RX_NO_STEM32")) {   // one thread per voxel x 32 channels
+  if (dt != RX_F32 && out->c % 32 == 0 && (out->c * 4) % 16 == 0) {   // one thread per voxel x 32 channels
     const long V = rx_act_voxels(out);
     const int G = (int)((V + 255) / 256 > 16384 ? 16384 : (V + 255) / 256);
     const size_t lds = (size_t)out->c * cin * TT * sizeof(float);
@@ -2409,17 +2388,6 @@ extern "C" int rx_adamw_flat_multi(int count, float* const* p, const float* cons
   const AdamArgs aa = adam_args(lr, beta1, beta2, eps, weight_decay, step);
   for (int i = 0; i < count; ++i)
     if (!p[i] || !grad[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] < 1) RX_FAIL(RX_EINVAL, "rx_adamw_flat_multi: bad tensor %d", i);
-  static const bool per_tensor = [] { const char* e = getenv("RX_ADAMW_PER_TENSOR"); return e && e[0] == '1'; }();   // A/B: the one-launch-per-tensor path
-  if (per_tensor) {
-    for (int i = 0; i < count; ++i) {
-      long blocks = (numel[i] + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(adamw_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p[i], grad[i], exp_avg[i], exp_avg_sq[i], clip,
-                         aa, numel[i]);
-    }
-    RX_CHECK_LAUNCH("rx_adamw_flat_multi");
-    return RX_OK;
-  }
   for (int i0 = 0; i0 < count;) {
     AdamMulti t;
     int k = 0;

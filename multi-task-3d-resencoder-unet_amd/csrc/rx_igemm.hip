@@ -436,25 +436,15 @@ static int igemm_launch(rx_dtype dt, const void* in, const void* w, const float*
   if (vmax <= 0 || g.nph <= 0) return RX_OK;
   // low-resolution layers: fat K steps, batch folded into M (see igemm_fat_kernel)
   {
-    static int fat_on = -1;
-    if (fat_on < 0) {
-      const char* e = getenv("RX_NO_FAT");
-      fat_on = e ? 0 : 1;
-    }
     const int KE = 16 * per16;
     const long NV = (long)N * g.ph[0].Vq;
-    if (fat_on && dt != RX_F32 && g.nph == 1 && g.Ci % KE == 0 && g.Co % 64 == 0 && NV <= 2048 && ws &&
+    if (dt != RX_F32 && g.nph == 1 && g.Ci % KE == 0 && g.Co % 64 == 0 && NV <= 2048 && ws &&
         g.ph[0].ntaps * (g.Ci / KE) >= 8 && g.ph[0].opz == 0 && g.ph[0].opy == 0 && g.ph[0].opx == 0 && g.osz == 1 && g.osy == 1 &&
         g.osx == 1) {
       const int mtiles = (int)((NV + 127) / 128);
       const int nsteps = g.ph[0].ntaps * (g.Ci / KE);
       const long base_wgs = (long)mtiles * (g.Co / 64);
-      static int fat_wgs = -1;
-      if (fat_wgs < 0) {
-        const char* e = getenv("RX_FAT_WGS");
-        fat_wgs = e ? atoi(e) : 512;
-      }
-      int ks = (int)((fat_wgs + base_wgs - 1) / base_wgs);
+      int ks = (int)((512 + base_wgs - 1) / base_wgs);      // aim at 512 workgroups
       if (ks > nsteps / 4) ks = nsteps / 4;   // >= 4 K steps per workgroup; also bounds the serial sum of the reduce
       if (ks < 1) ks = 1;
       while (ks > 1 && (size_t)ks * NV * g.Co * sizeof(float) > ws_bytes) --ks;
@@ -466,15 +456,10 @@ static int igemm_launch(rx_dtype dt, const void* in, const void* w, const float*
         rx_note_kernel("igemm_fat_kernel");
         dim3 grid(mtiles * ks, g.Co / 64);
         if (dt == RX_BF16) {
-          static bool attr = false;
-          if (!attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fat_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr = true;
-          }
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fat_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 #if RX_ABLATION
           {
-            const char* ea = getenv("RX_FAT_ABL");
-            const int abl = ea ? atoi(ea) : 0;
+            static const int abl = rx_env_mask("RX_FAT_ABL");
 #define RX_FAT_L(A)                                                                                                                     \
   case A:                                                                                                                               \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fat_kernel<bf16_t, A>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
@@ -491,11 +476,7 @@ static int igemm_launch(rx_dtype dt, const void* in, const void* w, const float*
           hipLaunchKernelGGL((igemm_fat_kernel<bf16_t>), grid, dim3(256), lds, st, (const bf16_t*)in, (const bf16_t*)w, (float*)ws, g, (int)NV, nsteps);
 #endif
         } else {
-          static bool attr = false;
-          if (!attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fat_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr = true;
-          }
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fat_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
           hipLaunchKernelGGL((igemm_fat_kernel<f16_t>), grid, dim3(256), lds, st, (const f16_t*)in, (const f16_t*)w, (float*)ws, g, (int)NV, nsteps);
         }
         // the reduce always runs here (even for ks == 1 the kernel only writes fp32 slabs): force its split path
@@ -545,8 +526,7 @@ static int igemm_launch(rx_dtype dt, const void* in, const void* w, const float*
 
 // rx_conv_halo.hip
 int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip, int accumulate,
-                     void* ws, size_t ws_bytes, hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks,
-                     const RxBwdStat* bs);
+                     hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks, const RxBwdStat* bs);
 void rx_inbwd_fused_finalize_launch(const float* partial, int N, int nchunks, int C, double V, const float* stats, float* m12, hipStream_t st);
 // rx_pointwise.hip
 int rx_pointwise_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, const int32_t stride[3],
@@ -587,7 +567,7 @@ extern "C" int rx_conv3d_fwd(rx_dtype dt, const rx_act* x, const void* w_fwd, co
       y->x != conv_out_dim(x->x, kernel[2], stride[2]))
     RX_FAIL(RX_EINVAL, "rx_conv3d_fwd: output geometry mismatch");
   if (is_333_s1(kernel, stride)) {
-    rc = rx_conv_halo_try(dt, x, w_fwd, bias, y, 0, 0, ws, wsb, (hipStream_t)stream, nullptr, 0, nullptr, nullptr);  // LDS-halo kernel
+    rc = rx_conv_halo_try(dt, x, w_fwd, bias, y, 0, 0, (hipStream_t)stream, nullptr, 0, nullptr, nullptr);  // LDS-halo kernel
     if (rc < 0) return rc;
     if (rc == 1) return RX_OK;
   }
@@ -634,17 +614,12 @@ extern "C" int rx_conv3d_bwd_data_instats(rx_dtype dt, const rx_act* dy, const v
   if (!rx_act_ok(dy) || !rx_act_ok(dx) || !w_bwd) RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_data_instats: bad arguments");
   int rc = check13(kernel, stride, "rx_conv3d_bwd_data_instats");
   if (rc) return rc;
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("RX_FUSED_BWD_STATS");
-    on = e ? atoi(e) : 1;
-  }
   const bool same = in_y->n == dx->n && in_y->z == dx->z && in_y->y == dx->y && in_y->x == dx->x && in_y->c == dx->c;
-  if (on && same && is_333_s1(kernel, stride) && dx->z == dy->z && dx->y == dy->y && dx->x == dy->x && in_y->ld % 4 == 0 &&
+  if (same && is_333_s1(kernel, stride) && dx->z == dy->z && dx->y == dy->y && dx->x == dy->x && in_y->ld % 4 == 0 &&
       !((uintptr_t)in_y->ptr & 7)) {
     RxBwdStat bs{in_y, in_stats, slope};
     int chunks = 0;
-    rc = rx_conv_halo_try(dt, dy, w_bwd, nullptr, dx, 1, accumulate, nullptr, 0, (hipStream_t)stream, (float*)ws, wsb, &chunks, &bs);
+    rc = rx_conv_halo_try(dt, dy, w_bwd, nullptr, dx, 1, accumulate, (hipStream_t)stream, (float*)ws, wsb, &chunks, &bs);
     if (rc < 0) return rc;
     if (rc == 1) {
       if (chunks > 0) {
@@ -669,13 +644,8 @@ extern "C" int rx_conv3d_fwd_stats(rx_dtype dt, const rx_act* x, const void* w_f
   int rc = check13(kernel, stride, "rx_conv3d_fwd_stats");
   if (rc) return rc;
   if (is_333_s1(kernel, stride) && y->n == x->n && y->z == x->z && y->y == x->y && y->x == x->x) {
-    static int fuse = -1;
-    if (fuse < 0) {
-      const char* e = getenv("RX_FUSED_STATS");
-      fuse = e ? atoi(e) : 1;
-    }
     int chunks = 0;
-    rc = rx_conv_halo_try(dt, x, w_fwd, bias, y, 0, 0, nullptr, 0, (hipStream_t)stream, fuse ? (float*)ws : nullptr, wsb, &chunks, nullptr);
+    rc = rx_conv_halo_try(dt, x, w_fwd, bias, y, 0, 0, (hipStream_t)stream, (float*)ws, wsb, &chunks, nullptr);
     if (rc < 0) return rc;
     if (rc == 1 && chunks > 0) {
       rx_stats_finalize_launch((const float*)ws, y->n, chunks, y->c, (double)rx_act_voxels(y), eps, stats, (hipStream_t)stream);
@@ -700,7 +670,7 @@ extern "C" int rx_conv3d_bwd_data(rx_dtype dt, const rx_act* dy, const void* w_b
       dy->x != conv_out_dim(dx->x, kernel[2], stride[2]))
     RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_data: geometry mismatch");
   if (is_333_s1(kernel, stride)) {
-    rc = rx_conv_halo_try(dt, dy, w_bwd, nullptr, dx, 1, accumulate, ws, wsb, (hipStream_t)stream, nullptr, 0, nullptr, nullptr);
+    rc = rx_conv_halo_try(dt, dy, w_bwd, nullptr, dx, 1, accumulate, (hipStream_t)stream, nullptr, 0, nullptr, nullptr);
     if (rc < 0) return rc;
     if (rc == 1) return RX_OK;
   }

@@ -98,12 +98,7 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const T* __restrict__ in
 // 1 = handled.  in: the tensor on the small grid (Zi, Yi, Xi); out voxel = s * in voxel + tap; w = [taps][Co][Ci] packed weights.
 int rx_pointwise_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, const int32_t stride[3],
                      int accumulate, hipStream_t st) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("RX_POINTWISE");
-    on = e ? atoi(e) : 1;
-  }
-  if (!on || dt == RX_F32 || in->cs || out->cs) return 0;
+  if (dt == RX_F32 || in->cs || out->cs) return 0;
   const int taps = stride[0] * stride[1] * stride[2];
   const int Ci = in->c, Co = out->c;
   if (Ci % 16 || Ci > 16 * RX_PW_MAXKS || Co % 32 || in->ld % 8 || out->ld % 8 || ((uintptr_t)in->ptr & 15) || ((uintptr_t)out->ptr & 15) ||

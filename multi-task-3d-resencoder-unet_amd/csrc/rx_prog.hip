@@ -18,7 +18,6 @@
 #include <map>
 #include <mutex>
 #include <string>
-#include <unordered_map>
 #include <utility>
 
 #include "rx_common.h"
@@ -184,11 +183,8 @@ static hipEvent_t* event_slot(int slot) {
   if (!g_event_made[slot]) {
     // These events only order streams of ONE device (producer kernel -> consumer kernel; every kernel still ends with its own
     // device-scope release), nobody synchronises the HOST on them: created without the system-scope fence (no cache write-back /
-    // invalidate towards the host when the event fires; cfg2 step 18.01 -> 17.84 ms).  RX_EVENT_FLAGS (A/B knob): 0 plain, 1 without
-    // the system-scope fence (default), 2 device-scope release.
-    static const int mode = [] { const char* v = getenv("RX_EVENT_FLAGS"); return v ? atoi(v) : 1; }();
-    unsigned flags = hipEventDisableTiming | (mode == 1 ? hipEventDisableSystemFence : mode == 2 ? hipEventReleaseToDevice : 0u);
-    if (hipEventCreateWithFlags(&g_events[slot], flags) != hipSuccess) return nullptr;
+    // invalidate towards the host when the event fires; cfg2 step 18.01 -> 17.84 ms).
+    if (hipEventCreateWithFlags(&g_events[slot], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) return nullptr;
     g_event_made[slot] = true;
   }
   return &g_events[slot];
@@ -210,15 +206,7 @@ extern "C" int rx_stream_wait(int slot, void* stream) {
   return RX_OK;
 }
 
-// ---- per-call-site caches for what the entry points used to ask the runtime / environment on EVERY launch --------------
-const char* rx_getenv_cached(const char* name) {
-  static thread_local std::unordered_map<const char*, const char*> cache;      // keyed by the literal's address
-  auto it = cache.find(name);
-  if (it != cache.end()) return it->second;
-  const char* v = getenv(name);
-  cache.emplace(name, v);
-  return v;
-}
+// ---- per-call-site cache for what the entry points used to ask the runtime on EVERY launch --------------------------------
 hipError_t rx_func_attr_once(const void* fn, hipFuncAttribute attr, int value) {
   // largest value already set per (device, kernel): the attribute belongs to the kernel's code object ON ONE DEVICE, so a
   // second device of the same process must get its own call

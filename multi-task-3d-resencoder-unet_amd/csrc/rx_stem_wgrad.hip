@@ -334,12 +334,8 @@ int rx_stem_fwd_mfma_try(rx_dtype dt, const float* x, int n, int cin, int z, int
   // here and computed garbage; found by tests/test_fuzz_gpu.py)
   if (dt == RX_F32 || out->c != 32 || out->ld % 4 || ((uintptr_t)out->ptr & 7) || K > 112 || cin > 4) return 0;
   const int NT = n * ((z + 3) / 4) * ((y + 3) / 4) * ((xx + 15) / 16);
-  static int maxb = -1;
-  if (maxb < 0) {
-    const char* e = getenv("RX_STEM_BLOCKS");
-    maxb = e ? atoi(e) : 1024;   // measured: 512 -> 162 us, 768 -> 131, 1024 -> 119, 1280 -> 147, 2048 -> 127, one tile per workgroup -> 193
-  }
-  int blocks = NT < maxb ? NT : maxb;       // 4 resident workgroups per CU, the weights / tap table are set up once per workgroup
+  // at most 1024 workgroups, measured: 512 -> 162 us, 768 -> 131, 1024 -> 119, 1280 -> 147, 2048 -> 127, one tile per workgroup -> 193
+  int blocks = NT < 1024 ? NT : 1024;       // 4 resident workgroups per CU, the weights / tap table are set up once per workgroup
   int per = (NT + blocks - 1) / blocks;
   blocks = (NT + per - 1) / per;
   const long so = rx_act_voxels(out) * (long)out->ld;

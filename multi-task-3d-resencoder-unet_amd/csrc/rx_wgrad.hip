@@ -262,12 +262,8 @@ static void wgrad_dispatch(int BR, int BC, dim3 grid, hipStream_t st, const void
   const size_t lds = 65536;
 #define RX_WG(BR_, BC_)                                                                                                            \
   do {                                                                                                                             \
-    static bool attr_set = false;                                                                                                  \
-    if (!attr_set) {                                                                                                               \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BR_, BC_>),                                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                             \
-      attr_set = true;                                                                                                             \
-    }                                                                                                                              \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BR_, BC_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                              (int)lds);                                                                                           \
     hipLaunchKernelGGL((wgrad_kernel<T, BR_, BC_>), grid, dim3(256), lds, st, (const T*)gt, (const T*)xt, slab, g);                \
   } while (0)
   if (BR == 64 && BC == 64)
@@ -332,7 +328,7 @@ extern "C" int rx_conv3d_bwd_weight(rx_dtype dt, const rx_act* x, const rx_act* 
   if (dy->n != x->n || dy->z != conv_out_dim(x->z, kernel[0], stride[0]) || dy->y != conv_out_dim(x->y, kernel[1], stride[1]) ||
       dy->x != conv_out_dim(x->x, kernel[2], stride[2]))
     RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_weight: geometry mismatch");
-  if (kernel[0] == 3 && kernel[1] == 3 && kernel[2] == 3 && ws && dw && !(getenv("RX_NO_STRIDED_WGH") && (stride[0] > 1 || stride[1] > 1 || stride[2] > 1))) {
+  if (kernel[0] == 3 && kernel[1] == 3 && kernel[2] == 3 && ws && dw) {
     int rc = rx_wgrad_halo_try(dt, x, dy, stride, dw, ws, ws_bytes, (hipStream_t)stream);  // LDS-halo kernel (16-bit types), stride 1 or 2
     if (rc < 0) return rc;
     if (rc == 1) return RX_OK;
@@ -499,14 +495,9 @@ static int convT_wgrad_splits(long NQ, size_t slab1) {
 // 1 = handled, 0 = not applicable (fall through to wgrad_kernel), < 0 error
 static int convT_wgrad_try(rx_dtype dt, const rx_act* x, const rx_act* dy, const int32_t stride[3], float* dw, void* ws, size_t ws_bytes,
                            hipStream_t st) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("RX_CONVT_WGRAD");
-    on = e ? atoi(e) : 1;
-  }
   const int taps = stride[0] * stride[1] * stride[2];
   const int R = x->c, C = dy->c;
-  if (!on || dt == RX_F32 || taps > 8 || R % 32 || C % 32 || x->ld % 8 || dy->ld % 8 || ((uintptr_t)x->ptr & 15) || ((uintptr_t)dy->ptr & 15)) return 0;
+  if (dt == RX_F32 || taps > 8 || R % 32 || C % 32 || x->ld % 8 || dy->ld % 8 || ((uintptr_t)x->ptr & 15) || ((uintptr_t)dy->ptr & 15)) return 0;
   const int NR = R / 32, NC = C / 32;
   if (!((NR == 2 && NC == 1) || (NR == 4 && NC == 2) || (NR == 1 && NC == 1) || (NR == 2 && NC == 2))) return 0;
   const long NQ = (long)x->n * rx_act_voxels(x);

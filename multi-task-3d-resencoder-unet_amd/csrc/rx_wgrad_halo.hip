@@ -287,159 +287,12 @@ __device__ __forceinline__ void wgh16_tile_mma(const lds_byte* gb, const lds_byt
 
 #define WGH16_BUF_BYTES ((256 + WGH16_HV) * 64)   // one (dY tile, X halo tile) pair: 57,856 bytes
 
-// One workgroup per CU (the pipelined loop wants ~370 registers per lane).  Measured and rejected: a second LDS tile buffer
-// (one barrier per tile) and issuing the next tile's loads piecewise between the MFMAs -- 4-14 % slower in isolation, and
-// a 115 KB workgroup no longer shares a CU with the main stream's convolutions (+1.2 ms per cfg2 step).
-template <typename T>
-__global__ __launch_bounds__(256, 1) void wgrad_halo16_kernel(const T* __restrict__ gt, const T* __restrict__ xt, float* __restrict__ slab,
-                                                              float* __restrict__ dw, const WgHaloGeom g) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // sG [256][32], sX [648][32]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int PPn = gridDim.x, lid = rx_xcd_remap(blockIdx.y * PPn + blockIdx.x, PPn * gridDim.y);
-  const int split = lid / PPn, pp = lid - split * PPn;
-  const int pr = pp / g.panels_c, pc = pp - pr * g.panels_c;
-  const int r0 = pr * 32, c0 = pc * 32;
-  const long xc0 = g.x_cs ? (long)pc * g.x_cs : (long)c0;      // where this panel's 32 input channels start
-  const int t_begin = split * g.tiles_per_split;
-  const int t_end = min(g.NT, t_begin + g.tiles_per_split);
-
-  const int chunk = tid & 3;
-  int xh[WGH16_XPIECES];                                     // packed halo coordinates (hz<<16 | hy<<8 | hx), -1 = none
-#pragma unroll
-  for (int p = 0; p < WGH16_XPIECES; ++p) {
-    const int row = (tid >> 2) + 64 * p;
-    const int hx = row % WGH16_HX, t = row / WGH16_HX;
-    xh[p] = row < WGH16_HV ? ((t / WGH16_HY) << 16) | ((t % WGH16_HY) << 8) | hx : -1;
-  }
-  const int g16 = lane >> 4, half = g16 & 1, h = g16 >> 1, l15 = lane & 15, q4 = l15 >> 2, p4 = l15 & 3;
-  const int lane_off = ((8 * h + q4) * 32 + 16 * half + 4 * p4) * 2;   // bytes: row 8h+q4, this lane's 4-channel column group
-
-  f32x16 acc[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-  // ---- staging: 15 sixteen-byte pieces per thread and tile (4 of dY, 11 of the X halo)
-  u32x4 gv[4], xv[WGH16_XPIECES];
-  int s_z0 = 0, s_y0 = 0, s_x0 = 0;
-  const T* s_gn = gt;
-  const T* s_xn = xt;
-  auto set_tile = [&](int tile) {       // wave-uniform decode of the tile being staged
-    int tx, ty, tz, n;
-    rx_tile_coords(tile, g.tx_n, g.ty_n, g.tz_n, g.order, n, tz, ty, tx);
-    s_z0 = tz * 4, s_y0 = ty * 4, s_x0 = tx * 16;
-    s_gn = gt + n * g.g_ss + r0 + chunk * 8;
-    s_xn = xt + n * g.x_ss + xc0 + chunk * 8;
-  };
-  auto issue_piece = [&](int p) {       // p in [0, 15); p is a compile-time constant at every call site
-    if (p < 4) {
-      const int v = (tid >> 2) + 64 * p;
-      const int z = s_z0 + (v >> 6), y = s_y0 + ((v >> 4) & 3), x = s_x0 + (v & 15);
-      u32x4 val = u32x4{0u, 0u, 0u, 0u};
-      if (z < g.Z && y < g.Y && x < g.X) val = *reinterpret_cast<const u32x4*>(s_gn + ((long)(z * g.Y + y) * g.X + x) * g.ldg);
-      gv[p] = val;
-    } else {
-      const int q = p - 4;
-      u32x4 val = u32x4{0u, 0u, 0u, 0u};
-      if (xh[q] >= 0) {
-        const int z = s_z0 + (xh[q] >> 16) - 1, y = s_y0 + ((xh[q] >> 8) & 255) - 1, x = s_x0 + (xh[q] & 255) - 1;
-        if ((unsigned)z < (unsigned)g.Z && (unsigned)y < (unsigned)g.Y && (unsigned)x < (unsigned)g.X)
-          val = *reinterpret_cast<const u32x4*>(s_xn + ((long)(z * g.Y + y) * g.X + x) * g.ldx);
-      }
-      xv[q] = val;
-    }
-  };
-  auto commit = [&](int buf) {          // staged registers -> LDS buffer `buf`
-    T* sG = reinterpret_cast<T*>(smem + buf * WGH16_BUF_BYTES);
-    T* sX = sG + 256 * 32;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) *reinterpret_cast<u32x4*>(sG + ((tid >> 2) + 64 * p) * 32 + chunk * 8) = gv[p];
-#pragma unroll
-    for (int p = 0; p < WGH16_XPIECES; ++p)
-      if (xh[p] >= 0) *reinterpret_cast<u32x4*>(sX + ((tid >> 2) + 64 * p) * 32 + chunk * 8) = xv[p];
-  };
-
-  if (t_begin < t_end) {
-    set_tile(t_begin);
-#pragma unroll
-    for (int p = 0; p < 15; ++p) issue_piece(p);
-  }
-  const lds_byte* gb = (const lds_byte*)(smem) + lane_off;
-  const lds_byte* xb = gb + 256 * 64;
-  auto stage = [](int) {};
-  // The WHOLE tile loop sits inside the per-wave arm: with the switch inside the loop the accumulators crossed a phi
-  // at every iteration and were copied AGPR <-> VGPR once per tile (112 v_accvgpr moves = 1 VALU op per MFMA).
-  auto run = [&](auto wc) {
-    constexpr int W = decltype(wc)::value;
-    for (int tile = t_begin; tile < t_end; ++tile) {
-      if (!RX_ABLATE(g, 1) || tile == t_begin) {
-        __syncthreads();          // every wave is done reading the previous tile
-        commit(0);
-        __syncthreads();
-        if (tile + 1 < t_end) {   // the next tile's loads stay in flight (in registers) behind this tile's MFMAs
-          set_tile(tile + 1);
-#pragma unroll
-          for (int p = 0; p < 15; ++p) issue_piece(p);
-        }
-      }
-      if (!RX_ABLATE(g, 2)) wgh16_tile_mma<T, W>(gb, xb, acc, stage);
-    }
-  };
-  switch (wave) {   // scalar branch: the tap set of a wave is a compile-time constant inside each arm
-    case 0: run(std::integral_constant<int, 0>{}); break;
-    case 1: run(std::integral_constant<int, 1>{}); break;
-    case 2: run(std::integral_constant<int, 2>{}); break;
-    default: run(std::integral_constant<int, 3>{}); break;
-  }
-
-  const int col = lane & 31, fh = lane >> 5;
-  if (g.S == 1) {   // single split: transpose through LDS, contiguous runs of dw (see the generic kernel)
-    float* sT = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        const int t = wave + 4 * j;
-        if (t < 27) {
-#pragma unroll
-          for (int r = 8 * hb; r < 8 * hb + 8; ++r) {
-            const int lr = (r & 3) + 8 * ((r >> 2) & 1) + 4 * fh;
-            sT[(lr * 32 + col) * 27 + t] = acc[j][r];
-          }
-        }
-      }
-      __syncthreads();
-      for (int idx = tid; idx < 16 * 216; idx += 256) {
-        const int lr = idx / 216, i = idx - lr * 216;
-        *reinterpret_cast<f32x4*>(dw + ((long)(r0 + 16 * hb + lr) * g.Cc + c0) * 27 + 4 * i) = *reinterpret_cast<const f32x4*>(sT + 4 * idx);
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    const int t = wave + 4 * j;
-    if (t < 27) {
-      float* out = slab + (((long)split * 27 + t) * g.R + r0) * g.Cc + c0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * fh;
-        out[(long)row * g.Cc + col] = acc[j][r];
-      }
-    }
-  }
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Wave-specialised variant of the 4x4x16 kernel: 512 threads = 4 CONSUMER waves (the MFMA loop above, 7 taps each, no
-// staging registers) + 4 PRODUCER waves (global -> registers -> LDS for the next tile), one of each per SIMD, over two
-// LDS tile buffers and ONE barrier per tile.  Ablation of the 256-thread kernel: MFMA loop alone 221 us, staging alone
-// 193 us, together 343 us (32->32 @128^3): in a single instruction stream the two only overlap by the load latency.
+// The 4x4x16 kernel is wave-specialised: 512 threads = 4 CONSUMER waves (the MFMA loop above, 7 taps each, no staging
+// registers) + 4 PRODUCER waves (global -> registers -> LDS for the next tile), one of each per SIMD, over two LDS tile
+// buffers and ONE barrier per tile.  Ablation of the retired 256-thread kernel that staged and multiplied in the same waves:
+// MFMA loop alone 221 us, staging alone 193 us, together 343 us (32->32 @128^3): in a single instruction stream the two only
+// overlap by the load latency.
 // Here the producers' address arithmetic, load waits and ds_writes run beside the consumers' MFMAs.
 // ---------------------------------------------------------------------------------------------------------------------
 // DMA = true: the producers move both tiles global -> LDS with buffer_load_dwordx4 ... lds (1 KiB per wave-instruction,
@@ -677,16 +530,8 @@ static int wgh_plan(const rx_act* x, const rx_act* dy, const int32_t stride[3], 
   const long PP = (long)(g->R / 32) * g->panels_c;
   // the wave-specialised 4x4x16 kernel runs ONE workgroup per CU: 256 workgroups are one full wave of the chip (half the
   // slab traffic and reduce work of 512); the generic kernel runs two per CU
-  long target = (!strided && TZ == 4 && TY == 4 && TX == 16 && !getenv("RX_WGH_S512")) ? 256 : 512;
+  long target = (!strided && TZ == 4 && TY == 4 && TX == 16) ? 256 : 512;
   if (target == 256 && g->NT * PP < 16 * 256) target = 512;   // few tiles (16^3 layers): shorter per-workgroup chains win
-  {
-    static long tgt_env = -1;   // RX_WGH_TARGET: workgroups aimed at by the split choice of the generic-tile kernel (experiments)
-    if (tgt_env < 0) {
-      const char* e = getenv("RX_WGH_TARGET");
-      tgt_env = e ? atol(e) : 0;
-    }
-    if (tgt_env > 0 && target == 512) target = tgt_env;
-  }
   long S = (target + PP - 1) / PP;
   if (PP >= 256) S = 1;  // the panel pairs alone fill the chip: accumulate every tile in registers, write dw directly
   if (S > g->NT) S = g->NT;
@@ -717,52 +562,27 @@ int rx_wgrad_halo_try(rx_dtype dt, const rx_act* x, const rx_act* dy, const int3
   if (!wgh_plan(x, dy, stride, &g, ws_bytes)) return 0;
   const size_t lds = (size_t)(RX_WGH_MAX_VT + RX_WGH_MAX_HV) * 64;
   dim3 grid((g.R / 32) * g.panels_c, g.S);
-  {
-    static int dbg = -1;
-    if (dbg < 0) {
-      const char* e = getenv("RX_DBG");
-      dbg = e ? atoi(e) : 0;
-    }
-    g.dbg = dbg;
-    static int order = -1;   // RX_TILE_ORDER: 0 raster, 1 (default) z-fastest walk of each split's tile range (rx_tile_coords)
-    if (order < 0) {
-      const char* e = getenv("RX_TILE_ORDER");
-      order = e ? atoi(e) : 1;
-    }
-    g.order = order;
-  }
+  static const int dbg = rx_env_mask("RX_DBG");
+  g.dbg = dbg;
+  g.order = 1;   // z-fastest walk of each split's tile range (rx_tile_coords)
   if (g.TZ == 4 && g.TY == 4 && g.TX == 16 && g.sz == 1 && g.sy == 1 && g.sx == 1) {   // compile-time tile
     const size_t lds16 = (size_t)WGH16_BUF_BYTES;
-    static bool attr16 = false;
-    static int ws_mode = 1, dma_mode = 1;
-    if (!attr16) {
-      const char* e = getenv("RX_WGH_WS");
-      ws_mode = e ? atoi(e) : 1;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<bf16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<f16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
-      const char* ed = getenv("RX_WGH_DMA");
-      dma_mode = ed ? atoi(ed) : 1;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-      attr16 = true;
-    }
-    rx_note_kernel(ws_mode ? "wgrad_halo16ws_kernel" : "wgrad_halo16_kernel");
-    const bool dma_ok = dma_mode && (long)g.N * g.g_ss * 2 < 0x7fffff00L &&
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<bf16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<f16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
+    rx_note_kernel("wgrad_halo16ws_kernel");
+    // the DMA producers address both tensors through 32-bit buffer offsets; larger tensors take the register-staged producers
+    const bool dma_ok = (long)g.N * g.g_ss * 2 < 0x7fffff00L &&
                         ((long)g.N * g.x_ss + (g.x_cs ? (long)(g.Cc / 32 - 1) * g.x_cs : 0)) * 2 < 0x7fffff00L;
-    if (ws_mode && dma_ok && dt == RX_BF16)
+    if (dma_ok && dt == RX_BF16)
       hipLaunchKernelGGL((wgrad_halo16ws_kernel<bf16_t, true>), grid, dim3(512), 2 * lds16, st, (const bf16_t*)dy->ptr, (const bf16_t*)x->ptr, (float*)ws, dw, g);
-    else if (ws_mode && dma_ok)
+    else if (dma_ok)
       hipLaunchKernelGGL((wgrad_halo16ws_kernel<f16_t, true>), grid, dim3(512), 2 * lds16, st, (const f16_t*)dy->ptr, (const f16_t*)x->ptr, (float*)ws, dw, g);
-    else if (ws_mode && dt == RX_BF16)
-      hipLaunchKernelGGL((wgrad_halo16ws_kernel<bf16_t, false>), grid, dim3(512), 2 * lds16, st, (const bf16_t*)dy->ptr, (const bf16_t*)x->ptr, (float*)ws, dw, g);
-    else if (ws_mode)
-      hipLaunchKernelGGL((wgrad_halo16ws_kernel<f16_t, false>), grid, dim3(512), 2 * lds16, st, (const f16_t*)dy->ptr, (const f16_t*)x->ptr, (float*)ws, dw, g);
     else if (dt == RX_BF16)
-      hipLaunchKernelGGL((wgrad_halo16_kernel<bf16_t>), grid, dim3(256), lds16, st, (const bf16_t*)dy->ptr, (const bf16_t*)x->ptr, (float*)ws, dw, g);
+      hipLaunchKernelGGL((wgrad_halo16ws_kernel<bf16_t, false>), grid, dim3(512), 2 * lds16, st, (const bf16_t*)dy->ptr, (const bf16_t*)x->ptr, (float*)ws, dw, g);
     else
-      hipLaunchKernelGGL((wgrad_halo16_kernel<f16_t>), grid, dim3(256), lds16, st, (const f16_t*)dy->ptr, (const f16_t*)x->ptr, (float*)ws, dw, g);
+      hipLaunchKernelGGL((wgrad_halo16ws_kernel<f16_t, false>), grid, dim3(512), 2 * lds16, st, (const f16_t*)dy->ptr, (const f16_t*)x->ptr, (float*)ws, dw, g);
     if (g.S > 1) rx_wgrad_reduce_launch((const float*)ws, g.S, 27, g.R, g.Cc, dw, st);
     hipError_t e16 = hipGetLastError();
     if (e16 != hipSuccess) {
@@ -773,20 +593,10 @@ int rx_wgrad_halo_try(rx_dtype dt, const rx_act* x, const rx_act* dy, const int3
   }
   rx_note_kernel("wgrad_halo_kernel");
   if (dt == RX_BF16) {
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-      attr = true;
-    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((wgrad_halo_kernel<bf16_t>), grid, dim3(256), lds, st, (const bf16_t*)dy->ptr, (const bf16_t*)x->ptr, (float*)ws, dw, g);
   } else {
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-      attr = true;
-    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((wgrad_halo_kernel<f16_t>), grid, dim3(256), lds, st, (const f16_t*)dy->ptr, (const f16_t*)x->ptr, (float*)ws, dw, g);
   }
   if (g.S > 1) rx_wgrad_reduce_launch((const float*)ws, g.S, 27, g.R, g.Cc, dw, st);

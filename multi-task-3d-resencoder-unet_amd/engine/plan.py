@@ -127,8 +127,8 @@ class Plan:
         import os
         # weight gradients on a side HIP stream (off the dependency chain); RX_OVERLAP_WGRAD=0 keeps one stream
         self.overlap_wgrad = os.environ.get("RX_OVERLAP_WGRAD", "1") != "0"
-        # dy slots per shape (RX_DY_RING): with 2 the main stream stalls whenever the side stream is more than one layer behind
-        self.dy_ring = max(2, int(os.environ.get("RX_DY_RING", "4")))
+        # dy slots per shape: with 2 the main stream stalls whenever the side stream is more than one layer behind
+        self.dy_ring = 4
         self._side = None
         self._ws2 = None
         self._dy_turn: Dict[tuple, int] = {}
@@ -639,22 +639,21 @@ class Plan:
                     rec.a["stats_to"] = nxt.a
                     nxt.a["stats_done"] = True
                 if (rec.kind == "stem" and nxt.kind == "inact" and nxt.a["y"] is rec.a["y"] and self.dtype != torch.float32
-                        and rec.a["y"].act.voxels > 512 and os.environ.get("RX_FUSED_STEM_STATS", "1") != "0"):      # rx_stem_conv_fwd_stats
+                        and rec.a["y"].act.voxels > 512):      # rx_stem_conv_fwd_stats
                     rec.a["stats_to"] = nxt.a
                     nxt.a["stats_done"] = True
             # block output -> AvgPool of the next block's skip path: one pass (rx_instnorm_act_pool_fwd) above the size the
             # single-launch InstanceNorm kernel takes
             producers = {id(r.a["out"]): r for r in tape if r.kind == "inact" and r.a["gate"] is None}
             for rec in tape:
-                if (rec.kind == "pool" and id(rec.a["x"]) in producers and rec.a["x"].act.voxels > 512
-                        and os.environ.get("RX_FUSED_POOL", "1") != "0"):
+                if rec.kind == "pool" and id(rec.a["x"]) in producers and rec.a["x"].act.voxels > 512:
                     src = producers[id(rec.a["x"])]
                     if "pool_to" not in src.a:
                         src.a["pool_to"] = rec.a
                         rec.a["fused"] = True
             # the layer under a task head: InstanceNorm apply + LeakyReLU + the head's 1x1x1 conv in one pass (the activated
             # output is written for the backward but not re-read by a separate head kernel)
-            if self.dtype != torch.float32 and os.environ.get("RX_FUSED_HEAD_FWD", "1") != "0":
+            if self.dtype != torch.float32:
                 for rec in tape:
                     if rec.kind != "head" or rec.a["k"] > 4:
                         continue
@@ -897,7 +896,7 @@ class Plan:
                     # the layer under a task head (no residual): its output gradient is rank K -- rebuilt from the logit gradient
                     # inside both InstanceNorm passes instead of written by the head and read back twice
                     if (gw[0] == "head" and a["gate"] is None and res is None and self.dtype != torch.float32
-                            and out.act.voxels > 512 and os.environ.get("RX_FUSED_HEAD_BWD", "1") != "0"):
+                            and out.act.voxels > 512):
                         heads = [r.a for r in tape if r.kind == "head" and r.a["x"] is out]
                         if len(heads) == 1 and heads[0]["k"] <= 4:
                             a["head_src"] = heads[0]
@@ -905,13 +904,12 @@ class Plan:
                             # ... and the head's own dw / db from the same reduce pass (the activation is recomputed from y): no
                             # head_bwd launch, and the forward does not store this layer's activated output at all.  Needs the
                             # forward's fused head (the un-fused head kernel reads the stored output) and an un-padded head weight.
-                            if (heads[0].get("fwd_fused") and heads[0]["w"] is self.params[heads[0]["widx"]]
-                                    and os.environ.get("RX_FUSED_HEAD_DW", "1") != "0"):
+                            if heads[0].get("fwd_fused") and heads[0]["w"] is self.params[heads[0]["widx"]]:
                                 a["head_dw_fused"] = True
                                 gw[1]["dw_fused"] = True
                     if (gw[0] == "conv" and a["gate"] is None and res is None and self.dtype != torch.float32
                             and out.act.full_buffer and out.act.root is None and out.act.c % 32 == 0 and out.act.voxels > 512
-                            and out.act.dims[3] >= 16 and os.environ.get("RX_FUSED_BWD_STATS", "1") != "0"):
+                            and out.act.dims[3] >= 16):
                         a["m12"] = torch.empty((self.B, out.act.c, 2), dtype=torch.float32, device=self.device)
                         a["m12_valid"] = False
                         gw[1]["inact"] = a          # that conv's backward-data step now also fills a["m12"]
@@ -944,8 +942,7 @@ class Plan:
                     # added on the fly and that pass (1R 1W over the full-resolution gradient) is gone too
                     pend = getattr(out, "_pool_pending", None)
                     out._pool_pending = None
-                    fuse_res = (gres is not None and not acc and res is not None and y.act.voxels > 512
-                                and os.environ.get("RX_FUSED_RES_BWD", "1") != "0")
+                    fuse_res = gres is not None and not acc and res is not None and y.act.voxels > 512
                     if pend is not None and not fuse_res:        # the deferred pool gradient runs as its own pass after all
                         b.append(lambda pend=pend: ops.avgpool_bwd(pend["gy"], pend["gx"], pend["stride"], True))
                         pend = None
@@ -1062,7 +1059,7 @@ class Plan:
                     ti = next(i for i, r in enumerate(tape) if r is rec)
                     prev = tape[ti - 1] if ti > 0 else None
                     if (acc and prev is not None and prev.kind == "inact" and prev.a["out"] is x and prev.a["res"] is not None
-                            and prev.a["gate"] is None and x.act.voxels > 512 and os.environ.get("RX_FUSED_POOL_BWD", "1") != "0"):
+                            and prev.a["gate"] is None and x.act.voxels > 512):
                         x._pool_pending = dict(gy=y.gact, gx=gx, stride=a["stride"])
                         continue
                     b.append(lambda a=a, gy=y.gact, gx=gx, acc=acc: ops.avgpool_bwd(gy, gx, a["stride"], acc))
@@ -1142,10 +1139,10 @@ class Plan:
 
     def _pack_entries(self, entries, side, defer=False):
         """re-pack `entries` (in first-use order) on `side` (or the current stream).  Table launches (rx_pack_multi, 40 tensors
-        each) in GROUPS of ~RX_PACK_GROUP_MB of parameters with one numbered event per group: the first convs of the forward
+        each) in GROUPS of ~96 MB of parameters with one numbered event per group: the first convs of the forward
         wait for the first (small) group only, the 512-channel stages' packing runs under the stages before them.  Was: one
         launch + one event per tensor, 66 launches of 17 us on average per cfg2 step."""
-        limit = int(float(os.environ.get("RX_PACK_GROUP_MB", "96")) * (1 << 20))
+        limit = 96 << 20
         groups, cur, cur_bytes = [], [], 0
         for ent in entries:
             nb = ent["param"].numel() * 4
@@ -1156,12 +1153,11 @@ class Plan:
             cur_bytes += nb
         if cur:
             groups.append(cur)
-        # RX_PACK_DELAY (default on): only the first group is packed now; the others (the 512-channel stages: 80 % of the bytes) are
+        # Only the first group is packed now; the others (the 512-channel stages: 80 % of the bytes) are
         # issued from inside the forward list, behind the full-resolution stage (see _forward_body) -- the packing then competes
         # with the 64^3 / 32^3 convolutions instead of the HBM-bound full-resolution InstanceNorm passes
         self._pack_deferred = None
-        if (defer and side is not None and len(groups) > 1 and self._pack_delay_at is not None
-                and os.environ.get("RX_PACK_DELAY", "1") != "0"):
+        if defer and side is not None and len(groups) > 1 and self._pack_delay_at is not None:
             self._pack_deferred = (groups[1:], side)
             for grp in groups[1:]:
                 for ent in grp:

@@ -15,7 +15,6 @@ Arithmetic is fp32 like torch's fused kernel; results agree with `torch.optim.Ad
 (tests/test_optim_gpu.py), not bit for bit (different FMA contraction).  CPU parameters are refused: this optimizer only
 exists for the engine."""
 import ctypes
-import os
 from ctypes import c_void_p
 
 import torch
@@ -43,7 +42,7 @@ class EngineAdamW(torch.optim.Optimizer):
         grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
         if not grads:
             return torch.zeros(())
-        if (float(norm_type) == 2.0 and os.environ.get("RX_ENGINE_GRAD_NORM", "1") != "0"
+        if (float(norm_type) == 2.0
                 and all(g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() for g in grads)):
             # two launches (table kernel + one-workgroup finalize) instead of torch's ~20: norm AND coefficient on the device
             n = len(grads)
