@@ -11,7 +11,9 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from test_ops_gpu import TOL, last_kernel, out_dim, rel, rnd, to_act
+from exact_ops import U32, assert_bits, assert_within, half_ulp, poisoned
+from test_ops_gpu import (TOL, check_norm_bwd, check_norm_fwd, check_stats, exact_conv_pass, exact_conv_ref, exact_convT_pass,
+                          last_kernel, lrelu_mask, nan_act, norm_bwd_ref, out_dim, rel, rnd, to_act)
 
 
 @pytest.fixture(scope="module")
@@ -59,7 +61,7 @@ def test_random_conv3d(ops, dtype, i):
     y_ref.backward(gy)
     xa = to_act(ops, x, dtype, ld=ci + c0, c0=c0)
     w_fwd, w_bwd = ops.pack_conv_weight(w.float().cuda(), dtype)
-    ya = ops.Act.zeros(n, *odims, co, dtype)
+    ya = nan_act(n, odims, co, dtype)
     ops.conv3d_fwd(xa, w_fwd, b.float().cuda() if with_bias else None, ya, k, s)
     kf = last_kernel(ops)
     assert rel(ya.to_ncdhw(), y_ref.detach()) < TOL[dtype], ("fwd", kf, ci, co, dims, k, s, n)
@@ -69,16 +71,25 @@ def test_random_conv3d(ops, dtype, i):
     ops.conv3d_bwd_data(gya, w_bwd, dxa, k, s, accumulate=True)
     kd = last_kernel(ops)
     assert rel(dxa.to_ncdhw(), base + xr.grad) < 2 * TOL[dtype], ("dgrad+", kd, ci, co, dims, k, s, n)
+    dxa = nan_act(n, dims, ci, dtype)
     ops.conv3d_bwd_data(gya, w_bwd, dxa, k, s, accumulate=False)
     assert rel(dxa.to_ncdhw(), xr.grad) < TOL[dtype], ("dgrad", kd, ci, co, dims, k, s, n)
     dw = torch.full((co, ci, *k), float("nan"), dtype=torch.float32, device="cuda")
     ops.conv3d_bwd_weight(xa, gya, dw, k, s)
     kw = last_kernel(ops)
-    assert rel(dw, wr.grad) < TOL[dtype], ("wgrad", kw, ci, co, dims, k, s, n)
+    assert rel(dw, wr.grad) < TOL[torch.float32], ("wgrad", kw, ci, co, dims, k, s, n)     # fp32 sums of exact products
     if with_bias:
-        db = torch.full((co,), float("nan"), device="cuda")
+        db = poisoned((co,))
         ops.channel_sum(gya, db)
-        assert rel(db, gy.sum((0, 2, 3, 4))) < 1e-4
+        assert rel(db, gy.sum((0, 2, 3, 4))) < 1e-5
+    # the same draw on exact integer data, on the same kernels
+    r = exact_conv_ref(("rconv", i), ci, co, dims, k, s, n, with_bias)
+    seen = exact_conv_pass(ops, dtype, r, k, s, c0)
+    assert (seen["fwd"], seen["dgrad+"], seen["wgrad"]) == (kf, kd, kw), (seen, kf, kd, kw)
+    if with_bias:
+        db = poisoned((co,))
+        ops.channel_sum(to_act(ops, r["gy"], dtype), db)
+        assert_bits(db, r["gy"].sum((0, 2, 3, 4)), torch.float32, "db", names=("c",))
 
 
 def convT_draws(n=16):
@@ -110,17 +121,23 @@ def test_random_convT3d(ops, dtype, i):
     xa = to_act(ops, x, dtype)
     w_fwd, w_bwd = ops.pack_convT_weight(w.float().cuda(), dtype)
     ya = to_act(ops, torch.zeros((n, 2 * co, *od), dtype=torch.float64), dtype)        # written into the first half of a concat
+    ya.t[..., :co] = float("nan")
     up = ops.Act(ya.t, 0, co)
     ops.convT3d_fwd(xa, w_fwd, b.float().cuda() if with_bias else None, up, s)
+    kf = last_kernel(ops)
     assert rel(up.to_ncdhw(), y_ref.detach()) < TOL[dtype], ("fwd", ci, co, dims, s, n)
     assert (ya.t[..., co:] == 0).all()                                                  # the other half is untouched
     gya = to_act(ops, gy, dtype)
-    dxa = ops.Act.zeros(n, *dims, ci, dtype)
+    dxa = nan_act(n, dims, ci, dtype)
     ops.convT3d_bwd_data(gya, w_bwd, dxa, s)
     assert rel(dxa.to_ncdhw(), xr.grad) < TOL[dtype], ("dgrad", ci, co, dims, s, n)
     dw = torch.full(tuple(w.shape), float("nan"), dtype=torch.float32, device="cuda")
     ops.convT3d_bwd_weight(xa, gya, dw, s)
-    assert rel(dw, wr.grad) < TOL[dtype], ("wgrad", ci, co, dims, s, n)
+    kw = last_kernel(ops)
+    assert rel(dw, wr.grad) < TOL[torch.float32], ("wgrad", ci, co, dims, s, n)         # fp32 sums of exact products
+    r = exact_conv_ref(("rconvT", i), ci, co, dims, None, s, n, with_bias, transposed=True)
+    seen = exact_convT_pass(ops, dtype, r, s)
+    assert (seen["fwd"], seen["wgrad"]) == (kf, kw), (seen, kf, kw)
 
 
 def norm_draws(n=24):
@@ -145,19 +162,26 @@ def test_random_instnorm_act(ops, dtype, i):
     ref = F.leaky_relu(z, slope) if slope != 1.0 else z
     ref.backward(g)
     ya, ra, ga = to_act(ops, y, dtype), to_act(ops, r, dtype), to_act(ops, g, dtype)
-    out = ops.Act.empty(n, *dims, c, dtype)
-    stats = torch.empty((n, c, 2), device="cuda")
+    out = nan_act(n, dims, c, dtype)
+    stats = poisoned((n, c, 2))
     ops.instnorm_fwd(ya, stats, out, slope, ra if with_res else None)
     assert rel(out.to_ncdhw(), ref.detach()) < TOL[dtype], ("fwd", c, dims, n, with_res, slope)
-    dy = ops.Act.empty(n, *dims, c, dtype)
+    check_stats(stats, y)
+    check_norm_fwd(out, y, stats, r if with_res else None, slope, dtype, f"fwd {(c, dims, n, with_res, slope)}")
+    dy = nan_act(n, dims, c, dtype)
     rbase = rnd((n, c, *dims), dtype, 24 + i, scale=0.2)
     dres = to_act(ops, rbase, dtype) if with_res else None
     # mask from the saved output for residual layers, from the sign of xhat otherwise (out = None)
     ops.instnorm_act_bwd(ga, ya, stats, out if (with_res and slope != 1.0) else None, dy, slope, dres, acc_res and with_res)
     assert rel(dy.to_ncdhw(), yr.grad) < 6 * TOL[dtype], ("bwd", c, dims, n, with_res, slope, rel(dy.to_ncdhw(), yr.grad))
+    mask = lrelu_mask(out if (with_res and slope != 1.0) else None, y, stats, slope)
+    check_norm_bwd(dy, g, y, stats, mask, slope, dtype, f"bwd {(c, dims, n, with_res, slope)}")
     if with_res:
         want = rr.grad + (rbase if acc_res else 0)
         assert rel(dres.to_ncdhw(), want) < 3 * TOL[dtype], ("dres", c, dims, n)
+        gp = norm_bwd_ref(g, y, stats, mask, slope)[2] + (rbase if acc_res else 0)      # g' (+ the old value): one or two roundings
+        e = 2 * U32 * g.abs() + U32 * gp.abs()
+        assert_within(dres.to_ncdhw(), gp, e + half_ulp(gp.abs() + e, dtype), "dres")
 
 
 # ---- fused entry points == their unfused sequences, at random extents around the sizes where the dispatch changes --------------
@@ -182,13 +206,15 @@ def test_random_fused_conv_norm_entry_points(ops, dtype, i):
     x = to_act(ops, rnd((n, c, *dims), dtype, seed=31 + i), dtype)
     w = rnd((c, c, 3, 3, 3), torch.float32, seed=32 + i, scale=(27 * c) ** -0.5).float().cuda()
     wf, wb = ops.pack_conv_weight(w, dtype)
-    y1, y2 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
-    s1, s2 = torch.empty((n, c, 2), device="cuda"), torch.empty((n, c, 2), device="cuda")
+    y1, y2 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
+    s1, s2 = poisoned((n, c, 2)), poisoned((n, c, 2))
     ops.conv3d_fwd(x, wf, None, y1, k, s)
     ops.instnorm_stats(y1, s1)
     ops.conv3d_fwd_stats(x, wf, None, y2, k, s, s2)
     assert torch.equal(y1.t, y2.t), (c, dims, n, last_kernel(ops))
     assert torch.allclose(s1, s2, rtol=5e-5, atol=5e-6), ((s1 - s2).abs().max().item(), c, dims, n)
+    for st in (s1, s2):
+        check_stats(st, y1, what=f"stats {(c, dims, n)}")
     # data gradient with the InstanceNorm-backward sums of the layer that produced x
     g = to_act(ops, rnd((n, c, *dims), dtype, seed=33 + i, scale=0.2), dtype)
     base = rnd((n, c, *dims), dtype, seed=34 + i, scale=0.1)
@@ -197,18 +223,23 @@ def test_random_fused_conv_norm_entry_points(ops, dtype, i):
     ops.conv3d_bwd_data(g, wb, dx1, k, s, acc)
     fused = ops.conv3d_bwd_data_instats(g, wb, dx2, k, s, acc, y1, s1, slope, m12)
     assert torch.equal(dx1.t, dx2.t), (c, dims, n, acc)
-    d1, d2 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
+    d1, d2 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
     ops.instnorm_act_bwd(dx1, y1, s1, None, d1, slope)
+    mask = lrelu_mask(None, y1, s1, slope)
+    check_norm_bwd(d1, dx1, y1, s1, mask, slope, dtype, f"dy {(c, dims, n, slope)}")
     if fused:
         ops.instnorm_act_bwd_apply(dx2, y1, s1, None, d2, m12, slope)
         a_, b_ = d2.tensor().double(), d1.tensor().double()
         assert ((a_ - b_).norm() / b_.norm().clamp_min(1e-30)).item() < 5e-3, (c, dims, n, slope)
+        # the fused sums may read g' before its rounding into the storage type: half an ulp of g more
+        check_norm_bwd(d2, dx1, y1, s1, mask, slope, dtype, f"dy fused {(c, dims, n, slope)}",
+                       d_g=half_ulp(dx1.to_ncdhw().double().cpu().abs(), dtype))
     # block epilogue + pool of the next skip path
     if all(d % 2 == 0 for d in dims):
         res = to_act(ops, rnd((n, c, *dims), dtype, seed=35 + i), dtype)
         pd = tuple(d // 2 for d in dims)
-        o1, o2 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
-        p1, p2 = ops.Act.empty(n, *pd, c, dtype), ops.Act.empty(n, *pd, c, dtype)
+        o1, o2 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
+        p1, p2 = nan_act(n, pd, c, dtype), nan_act(n, pd, c, dtype)
         ops.instnorm_act_fwd(y1, s1, o1, 0.01, res)
         ops.avgpool_fwd(o1, p1, (2, 2, 2))
         ops.instnorm_act_pool_fwd(y1, s1, o2, p2, (2, 2, 2), 0.01, res)

@@ -1,10 +1,20 @@
 """GPU (-m gpu): every C-ABI entry point of librxunet.so against a plain torch CPU fp64 reference
 of the torch primitive it replaces.  fp32 mode must agree to ~1e-5 (exact-fp32 MFMA / VALU);
 bf16/f16 modes are checked against the same reference evaluated on inputs rounded to the storage
-type (tolerance = a few ulps of the 8/11-bit mantissa on the output rounding, stated per test)."""
+type (tolerance = a few ulps of the 8/11-bit mantissa on the output rounding, stated per test).
+Those per-tensor bars are backed by per-element checks (tests/exact_ops.py): the conv-family entry points run a second pass on
+exact integer data whose every output must be round-to-nearest-even of the fp64 reference (fp32 outputs bit for bit), the
+InstanceNorm / pool entry points are held per element to bounds from the fp32 error analysis of their formula, and outputs are
+NaN-poisoned and written between guard channels."""
+import math
+import zlib
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+from exact_ops import (U32, Guarded, assert_bits, assert_exact_precondition, assert_within, exact_tensor, gamma, half_ulp,
+                       poisoned)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +52,133 @@ def to_act(ops, x_ncdhw, dtype, ld=None, c0=0):
 
 def out_dim(i, k, s):
     return (i + 2 * ((k - 1) // 2) - k) // s + 1
+
+
+def nan_act(n, dims, c, dtype):
+    """a NaN-poisoned output activation, for a call that must write every element"""
+    from mt3d_amd.engine.ops import Act
+    return Act(poisoned((n, *dims, c), dtype))
+
+
+# ---- exact pass: integer data (tests/exact_ops.py), one fp64 reference per case shared by the three dtypes ----------------------
+_EXACT = {}
+DW_NAMES = ("co", "ci", "kz", "ky", "kx")
+
+
+def _seed(key):
+    return zlib.crc32(repr(key).encode()) % 100000
+
+
+def int_range(terms):
+    """the widest integer range [-h, h] (h <= 4) whose cheap bound terms * h^2 keeps every fp32 partial sum exact"""
+    h = 4
+    while h > 1 and terms * h * h >= 2 ** 23:
+        h -= 1
+    return h
+
+
+def exact_conv_ref(key, ci, co, dims, k, s, n, with_bias=True, transposed=False):
+    """x (scale 1/4), w (1/8), bias (1/32), dy (1/4) and the old dx of an accumulate (1/32) as integers; y, dx, dw of F.conv3d /
+    F.conv_transpose3d in fp64, with the exactness precondition of every output asserted"""
+    if key in _EXACT:
+        return _EXACT[key]
+    sd = _seed(key)
+    taps = math.prod(k if not transposed else s)
+    pad = [(kk - 1) // 2 for kk in k] if not transposed else [0, 0, 0]
+    G = torch.nn.grad
+    if transposed:
+        odims = tuple(d * ss for d, ss in zip(dims, s))
+        t_fwd, t_dgrad, t_wgrad = ci, co * taps, n * math.prod(dims)
+        wshape = (ci, co, *s)
+        conv = lambda x_, w_: F.conv_transpose3d(x_, w_, stride=s)                                   # noqa: E731
+        dgrad = lambda g_, w_: F.conv3d(g_, w_, stride=s)                                            # noqa: E731
+        wgrad = lambda x_, g_: G.conv3d_weight(g_, wshape, x_, stride=s)                              # noqa: E731
+    else:
+        odims = tuple(out_dim(d, kk, ss) for d, kk, ss in zip(dims, k, s))
+        t_fwd, t_dgrad, t_wgrad = ci * taps, co * taps, n * math.prod(odims)
+        wshape = (co, ci, *k)
+        conv = lambda x_, w_: F.conv3d(x_, w_, stride=s, padding=pad)                               # noqa: E731
+        dgrad = lambda g_, w_: G.conv3d_input((n, ci, *dims), w_, g_, stride=s, padding=pad)          # noqa: E731
+        wgrad = lambda x_, g_: G.conv3d_weight(x_, wshape, g_, stride=s, padding=pad)                 # noqa: E731
+    h = int_range(max(t_fwd, t_dgrad, t_wgrad))
+    x = exact_tensor((n, ci, *dims), sd, -h, h, 0.5, 2.0 ** -2)
+    w = exact_tensor(wshape, sd + 1, -h, h, 0.5, 2.0 ** -3)
+    b = exact_tensor((co,), sd + 2, -16, 16, 1.0, 2.0 ** -5) if with_bias else None
+    gy = exact_tensor((n, co, *odims), sd + 3, -h, h, 0.5, 2.0 ** -2)
+    base = exact_tensor((n, ci, *dims), sd + 4, -h, h, 0.5, 2.0 ** -5)
+    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    y = conv(xr, wr)
+    y.backward(gy)
+    y = y.detach() + (b.view(1, -1, 1, 1, 1) if with_bias else 0)
+    assert tuple(y.shape[2:]) == odims
+    assert_exact_precondition(conv, (x, w), 2.0 ** -5, terms=t_fwd, extra=b, what="y")
+    assert_exact_precondition(dgrad, (gy, w), 2.0 ** -5, terms=t_dgrad, extra=base, what="dx")
+    assert_exact_precondition(wgrad, (x, gy), 2.0 ** -4, terms=t_wgrad, out16=False, what="dw")
+    _EXACT[key] = r = dict(x=x, w=w, b=b, gy=gy, base=base, y=y, dx=xr.grad, dw=wr.grad, odims=odims)
+    return r
+
+
+def exact_conv_pass(ops, dtype, r, k, s, c0):
+    """the conv3d entry points on exact data: y, dx and dx += as round to nearest even of the fp64 reference, dw (fp32) bit for bit;
+    every output NaN-poisoned (accumulate: the old values) between guard channels.  Returns the kernels that ran."""
+    x, w, b, gy = r["x"], r["w"], r["b"], r["gy"]
+    n, ci = x.shape[:2]
+    co = w.shape[0]
+    dims, odims = tuple(x.shape[2:]), r["odims"]
+    seen = {}
+    xa = to_act(ops, x, dtype, ld=ci + c0, c0=c0)
+    w_fwd, w_bwd = ops.pack_conv_weight(w.float().cuda(), dtype)
+    y = Guarded(n, odims, co, dtype)
+    ops.conv3d_fwd(xa, w_fwd, b.float().cuda() if b is not None else None, y.act(ops), k, s)
+    seen["fwd"] = last_kernel(ops)
+    y.check(f"y ({seen['fwd']})")
+    assert_bits(y.ncdhw(), r["y"], dtype, f"y ({seen['fwd']})")
+    gya = to_act(ops, gy, dtype)
+    dx = Guarded(n, dims, ci, dtype)
+    ops.conv3d_bwd_data(gya, w_bwd, dx.act(ops), k, s, accumulate=False)
+    seen["dgrad"] = last_kernel(ops)
+    dx.check(f"dx ({seen['dgrad']})")
+    assert_bits(dx.ncdhw(), r["dx"], dtype, f"dx ({seen['dgrad']})")
+    dxa = Guarded(n, dims, ci, dtype, init_ncdhw=r["base"])
+    ops.conv3d_bwd_data(gya, w_bwd, dxa.act(ops), k, s, accumulate=True)
+    seen["dgrad+"] = last_kernel(ops)
+    dxa.check(f"dx+ ({seen['dgrad+']})")
+    assert_bits(dxa.ncdhw(), r["base"] + r["dx"], dtype, f"dx+ ({seen['dgrad+']})")   # old + new, rounded once
+    dw = poisoned(w.shape)
+    ops.conv3d_bwd_weight(xa, gya, dw, k, s)
+    seen["wgrad"] = last_kernel(ops)
+    assert_bits(dw, r["dw"], torch.float32, f"dw ({seen['wgrad']})", names=DW_NAMES)
+    return seen
+
+
+def exact_convT_pass(ops, dtype, r, s):
+    """the transposed-conv entry points on exact data, `up` written into the first half of a concat between guard channels"""
+    x, w, b, gy = r["x"], r["w"], r["b"], r["gy"]
+    n, ci = x.shape[:2]
+    co = w.shape[1]
+    dims, odims = tuple(x.shape[2:]), r["odims"]
+    seen = {}
+    xa = to_act(ops, x, dtype)
+    w_fwd, w_bwd = ops.pack_convT_weight(w.float().cuda(), dtype)
+    up = Guarded(n, odims, co, dtype)
+    ops.convT3d_fwd(xa, w_fwd, b.float().cuda() if b is not None else None, up.act(ops), s)
+    seen["fwd"] = last_kernel(ops)
+    up.check(f"up ({seen['fwd']})")
+    assert_bits(up.ncdhw(), r["y"], dtype, f"up ({seen['fwd']})")
+    gya = to_act(ops, gy, dtype, ld=2 * co, c0=0)
+    dx = Guarded(n, dims, ci, dtype)
+    ops.convT3d_bwd_data(gya, w_bwd, dx.act(ops), s)
+    dx.check("dx")
+    assert_bits(dx.ncdhw(), r["dx"], dtype, f"dx ({last_kernel(ops)})")
+    dxa = Guarded(n, dims, ci, dtype, init_ncdhw=r["base"])
+    ops.convT3d_bwd_data(gya, w_bwd, dxa.act(ops), s, True)
+    dxa.check("dx+")
+    assert_bits(dxa.ncdhw(), r["base"] + r["dx"], dtype, f"dx+ ({last_kernel(ops)})")
+    dw = poisoned(w.shape)
+    ops.convT3d_bwd_weight(xa, gya, dw, s)
+    seen["wgrad"] = last_kernel(ops)
+    assert_bits(dw, r["dw"], torch.float32, f"dw ({seen['wgrad']})", names=("ci", "co", "kz", "ky", "kx"))
+    return seen
 
 
 CONV_CASES = [
@@ -114,7 +251,7 @@ def test_conv3d_fwd_bwd(ops, dtype, case):
 
     xa = to_act(ops, x, dtype, ld=ci + 32, c0=32)       # read through a channel slice (concat view)
     w_fwd, w_bwd = ops.pack_conv_weight(w.float().cuda(), dtype)
-    ya = ops.Act.zeros(n, *odims, co, dtype)
+    ya = nan_act(n, odims, co, dtype)
     ops.conv3d_fwd(xa, w_fwd, b.float().cuda(), ya, k, s)
     seen["fwd"] = last_kernel(ops)
     assert rel(ya.to_ncdhw(), y_ref.detach()) < TOL[dtype]
@@ -123,20 +260,121 @@ def test_conv3d_fwd_bwd(ops, dtype, case):
     assert rel(ya.to_ncdhw(), (y_ref.detach() - b.view(1, -1, 1, 1, 1))) < TOL[dtype]
 
     gya = to_act(ops, gy, dtype)
-    dxa = ops.Act.zeros(n, *dims, ci, dtype)
+    dxa = nan_act(n, dims, ci, dtype)
     ops.conv3d_bwd_data(gya, w_bwd, dxa, k, s, accumulate=False)
     seen["dgrad"] = last_kernel(ops)
     assert rel(dxa.to_ncdhw(), xr.grad) < TOL[dtype]
     ops.conv3d_bwd_data(gya, w_bwd, dxa, k, s, accumulate=True)      # dx += ...
     assert rel(dxa.to_ncdhw(), 2 * xr.grad) < 2 * TOL[dtype]
 
-    dw = torch.empty((co, ci, *k), dtype=torch.float32, device="cuda")
+    dw = poisoned((co, ci, *k))
     ops.conv3d_bwd_weight(xa, gya, dw, k, s)
     seen["wgrad"] = last_kernel(ops)
-    assert rel(dw, wr.grad) < TOL[dtype]
+    assert rel(dw, wr.grad) < TOL[torch.float32]       # fp32 output of exact products and fp32 sums, in every mode
+    # the same shapes on exact integer data: every output element is pinned, on the same kernels
+    seen_exact = exact_conv_pass(ops, dtype, exact_conv_ref(("conv", case), ci, co, dims, k, s, n), k, s, 32)
     if dtype != torch.float32 and case in EXPECT_KERNELS:
         for which, want in zip(("fwd", "dgrad", "wgrad"), EXPECT_KERNELS[case]):
             assert want is None or seen[which] == want, (case, which, seen)
+    assert {w: seen_exact[w] for w in seen} == seen, (case, seen, seen_exact)      # both passes run the same kernels
+
+
+# ---- per-element bounds for the InstanceNorm kernels (not exact: fp32 statistics, a normalised value, a cancellation) ------------
+def _ncdhw(t):
+    """an Act, a (n, c, z, y, x) tensor or None -> fp64 CPU NCDHW"""
+    if t is None:
+        return None
+    return (t.to_ncdhw() if hasattr(t, "to_ncdhw") else t).detach().double().cpu()
+
+
+def _mr(stats, n, c):
+    st = stats.detach().double().cpu().view(n, c, 2)
+    return st[..., 0].view(n, c, 1, 1, 1), st[..., 1].view(n, c, 1, 1, 1)
+
+
+def check_stats(stats, y, eps=1e-5, what="stats", keep=None):
+    """(mean, rstd) of every (n, c) plane against fp64.  The sums of y and y^2 are fp32 sums of V terms in some order, each within
+    gamma_V of the sum of magnitudes; so |mean - mean64| <= (gamma_V + 4u) mean|y| and the variance errs by at most
+    (gamma_V + 8u) (E[y^2] + 2 |mean| mean|y|), which moves rstd = (var + eps)^-1/2 by at most half that over var + eps, plus 4u.
+    keep: (n, c) 0/1 of a channel dropout -- dropped planes must have rstd exactly 0."""
+    y = _ncdhw(y)
+    n, c = y.shape[:2]
+    V = y[0, 0].numel()
+    mean_d, rstd_d = _mr(stats, n, c)
+    mean, var = y.mean((2, 3, 4), keepdim=True), y.var((2, 3, 4), unbiased=False, keepdim=True)
+    rstd = (var + eps).rsqrt()
+    am, a2 = y.abs().mean((2, 3, 4), keepdim=True), (y * y).mean((2, 3, 4), keepdim=True)
+    names = ("n", "c", "_", "_", "_")
+    assert_within(mean_d, mean, (gamma(V) + 4 * U32) * am + 1e-30, f"{what}: mean", names=names)
+    b_r = rstd * ((gamma(V) + 8 * U32) * (a2 + 2 * mean.abs() * am) / (2 * (var + eps)) + 4 * U32)
+    if keep is not None:
+        k = keep.double().cpu().view(n, c, 1, 1, 1)
+        assert (rstd_d[k == 0] == 0).all(), f"{what}: a dropped plane has rstd != 0"
+        rstd_d = torch.where(k == 0, rstd, rstd_d)
+    assert_within(rstd_d, rstd, b_r, f"{what}: rstd", names=names)
+
+
+def check_norm_fwd(got, y, stats, res, slope, dtype, what="norm fwd"):
+    """out = lrelu((y - mean) * rstd + res), per element, given the device statistics (check_stats bounds them on their own).  In
+    fp32 the subtraction, the product, the residual add, the slope (fl(slope)) and its product make at most 5 roundings of u
+    relative to |y - mean| * rstd + |res|; then one rounding into the storage type (half an ulp).  A pre-activation strictly
+    within that fp32 bound of 0 may take either LeakyReLU branch: those elements are exempt, and at most 0.1 % of the tensor may
+    be (a pre-activation of exactly 0 with a zero bound -- a dropped plane -- is 0 on both)."""
+    y, res = _ncdhw(y), _ncdhw(res)
+    mean, rstd = _mr(stats, *y.shape[:2])
+    t = (y - mean) * rstd
+    pre = t + (res if res is not None else 0)
+    e32 = 5 * U32 * (t.abs() + (res.abs() if res is not None else 0))
+    ref = pre if slope == 1.0 else torch.where(pre > 0, pre, pre * slope)
+    exempt = (pre.abs() < e32) if slope != 1.0 else None
+    assert_within(_ncdhw(got), ref, e32 + half_ulp(ref.abs() + e32, dtype), what, exempt=exempt)
+
+
+def norm_bwd_ref(g, y, stats, mask, slope):
+    """fp64 dy = rstd (g' - mean g' - xhat mean(g' xhat)), g' = g * (mask ? 1 : slope), from the device statistics; with the bound
+    of its fp32 evaluation.  The two means are fp32 sums of V terms (gamma_V of the sums of magnitudes, plus 6u for g' = g *
+    fl(slope), xhat, the product and the division by V); per element, g' (2u), xhat (2u), xhat * mean(g' xhat), the two
+    subtractions and the product by rstd add 8u of the magnitude terms |g'| + |mean g'| + |xhat| |mean(g' xhat)| (scaled by rstd;
+    not by the result, which cancels)."""
+    g, y = _ncdhw(g), _ncdhw(y)
+    n, c = y.shape[:2]
+    V = y[0, 0].numel()
+    mean, rstd = _mr(stats, n, c)
+    xh = (y - mean) * rstd
+    gp = g if mask is None else torch.where(mask, g, g * slope)
+    m1 = gp.mean((2, 3, 4), keepdim=True)
+    m2 = (gp * xh).mean((2, 3, 4), keepdim=True)
+    ref = rstd * (gp - m1 - xh * m2)
+    s1, s2 = gp.abs().mean((2, 3, 4), keepdim=True), (gp * xh).abs().mean((2, 3, 4), keepdim=True)
+    e32 = rstd * ((gamma(V) + 6 * U32) * (s1 + xh.abs() * s2) + 8 * U32 * (gp.abs() + m1.abs() + xh.abs() * m2.abs()))
+    return ref, e32, gp
+
+
+def check_norm_bwd(got, g, y, stats, mask, slope, dtype, what="norm bwd", d_g=None):
+    """per element within norm_bwd_ref's fp32 bound plus half an ulp of the storage type (got: one output or a tuple of them, all
+    of the same reference).  d_g: a per-element bound on the error of g itself (a gradient the kernel forms on the fly), carried
+    through rstd (g' - mean g' - xhat mean(g' xhat))"""
+    ref, e32, _ = norm_bwd_ref(g, y, stats, mask, slope)
+    if d_g is not None:
+        yd = _ncdhw(y)
+        mean, rstd = _mr(stats, *yd.shape[:2])
+        xa = ((yd - mean) * rstd).abs()
+        e32 = e32 + rstd * (d_g + d_g.mean((2, 3, 4), keepdim=True) + xa * (d_g * xa).mean((2, 3, 4), keepdim=True))
+    bound = e32 + half_ulp(ref.abs() + e32, dtype)
+    for one in (got if isinstance(got, tuple) else (got,)):
+        assert_within(_ncdhw(one), ref, bound, what)
+
+
+def lrelu_mask(out, y, stats, slope):
+    """the LeakyReLU mask the backward kernels use: out > 0 from the saved output, else xhat > 0 (the sign of y - mean is exact
+    in fp32); None for slope 1"""
+    if slope == 1.0:
+        return None
+    if out is not None:
+        return _ncdhw(out) > 0
+    y = _ncdhw(y)
+    mean, rstd = _mr(stats, *y.shape[:2])
+    return (y - mean) * rstd > 0
 
 
 CONVT_CASES = [
@@ -174,24 +412,29 @@ def test_convT3d_fwd_bwd(ops, dtype, case):
     w_fwd, w_bwd = ops.pack_convT_weight(w.float().cuda(), dtype)
     # write straight into channels [0, co) of a 2*co-wide concat buffer (decoder.py:146-147)
     cat = ops.Act(torch.full((n, *odims, 2 * co), 3.0, dtype=dtype, device="cuda"))
+    cat.t[..., :co] = float("nan")
     ops.convT3d_fwd(xa, w_fwd, b.float().cuda(), cat.slice(0, co), s)
+    seen = {"fwd": last_kernel(ops)}
     if dtype != torch.float32 and n * dims[0] * dims[1] * dims[2] >= 4096 and ci <= 128:
-        assert last_kernel(ops) == "pointwise_kernel"
+        assert seen["fwd"] == "pointwise_kernel"
     assert rel(cat.slice(0, co).to_ncdhw(), y_ref.detach()) < TOL[dtype]
     assert torch.all(cat.slice(co, co).tensor() == 3.0)              # the skip half is untouched
 
     gya = to_act(ops, gy, dtype, ld=2 * co, c0=0)
-    dxa = ops.Act.zeros(n, *dims, ci, dtype)
+    dxa = nan_act(n, dims, ci, dtype)
     ops.convT3d_bwd_data(gya, w_bwd, dxa, s)
     nv = n * dims[0] * dims[1] * dims[2]
     assert rel(dxa.to_ncdhw(), xr.grad) < TOL[dtype]
     ops.convT3d_bwd_data(gya, w_bwd, dxa, s, True)                    # accumulate (a second decoder's gradient)
     assert rel(dxa.to_ncdhw(), 2 * xr.grad) < 2 * TOL[dtype]
-    dw = torch.empty((ci, co, *s), dtype=torch.float32, device="cuda")
+    dw = poisoned((ci, co, *s))
     ops.convT3d_bwd_weight(xa, gya, dw, s)
+    seen["wgrad"] = last_kernel(ops)
     if dtype != torch.float32 and nv >= 32768 and (ci // 32, co // 32) in ((2, 1), (4, 2), (1, 1), (2, 2)):
-        assert last_kernel(ops) == "convT_wgrad_kernel"
-    assert rel(dw, wr.grad) < TOL[dtype]
+        assert seen["wgrad"] == "convT_wgrad_kernel"
+    assert rel(dw, wr.grad) < TOL[torch.float32]       # fp32 output of exact products and fp32 sums, in every mode
+    seen_exact = exact_convT_pass(ops, dtype, exact_conv_ref(("convT", case), ci, co, dims, None, s, n, transposed=True), s)
+    assert {w: seen_exact[w] for w in seen} == seen, (case, seen, seen_exact)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -203,41 +446,61 @@ def test_instnorm_lrelu_residual(ops, dtype, c, dims):
     r = rnd((n, c, *dims), dtype, 10)
     g = rnd((n, c, *dims), dtype, 11)
     ya, ra, ga = to_act(ops, y, dtype), to_act(ops, r, dtype), to_act(ops, g, dtype)
-    stats = torch.empty((n, c, 2), dtype=torch.float32, device="cuda")
+    stats = poisoned((n, c, 2))
     ops.instnorm_stats(ya, stats)
     mean_ref = y.mean(dim=(2, 3, 4))
     var_ref = y.var(dim=(2, 3, 4), unbiased=False)
     assert rel(stats[..., 0], mean_ref) < 1e-5
     assert rel(stats[..., 1], (var_ref + 1e-5).rsqrt()) < 1e-5
+    check_stats(stats, y)
     for with_res, slope in [(False, 0.01), (True, 0.01), (False, 1.0)]:
         yr = y.clone().requires_grad_(True)
         rr = r.clone().requires_grad_(True)
         pre = F.instance_norm(yr, eps=1e-5) + (rr if with_res else 0.0)
         ref = F.leaky_relu(pre, slope) if slope != 1.0 else pre
-        oa = ops.Act.zeros(n, *dims, c, dtype)
+        og = Guarded(n, dims, c, dtype)
+        oa = og.act(ops)
         ops.instnorm_act_fwd(ya, stats, oa, slope, ra if with_res else None)
         assert rel(oa.to_ncdhw(), ref.detach()) < TOL[dtype]
+        og.check("out")
+        check_norm_fwd(oa, y, stats, r if with_res else None, slope, dtype, "out")
         # fused stats+apply entry point (single launch on small tensors) must agree with the two-call path
-        ob, stats2 = ops.Act.zeros(n, *dims, c, dtype), torch.zeros_like(stats)
+        ob, stats2 = nan_act(n, dims, c, dtype), poisoned((n, c, 2))
         ops.instnorm_fwd(ya, stats2, ob, slope, ra if with_res else None)
         assert rel(stats2, stats) < 1e-5
         assert rel(ob.to_ncdhw(), oa.to_ncdhw()) < (1e-6 if dtype == torch.float32 else TOL[dtype])
+        check_stats(stats2, y, what="stats (fused)")
+        check_norm_fwd(ob, y, stats2, r if with_res else None, slope, dtype, "out (fused)")
         # backward: feed the mask from the reference output (rounded) so both sides agree on signs
         out_ref_act = to_act(ops, ref.detach().to(dtype).double(), dtype)
         ref.backward(g)
-        dya = ops.Act.zeros(n, *dims, c, dtype)
-        dra = ops.Act.zeros(n, *dims, c, dtype) if with_res else None
+        dyg = Guarded(n, dims, c, dtype)
+        drg = Guarded(n, dims, c, dtype) if with_res else None
+        dya, dra = dyg.act(ops), drg.act(ops) if with_res else None
         ops.instnorm_act_bwd(ga, ya, stats, out_ref_act if slope != 1.0 else None, dya, slope, dra, False)
         assert rel(dya.to_ncdhw(), yr.grad) < 3 * TOL[dtype]
+        mask = lrelu_mask(out_ref_act, y, stats, slope)
+        dyg.check("dy")
+        check_norm_bwd(dya, g, y, stats, mask, slope, dtype, "dy")
         if not with_res and slope != 1.0:
             # no residual: the mask is the sign of the normalised value, the saved output is not needed at all
-            dyb = ops.Act.zeros(n, *dims, c, dtype)
+            dyb = nan_act(n, dims, c, dtype)
             ops.instnorm_act_bwd(ga, ya, stats, None, dyb, slope, None, False)
             assert rel(dyb.to_ncdhw(), yr.grad) < 3 * TOL[dtype]
+            check_norm_bwd(dyb, g, y, stats, lrelu_mask(None, y, stats, slope), slope, dtype, "dy (sign mask)")
         if with_res:
             assert rel(dra.to_ncdhw(), rr.grad) < TOL[dtype]
+            drg.check("d_residual")
+            gp = g if mask is None else torch.where(mask, g, g * slope)       # g' = g * lrelu'(out): fl(slope) and the product
+            e = 2 * U32 * gp.abs()
+            assert_within(dra.to_ncdhw(), gp, e + half_ulp(gp.abs() + e, dtype), "d_residual")
+            old = dra.to_ncdhw().double().cpu()
             ops.instnorm_act_bwd(ga, ya, stats, out_ref_act, dya, slope, dra, True)   # accumulate
             assert rel(dra.to_ncdhw(), 2 * rr.grad) < 2 * TOL[dtype]
+            drg.check("d_residual +=")
+            want = old + gp
+            e = U32 * (want.abs() + 2 * gp.abs())
+            assert_within(dra.to_ncdhw(), want, e + half_ulp(want.abs() + e, dtype), "d_residual +=")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -255,8 +518,8 @@ def test_channel_dropout_as_masked_statistics(ops, dtype, c, dims):
     ref = F.leaky_relu(F.instance_norm(yr * (keep.double() / (1 - p)).view(n, c, 1, 1, 1), eps=eps), slope)
     ref.backward(gv)
     ya, ga = to_act(ops, yv, dtype), to_act(ops, gv, dtype)
-    out, dy = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
-    stats = torch.empty((n, c, 2), device="cuda")
+    out, dy = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
+    stats = poisoned((n, c, 2))
     ops.instnorm_stats(ya, stats, eps * (1 - p) ** 2)
     ops.instnorm_stats_mask(stats, keep.cuda())
     ops.instnorm_act_fwd(ya, stats, out, slope)
@@ -269,6 +532,10 @@ def test_channel_dropout_as_masked_statistics(ops, dtype, c, dims):
     d = dy.to_ncdhw().double().cpu()
     assert (d[keep == 0] == 0).all()
     assert rel(d, yr.grad) < 5 * TOL[dtype]          # (cancellation in the norm backward + the output rounding)
+    # per element, from the device statistics (themselves within their fp32 bound of the fp64 ones)
+    check_stats(stats, ya, eps * (1 - p) ** 2, keep=keep)                 # (ya, ga: the values as stored)
+    check_norm_fwd(out, ya, stats, None, slope, dtype, "out")
+    check_norm_bwd(dy, ga, ya, stats, lrelu_mask(None, ya, stats, slope), slope, dtype, "dy")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -282,14 +549,51 @@ def test_avgpool(ops, dtype, s):
     ref.backward(g)
     xa = to_act(ops, x, dtype)
     odims = tuple(d // ss for d, ss in zip(dims, s))
-    ya = ops.Act.zeros(n, *odims, c, dtype)
+    ya = nan_act(n, odims, c, dtype)
     ops.avgpool_fwd(xa, ya, s)
     assert rel(ya.to_ncdhw(), ref.detach()) < TOL[dtype]
-    dxa = ops.Act.zeros(n, *dims, c, dtype)
+    K = s[0] * s[1] * s[2]
+    e = (gamma(K) + 2 * U32) * F.avg_pool3d(x.abs(), s, s)          # an fp32 sum of K terms, the scale 1/K and its product
+    assert_within(ya.to_ncdhw(), ref, e + half_ulp(ref.abs() + e, dtype), "pool")
+    dxa = nan_act(n, dims, c, dtype)
     ops.avgpool_bwd(to_act(ops, g, dtype), dxa, s)
     assert rel(dxa.to_ncdhw(), xr.grad) < TOL[dtype]
     ops.avgpool_bwd(to_act(ops, g, dtype), dxa, s, accumulate=True)
     assert rel(dxa.to_ncdhw(), 2 * xr.grad) < 2 * TOL[dtype]
+    # exact data: a power-of-two window is exact (sum, then a power-of-two scale: one rounding into the storage type); the
+    # divisor 27 is within 1 ulp (fl(1/27) and the product each err by u relative, then the output rounding)
+    xe = exact_tensor((n, c, *dims), _seed(("pool", s)), -4, 4, 0.5, 2.0 ** -2)
+    ge = exact_tensor((n, c, *odims), _seed(("pool", s)) + 1, -4, 4, 0.5, 2.0 ** -2)
+    base = exact_tensor((n, c, *dims), _seed(("pool", s)) + 2, -4, 4, 0.5, 2.0 ** -2)
+    pe = F.avg_pool3d(xe, s, s)
+    de = ge
+    for ax, ss in enumerate(s):
+        de = de.repeat_interleave(ss, dim=2 + ax)
+    de = de / K
+    pool2 = K & (K - 1) == 0
+
+    def check(got, want, what):
+        if pool2:
+            assert_bits(got, want, dtype, what)
+        else:
+            e = 2.0001 * U32 * want.abs()
+            assert_within(got, want, e + half_ulp(want.abs() + e, dtype), what)
+    yg = Guarded(n, odims, c, dtype)
+    ops.avgpool_fwd(to_act(ops, xe, dtype), yg.act(ops), s)
+    yg.check("pool")
+    check(yg.ncdhw(), pe, "pool (exact data)")
+    dg = Guarded(n, dims, c, dtype)
+    ops.avgpool_bwd(to_act(ops, ge, dtype), dg.act(ops), s)
+    dg.check("pool dx")
+    check(dg.ncdhw(), de, "pool dx (exact data)")
+    dga = Guarded(n, dims, c, dtype, init_ncdhw=base)
+    ops.avgpool_bwd(to_act(ops, ge, dtype), dga.act(ops), s, accumulate=True)
+    dga.check("pool dx+")
+    if pool2:
+        assert_bits(dga.ncdhw(), base + de, dtype, "pool dx+ (exact data)")        # old + g / K: one rounding
+    else:
+        e = 2.0001 * U32 * de.abs() + U32 * (base + de).abs()
+        assert_within(dga.ncdhw(), base + de, e + half_ulp((base + de).abs() + e, dtype), "pool dx+ (exact data)")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -298,7 +602,7 @@ def test_avgpool(ops, dtype, s):
                                    (12, (3, 3, 3)), (16, (3, 3, 3)), (16, (1, 3, 3))])                               # weights beyond 48 KB of LDS
 def test_stem(ops, dtype, cin, k):
     n, co, dims = 2, 32, (6, 9, 10)
-    x = rnd((n, cin, *dims), torch.float32, 14)
+    x = rnd((n, cin, *dims), dtype, 14)        # an image representable in the compute type (16-bit modes round it on the device)
     w = rnd((co, cin, *k), torch.float32, 15, scale=0.3)
     b = rnd((co,), torch.float32, 16)
     wr = w.clone().requires_grad_(True)
@@ -306,13 +610,13 @@ def test_stem(ops, dtype, cin, k):
     g = rnd(tuple(ref.shape), dtype, 17)
     ref.backward(g)
     xd = x.float().cuda().contiguous()
-    oa = ops.Act.zeros(n, *dims, co, dtype)
+    oa = nan_act(n, dims, co, dtype)
     ops.stem_conv_fwd(xd, w.float().cuda(), b.float().cuda(), oa, k)
     assert rel(oa.to_ncdhw(), ref.detach()) < TOL[dtype]
     # conv + InstanceNorm statistics in one call (one pass on the MFMA kernel, the two calls elsewhere): the same output bits,
     # (mean, rstd) of the values as stored
-    ob = ops.Act.zeros(n, *dims, co, dtype)
-    st_f, st_s = torch.zeros((n, co, 2), device="cuda"), torch.zeros((n, co, 2), device="cuda")
+    ob = nan_act(n, dims, co, dtype)
+    st_f, st_s = poisoned((n, co, 2)), poisoned((n, co, 2))
     ops.stem_conv_fwd_stats(xd, w.float().cuda(), b.float().cuda(), ob, k, st_f)
     assert torch.equal(ob.tensor(), oa.tensor())
     ops.instnorm_stats(oa, st_s)
@@ -320,10 +624,35 @@ def test_stem(ops, dtype, cin, k):
     mean, var = yv.mean(dim=(2, 3, 4)), yv.var(dim=(2, 3, 4), unbiased=False)
     for st in (st_f, st_s):
         assert rel(st[..., 0].cpu().double(), mean) < 1e-5 and rel(st[..., 1].cpu().double(), (var + 1e-5).rsqrt()) < 1e-5
-    dw = torch.empty((co, cin, *k), dtype=torch.float32, device="cuda")
+    dw = poisoned((co, cin, *k))
     ops.stem_conv_bwd_weight(xd, to_act(ops, g, dtype), dw, k)
-    # 16-bit modes run the MFMA kernel, which rounds the image to the compute dtype (fp32 mode stays exact)
-    assert rel(dw, wr.grad) < (2e-5 if dtype == torch.float32 else TOL[dtype])
+    # the image is representable in the compute type the 16-bit MFMA kernel rounds it to: exact products, fp32 sums
+    assert rel(dw, wr.grad) < 2e-5
+    # exact pass: integer image, dyadic weights and bias -- y (both entry points) rounded once, dw bit for bit
+    r = _EXACT.get(("stem", cin, k))
+    if r is None:
+        sd = _seed(("stem", cin, k))
+        xe = exact_tensor((n, cin, *dims), sd, -4, 4, 0.5, 2.0 ** -2)
+        we = exact_tensor((co, cin, *k), sd + 1, -4, 4, 0.5, 2.0 ** -3)
+        be = exact_tensor((co,), sd + 2, -16, 16, 1.0, 2.0 ** -5)
+        ge = exact_tensor((n, co, *dims), sd + 3, -4, 4, 0.5, 2.0 ** -2)
+        wre = we.clone().requires_grad_(True)
+        ye = F.conv3d(xe, wre, be, padding=[(kk - 1) // 2 for kk in k])
+        ye.backward(ge)
+        taps = k[0] * k[1] * k[2]
+        assert_exact_precondition(None, (xe, we), 2.0 ** -5, terms=cin * taps, extra=be, what="stem y")
+        assert_exact_precondition(None, (xe, ge), 2.0 ** -4, terms=n * dims[0] * dims[1] * dims[2], out16=False, what="stem dw")
+        r = _EXACT[("stem", cin, k)] = dict(x=xe, w=we, b=be, g=ge, y=ye.detach(), dw=wre.grad)
+    xe = r["x"].float().cuda().contiguous()
+    ya, yb = Guarded(n, dims, co, dtype), Guarded(n, dims, co, dtype)
+    ops.stem_conv_fwd(xe, r["w"].float().cuda(), r["b"].float().cuda(), ya.act(ops), k)
+    ops.stem_conv_fwd_stats(xe, r["w"].float().cuda(), r["b"].float().cuda(), yb.act(ops), k, poisoned((n, co, 2)))
+    for yy in (ya, yb):
+        yy.check("stem y")
+        assert_bits(yy.ncdhw(), r["y"], dtype, "stem y")
+    dwe = poisoned((co, cin, *k))
+    ops.stem_conv_bwd_weight(xe, to_act(ops, r["g"], dtype), dwe, k)
+    assert_bits(dwe, r["dw"], torch.float32, "stem dw", names=DW_NAMES)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -339,7 +668,7 @@ def test_head(ops, dtype, k):
     g = rnd(tuple(ref.shape), torch.float32, 21)
     ref.backward(g)
     xa = to_act(ops, x, dtype)
-    out = torch.empty((n, k, *dims), dtype=torch.float32, device="cuda")
+    out = poisoned((n, k, *dims))
     wd, bd = w.float().cuda(), b.float().cuda()
     ops.head_fwd(xa, wd, bd, out)
     assert rel(out, ref.detach()) < 2e-5          # fp32 accumulate of exactly representable inputs
@@ -347,20 +676,45 @@ def test_head(ops, dtype, k):
     assert rel(out, torch.sigmoid(ref.detach())) < 2e-5
     ops.head_fwd(xa, wd, bd, out, lib.RX_ACT_SOFTMAX)
     assert rel(out, torch.softmax(ref.detach(), 1)) < 2e-5
-    dxa = ops.Act.zeros(n, *dims, c, dtype)
-    dw = torch.empty((k, c), dtype=torch.float32, device="cuda")
-    db = torch.empty((k,), dtype=torch.float32, device="cuda")
+    dxa = nan_act(n, dims, c, dtype)
+    dw, db = poisoned((k, c)), poisoned((k,))
     ops.head_bwd(g.float().cuda().contiguous(), xa, wd, dxa, dw, db)
     assert rel(dxa.to_ncdhw(), xr.grad) < TOL[dtype]
     assert rel(dw, wr.grad) < 2e-5
     assert rel(db, br.grad) < 2e-5
+    # exact pass: integer activations, dyadic w / b / dout -- logits, dw, db (fp32) bit for bit, dx rounded once
+    r = _EXACT.get(("head", k))
+    if r is None:
+        sd = _seed(("head", k))
+        xe = exact_tensor((n, c, *dims), sd, -4, 4, 0.5, 2.0 ** -2)
+        we = exact_tensor((k, c), sd + 1, -4, 4, 0.5, 2.0 ** -3)
+        be = exact_tensor((k,), sd + 2, -16, 16, 1.0, 2.0 ** -5)
+        ge = exact_tensor((n, k, *dims), sd + 3, -4, 4, 0.5, 2.0 ** -2)
+        xre, wre, bre = (t.clone().requires_grad_(True) for t in (xe, we, be))
+        le = F.conv3d(xre, wre.view(k, c, 1, 1, 1), bre)
+        le.backward(ge)
+        assert_exact_precondition(None, (xe, we), 2.0 ** -5, terms=c, extra=be, out16=False, what="logits")
+        assert_exact_precondition(None, (ge, we), 2.0 ** -5, terms=k, what="head dx")
+        assert_exact_precondition(None, (ge, xe), 2.0 ** -4, terms=n * dims[0] * dims[1] * dims[2], out16=False, what="head dw")
+        r = _EXACT[("head", k)] = dict(x=xe, w=we, b=be, g=ge, logits=le.detach(), dx=xre.grad, dw=wre.grad, db=bre.grad)
+    xe = to_act(ops, r["x"], dtype)
+    we, be, ge = r["w"].float().cuda(), r["b"].float().cuda(), r["g"].float().cuda().contiguous()
+    le = poisoned((n, k, *dims))
+    ops.head_fwd(xe, we, be, le)
+    assert_bits(le, r["logits"], torch.float32, "logits")
+    dxe, dwe, dbe = Guarded(n, dims, c, dtype), poisoned((k, c)), poisoned((k,))
+    ops.head_bwd(ge, xe, we, dxe.act(ops), dwe, dbe)
+    dxe.check("head dx")
+    assert_bits(dxe.ncdhw(), r["dx"], dtype, "head dx")
+    assert_bits(dwe, r["dw"], torch.float32, "head dw", names=("k", "c"))
+    assert_bits(dbe, r["db"], torch.float32, "head db", names=("k",))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_channel_sum_and_pack(ops, dtype):
     n, c, dims = 2, 64, (5, 6, 7)
     x = rnd((n, c, *dims), dtype, 22)
-    out = torch.empty((c,), dtype=torch.float32, device="cuda")
+    out = poisoned((c,))
     ops.channel_sum(to_act(ops, x, dtype), out)
     assert rel(out, x.sum(dim=(0, 2, 3, 4))) < 1e-5
     w = rnd((96, 64, 3, 3, 3), dtype, 23)
@@ -403,9 +757,8 @@ def test_conv3d_fwd_stats(ops, dtype, case):
     w = rnd((co, ci, 3, 3, 3), torch.float32, seed=4, scale=0.1).float().cuda()
     b = rnd((co,), torch.float32, seed=5).float().cuda()
     wf, _ = ops.pack_conv_weight(w, dtype)
-    y1, y2 = ops.Act.empty(n, *dims, co, dtype), ops.Act.empty(n, *dims, co, dtype)
-    s1 = torch.empty((n, co, 2), device="cuda")
-    s2 = torch.empty((n, co, 2), device="cuda")
+    y1, y2 = nan_act(n, dims, co, dtype), nan_act(n, dims, co, dtype)
+    s1, s2 = poisoned((n, co, 2)), poisoned((n, co, 2))
     k, s = (3, 3, 3), (1, 1, 1)
     ops.conv3d_fwd(x, wf, b, y1, k, s)
     ops.instnorm_stats(y1, s1)
@@ -413,6 +766,8 @@ def test_conv3d_fwd_stats(ops, dtype, case):
     torch.cuda.synchronize()
     assert torch.equal(y1.t, y2.t)
     assert torch.allclose(s1, s2, rtol=2e-5, atol=2e-6), (s1 - s2).abs().max()
+    for st in (s1, s2):                                 # each within its fp32 bound of the fp64 statistics of y as stored
+        check_stats(st, y1)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -421,11 +776,11 @@ def test_instnorm_act_pool_fwd_is_the_two_calls(ops, dtype, stride):
     n, c, dims = 2, 32, (8, 12, 20)
     y = to_act(ops, rnd((n, c, *dims), dtype, seed=1), dtype)
     res = to_act(ops, rnd((n, c, *dims), dtype, seed=2), dtype, ld=64, c0=32)        # residual inside a wider buffer
-    stats = torch.empty((n, c, 2), device="cuda")
+    stats = poisoned((n, c, 2))
     ops.instnorm_stats(y, stats)
     pd = tuple(d // s for d, s in zip(dims, stride))
-    o1, o2 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
-    p1, p2 = ops.Act.empty(n, *pd, c, dtype), ops.Act.empty(n, *pd, c, dtype)
+    o1, o2 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
+    p1, p2 = nan_act(n, pd, c, dtype), nan_act(n, pd, c, dtype)
     ops.instnorm_act_fwd(y, stats, o1, 0.01, res)
     ops.avgpool_fwd(o1, p1, stride)
     ops.instnorm_act_pool_fwd(y, stats, o2, p2, stride, 0.01, res)
@@ -446,14 +801,22 @@ def test_planar_concat_convs_equal_interleaved(ops, dtype):
     w = rnd((32, 64, 3, 3, 3), torch.float32, 2, scale=0.05).float().cuda()
     wf, wb = ops.pack_conv_weight(w, dtype)
     k, s = (3, 3, 3), (1, 1, 1)
-    y1, y2 = ops.Act.empty(n, *dims, 32, dtype), ops.Act.empty(n, *dims, 32, dtype)
+    y1, y2 = nan_act(n, dims, 32, dtype), nan_act(n, dims, 32, dtype)
     ops.conv3d_fwd(inter, wf, None, y1, k, s)
     ops.conv3d_fwd(planar, wf, None, y2, k, s)
-    st1, st2 = torch.empty((n, 32, 2), device="cuda"), torch.empty((n, 32, 2), device="cuda")
+    st1, st2 = poisoned((n, 32, 2)), poisoned((n, 32, 2))
     ops.conv3d_fwd_stats(planar, wf, None, y2, k, s, st2)
     ops.instnorm_stats(y1, st1)
     torch.cuda.synchronize()
     assert torch.equal(y1.t, y2.t) and torch.allclose(st1, st2, rtol=2e-5, atol=2e-6)
+    # written into the middle plane of a planar concat (as a decoder conv writes its half of the next concat): the same bits, the
+    # neighbouring planes untouched
+    root3 = torch.full((3, n, *dims, 32), -97.0, dtype=dtype, device="cuda")
+    root3[1] = float("nan")
+    before = root3[0::2].clone()
+    ops.conv3d_fwd(inter, wf, None, ops.Act.planar(root3, 1), k, s)
+    torch.cuda.synchronize()
+    assert torch.equal(root3[1], y1.t) and torch.equal(root3[0::2].view(torch.int16), before.view(torch.int16))
     gy = to_act(ops, rnd((n, 32, *dims), dtype, 3, scale=0.1), dtype)
     base = rnd((n, 64, *dims), dtype, 4, scale=0.1)
     for acc in (False, True):
@@ -463,7 +826,7 @@ def test_planar_concat_convs_equal_interleaved(ops, dtype):
         ops.conv3d_bwd_data(gy, wb, d2, k, s, acc)
         torch.cuda.synchronize()
         assert torch.equal(d1.t, d2.tensor()), acc
-    dw1, dw2 = torch.empty_like(w), torch.empty_like(w)
+    dw1, dw2 = torch.full_like(w, float("nan")), torch.full_like(w, float("nan"))
     ops.conv3d_bwd_weight(inter, gy, dw1, k, s)
     ops.conv3d_bwd_weight(planar, gy, dw2, k, s)
     torch.cuda.synchronize()
@@ -492,7 +855,7 @@ def test_conv3d_bwd_data_instats(ops, dtype, slope, accumulate, c, dims):
     yv = to_act(ops, rnd((n, c, *dims), dtype, seed=3) + 0.3, dtype)
     base = rnd((n, c, *dims), dtype, seed=5, scale=0.1)
     dx1, dx2 = to_act(ops, base, dtype), to_act(ops, base, dtype)
-    stats = torch.empty((n, c, 2), device="cuda")
+    stats = poisoned((n, c, 2))
     ops.instnorm_stats(yv, stats)
     m12 = torch.full((n, c, 2), float("nan"), device="cuda")
     k, s = (3, 3, 3), (1, 1, 1)
@@ -512,12 +875,21 @@ def test_conv3d_bwd_data_instats(ops, dtype, slope, accumulate, c, dims):
     got = m12.double().cpu()
     scale = want.abs().max().item()
     assert torch.isfinite(got).all() and (got - want).abs().max().item() < 2e-4 * scale + 1e-7
-    dy1, dy2 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
+    # per (n, c): fp32 sums of V terms -> gamma_V (+ 6u for xhat and the products) of the sums of magnitudes; the epilogue may sum
+    # g' before its rounding into the storage type: half an ulp of each term more
+    V = dims[0] * dims[1] * dims[2]
+    hu = half_ulp(g.abs(), dtype)
+    bnd = torch.stack([g.abs().mean((2, 3, 4)), (g * xh).abs().mean((2, 3, 4))], -1) * (gamma(V) + 6 * U32) + \
+        torch.stack([hu.mean((2, 3, 4)), (hu * xh.abs()).mean((2, 3, 4))], -1)
+    assert_within(got, want, bnd, "m12", names=("n", "c", "m"))
+    dy1, dy2 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
     ops.instnorm_act_bwd(dx1, yv, stats, None, dy1, slope)
     ops.instnorm_act_bwd_apply(dx2, yv, stats, None, dy2, m12, slope)
     torch.cuda.synchronize()
     a_, b_ = dy2.tensor().double().cpu(), dy1.tensor().double().cpu()
     assert ((a_ - b_).norm() / b_.norm()).item() < 3e-3
+    mask = lrelu_mask(None, yv, stats, slope)
+    check_norm_bwd((dy1, dy2), dx1, yv, stats, mask, slope, dtype, "dy")         # both within the bound of the stored dx
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -532,14 +904,14 @@ def test_instnorm_act_bwd_head_is_head_bwd_then_instnorm_bwd(ops, dtype, k, slop
     out = to_act(ops, rnd((n, c, *dims), dtype, seed=22), dtype)
     dout = rnd((n, k, *dims), torch.float32, seed=23, scale=0.01).float().cuda().contiguous()
     w = rnd((k, c), torch.float32, seed=24).float().cuda().contiguous()
-    stats = torch.empty((n, c, 2), device="cuda")
+    stats = poisoned((n, c, 2))
     ops.instnorm_stats(y, stats)
-    g = ops.Act.empty(n, *dims, c, dtype)
-    dw, db = torch.empty((k, c), device="cuda"), torch.empty((k,), device="cuda")
-    dy1, dy2 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
+    g = nan_act(n, dims, c, dtype)
+    dw, db = poisoned((k, c)), poisoned((k,))
+    dy1, dy2 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
     ops.head_bwd(dout, out, w, g, dw, db)
     ops.instnorm_act_bwd(g, y, stats, None, dy1, slope)
-    dw2, db2 = torch.empty_like(dw), torch.empty_like(db)
+    dw2, db2 = torch.full_like(dw, float("nan")), torch.full_like(db, float("nan"))
     ops.head_bwd(dout, out, w, None, dw2, db2)
     ops.instnorm_act_bwd_head(dout, w, y, stats, dy2, slope)
     torch.cuda.synchronize()
@@ -548,14 +920,14 @@ def test_instnorm_act_bwd_head_is_head_bwd_then_instnorm_bwd(ops, dtype, k, slop
     # round 3: the head's own dw / db out of the same reduce pass, the activation recomputed from y (`out` here must then BE the
     # activation of y: rebuild it with the forward kernel) -- no head_bwd launch, dy unchanged bit for bit
     b0 = torch.zeros((k,), device="cuda")
-    logits = torch.empty((n, k, *dims), device="cuda")
-    act_out = ops.Act.empty(n, *dims, c, dtype)
+    logits = poisoned((n, k, *dims))
+    act_out = nan_act(n, dims, c, dtype)
     ops.instnorm_act_head_fwd(y, stats, act_out, w, b0, logits, 0, slope)
-    logits2 = torch.empty_like(logits)
+    logits2 = torch.full_like(logits, float("nan"))
     ops.instnorm_act_head_fwd(y, stats, None, w, b0, logits2, 0, slope)            # nobody needs the activated output: not stored
-    dw_ref, db_ref = torch.empty_like(dw), torch.empty_like(db)
+    dw_ref, db_ref = torch.full_like(dw, float("nan")), torch.full_like(db, float("nan"))
     ops.head_bwd(dout, act_out, w, None, dw_ref, db_ref)
-    dw3, db3, dy3 = torch.empty_like(dw), torch.empty_like(db), ops.Act.empty(n, *dims, c, dtype)
+    dw3, db3, dy3 = torch.full_like(dw, float("nan")), torch.full_like(db, float("nan")), nan_act(n, dims, c, dtype)
     ops.instnorm_act_bwd_head(dout, w, y, stats, dy3, slope, dw=dw3, db=db3)
     torch.cuda.synchronize()
     assert torch.equal(logits, logits2)
@@ -572,6 +944,12 @@ def test_instnorm_act_bwd_head_is_head_bwd_then_instnorm_bwd(ops, dtype, k, slop
     m2 = (gd * xh).mean(dim=(1, 2, 3), keepdim=True)
     ref = rstd * (gd - m1 - xh * m2)
     assert rel(dy2.t.float().cpu(), ref.float().cpu()) < (6e-3 if dtype == torch.bfloat16 else 8e-4)
+    # per element: g = dout x w is an fp32 sum of k products (gamma_k of the magnitudes), stored in the storage type (half an ulp)
+    g_un = torch.einsum("nkzyx,kc->nczyx", dout.double(), w.double()).cpu()
+    e_g = gamma(k) * torch.einsum("nkzyx,kc->nczyx", dout.double().abs(), w.double().abs()).cpu()
+    d_g = e_g + half_ulp(g_un.abs() + e_g, dtype)
+    mask = lrelu_mask(None, y, stats, slope)
+    check_norm_bwd((dy1, dy2, dy3), g_un, y, stats, mask, slope, dtype, "dy", d_g=d_g)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -585,17 +963,24 @@ def test_instnorm_act_head_fwd_is_the_two_calls(ops, dtype, k, act):
     y = to_act(ops, rnd((n, c, *dims), dtype, seed=31), dtype)
     w = rnd((k, c), torch.float32, seed=32, scale=0.3).float().cuda().contiguous()
     b = rnd((k,), torch.float32, seed=33).float().cuda().contiguous()
-    stats = torch.empty((n, c, 2), device="cuda")
+    stats = poisoned((n, c, 2))
     ops.instnorm_stats(y, stats)
-    o1, o2 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
-    l1 = torch.empty((n, k, *dims), device="cuda")
-    l2 = torch.empty((n, k, *dims), device="cuda")
+    o1, o2 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
+    l1 = poisoned((n, k, *dims))
+    l2 = poisoned((n, k, *dims))
     ops.instnorm_act_fwd(y, stats, o1, 0.01)
     ops.head_fwd(o1, w, b, l1, codes[act])
     ops.instnorm_act_head_fwd(y, stats, o2, w, b, l2, codes[act], 0.01)
     torch.cuda.synchronize()
     assert torch.equal(o1.t, o2.t)
     assert torch.allclose(l1, l2, rtol=2e-6, atol=2e-6), (l1 - l2).abs().max()     # same products, fp32 sums differ in the last bit
+    check_norm_fwd(o1, y, stats, None, 0.01, dtype, "out")
+    if act == 0:        # logits = w . out (as stored) + b: an fp32 sum of c exact products and the bias
+        od = o1.to_ncdhw().double().cpu()
+        want = torch.einsum("nczyx,kc->nkzyx", od, w.double().cpu()) + b.double().cpu().view(1, k, 1, 1, 1)
+        e = gamma(c + 1) * (torch.einsum("nczyx,kc->nkzyx", od.abs(), w.double().cpu().abs()) + b.double().cpu().abs().view(1, k, 1, 1, 1))
+        for lg in (l1, l2):
+            assert_within(lg, want, e, "logits")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -642,7 +1027,7 @@ def test_instnorm_act_bwd_res_masked_gradient_written_once(ops, dtype, pool):
     y = to_act(ops, rnd((n, c, *dims), dtype, seed=41), dtype)
     out = to_act(ops, rnd((n, c, *dims), dtype, seed=42), dtype)
     g0 = rnd((n, c, *dims), dtype, seed=43, scale=0.1)
-    stats = torch.empty((n, c, 2), device="cuda")
+    stats = poisoned((n, c, 2))
     ops.instnorm_stats(y, stats)
     pd = tuple(d // s for d, s in zip(dims, pool)) if pool else None
     pg = to_act(ops, rnd((n, c, *pd), dtype, seed=44, scale=0.1), dtype) if pool else None
@@ -650,11 +1035,11 @@ def test_instnorm_act_bwd_res_masked_gradient_written_once(ops, dtype, pool):
     g1 = to_act(ops, g0, dtype, ld=2 * c, c0=c)
     if pool:
         ops.avgpool_bwd(pg, g1, pool, True)
-    dy1, dr1 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
+    dy1, dr1 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
     ops.instnorm_act_bwd(g1, y, stats, out, dy1, slope, dr1, False)
     # fused
     g2 = to_act(ops, g0, dtype, ld=2 * c, c0=c)
-    dy2, dr2 = ops.Act.empty(n, *dims, c, dtype), ops.Act.empty(n, *dims, c, dtype)
+    dy2, dr2 = nan_act(n, dims, c, dtype), nan_act(n, dims, c, dtype)
     ops.instnorm_act_bwd_res(g2, y, stats, out, dy2, dr2, slope, pool_dy=pg, pool_stride=pool or (1, 1, 1))
     torch.cuda.synchronize()
     tol = TOL[dtype]
@@ -673,9 +1058,22 @@ def test_instnorm_act_bwd_res_masked_gradient_written_once(ops, dtype, pool):
     ref = rstd * (gd - gd.mean(dim=(1, 2, 3), keepdim=True) - xh * (gd * xh).mean(dim=(1, 2, 3), keepdim=True))
     assert rel(dr2.t.float().cpu(), gd.float().cpu()) < tol
     assert rel(dy2.t.float().cpu(), ref.float().cpu()) < 3 * tol
+    # per element: g' = (g + pool term) * lrelu'(out) in fp32 -- the pool scale and product, the add and the slope product, 4u of
+    # |g| + |pool term| -- then one rounding into d_residual.  dy: the norm-backward bound of g', plus the error of g' itself carried
+    # through rstd (g' - mean g' - xhat mean(g' xhat)), counting half an ulp more in case the sums read g' as stored
+    g_abs = to_act(ops, g0, dtype).t.double().abs() + ((up / (pool[0] * pool[1] * pool[2])).abs() if pool else 0)
+    e_g = 4 * U32 * g_abs
+    gd_c, e_c = gd.permute(0, 4, 1, 2, 3).cpu(), e_g.permute(0, 4, 1, 2, 3).cpu()
+    assert_within(dr2.to_ncdhw(), gd_c, e_c + half_ulp(gd_c.abs() + e_c, dtype), "d_residual")
+    ref_c, e32, _ = norm_bwd_ref(gd_c, y, stats, None, 1.0)
+    rstd_c = stats[..., 1].double().cpu().view(n, c, 1, 1, 1)
+    xh_c = xh.permute(0, 4, 1, 2, 3).cpu()
+    d_g = e_c + half_ulp(gd_c.abs() + e_c, dtype)
+    e_dy = e32 + rstd_c * (d_g + d_g.mean((2, 3, 4), keepdim=True) + xh_c.abs() * (d_g * xh_c.abs()).mean((2, 3, 4), keepdim=True))
+    assert_within(dy2.to_ncdhw(), ref_c, e_dy + half_ulp(ref_c.abs() + e_dy, dtype), "dy")
     # in place (d_residual == g) is allowed: same results
     g3 = to_act(ops, g0, dtype)
-    dy3 = ops.Act.empty(n, *dims, c, dtype)
+    dy3 = nan_act(n, dims, c, dtype)
     ops.instnorm_act_bwd_res(g3, y, stats, out, dy3, g3, slope, pool_dy=pg, pool_stride=pool or (1, 1, 1))
     torch.cuda.synchronize()
     assert torch.equal(g3.t, dr2.t) and torch.equal(dy3.t, dy2.t)
