@@ -317,6 +317,36 @@ int rx_event_slots_in_use(void);
 int rx_event_record(int slot, void* stream);
 int rx_stream_wait(int slot, void* stream);
 
+/* ---- streaming sliding-window inference (reference inference.py:115-157 patch loop, :166-210 overlap processing, :251-263
+ *      cast; dataloading/inference_dataset.py:60-71 input normalisation).  Volumes on the device are RING SLABS: a
+ *      (C, ring, Y, X) array whose ring row r holds volume row z with z % ring == r, so rows can be replaced as the window
+ *      moves down Z.  `origins` is a HOST array of batch x (z, y, x) patch origins, z an absolute volume row (batch <= 32).
+ *      No entry point here records itself into a launch program. ---------------------------------------------------------- */
+typedef enum { RX_SW_U8 = 0, RX_SW_U16 = 1, RX_SW_F32 = 2 } rx_sw_in_dtype;
+typedef enum { RX_SW_SCALE = 0, RX_SW_ZSCORE = 1 } rx_sw_norm;
+typedef enum { RX_SW_BLEND_AVERAGE = 0, RX_SW_BLEND_UNIT = 1, RX_SW_BLEND_NONE = 2 } rx_sw_blend;
+typedef enum { RX_SW_CAST_U8 = 0, RX_SW_CAST_U16 = 1 } rx_sw_cast;
+/* fp64 scratch of the zscore statistics of rx_sw_gather */
+size_t rx_sw_gather_workspace(int batch, int cin, int pz, int py, int px);
+/* input slab -> out (batch, cin, pz, py, px) fp32, contiguous and 16-byte aligned.  RX_SW_SCALE: uint8 / 255, uint16 / 65535,
+ * fp32 as is (fp32 division, dataset.py:179-184).  RX_SW_ZSCORE: then (v - mean) / max(std, 1e-10) per patch over all its
+ * channels, population std, statistics summed in fp64 in a fixed order (ws: rx_sw_gather_workspace() bytes). */
+int rx_sw_gather(int in_dtype, const void* slab, int cin, int ring, int y, int x, int batch, const int32_t* origins, int pz,
+                 int py, int px, int norm, float* out, void* ws, size_t ws_bytes, void* stream);
+/* one task's logits (batch, c, pz, py, px) fp32 -> act (rx_head_act, fp32, softmax over c with the max subtracted) -> for the
+ * first `valid` patches, in patch order: sum (c, ring, Y, X) += weight * p and, if wsum != NULL, wsum (ring, Y, X) += weight,
+ * weight a (pz, py, px) fp32 table.  Deterministic (no atomics): each destination voxel adds the patches in order.  The rows
+ * [min z, max z + pz) of the batch must fit the ring. */
+int rx_sw_accumulate(const float* logits, int batch, int valid, int c, int pz, int py, int px, const int32_t* origins, int act,
+                     const float* weight, float* sum, float* wsum, int ring, int y, int x, void* stream);
+/* volume rows [z0, z0 + rows) of the ring accumulators -> blended (c, rows, Y, X) fp32 and final (c, rows, Y, X) uint8
+ * (RX_SW_CAST_U8: clip(v*255, 0, 255)) or uint16 (RX_SW_CAST_U16: clip((v+1)/2*65535, 0, 65535)), truncating.  Where wsum > 0:
+ * RX_SW_BLEND_AVERAGE v = s / wsum, RX_SW_BLEND_UNIT (c == 3) v = s / (sqrt(sum s^2) + 1e-8), RX_SW_BLEND_NONE v = s; elsewhere
+ * v = s.  wsum_out (optional): the weight sum of those rows.  reset 1: the rows of sum are zeroed after reading, 2: those of
+ * wsum too (ring rows are then ready for the rows that follow). */
+int rx_sw_finalize(float* sum, float* wsum, int c, int ring, int y, int x, int z0, int rows, int blend, int cast, int reset,
+                   float* blended, void* final_out, float* wsum_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,17 @@ class ConfigManager:
         self.infer_patch_size = tuple(ic.get("patch_size", self.train_patch_size))
         self.infer_batch_size = int(ic.get("batch_size", self.train_batch_size))
         self.infer_output_path = ic.get("output_path", "./outputs")
+        # streaming inference (inference.StreamingInferer); optional keys, none of them in the reference's config
+        self.infer_input_path = ic.get("input_path", None)
+        self.infer_overlap = float(ic.get("overlap", 0.5))
+        tg = ic.get("targets") or self.tasks
+        if isinstance(tg, list):        # the reference's task files list them as [{name: {...}}, ...]
+            tg = {k: v for item in tg if isinstance(item, dict) for k, v in item.items()}
+        self.infer_targets = dict(tg)
+        self.infer_blend = str(ic.get("blend", "uniform")).lower()
+        self.infer_normalization = str(ic.get("normalization", "scale")).lower()
+        gb = ic.get("max_device_gb", None)
+        self.infer_max_device_gb = None if gb is None else float(gb)
         if verbose:
             self._print_summary()
 

@@ -1,0 +1,431 @@
+// rx_infer.hip -- the per-patch work of streaming sliding-window inference around the network forward (reference
+// inference.py:115-157 patch loop, :166-210 overlap processing, :251-263 cast; dataloading/inference_dataset.py:60-71 input
+// normalisation).  Volumes live on the device as RING SLABS: a (C, R, Y, X) array whose ring row r holds absolute volume row z
+// with z % R == r.  Three entry points:
+//   rx_sw_gather      input slab (uint8 / uint16 / fp32) -> B patches, contiguous fp32 (B, Cin, pz, py, px), /255 or /65535
+//                     ("scale") and optionally the per-patch standardisation ("zscore")
+//   rx_sw_accumulate  one task's logits (B, c, pz, py, px) -> activation -> sum += w * p and wsum += w on the ring accumulators
+//   rx_sw_finalize    finished rows -> blended fp32 + uint8 / uint16 final (+ the weight sum), accumulators reset for reuse
+// Deterministic: no atomics.  rx_sw_accumulate runs one thread per 4 destination voxels of the batch's bounding box, each adding
+// the batch's patches in patch order -- the same additions, in the same order, as one launch per patch, with every destination
+// read and written once per batch instead of once per covering patch (patches of one batch overlap by design).
+// Floating-point contraction is off in this file: every product and sum rounds like the numpy / torch statement it restates.
+#include "rx_common.h"
+
+#pragma clang fp contract(off)
+
+#define RX_SW_MAXB 32        // patches per call (kernel-argument table)
+#define RX_SW_BLOCK 256
+#define RX_SW_STAT_CHUNKS 64 // blocks per patch of the zscore partial sums
+
+struct SwPatches {
+  int32_t oz[RX_SW_MAXB], oy[RX_SW_MAXB], ox[RX_SW_MAXB];
+};
+
+static int sw_patches(const int32_t* origins, int batch, int R, int Y, int X, int pz, int py, int px, SwPatches& p,
+                      const char* who) {
+  if (!origins || batch < 1 || batch > RX_SW_MAXB) RX_FAIL(RX_EINVAL, "%s: batch must be 1..%d", who, RX_SW_MAXB);
+  if (pz < 1 || py < 1 || px < 1 || pz > R || py > Y || px > X)
+    RX_FAIL(RX_EINVAL, "%s: patch (%d,%d,%d) does not fit the slab (ring %d, %d, %d)", who, pz, py, px, R, Y, X);
+  for (int b = 0; b < batch; ++b) {
+    const int z = origins[3 * b], y = origins[3 * b + 1], x = origins[3 * b + 2];
+    if (z < 0 || y < 0 || x < 0 || y + py > Y || x + px > X)
+      RX_FAIL(RX_EINVAL, "%s: patch %d at (%d,%d,%d) leaves the slab (%d, %d)", who, b, z, y, x, Y, X);
+    p.oz[b] = z, p.oy[b] = y, p.ox[b] = x;
+  }
+  return RX_OK;
+}
+
+// ---- gather ---------------------------------------------------------------------------------------------------------
+struct GatherGeom {
+  int cin, R, Y, X, pz, py, px, pxq;   // pxq: quads of 4 outputs per patch row
+  float div;                           // 0: fp32 input as is; otherwise the divisor 255 / 65535
+  long total;                          // B * cin * pz * py * pxq
+};
+
+template <typename T>
+__device__ inline float sw_scale(T v, float div) {
+  return div == 0.f ? (float)v : (float)v / div;   // true division: bit-exact against numpy's float32 `img /= 255.0`
+}
+
+template <typename T>
+__global__ __launch_bounds__(RX_SW_BLOCK) void sw_gather_kernel(const T* __restrict__ slab, float* __restrict__ out, GatherGeom g,
+                                                                SwPatches p) {
+  const long q = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x;
+  if (q >= g.total) return;
+  long r = q;
+  const int xq = (int)(r % g.pxq);
+  r /= g.pxq;
+  const int ly = (int)(r % g.py);
+  r /= g.py;
+  const int lz = (int)(r % g.pz);
+  r /= g.pz;
+  const int ci = (int)(r % g.cin);
+  const int b = (int)(r / g.cin);
+  const int zr = (p.oz[b] + lz) % g.R;
+  const T* src = slab + (((long)ci * g.R + zr) * g.Y + p.oy[b] + ly) * g.X + p.ox[b];
+  float* dst = out + (((long)(b * g.cin + ci) * g.pz + lz) * g.py + ly) * g.px;
+  const int x0 = xq * 4;
+  if ((g.px & 3) == 0) {
+    // patch origins put the source row at any alignment: four coalesced scalar loads, one 16-byte store
+    f32x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = sw_scale(src[x0 + i], g.div);
+    *reinterpret_cast<f32x4*>(dst + x0) = v;
+  } else {
+    for (int i = 0; i < 4 && x0 + i < g.px; ++i) dst[x0 + i] = sw_scale(src[x0 + i], g.div);
+  }
+}
+
+// zscore: per-patch (sum, sum of squares) in fp64, fixed order (thread-strided loop, xor-shuffle, waves in index order), then
+// one block per patch slice sums the chunk partials in index order and applies (x - mean) / max(std, 1e-10) in place
+__global__ __launch_bounds__(RX_SW_BLOCK) void sw_stat_partial_kernel(const float* __restrict__ x, long n, double* __restrict__ part) {
+  const int b = blockIdx.y, chunk = blockIdx.x;
+  const long per = (n + gridDim.x - 1) / gridDim.x;
+  const long lo = chunk * per, hi = lo + per < n ? lo + per : n;
+  const float* xb = x + (long)b * n;
+  double s = 0.0, s2 = 0.0;
+  for (long i = lo + threadIdx.x; i < hi; i += RX_SW_BLOCK) {
+    const double v = xb[i];
+    s += v;
+    s2 += v * v;
+  }
+  s = wave_sum_d(s);
+  s2 = wave_sum_d(s2);
+  __shared__ double red[2][RX_SW_BLOCK / RX_WAVE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[0][wave] = s, red[1][wave] = s2;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, a2 = 0.0;
+    for (int w = 0; w < RX_SW_BLOCK / RX_WAVE; ++w) a += red[0][w], a2 += red[1][w];
+    part[((long)b * gridDim.x + chunk) * 2] = a;
+    part[((long)b * gridDim.x + chunk) * 2 + 1] = a2;
+  }
+}
+
+__global__ __launch_bounds__(RX_SW_BLOCK) void sw_standardize_kernel(float* __restrict__ x, long n, const double* __restrict__ part,
+                                                                      int chunks) {
+  const int b = blockIdx.y;
+  __shared__ float ms[2];
+  if (threadIdx.x == 0) {
+    double s = 0.0, s2 = 0.0;
+    for (int c = 0; c < chunks; ++c) s += part[((long)b * chunks + c) * 2], s2 += part[((long)b * chunks + c) * 2 + 1];
+    const double mean = s / (double)n;
+    double var = s2 / (double)n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const float sd = (float)sqrt(var);
+    ms[0] = (float)mean;
+    ms[1] = sd > 1e-10f ? sd : 1e-10f;
+  }
+  __syncthreads();
+  const float mean = ms[0], sd = ms[1];
+  float* xb = x + (long)b * n;
+  const long nq = n / 4;
+  if ((n & 3) == 0) {       // each patch starts 16-byte aligned
+    for (long i = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x; i < nq; i += (long)gridDim.x * RX_SW_BLOCK) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(xb + 4 * i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = (v[k] - mean) / sd;
+      *reinterpret_cast<f32x4*>(xb + 4 * i) = v;
+    }
+  } else {
+    for (long i = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * RX_SW_BLOCK) xb[i] = (xb[i] - mean) / sd;
+  }
+}
+
+static int sw_stat_chunks(long n) {
+  long c = (n + 4 * RX_SW_BLOCK - 1) / (4 * RX_SW_BLOCK);
+  return (int)(c < 1 ? 1 : c > RX_SW_STAT_CHUNKS ? RX_SW_STAT_CHUNKS : c);
+}
+
+extern "C" size_t rx_sw_gather_workspace(int batch, int cin, int pz, int py, int px) {
+  if (batch < 1 || cin < 1 || pz < 1 || py < 1 || px < 1) return 0;
+  return (size_t)batch * sw_stat_chunks((long)cin * pz * py * px) * 2 * sizeof(double);
+}
+
+extern "C" int rx_sw_gather(int in_dtype, const void* slab, int cin, int ring, int y, int x, int batch, const int32_t* origins,
+                            int pz, int py, int px, int norm, float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (!slab || !out || cin < 1 || ring < 1 || y < 1 || x < 1) RX_FAIL(RX_EINVAL, "rx_sw_gather: bad arguments");
+  if (in_dtype < RX_SW_U8 || in_dtype > RX_SW_F32) RX_FAIL(RX_EINVAL, "rx_sw_gather: unknown input dtype %d", in_dtype);
+  if (norm != RX_SW_SCALE && norm != RX_SW_ZSCORE) RX_FAIL(RX_EINVAL, "rx_sw_gather: unknown normalization %d", norm);
+  if ((uintptr_t)out & 15) RX_FAIL(RX_EINVAL, "rx_sw_gather: output must be 16-byte aligned");
+  SwPatches p;
+  if (int rc = sw_patches(origins, batch, ring, y, x, pz, py, px, p, "rx_sw_gather")) return rc;
+  const long n = (long)cin * pz * py * px;
+  if (norm == RX_SW_ZSCORE && (!ws || ws_bytes < rx_sw_gather_workspace(batch, cin, pz, py, px)))
+    RX_FAIL(RX_EWORKSPACE, "rx_sw_gather: zscore needs rx_sw_gather_workspace() bytes of workspace");
+  hipStream_t st = (hipStream_t)stream;
+  GatherGeom g;
+  g.cin = cin, g.R = ring, g.Y = y, g.X = x, g.pz = pz, g.py = py, g.px = px, g.pxq = (px + 3) / 4;
+  g.div = in_dtype == RX_SW_U8 ? 255.f : in_dtype == RX_SW_U16 ? 65535.f : 0.f;
+  g.total = (long)batch * cin * pz * py * g.pxq;
+  const dim3 grid((unsigned)((g.total + RX_SW_BLOCK - 1) / RX_SW_BLOCK));
+  if (in_dtype == RX_SW_U8)
+    hipLaunchKernelGGL(sw_gather_kernel<uint8_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint8_t*)slab, out, g, p);
+  else if (in_dtype == RX_SW_U16)
+    hipLaunchKernelGGL(sw_gather_kernel<uint16_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint16_t*)slab, out, g, p);
+  else
+    hipLaunchKernelGGL(sw_gather_kernel<float>, grid, dim3(RX_SW_BLOCK), 0, st, (const float*)slab, out, g, p);
+  if (norm == RX_SW_ZSCORE) {
+    const int chunks = sw_stat_chunks(n);
+    hipLaunchKernelGGL(sw_stat_partial_kernel, dim3(chunks, batch), dim3(RX_SW_BLOCK), 0, st, (const float*)out, n, (double*)ws);
+    long gx = (n / 4 + RX_SW_BLOCK - 1) / RX_SW_BLOCK;
+    gx = gx < 1 ? 1 : gx > 1024 ? 1024 : gx;
+    hipLaunchKernelGGL(sw_standardize_kernel, dim3((unsigned)gx, batch), dim3(RX_SW_BLOCK), 0, st, out, n, (const double*)ws, chunks);
+  }
+  RX_CHECK_LAUNCH("rx_sw_gather");
+  return RX_OK;
+}
+
+// ---- accumulate -----------------------------------------------------------------------------------------------------
+struct AccGeom {
+  int c, pz, py, px, R, Y, X, act, npatch;
+  int bz0, by0, bx0;        // bounding box origin (bx0 rounded down to a multiple of 4 on the vector path)
+  int bny, bnq;             // rows and x-quads of the box
+  int bx1;                  // exclusive x end of the box
+  long total;               // box rows * bny * bnq
+};
+
+__device__ inline float sw_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
+
+// offset (lz*py + ly)*px + lx of voxel (z, y, x) in patch b, or -1 outside it.  b is wave-uniform: the origins are scalar loads.
+__device__ inline int sw_local(const AccGeom& g, const SwPatches& p, int b, int z, int y, int x) {
+  const int lz = z - p.oz[b], ly = y - p.oy[b], lx = x - p.ox[b];
+  return (lz >= 0 && lz < g.pz && ly >= 0 && ly < g.py && lx >= 0 && lx < g.px) ? (lz * g.py + ly) * g.px + lx : -1;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RX_SW_BLOCK) void sw_accumulate_kernel(const float* __restrict__ logits, const float* __restrict__ w,
+                                                                    float* __restrict__ sum, float* __restrict__ wsum, AccGeom g,
+                                                                    SwPatches p) {
+  const long q = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x;
+  if (q >= g.total) return;
+  const int xq = (int)(q % g.bnq);
+  const int yy = (int)((q / g.bnq) % g.bny);
+  const int z = g.bz0 + (int)(q / ((long)g.bnq * g.bny));
+  const int y = g.by0 + yy, x0 = g.bx0 + 4 * xq;
+  const long plane = (long)g.Y * g.X, cstride = (long)g.R * plane;
+  const long base = (long)(z % g.R) * plane + (long)y * g.X + x0;
+  const long pvol = (long)g.pz * g.py * g.px;
+  // quads that straddle the box edge: only voxels inside [bx0, bx1) are read and written on the scalar path; on the vector path
+  // the whole quad is inside the row (X % 4 == 0) and voxels no patch covers are written back unchanged
+  if (wsum) {
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    if (VEC) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(wsum + base);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = v[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (x0 + i < g.bx1) a[i] = wsum[base + i];
+    }
+    for (int b = 0; b < g.npatch; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int l = sw_local(g, p, b, z, y, x0 + i);
+        if (l >= 0) a[i] = a[i] + w[l];
+      }
+    if (VEC) {
+      *reinterpret_cast<f32x4*>(wsum + base) = f32x4{a[0], a[1], a[2], a[3]};
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (x0 + i < g.bx1) wsum[base + i] = a[i];
+    }
+  }
+  for (int ch = 0; ch < g.c; ++ch) {
+    float* sp = sum + ch * cstride + base;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    if (VEC) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(sp);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = v[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (x0 + i < g.bx1) a[i] = sp[i];
+    }
+    for (int b = 0; b < g.npatch; ++b) {
+      const float* lb = logits + (long)b * g.c * pvol;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int l = sw_local(g, p, b, z, y, x0 + i);
+        if (l < 0) continue;
+        float pr = lb[ch * pvol + l];
+        if (g.act == RX_ACT_SIGMOID) {
+          pr = sw_sigmoid(pr);
+        } else if (g.act == RX_ACT_SOFTMAX) {   // torch.softmax over the channels: exp(x - max) / sum exp(x - max)
+          float mx = lb[l];
+          for (int k = 1; k < g.c; ++k) mx = fmaxf(mx, lb[k * pvol + l]);
+          float den = 0.f;
+          for (int k = 0; k < g.c; ++k) den = den + expf(lb[k * pvol + l] - mx);
+          pr = expf(pr - mx) / den;
+        }
+        a[i] = a[i] + w[l] * pr;
+      }
+    }
+    if (VEC) {
+      *reinterpret_cast<f32x4*>(sp) = f32x4{a[0], a[1], a[2], a[3]};
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (x0 + i < g.bx1) sp[i] = a[i];
+    }
+  }
+}
+
+extern "C" int rx_sw_accumulate(const float* logits, int batch, int valid, int c, int pz, int py, int px, const int32_t* origins,
+                                int act, const float* weight, float* sum, float* wsum, int ring, int y, int x, void* stream) {
+  if (!logits || !weight || !sum || c < 1 || ring < 1 || y < 1 || x < 1 || valid < 0 || valid > batch)
+    RX_FAIL(RX_EINVAL, "rx_sw_accumulate: bad arguments");
+  if (act != RX_ACT_NONE && act != RX_ACT_SIGMOID && act != RX_ACT_SOFTMAX) RX_FAIL(RX_EINVAL, "rx_sw_accumulate: unknown activation %d", act);
+  SwPatches p;
+  if (int rc = sw_patches(origins, batch, ring, y, x, pz, py, px, p, "rx_sw_accumulate")) return rc;
+  if (valid == 0) return RX_OK;
+  AccGeom g;
+  g.c = c, g.pz = pz, g.py = py, g.px = px, g.R = ring, g.Y = y, g.X = x, g.act = act, g.npatch = valid;
+  int z0 = p.oz[0], z1 = p.oz[0], y0 = p.oy[0], y1 = p.oy[0], x0 = p.ox[0], x1 = p.ox[0];
+  for (int b = 1; b < valid; ++b) {
+    z0 = p.oz[b] < z0 ? p.oz[b] : z0, z1 = p.oz[b] > z1 ? p.oz[b] : z1;
+    y0 = p.oy[b] < y0 ? p.oy[b] : y0, y1 = p.oy[b] > y1 ? p.oy[b] : y1;
+    x0 = p.ox[b] < x0 ? p.ox[b] : x0, x1 = p.ox[b] > x1 ? p.ox[b] : x1;
+  }
+  // every row of the box must own a ring row of its own: rows [z0, z1 + pz) are live together
+  if (z1 + pz - z0 > ring) RX_FAIL(RX_EINVAL, "rx_sw_accumulate: patches span %d rows, the ring holds %d", z1 + pz - z0, ring);
+  const bool vec = (x & 3) == 0 && ((uintptr_t)sum & 15) == 0 && (!wsum || ((uintptr_t)wsum & 15) == 0);
+  g.bz0 = z0, g.by0 = y0, g.bx0 = vec ? (x0 & ~3) : x0, g.bx1 = x1 + px;
+  g.bny = y1 + py - y0, g.bnq = (g.bx1 - g.bx0 + 3) / 4;
+  g.total = (long)(z1 + pz - z0) * g.bny * g.bnq;
+  const dim3 grid((unsigned)((g.total + RX_SW_BLOCK - 1) / RX_SW_BLOCK));
+  hipStream_t st = (hipStream_t)stream;
+  if (vec)
+    hipLaunchKernelGGL(sw_accumulate_kernel<true>, grid, dim3(RX_SW_BLOCK), 0, st, logits, weight, sum, wsum, g, p);
+  else
+    hipLaunchKernelGGL(sw_accumulate_kernel<false>, grid, dim3(RX_SW_BLOCK), 0, st, logits, weight, sum, wsum, g, p);
+  RX_CHECK_LAUNCH("rx_sw_accumulate");
+  return RX_OK;
+}
+
+// ---- finalize -------------------------------------------------------------------------------------------------------
+struct FinGeom {
+  int c, R, z0, rows, blend, cast, reset;
+  long plane, qpr, nq;      // voxels per row; quads per row; quads per launch
+};
+
+__device__ inline float sw_cast_val(float v, int cast) {
+  if (cast == RX_SW_CAST_U16) {
+    const float t = (v + 1.0f) / 2.0f * 65535.0f;
+    return fminf(fmaxf(t, 0.f), 65535.f);
+  }
+  return fminf(fmaxf(v * 255.0f, 0.f), 255.f);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RX_SW_BLOCK) void sw_finalize_kernel(float* __restrict__ sum, float* __restrict__ wsum,
+                                                                  float* __restrict__ blended, void* __restrict__ final_out,
+                                                                  float* __restrict__ wsum_out, FinGeom g) {
+  const long q = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x;
+  if (q >= g.nq) return;
+  const int row = (int)(q / g.qpr);
+  const long v0 = (q % g.qpr) * 4;
+  const long src = (long)((g.z0 + row) % g.R) * g.plane + v0, dst = (long)row * g.plane + v0;
+  const long cs = (long)g.R * g.plane, os = (long)g.rows * g.plane;
+  const int nv = g.plane - v0 < 4 ? (int)(g.plane - v0) : 4;
+  float wv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (VEC) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(wsum + src);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wv[i] = t[i];
+  } else {
+    for (int i = 0; i < nv; ++i) wv[i] = wsum[src + i];
+  }
+  float mag[4] = {1.f, 1.f, 1.f, 1.f};
+  if (g.blend == RX_SW_BLEND_UNIT) {   // sqrt(s0^2 + s1^2 + s2^2) + 1e-8, the oracle's order of operations
+    for (int i = 0; i < nv; ++i) {
+      const float a = sum[src + i], b = sum[cs + src + i], c = sum[2 * cs + src + i];
+      mag[i] = sqrtf(a * a + b * b + c * c) + 1e-8f;
+    }
+  }
+  for (int ch = 0; ch < g.c; ++ch) {
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    float* sp = sum + ch * cs + src;
+    if (VEC) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(sp);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s[i] = t[i];
+    } else {
+      for (int i = 0; i < nv; ++i) s[i] = sp[i];
+    }
+    float o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float v = s[i];
+      if (wv[i] > 0.f) {
+        if (g.blend == RX_SW_BLEND_AVERAGE) v = v / wv[i];
+        else if (g.blend == RX_SW_BLEND_UNIT) v = v / mag[i];
+      }
+      o[i] = v;
+    }
+    float* bp = blended + ch * os + dst;
+    if (VEC) {
+      *reinterpret_cast<f32x4*>(bp) = f32x4{o[0], o[1], o[2], o[3]};
+      if (g.reset) *reinterpret_cast<f32x4*>(sp) = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+      for (int i = 0; i < nv; ++i) {
+        bp[i] = o[i];
+        if (g.reset) sp[i] = 0.f;
+      }
+    }
+    if (g.cast == RX_SW_CAST_U16) {   // clip, then truncation toward zero as numpy's astype
+      uint16_t* fp = (uint16_t*)final_out + ch * os + dst;
+      uint32_t u[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) u[i] = (uint32_t)(int)sw_cast_val(o[i], g.cast);
+      if (VEC) *reinterpret_cast<u32x2*>(fp) = u32x2{u[0] | (u[1] << 16), u[2] | (u[3] << 16)};
+      else for (int i = 0; i < nv; ++i) fp[i] = (uint16_t)u[i];
+    } else {
+      uint8_t* fp = (uint8_t*)final_out + ch * os + dst;
+      uint32_t u[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) u[i] = (uint32_t)(int)sw_cast_val(o[i], g.cast);
+      if (VEC) *reinterpret_cast<uint32_t*>(fp) = u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24);
+      else for (int i = 0; i < nv; ++i) fp[i] = (uint8_t)u[i];
+    }
+  }
+  if (wsum_out) {
+    if (VEC) *reinterpret_cast<f32x4*>(wsum_out + dst) = f32x4{wv[0], wv[1], wv[2], wv[3]};
+    else for (int i = 0; i < nv; ++i) wsum_out[dst + i] = wv[i];
+  }
+  if (g.reset == 2) {
+    if (VEC) *reinterpret_cast<f32x4*>(wsum + src) = f32x4{0.f, 0.f, 0.f, 0.f};
+    else for (int i = 0; i < nv; ++i) wsum[src + i] = 0.f;
+  }
+}
+
+extern "C" int rx_sw_finalize(float* sum, float* wsum, int c, int ring, int y, int x, int z0, int rows, int blend, int cast,
+                              int reset, float* blended, void* final_out, float* wsum_out, void* stream) {
+  if (!sum || !wsum || !blended || !final_out || c < 1 || ring < 1 || y < 1 || x < 1 || z0 < 0 || rows < 0 || rows > ring)
+    RX_FAIL(RX_EINVAL, "rx_sw_finalize: bad arguments");
+  if (blend < RX_SW_BLEND_AVERAGE || blend > RX_SW_BLEND_NONE) RX_FAIL(RX_EINVAL, "rx_sw_finalize: unknown blend %d", blend);
+  if (blend == RX_SW_BLEND_UNIT && c != 3) RX_FAIL(RX_EINVAL, "rx_sw_finalize: unit-length blending needs 3 channels (got %d)", c);
+  if (cast != RX_SW_CAST_U8 && cast != RX_SW_CAST_U16) RX_FAIL(RX_EINVAL, "rx_sw_finalize: unknown cast %d", cast);
+  if (reset < 0 || reset > 2) RX_FAIL(RX_EINVAL, "rx_sw_finalize: reset must be 0, 1 or 2");
+  if (rows == 0) return RX_OK;
+  FinGeom g;
+  g.c = c, g.R = ring, g.z0 = z0, g.rows = rows, g.blend = blend, g.cast = cast, g.reset = reset;
+  g.plane = (long)y * x;
+  g.qpr = (g.plane + 3) / 4;
+  g.nq = g.qpr * rows;
+  const uintptr_t al = (uintptr_t)sum | (uintptr_t)wsum | (uintptr_t)blended | (uintptr_t)(wsum_out ? wsum_out : blended);
+  const bool vec = (g.plane & 3) == 0 && (al & 15) == 0 && ((uintptr_t)final_out & 7) == 0;
+  const dim3 grid((unsigned)((g.nq + RX_SW_BLOCK - 1) / RX_SW_BLOCK));
+  hipStream_t st = (hipStream_t)stream;
+  if (vec)
+    hipLaunchKernelGGL(sw_finalize_kernel<true>, grid, dim3(RX_SW_BLOCK), 0, st, sum, wsum, blended, final_out, wsum_out, g);
+  else
+    hipLaunchKernelGGL(sw_finalize_kernel<false>, grid, dim3(RX_SW_BLOCK), 0, st, sum, wsum, blended, final_out, wsum_out, g);
+  RX_CHECK_LAUNCH("rx_sw_finalize");
+  return RX_OK;
+}

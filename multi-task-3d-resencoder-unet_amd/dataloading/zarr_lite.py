@@ -113,6 +113,30 @@ def open(path, mode="r"):   # noqa: A001  (mirrors zarr.open)
     return Array(path)
 
 
+def _write_meta(path, shape, chunks, dtype, compressor, fill_value, dimension_separator):
+    meta = dict(zarr_format=2, shape=list(shape), chunks=list(chunks), dtype=np.dtype(dtype).str, order="C",
+                fill_value=fill_value, filters=None, dimension_separator=dimension_separator,
+                compressor=None if compressor is None else {"id": "zlib", "level": 1})
+    with builtins.open(os.path.join(path, ".zarray"), "w") as f:
+        json.dump(meta, f)
+
+
+def _store_chunk(path, idx, sub, chunks, fill_value, compressor, dimension_separator):
+    """one chunk: `sub` (the part inside the array) padded to the full chunk size; all-fill chunks are skipped like zarr does"""
+    block = np.full(chunks, fill_value, dtype=sub.dtype)
+    block[tuple(slice(0, n) for n in sub.shape)] = sub
+    if not (block != fill_value).any():
+        return
+    raw = block.tobytes(order="C")
+    if compressor == "zlib":
+        raw = zlib.compress(raw, 1)
+    name = dimension_separator.join(str(i) for i in idx)
+    fn = os.path.join(path, *name.split("/")) if dimension_separator == "/" else os.path.join(path, name)
+    os.makedirs(os.path.dirname(fn), exist_ok=True)
+    with builtins.open(fn, "wb") as f:
+        f.write(raw)
+
+
 def write_array(path, data, chunks, compressor=None, fill_value=0, dimension_separator="."):
     """write `data` as a zarr v2 directory store (compressor None or 'zlib'); all-fill chunks are skipped like zarr does"""
     data = np.asarray(data)
@@ -120,25 +144,59 @@ def write_array(path, data, chunks, compressor=None, fill_value=0, dimension_sep
     if compressor not in (None, "zlib"):
         raise ZarrLiteError("write_array: compressor None or 'zlib'")
     os.makedirs(path, exist_ok=True)
-    meta = dict(zarr_format=2, shape=list(data.shape), chunks=list(chunks), dtype=data.dtype.str, order="C",
-                fill_value=fill_value, filters=None, dimension_separator=dimension_separator,
-                compressor=None if compressor is None else {"id": "zlib", "level": 1})
-    with builtins.open(os.path.join(path, ".zarray"), "w") as f:
-        json.dump(meta, f)
+    _write_meta(path, data.shape, chunks, data.dtype, compressor, fill_value, dimension_separator)
     grid = [(s + c - 1) // c for s, c in zip(data.shape, chunks)]
     for idx in np.ndindex(*grid):
-        block = np.full(chunks, fill_value, dtype=data.dtype)
         sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, chunks, data.shape))
-        sub = data[sl]
-        block[tuple(slice(0, n) for n in sub.shape)] = sub
-        if not (block != fill_value).any():
-            continue
-        raw = block.tobytes(order="C")
-        if compressor == "zlib":
-            raw = zlib.compress(raw, 1)
-        name = dimension_separator.join(str(i) for i in idx)
-        fn = os.path.join(path, *name.split("/")) if dimension_separator == "/" else os.path.join(path, name)
-        os.makedirs(os.path.dirname(fn), exist_ok=True)
-        with builtins.open(fn, "wb") as f:
-            f.write(raw)
+        _store_chunk(path, idx, data[sl], chunks, fill_value, compressor, dimension_separator)
     return Array(path)
+
+
+class ChunkedWriter:
+    """A zarr v2 array filled one block of Z rows at a time, for outputs that never exist whole on the host.
+
+    Z is the third axis from the end ((Z, Y, X) or (C, Z, Y, X)).  `write_rows(z0, block)` takes rows [z0, z0 + n): z0 on a chunk
+    boundary and n a whole number of chunk rows, or the rows up to the end of the array (the partial edge chunks are stored at full
+    chunk size, as `write_array` does).  Every chunk is an independent file, so the chunk writes of one call may run on a thread
+    pool (`pool.submit`; zlib releases the GIL): the call then returns the futures.  Refuses an existing path."""
+
+    def __init__(self, path, shape, chunks, dtype, compressor=None, fill_value=0, dimension_separator="."):
+        self.path = str(path)
+        self.shape = tuple(int(s) for s in shape)
+        self.chunks = tuple(int(c) for c in chunks)
+        self.dtype = np.dtype(dtype)
+        if compressor not in (None, "zlib"):
+            raise ZarrLiteError("ChunkedWriter: compressor None or 'zlib'")
+        if dimension_separator not in (".", "/"):
+            raise ZarrLiteError("ChunkedWriter: dimension_separator '.' or '/'")
+        if len(self.shape) < 3 or len(self.chunks) != len(self.shape):
+            raise ZarrLiteError(f"ChunkedWriter: shape {self.shape} / chunks {self.chunks}: need (..., Z, Y, X) and one chunk per axis")
+        if os.path.exists(self.path):
+            raise FileExistsError(f"{self.path} already exists")
+        self.compressor, self.fill_value, self.sep = compressor, fill_value, dimension_separator
+        self.axis = len(self.shape) - 3
+        os.makedirs(self.path)
+        _write_meta(self.path, self.shape, self.chunks, self.dtype, compressor, fill_value, dimension_separator)
+
+    def write_rows(self, z0, block, pool=None):
+        block = np.asarray(block)
+        if block.dtype != self.dtype:
+            raise ZarrLiteError(f"write_rows: dtype {block.dtype}, array is {self.dtype}")
+        a, cz, Z = self.axis, self.chunks[self.axis], self.shape[self.axis]
+        n = block.shape[a]
+        want = self.shape[:a] + (n,) + self.shape[a + 1:]
+        if block.shape != want:
+            raise ZarrLiteError(f"write_rows: block {block.shape}, expected {want}")
+        if z0 % cz or n < 1 or z0 + n > Z or (n % cz and z0 + n != Z):
+            raise ZarrLiteError(f"write_rows: rows [{z0}, {z0 + n}) are not whole chunk rows of {cz} (Z = {Z})")
+        grid = [(s + c - 1) // c for s, c in zip(block.shape, self.chunks)]
+        futures = []
+        for idx in np.ndindex(*grid):
+            sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, self.chunks, block.shape))
+            gidx = idx[:a] + (idx[a] + z0 // cz,) + idx[a + 1:]
+            args = (self.path, gidx, block[sl], self.chunks, self.fill_value, self.compressor, self.sep)
+            if pool is None:
+                _store_chunk(*args)
+            else:
+                futures.append(pool.submit(_store_chunk, *args))
+        return futures

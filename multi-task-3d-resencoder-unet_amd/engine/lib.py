@@ -13,6 +13,10 @@ LIB_PATH = os.environ.get("RX_LIBRARY") or os.path.join(os.path.dirname(_HERE), 
 RX_F32, RX_BF16, RX_F16 = 0, 1, 2
 RX_ACT_NONE, RX_ACT_SIGMOID, RX_ACT_SOFTMAX = 0, 1, 2
 DTYPE_CODE = {torch.float32: RX_F32, torch.bfloat16: RX_BF16, torch.float16: RX_F16}
+RX_SW_U8, RX_SW_U16, RX_SW_F32 = 0, 1, 2
+RX_SW_SCALE, RX_SW_ZSCORE = 0, 1
+RX_SW_BLEND_AVERAGE, RX_SW_BLEND_UNIT, RX_SW_BLEND_NONE = 0, 1, 2
+RX_SW_CAST_U8, RX_SW_CAST_U16 = 0, 1
 
 
 class RxError(RuntimeError):
@@ -121,6 +125,13 @@ _SIGNATURES = {
     "rx_stream_wait": (c_int, [c_int, c_void_p]),
     "rx_adamw_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_double, c_int,
                               c_long, c_void_p]),
+    "rx_sw_gather_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "rx_sw_gather": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                             c_void_p, c_size_t, c_void_p]),
+    "rx_sw_accumulate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_int, c_int, c_int, c_void_p]),
+    "rx_sw_finalize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@ asked for raw logits (`NetworkFromConfig.forward_logits`) -- the activation is a
 inference.py:121-133 does it from the target's `activation` key, never twice, so a CPU tensor is an error as everywhere
 else in this package.  Accumulation / blending are a handful of torch slice ops on device tensors: plumbing, not kernels.
 """
+import ctypes
 import json
 import os
 from typing import Dict, Optional, Sequence, Tuple
@@ -176,3 +177,460 @@ class SlidingWindowInferer:
             zarr_lite.write_array(os.path.join(store, f"{name}_count"), cnt, (pz, py, px), compressor=compressor)
             zarr_lite.write_array(os.path.join(store, f"{name}_final"), final_np, chunks, compressor=compressor)
         return store
+
+
+# ---- Gaussian importance map (reference inference/helpers.py:8-91) -------------------------------------------------------------
+def _gaussian_kernel1d(sigma: float, radius: int) -> np.ndarray:
+    """scipy.ndimage's order-0 kernel: exp(-x^2 / 2 sigma^2) on [-radius, radius], normalised, float64"""
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return phi / phi.sum()
+
+
+def gaussian_importance_map(patch: Sequence[int], sigma_scale: float = 1.0 / 8, value_scaling_factor: float = 1.0) -> np.ndarray:
+    """float32 (pz, py, px) blending weights: `compute_gaussian_3d` (helpers.py:8-68) without scipy.
+
+    The reference filters a unit delta at `dim // 2` with `scipy.ndimage.gaussian_filter(sigma = dim * sigma_scale,
+    mode='constant')`.  For a delta that filter is separable and exact to restate: scipy runs one 1-D pass per axis (axis 0 first;
+    axes with sigma <= 1e-15 skipped), each pass sums in float64 with the kernel of `_gaussian_kernel1d` (radius
+    int(4 sigma + 0.5)) and rounds to the float32 output; along a line with one non-zero value the sum IS that value times one tap.
+    So pass k turns the float32 result of pass k-1 into float32(float64(v) * w_k[i]), which is what is computed here.  Then, as the
+    reference: divide by the max over the peak value, replace exact zeros by the smallest positive value."""
+    patch = tuple(int(d) for d in patch)
+    g = np.ones((1,) * len(patch), dtype=np.float32)
+    for axis, dim in enumerate(patch):
+        sigma = dim * sigma_scale
+        line = np.zeros(dim, dtype=np.float64)
+        c = dim // 2
+        if sigma > 1e-15:
+            radius = int(4.0 * float(sigma) + 0.5)
+            k = _gaussian_kernel1d(float(sigma), radius)
+            lo, hi = max(0, c - radius), min(dim, c + radius + 1)
+            line[lo:hi] = k[lo - c + radius:hi - c + radius]
+        else:
+            line[c] = 1.0
+        shape = [1] * len(patch)
+        shape[axis] = dim
+        g = (g.astype(np.float64) * line.reshape(shape)).astype(np.float32)
+    g /= (g.max() / value_scaling_factor)
+    g[g == 0] = g[g > 0].min()
+    return np.ascontiguousarray(g)
+
+
+_WEIGHT_CACHE: Dict[tuple, torch.Tensor] = {}
+
+
+def _device_weights(kind: str, patch: Tuple[int, int, int], device) -> torch.Tensor:
+    """the patch-shaped weight table on the device, uploaded once per (kind, patch, device)"""
+    key = (kind, tuple(patch), str(device))
+    w = _WEIGHT_CACHE.get(key)
+    if w is None:
+        host = gaussian_importance_map(patch) if kind == "gaussian" else np.ones(patch, dtype=np.float32)
+        w = torch.from_numpy(host).to(device)
+        _WEIGHT_CACHE[key] = w
+    return w
+
+
+# ---- streaming schedule (pure: testable without a device) ------------------------------------------------------------------
+def stream_schedule(shape: Sequence[int], patch: Sequence[int], overlap: float, batch_size: int, cin: int = 1,
+                    in_itemsize: int = 1, acc_channels: int = 1, out_bytes_per_voxel: int = 0) -> dict:
+    """Positions -> the order of work of `StreamingInferer`, one step per z-origin z_k (all_positions is z-major):
+
+      load      input rows [lo, hi) to bring to the device (hi = z_k + pz; rows already there are not read again)
+      batches   [(B positions, valid)] of the patches at z_k; the last is padded by repeating its last patch (one plan shape)
+      finalize  rows [lo, hi) no later patch touches (hi = z_{k+1}, the volume end at the last step): blended, cast, copied out
+      write     output rows [lo, hi) whose chunk rows (chunk = patch) are now complete
+
+    Device arrays are rings of `ring` = pz rows (the rows [z_k, z_k + pz) are the only ones live at step k: rows below z_k were
+    finalized at step k-1), so the reported bytes do not depend on Z:
+      accumulator_bytes  fp32 sums of every channel plus the weight sum
+      input_bytes        the input ring (and `staging_bytes` covers the largest finalize block: blended + final + weight sum)
+      patch_bytes        the fp32 (B, Cin, pz, py, px) batch the network reads
+    """
+    Z, Y, X = (int(s) for s in shape)
+    pz = int(patch[0])
+    pos = all_positions((Z, Y, X), patch, overlap)
+    B = max(1, min(int(batch_size), len(pos)))
+    rows: Dict[int, list] = {}
+    for p in pos:
+        rows.setdefault(p[0], []).append(p)
+    zs = sorted(rows)
+    steps, loaded, fin, written = [], 0, 0, 0
+    for k, zk in enumerate(zs):
+        batches = []
+        row = rows[zk]
+        for i in range(0, len(row), B):
+            chunk = row[i:i + B]
+            batches.append((tuple(chunk) + (chunk[-1],) * (B - len(chunk)), len(chunk)))
+        load = (max(loaded, zk), zk + pz)
+        loaded = zk + pz
+        f_hi = zs[k + 1] if k + 1 < len(zs) else Z
+        w_hi = Z if f_hi == Z else (f_hi // pz) * pz
+        steps.append(dict(z=zk, load=load, batches=batches, finalize=(fin, f_hi), write=(written, max(written, w_hi))))
+        fin, written = f_hi, max(written, w_hi)
+    max_fin = max(s["finalize"][1] - s["finalize"][0] for s in steps)
+    plane = Y * X
+    acc = pz * plane * 4 * (int(acc_channels) + 1)
+    inp = int(cin) * pz * plane * int(in_itemsize)
+    staging = max_fin * plane * int(out_bytes_per_voxel)
+    patch_b = B * int(cin) * int(np.prod(patch)) * 4
+    return dict(positions=pos, batch=B, ring=pz, steps=steps, max_finalize_rows=max_fin, accumulator_bytes=acc,
+                input_bytes=inp, staging_bytes=staging, patch_bytes=patch_b, device_bytes=acc + inp + staging + patch_b)
+
+
+_IN_CODES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2}     # RX_SW_U8 / U16 / F32
+_ACT_CODES = {"none": 0, "sigmoid": 1, "softmax": 2}                                        # rx_head_act
+
+
+def _open_source(source):
+    if isinstance(source, (str, os.PathLike)):
+        from .dataloading import zarr_lite
+        source = zarr_lite.open(str(source))
+    if len(source.shape) not in (3, 4):
+        raise ValueError(f"source must be (Z, Y, X) or (C, Z, Y, X), got shape {tuple(source.shape)}")
+    dt = np.dtype(source.dtype)
+    if dt not in _IN_CODES:
+        raise ValueError(f"source dtype {dt}: streaming inference reads uint8, uint16 or float32")
+    return source
+
+
+class StreamingInferer:
+    """Out-of-core sliding-window inference: `StreamingInferer(model, ...).run(source, output_path)` -> `<output_path>/predictions.zarr`.
+
+    The volume is read slab by slab (rows [z_k, z_k + pz) of each z-origin, see `stream_schedule`) and the output is written chunk
+    row by chunk row; device memory is O(pz * Y * X), independent of Z.  The work around the network forward is HIP
+    (csrc/rx_infer.hip): gather + normalisation of the patches, activation + weighted accumulation, finalize + integer cast.
+
+    model / targets / patch_size / batch_size / overlap / compute_dtype: as `SlidingWindowInferer`.
+    blend          "uniform" (the reference's rule, default): every patch weighs 1, so `<t>_count` is the patch count and the
+                   result is `SlidingWindowInferer`'s; "gaussian": patches weighted by `gaussian_importance_map(patch)`, `<t>_count`
+                   then holds the Gaussian weight SUM and the average is sum(w p) / sum(w).
+    normalization  "scale" (default): uint8 / 255, uint16 / 65535, float32 as is (the training feeder, dataset.py:179-184);
+                   "zscore": then (x - mean) / max(std, 1e-10) per patch over all voxels and channels (population std), the
+                   reference inference dataset's pytorch3dunet `Standardize(channelwise=False)` -- that package is not available
+                   here, so this parity is UNPINNED; the statistics are summed in fp64 in a fixed order.
+    max_device_bytes  refuse (before any launch) a volume whose slab, plan included, does not fit.  No Y/X tiling.
+    source         a zarr path, a `zarr_lite` array, or any numpy-sliceable (Z, Y, X) / (C, Z, Y, X) array (e.g. a memmap) of
+                   uint8 / uint16 / float32.
+    The output store has `write_store`'s array set, dtypes, shapes and chunking (= patch), zlib or raw chunks.  Host work
+    overlaps the device: the next slab is read on a worker thread; D2H results are assembled and compressed on a pool of at most
+    16 threads.
+    """
+
+    def __init__(self, model, targets: Optional[dict] = None, patch_size: Optional[Sequence[int]] = None, batch_size: int = 2,
+                 overlap: float = 0.5, compute_dtype: Optional[torch.dtype] = torch.bfloat16, blend: str = "uniform",
+                 normalization: str = "scale", max_device_bytes: Optional[int] = None, device="cuda", io_threads: int = 16):
+        self.model = model
+        self.targets = dict(targets if targets is not None else model.tasks)
+        self.patch = tuple(int(p) for p in (patch_size if patch_size is not None else model.patch_size))
+        if len(self.patch) != 3:
+            raise ValueError("sliding-window inference is implemented for 3-D patches")
+        self.batch_size = int(batch_size)
+        if not 1 <= self.batch_size <= 32:
+            raise ValueError("batch_size must be 1..32")
+        self.overlap = float(overlap)
+        self.compute_dtype = compute_dtype
+        self.blend = str(blend).lower()
+        if self.blend not in ("uniform", "gaussian"):
+            raise ValueError(f"blend must be 'uniform' or 'gaussian', got {blend!r}")
+        self.normalization = str(normalization).lower()
+        if self.normalization not in ("scale", "zscore"):
+            raise ValueError(f"normalization must be 'scale' or 'zscore', got {normalization!r}")
+        self.max_device_bytes = max_device_bytes
+        self.device = torch.device(device)
+        self.io_threads = max(1, min(16, int(io_threads)))
+        self.last_schedule = None
+        self.last_timing = None
+
+    def _task_modes(self, name, t):
+        from .engine import lib as L
+        c = int(t["channels"])
+        if name.lower() == "normals":
+            return c, (L.RX_SW_BLEND_UNIT if c == 3 else L.RX_SW_BLEND_NONE), L.RX_SW_CAST_U16, np.uint16
+        return c, L.RX_SW_BLEND_AVERAGE, L.RX_SW_CAST_U8, np.uint8
+
+    def schedule(self, shape, cin: int = 1, in_itemsize: int = 1) -> dict:
+        sc = sum(int(t["channels"]) for t in self.targets.values())
+        out_b = 4 + sum(int(t["channels"]) * (4 + (2 if n.lower() == "normals" else 1)) for n, t in self.targets.items())
+        return stream_schedule(shape, self.patch, self.overlap, self.batch_size, cin, in_itemsize, sc, out_b)
+
+    @torch.no_grad()
+    def run(self, source, output_path: str, compressor: Optional[str] = "zlib") -> str:
+        import threading
+        import time
+        from concurrent.futures import ThreadPoolExecutor
+        from .dataloading import zarr_lite
+        from .engine import lib as L
+        store = os.path.join(output_path, "predictions.zarr")
+        if os.path.isdir(store):
+            raise FileExistsError(f"Zarr store '{store}' already exists. Aborting to prevent overwrite.")
+        src = _open_source(source)
+        four = len(src.shape) == 4
+        cin = int(src.shape[0]) if four else 1
+        Z, Y, X = (int(s) for s in src.shape[-3:])
+        in_dt = np.dtype(src.dtype)
+        pz, py, px = self.patch
+        sched = self.schedule((Z, Y, X), cin, in_dt.itemsize)
+        self.last_schedule = sched
+        B = sched["batch"]
+        L.require_device()
+        dev = self.device
+
+        # the plan for (B, Cin, patch) -- allocation only -- then the budget check, before any launch
+        was_training = self.model.training
+        prev_dtype = getattr(self.model, "compute_dtype", None)
+        self.model.eval()
+        if self.compute_dtype is not None:
+            self.model.compute_dtype = self.compute_dtype
+        try:
+            plan = self.model.plan_for(torch.Size((B, cin, pz, py, px)), self.model._resolve_dtype(), dev, False)
+            if self.max_device_bytes is not None:
+                need = sched["device_bytes"] + int(plan.bytes_alloc)
+                if need > self.max_device_bytes:
+                    raise MemoryError(f"streaming inference needs {need / 2**30:.3f} GiB on the device for one slab of {pz} x {Y} x {X} "
+                                      f"(plan {plan.bytes_alloc / 2**30:.3f} GiB included), the budget is "
+                                      f"{self.max_device_bytes / 2**30:.3f} GiB; Y/X tiling is not implemented")
+            return self._run(src, four, cin, (Z, Y, X), in_dt, sched, plan, store, compressor, zarr_lite, L,
+                             ThreadPoolExecutor, threading, time)
+        finally:
+            self.model.compute_dtype = prev_dtype
+            self.model.train(was_training)
+
+    def _run(self, src, four, cin, shape, in_dt, sched, plan, store, compressor, zarr_lite, L, ThreadPoolExecutor, threading, time):
+        Z, Y, X = shape
+        pz, py, px = self.patch
+        B, R = sched["batch"], sched["ring"]
+        dev = self.device
+        lib = L.load()
+        t_start = time.perf_counter()
+
+        # device state: input ring, accumulators (one wsum shared by every task), finalize staging, the batch, weights
+        tdt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.int16, np.dtype(np.float32): torch.float32}[in_dt]
+        ring_in = torch.empty((cin, R, Y, X), dtype=tdt, device=dev)
+        tasks = []
+        for name, t in self.targets.items():
+            c, blend, cast, fdt = self._task_modes(name, t)
+            act = _ACT_CODES.get(str(t.get("activation", "none") or "none").lower(), 0)
+            tasks.append(dict(name=name, c=c, blend=blend, cast=cast, fdt=fdt, act=act,
+                              sum=torch.zeros((c, R, Y, X), dtype=torch.float32, device=dev)))
+        wsum = torch.zeros((R, Y, X), dtype=torch.float32, device=dev)
+        # finalize blocks of n <= F rows are written as contiguous (c, n, Y, X) arrays: flat buffers, viewed per block
+        F = sched["max_finalize_rows"]
+        for tk in tasks:
+            tk["tdt"] = torch.uint8 if tk["fdt"] == np.uint8 else torch.int16
+            tk["blended"] = torch.empty((tk["c"] * F * Y * X,), dtype=torch.float32, device=dev)
+            tk["final"] = torch.empty((tk["c"] * F * Y * X,), dtype=tk["tdt"], device=dev)
+        wsum_out = torch.empty((F, Y, X), dtype=torch.float32, device=dev)
+        xb = torch.empty((B, cin, pz, py, px), dtype=torch.float32, device=dev)
+        weights = _device_weights(self.blend, self.patch, dev)
+        ws_b = lib.rx_sw_gather_workspace(B, cin, pz, py, px) if self.normalization == "zscore" else 0
+        ws = torch.empty((max(1, ws_b // 8),), dtype=torch.float64, device=dev)
+        norm = L.RX_SW_ZSCORE if self.normalization == "zscore" else L.RX_SW_SCALE
+        in_code = _IN_CODES[in_dt]
+        O3 = ctypes.c_int32 * (3 * B)
+
+        # output store
+        os.makedirs(store)
+        with open(os.path.join(store, ".zgroup"), "w") as f:
+            json.dump({"zarr_format": 2}, f)
+        writers = {}
+        for tk in tasks:
+            c, n = tk["c"], tk["name"]
+            shp, ch = ((Z, Y, X), (pz, py, px)) if c == 1 else ((c, Z, Y, X), (c, pz, py, px))
+            writers[n] = (zarr_lite.ChunkedWriter(os.path.join(store, f"{n}_sum"), shp, ch, np.float32, compressor),
+                          zarr_lite.ChunkedWriter(os.path.join(store, f"{n}_count"), (Z, Y, X), (pz, py, px), np.float32, compressor),
+                          zarr_lite.ChunkedWriter(os.path.join(store, f"{n}_final"), shp, ch, tk["fdt"], compressor))
+
+        # host staging: two pinned input buffers and two pinned output sets, each guarded by an event
+        # (flat as well: every asynchronous copy below is contiguous on both sides)
+        in_pin = [torch.empty((cin * pz * Y * X,), dtype=tdt).pin_memory() for _ in range(2)]
+        in_ev = [None, None]
+        out_pin = [dict(w=torch.empty((F, Y, X), dtype=torch.float32).pin_memory(),
+                        **{tk["name"]: (torch.empty((tk["c"] * F * Y * X,), dtype=torch.float32).pin_memory(),
+                                        torch.empty((tk["c"] * F * Y * X,), dtype=tk["tdt"]).pin_memory()) for tk in tasks})
+                   for _ in range(2)]
+        out_busy = [None, None]
+        # rows finalized but not yet written (at most one chunk row plus one finalize block)
+        pend_rows = pz + F
+        pend = {tk["name"]: (np.zeros((tk["c"], pend_rows, Y, X), np.float32), np.zeros((tk["c"], pend_rows, Y, X), tk["fdt"]))
+                for tk in tasks}
+        pend_w = np.zeros((pend_rows, Y, X), np.float32)
+        state = dict(base=0)          # volume row of pend[..., 0, :, :]
+        timing = dict(read_s=0.0, write_wait_s=0.0)
+        lock = threading.Lock()
+
+        chunks = getattr(src, "chunks", None)
+        cy = int(chunks[-2]) if chunks is not None and len(chunks) == len(src.shape) else Y
+
+        def read_piece(a, lo, hi, y0, y1):
+            a[:, :, y0:y1] = src[:, lo:hi, y0:y1] if four else src[lo:hi, y0:y1][None]
+
+        def read_rows(lo, hi):
+            """rows [lo, hi) of every channel, read as columns of whole chunks on the I/O pool (zlib releases the GIL)"""
+            t0 = time.perf_counter()
+            a = np.empty((cin, hi - lo, Y, X), in_dt)
+            for f in [pool.submit(read_piece, a, lo, hi, y0, min(Y, y0 + cy)) for y0 in range(0, Y, cy)]:
+                f.result()
+            if a.dtype == np.uint16:
+                a = a.view(np.int16)
+            with lock:
+                timing["read_s"] += time.perf_counter() - t0
+            return a
+
+        pool = ThreadPoolExecutor(max_workers=self.io_threads)
+        reader = ThreadPoolExecutor(max_workers=1)
+        drainer = ThreadPoolExecutor(max_workers=1)
+        chunk_futs = []
+
+        def drain(slot, ev, f_lo, n, w_lo, w_hi):
+            """host side of one finalize block: wait for its D2H, park the rows, hand complete chunk rows to the pool"""
+            ev.synchronize()
+            o = out_pin[slot]
+            off = f_lo - state["base"]
+            pend_w[off:off + n] = o["w"][:n].numpy()
+            for tk in tasks:
+                b, f = o[tk["name"]]
+                m4 = (tk["c"], n, Y, X)
+                pend[tk["name"]][0][:, off:off + n] = b[:tk["c"] * n * Y * X].view(m4).numpy()
+                fv = f[:tk["c"] * n * Y * X].view(m4).numpy()
+                pend[tk["name"]][1][:, off:off + n] = fv.view(np.uint16) if tk["fdt"] == np.uint16 else fv
+            if w_hi > w_lo:
+                m = w_hi - w_lo
+                assert w_lo == state["base"]
+                wblk = pend_w[:m].copy()
+                for tk in tasks:
+                    s_w, c_w, f_w = writers[tk["name"]]
+                    bb, ff = pend[tk["name"]][0][:, :m].copy(), pend[tk["name"]][1][:, :m].copy()
+                    if tk["c"] == 1:
+                        bb, ff = bb[0], ff[0]
+                    chunk_futs.extend(s_w.write_rows(w_lo, bb, pool))
+                    chunk_futs.extend(c_w.write_rows(w_lo, wblk, pool))
+                    chunk_futs.extend(f_w.write_rows(w_lo, ff, pool))
+                keep = off + n - m
+                pend_w[:keep] = pend_w[m:m + keep].copy()
+                for tk in tasks:
+                    for arr in pend[tk["name"]]:
+                        arr[:, :keep] = arr[:, m:m + keep].copy()
+                state["base"] = w_hi
+
+        steps = sched["steps"]
+        nxt = reader.submit(read_rows, *steps[0]["load"])
+        drains = []
+        n_fwd = 0
+        stream = torch.cuda.current_stream(dev)
+        sp = L.stream_ptr()
+        try:
+            for k, st in enumerate(steps):
+                lo, hi = st["load"]
+                host = nxt.result()
+                if k + 1 < len(steps):
+                    nl, nh = steps[k + 1]["load"]
+                    nxt = reader.submit(read_rows, nl, nh)
+                if hi > lo:
+                    slot = k % 2
+                    if in_ev[slot] is not None:
+                        in_ev[slot].synchronize()
+                    pin = in_pin[slot][:cin * (hi - lo) * Y * X].view(cin, hi - lo, Y, X)
+                    pin.copy_(torch.from_numpy(host))
+                    z = lo
+                    while z < hi:                          # ring rows wrap: at most two contiguous pieces per channel
+                        r0 = z % R
+                        seg = min(hi - z, R - r0)
+                        for ci in range(cin):
+                            ring_in[ci, r0:r0 + seg].copy_(pin[ci, z - lo:z - lo + seg], non_blocking=True)
+                        z += seg
+                    ev = torch.cuda.Event()
+                    ev.record(stream)
+                    in_ev[slot] = ev
+                for chunk, valid in st["batches"]:
+                    org = O3(*[v for p in chunk for v in p])
+                    L.check(lib.rx_sw_gather(in_code, ring_in.data_ptr(), cin, R, Y, X, B, org, pz, py, px, norm, xb.data_ptr(),
+                                             ws.data_ptr(), ws_b, sp), "rx_sw_gather")
+                    outs = plan.run_forward(xb, apply_act=False)     # the plan's own head buffers, read before the next forward
+                    n_fwd += 1
+                    for i, tk in enumerate(tasks):
+                        L.check(lib.rx_sw_accumulate(outs[tk["name"]].data_ptr(), B, valid, tk["c"], pz, py, px, org, tk["act"],
+                                                     weights.data_ptr(), tk["sum"].data_ptr(), wsum.data_ptr() if i == 0 else None,
+                                                     R, Y, X, sp), "rx_sw_accumulate")
+                f_lo, f_hi = st["finalize"]
+                n = f_hi - f_lo
+                if n > 0:
+                    slot = k % 2
+                    if out_busy[slot] is not None:                     # its previous block has been parked on the host
+                        t0 = time.perf_counter()
+                        out_busy[slot].result()
+                        timing["write_wait_s"] += time.perf_counter() - t0
+                    o = out_pin[slot]
+                    for i, tk in enumerate(tasks):
+                        L.check(lib.rx_sw_finalize(tk["sum"].data_ptr(), wsum.data_ptr(), tk["c"], R, Y, X, f_lo, n, tk["blend"],
+                                                   tk["cast"], 2 if i == len(tasks) - 1 else 1, tk["blended"].data_ptr(),
+                                                   tk["final"].data_ptr(), wsum_out.data_ptr() if i == 0 else None, sp),
+                                "rx_sw_finalize")
+                        b, f = o[tk["name"]]
+                        m = tk["c"] * n * Y * X
+                        b[:m].copy_(tk["blended"][:m], non_blocking=True)
+                        f[:m].copy_(tk["final"][:m], non_blocking=True)
+                    o["w"][:n].copy_(wsum_out[:n], non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(stream)
+                    w_lo, w_hi = st["write"]
+                    out_busy[slot] = drainer.submit(drain, slot, ev, f_lo, n, w_lo, w_hi)
+                    drains.append(out_busy[slot])
+            for d in drains:
+                d.result()
+            t0 = time.perf_counter()
+            for fu in chunk_futs:
+                fu.result()
+            timing["write_wait_s"] += time.perf_counter() - t0
+        finally:
+            reader.shutdown(wait=True)
+            drainer.shutdown(wait=True)
+            pool.shutdown(wait=True)
+        timing.update(total_s=time.perf_counter() - t_start, forwards=n_fwd, patches=len(sched["positions"]))
+        self.last_timing = timing
+        return store
+
+
+# ---- command line: `python -m mt3d_amd.inference --config_path X` ---------------------------------------------------------------
+def load_model(mgr, device="cuda"):
+    """NetworkFromConfig(mgr) with the weights of `inference_config.checkpoint_path`, loaded as the trainer resumes
+    (checkpoint["model"], `_orig_mod.` prefixes of a compiled model stripped, train.py:251-252)"""
+    from .builders.build_network_from_config import NetworkFromConfig
+    model = NetworkFromConfig(mgr).to(device)
+    if not mgr.infer_checkpoint_path:
+        raise ValueError("inference_config.checkpoint_path is required")
+    ck = torch.load(mgr.infer_checkpoint_path, map_location=device, weights_only=True)
+    sd = ck["model"] if isinstance(ck, dict) and "model" in ck else ck
+    model.load_state_dict({(k[len("_orig_mod."):] if k.startswith("_orig_mod.") else k): v for k, v in sd.items()})
+    return model
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description="Streaming sliding-window inference of the multi-task 3-D ResEnc U-Net (HIP engine).")
+    ap.add_argument("--config_path", type=str, required=True)
+    ap.add_argument("--input_path", type=str, default=None, help="overrides inference_config.input_path")
+    ap.add_argument("--output_path", type=str, default=None, help="overrides inference_config.output_path")
+    ap.add_argument("--compressor", choices=["zlib", "none"], default="zlib")
+    ap.add_argument("--write_layers", action="store_true", help="(reference option: per-slice image layers; needs cv2)")
+    ap.add_argument("--verbose", action="store_true")
+    a = ap.parse_args(argv)
+    if a.write_layers:
+        raise SystemExit("--write_layers writes image slices with cv2 (OpenCV), which is not available in this environment; "
+                         "the zarr store is the only output")
+    from .configuration.config_manager import ConfigManager
+    mgr = ConfigManager(a.config_path, verbose=a.verbose)
+    src = a.input_path or mgr.infer_input_path
+    if not src:
+        raise SystemExit("no input: set inference_config.input_path or pass --input_path")
+    gb = mgr.infer_max_device_gb
+    runner = StreamingInferer(load_model(mgr), mgr.infer_targets, mgr.infer_patch_size, mgr.infer_batch_size, mgr.infer_overlap,
+                              blend=mgr.infer_blend, normalization=mgr.infer_normalization,
+                              max_device_bytes=None if gb is None else int(gb * 2**30))
+    store = runner.run(src, a.output_path or mgr.infer_output_path, compressor=None if a.compressor == "none" else "zlib")
+    print(store, flush=True)
+    return store
+
+
+if __name__ == "__main__":
+    main()

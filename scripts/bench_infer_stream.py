@@ -1,0 +1,116 @@
+"""Streaming sliding-window inference (inference.StreamingInferer) against the HBM-resident SlidingWindowInferer on the same volume:
+the cfg2 network, bf16, 128^3 patches, overlap 0.5, a synthetic uint8 zarr of 256 x 768 x 768 (default) on local disk.
+
+    python scripts/bench_infer_stream.py [--z 256 --yx 768] [--runs 3] [--modes raw,zlib,resident] [--keep DIR]
+
+Alternates the modes run by run and prints one JSON line per run and a summary line: patches/s and Mvoxel/s of volume, and for the
+streaming runs where the host time went (slab reads, waits for the chunk writers).  `--modes raw --runs 1` under
+`rocprofv3 --kernel-trace --stats` gives the per-kernel times of rx_sw_gather / rx_sw_accumulate / rx_sw_finalize."""
+import argparse
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench as B  # noqa: E402
+import mt3d_amd  # noqa: E402,F401
+from mt3d_amd.builders.build_network_from_config import NetworkFromConfig  # noqa: E402
+from mt3d_amd.dataloading import zarr_lite  # noqa: E402
+from mt3d_amd.inference import SlidingWindowInferer, StreamingInferer, all_positions  # noqa: E402
+
+
+def synthetic_volume(path, Z, YX, patch):
+    """smooth uint8 structure plus noise (compresses like a real scan would, roughly), written chunk row by chunk row"""
+    from concurrent.futures import ThreadPoolExecutor
+    rng = np.random.default_rng(0)
+    w = zarr_lite.ChunkedWriter(path, (Z, YX, YX), patch, np.uint8, "zlib")
+    yy, xx = np.meshgrid(np.arange(YX), np.arange(YX), indexing="ij")
+    with ThreadPoolExecutor(16) as pool:
+        futs = []
+        for z0 in range(0, Z, patch[0]):
+            z1 = min(Z, z0 + patch[0])
+            zz = np.arange(z0, z1)[:, None, None]
+            base = 128 + 60 * np.sin(zz / 23.0 + yy / 31.0) * np.cos(xx / 17.0)
+            blk = np.clip(base + rng.normal(0, 12, size=base.shape), 0, 255).astype(np.uint8)
+            futs += w.write_rows(z0, blk, pool)
+        for f in futs:
+            f.result()
+    return zarr_lite.open(path)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--z", type=int, default=256)
+    ap.add_argument("--yx", type=int, default=768)
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--modes", default="raw,zlib,resident")
+    ap.add_argument("--keep", default=None, help="work directory to use (default: a temporary one, removed at the end)")
+    a = ap.parse_args()
+    patch = (128, 128, 128)
+    work = a.keep or tempfile.mkdtemp(prefix="infer_stream_")
+    os.makedirs(work, exist_ok=True)
+    try:
+        t0 = time.perf_counter()
+        src = os.path.join(work, "vol.zarr")
+        arr = zarr_lite.open(src) if os.path.exists(src) else synthetic_volume(src, a.z, a.yx, patch)
+        print(json.dumps({"setup": "volume", "shape": arr.shape, "seconds": round(time.perf_counter() - t0, 2)}), flush=True)
+        w = dict(B.WORKLOADS["cfg2"])
+        torch.manual_seed(0)
+        net = NetworkFromConfig(B.make_mgr(w)).cuda()
+        targets = {"sheet": {"channels": 1, "activation": "sigmoid"}}
+        shape = tuple(arr.shape)
+        n_pos = len(all_positions(shape, patch, 0.5))
+        vox = float(np.prod(shape))
+        resident = None
+        modes = a.modes.split(",")
+        results = {m: [] for m in modes}
+        # run 0 of each mode is a warm-up (plan build, lazy buffers, program recording); the modes alternate run by run
+        order = [(r, m) for r in range(a.runs + 1) for m in modes]
+        for r, m in order:
+            torch.cuda.synchronize()
+            if m == "resident":
+                if resident is None:
+                    resident = torch.from_numpy(arr[...].astype(np.float32) / np.float32(255.0)).cuda()[None]
+                inf = SlidingWindowInferer(net, targets, patch, batch_size=a.batch, overlap=0.5, compute_dtype=torch.bfloat16)
+                t = time.perf_counter()
+                out = inf(resident)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t
+                del out
+                extra = {}
+            else:
+                out_dir = os.path.join(work, f"out_{m}_{r}")
+                inf = StreamingInferer(net, targets, patch, batch_size=a.batch, overlap=0.5, compute_dtype=torch.bfloat16)
+                t = time.perf_counter()
+                inf.run(src, out_dir, compressor=None if m == "raw" else "zlib")
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t
+                tm = inf.last_timing
+                extra = {"read_s": round(tm["read_s"], 3), "write_wait_s": round(tm["write_wait_s"], 3),
+                         "device_MiB": round(inf.last_schedule["device_bytes"] / 2**20, 1)}
+                shutil.rmtree(out_dir, ignore_errors=True)
+            rec = dict(mode=m, run=r, warmup=r == 0, seconds=round(dt, 3), patches_per_s=round(n_pos / dt, 2),
+                       mvoxel_per_s=round(vox / dt / 1e6, 2), **extra)
+            print(json.dumps(rec), flush=True)
+            if r > 0:
+                results[m].append(dt)
+        summ = {m: dict(median_s=round(float(np.median(v)), 3), patches_per_s=round(n_pos / float(np.median(v)), 2),
+                        mvoxel_per_s=round(vox / float(np.median(v)) / 1e6, 2)) for m, v in results.items() if v}
+        if "resident" in summ:
+            for m in summ:
+                summ[m]["vs_resident"] = round(summ["resident"]["median_s"] / summ[m]["median_s"], 3)
+        print(json.dumps({"summary": summ, "patches": n_pos, "shape": shape, "batch": a.batch}), flush=True)
+    finally:
+        if not a.keep:
+            shutil.rmtree(work, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
