@@ -347,6 +347,49 @@ int rx_sw_accumulate(const float* logits, int batch, int valid, int c, int pz, i
 int rx_sw_finalize(float* sum, float* wsum, int c, int ring, int y, int x, int z0, int rows, int blend, int cast, int reset,
                    float* blended, void* final_out, float* wsum_out, void* stream);
 
+/* ---- training augmentation on the device (reference dataloading/dataset.py:171-205; host restatement dataloading/augment.py).
+ *      The image batch is contiguous fp32 (batch, c, z, y, x).  Parameters are drawn on the host and passed as ONE table per
+ *      batch: `batch` rx_aug_sample records followed by a pool of 4-byte words that the records' offsets index (fp32 (z, y)
+ *      factor planes, fp32 k x k filter weights in row-major tap order, int32 index tables of downscale: z source rows, then y
+ *      source columns).  Every entry point takes the table twice: `host_table`, read during the call to validate every size,
+ *      offset and box (a bad table returns RX_EINVAL before anything is launched), and `table`, the same bytes on the device,
+ *      16-byte aligned, copied by the caller on `stream`.  A sample applies, in this order:
+ *        two pointwise stages  RX_AUG_PW_AFFINE v = clip(v * pw_a + pw_b)   RX_AUG_PW_PLANE v = clip(v * pool[pw_off + z*Y + y] + pw_b)
+ *                              RX_AUG_PW_NOISE  v = clip(v + pw_a * n), n standard normal: Philox4x32-10, key (key_lo, key_hi),
+ *                              counter = (linear (z, y, x) index of the voxel) / 4 -- the channel is not part of it --, the top 24
+ *                              bits of each output + 1 scaled by 2^-24 -> uniforms in (0, 1], Box-Muller pairs (u0, u1), (u2, u3)
+ *                              -> n0 = r0 cos, n1 = r0 sin, n2 = r1 cos, n3 = r1 sin, voxel i of the quad takes n_i;
+ *        one group-3 member    RX_AUG_G3_FILTER k x k correlation in the (z, y) plane, k odd in 3..21, border reflect-101, fp32
+ *                              sum in row-major tap order, then clip;  RX_AUG_G3_DOWNSCALE v = src[zi[z], yi[y], x];
+ *        nbox dropout boxes    (z0, y0, x0, d, h, w) inside the patch, filled with `fill`.
+ *      clip is to [0, 1]; products and sums are separate fp32 operations (no FMA contraction).  Deterministic, no atomics. */
+#define RX_AUG_MAX_K 21
+#define RX_AUG_MAX_BOXES 4
+typedef enum { RX_AUG_PW_NONE = 0, RX_AUG_PW_AFFINE = 1, RX_AUG_PW_PLANE = 2, RX_AUG_PW_NOISE = 3 } rx_aug_pw_mode;
+typedef enum { RX_AUG_G3_NONE = 0, RX_AUG_G3_FILTER = 1, RX_AUG_G3_DOWNSCALE = 2 } rx_aug_g3_mode;
+typedef struct {
+  int32_t pw_mode[2];
+  float pw_a[2], pw_b[2]; /* factor (AFFINE) or sigma (NOISE); offset */
+  int32_t pw_off[2];      /* pool word of the (z, y) plane (PLANE) */
+  uint32_t key_lo, key_hi;
+  int32_t g3_mode, k, g3_off; /* pool word of the k*k weights or of the z + y indices */
+  int32_t nbox;
+  int32_t box[RX_AUG_MAX_BOXES][6];
+  float fill;
+  int32_t pad_; /* 160 bytes: the pool that follows stays 16-byte aligned */
+} rx_aug_sample;
+/* bytes of the scratch batch that samples with a group-3 member pass through */
+size_t rx_aug_workspace(int batch, int c, int z, int y, int x);
+/* pass 1: the pointwise stages of every sample; a sample without a group-3 member also gets its boxes and lands in `out`, the
+ * others land in `scratch` (may be NULL when no sample has one).  1 read + 1 write per voxel; in != out. */
+int rx_aug_pointwise(const float* in, float* out, float* scratch, size_t scratch_bytes, int batch, int c, int z, int y, int x,
+                     const rx_aug_sample* host_table, const void* table, long pool_words, void* stream);
+/* pass 2: the group-3 member and the boxes of the samples that have one, scratch -> out; other samples are not touched. */
+int rx_aug_filter_zy(const float* scratch, float* out, int batch, int c, int z, int y, int x, const rx_aug_sample* host_table,
+                     const void* table, long pool_words, void* stream);
+/* test hook: the raw Philox outputs behind the noise of the first n voxels of a patch, out[i] = philox(key, i / 4)[i % 4] */
+int rx_aug_philox_u32(uint64_t key, long n, uint32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

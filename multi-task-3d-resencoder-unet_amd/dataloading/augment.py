@@ -10,7 +10,8 @@ parameter ranges are albumentations' documented defaults as far as they are publ
 members of a `OneOf` all carry the default p = 0.5, so the choice among them is uniform, and a transform without an explicit p
 fires with its default 0.5.
 
-Host-side numpy work in the DataLoader workers, like the reference's; nothing here touches the GPU path."""
+Host-side numpy work in the DataLoader workers, like the reference's; nothing here touches the GPU path.  The same stack as HIP
+kernels, with the parameters drawn here on the host: `augment_device.py` (`dataset_config.augment: "device"`)."""
 import numpy as np
 import torch
 from scipy import ndimage
@@ -69,27 +70,37 @@ def _filter_plane(img, kernel):
     return ndimage.correlate(img, kernel[:, :, None].astype(np.float32), mode="mirror")
 
 
-def motion_blur(img, rng):
-    """MotionBlur: blur_limit (3, 7): a normalised line through a k x k kernel at a random angle (the centre shifts and the
-    direction bias of the newer releases are not modelled)"""
+def motion_blur_kernel(rng):
+    """the k x k kernel of `motion_blur` (shared with augment_device.draw_params: same draws, same statements)"""
     k = int(rng.choice([3, 5, 7]))
     ang = np.deg2rad(rng.uniform(0.0, 360.0))
     kern = np.zeros((k, k), np.float32)
     c = (k - 1) / 2.0
     for t in np.linspace(-c, c, 4 * k):
         kern[int(round(c + t * np.sin(ang))), int(round(c + t * np.cos(ang)))] = 1.0
-    return _clip(_filter_plane(img, kern / kern.sum()))
+    return kern / kern.sum()
 
 
-def defocus(img, rng):
-    """Defocus: radius (3, 10), alias_blur (0.1, 0.5): a disc of that radius, its edge softened by a Gaussian of sigma alias_blur"""
+def motion_blur(img, rng):
+    """MotionBlur: blur_limit (3, 7): a normalised line through a k x k kernel at a random angle (the centre shifts and the
+    direction bias of the newer releases are not modelled)"""
+    return _clip(_filter_plane(img, motion_blur_kernel(rng)))
+
+
+def defocus_kernel(rng):
+    """the (2r + 1)^2 kernel of `defocus`"""
     r = int(rng.integers(3, 11))
     alias = rng.uniform(0.1, 0.5)
     ax = np.arange(-r, r + 1)
     yy, xx = np.meshgrid(ax, ax, indexing="ij")
     disc = ((yy * yy + xx * xx) <= r * r).astype(np.float32)
     disc = ndimage.gaussian_filter(disc, alias, mode="constant")
-    return _clip(_filter_plane(img, disc / disc.sum()))
+    return disc / disc.sum()
+
+
+def defocus(img, rng):
+    """Defocus: radius (3, 10), alias_blur (0.1, 0.5): a disc of that radius, its edge softened by a Gaussian of sigma alias_blur"""
+    return _clip(_filter_plane(img, defocus_kernel(rng)))
 
 
 def downscale(img, rng):
@@ -104,9 +115,8 @@ def downscale(img, rng):
     return np.ascontiguousarray(small[up_r][:, up_c])
 
 
-def advanced_blur(img, rng):
-    """AdvancedBlur: blur_limit (3, 7), sigma_x / sigma_y (0.2, 1.0), rotate (-90, 90), beta (0.5, 8), noise (0.9, 1.1): a
-    rotated generalised-Gaussian kernel exp(-(q^beta) / 2), q the anisotropic squared radius, with multiplicative kernel noise"""
+def advanced_blur_kernel(rng):
+    """the k x k kernel of `advanced_blur`"""
     k = int(rng.choice([3, 5, 7]))
     sx, sy = rng.uniform(0.2, 1.0), rng.uniform(0.2, 1.0)
     ang = np.deg2rad(rng.uniform(-90.0, 90.0))
@@ -117,7 +127,13 @@ def advanced_blur(img, rng):
     yr = -xx * np.sin(ang) + yy * np.cos(ang)
     q = (xr / sx) ** 2 + (yr / sy) ** 2
     kern = np.exp(-0.5 * np.power(q, beta)) * rng.uniform(0.9, 1.1, size=(k, k))
-    return _clip(_filter_plane(img, (kern / kern.sum()).astype(np.float32)))
+    return (kern / kern.sum()).astype(np.float32)
+
+
+def advanced_blur(img, rng):
+    """AdvancedBlur: blur_limit (3, 7), sigma_x / sigma_y (0.2, 1.0), rotate (-90, 90), beta (0.5, 8), noise (0.9, 1.1): a
+    rotated generalised-Gaussian kernel exp(-(q^beta) / 2), q the anisotropic squared radius, with multiplicative kernel noise"""
+    return _clip(_filter_plane(img, advanced_blur_kernel(rng)))
 
 
 # ---- volumetric ----------------------------------------------------------------------------------------------------------

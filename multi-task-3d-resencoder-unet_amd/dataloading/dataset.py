@@ -5,7 +5,8 @@
 `ZarrSegmentationDataset3D` reads real zarr v2 volumes through `zarr_lite` (the `zarr` package is absent here): same
 constructor, valid-patch search, cache file, dtype scaling and item layout as the reference; its augmentations need
 albumentations / volumentations (absent): `dataloading/augment.py` restates the stack in numpy (parity unpinned) and is applied
-by default with ONE warning saying so (`dataset_config.augment: "restated"` acknowledges it, `false` feeds raw patches); remote
+by default with ONE warning saying so (`dataset_config.augment: "restated"` acknowledges it, `false` feeds raw patches, `"device"`
+feeds raw patches and leaves the stack to the HIP kernels behind `augment_device.DeviceAugmenter`); remote
 (http) stores are refused (no network)."""
 import json
 import os
@@ -124,11 +125,14 @@ class ZarrSegmentationDataset3D(Dataset):
         # the reference's recipe augments every item (dataset.py:171-205: brightness / noise / blur OneOf groups,
         # CoarseDropout3D) with albumentations / volumentations, which are not installed here.  `augment.py` restates that
         # stack; say ONCE per process that it is a restatement instead of silently training a slightly different recipe.
-        # dataset_config.augment: true (default) = restated stack + the warning, "restated" = acknowledged, false = raw patches
+        # dataset_config.augment: true (default) = restated stack + the warning, "restated" = acknowledged, false = raw patches,
+        # "device" = raw patches here, the same stack as HIP kernels on the batch once it is on the device (augment_device.py;
+        # the trainer reads `device_augment`)
         mode = getattr(mgr, "dataset_config", {}).get("augment", True)
-        if isinstance(mode, str) and mode.lower() not in ("restated", "true", "false"):
-            raise ValueError(f"dataset_config.augment: {mode!r} (true, false or \"restated\")")
-        self.augment = (mode.lower() != "false") if isinstance(mode, str) else bool(mode)
+        if isinstance(mode, str) and mode.lower() not in ("restated", "true", "false", "device"):
+            raise ValueError(f"dataset_config.augment: {mode!r} (true, false, \"restated\" or \"device\")")
+        self.device_augment = isinstance(mode, str) and mode.lower() == "device"
+        self.augment = (mode.lower() not in ("false", "device")) if isinstance(mode, str) else bool(mode)
         if self.augment and not (isinstance(mode, str) and mode.lower() == "restated") and not ZarrSegmentationDataset3D._warned:
             ZarrSegmentationDataset3D._warned = True
             warnings.warn("ZarrSegmentationDataset3D: the reference's augmentation stack (dataloading/dataset.py:171-205) needs "

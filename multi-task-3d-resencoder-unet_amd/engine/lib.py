@@ -17,6 +17,9 @@ RX_SW_U8, RX_SW_U16, RX_SW_F32 = 0, 1, 2
 RX_SW_SCALE, RX_SW_ZSCORE = 0, 1
 RX_SW_BLEND_AVERAGE, RX_SW_BLEND_UNIT, RX_SW_BLEND_NONE = 0, 1, 2
 RX_SW_CAST_U8, RX_SW_CAST_U16 = 0, 1
+RX_AUG_PW_NONE, RX_AUG_PW_AFFINE, RX_AUG_PW_PLANE, RX_AUG_PW_NOISE = 0, 1, 2, 3
+RX_AUG_G3_NONE, RX_AUG_G3_FILTER, RX_AUG_G3_DOWNSCALE = 0, 1, 2
+RX_AUG_MAX_K, RX_AUG_MAX_BOXES = 21, 4
 
 
 class RxError(RuntimeError):
@@ -132,6 +135,11 @@ _SIGNATURES = {
                                  c_int, c_int, c_int, c_void_p]),
     "rx_sw_finalize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
+    "rx_aug_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "rx_aug_pointwise": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long,
+                                 c_void_p]),
+    "rx_aug_filter_zy": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
+    "rx_aug_philox_u32": (c_int, [ctypes.c_uint64, c_long, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -626,6 +626,46 @@ def masked_cosine_loss_bwd(pred, target, coef, grad_loss):
     return dpred
 
 
+# ---- training augmentation on the device (dataloading/augment_device.py draws the parameters and packs the table) -------------
+def aug_pointwise(image, out, scratch, host_table, table, pool_words):
+    """pass 1 on a contiguous fp32 (B, C, Z, Y, X) batch; `host_table`: the pinned / host uint8 tensor holding the same bytes as the
+    device tensor `table`; `scratch` None when no sample has a group-3 member"""
+    b, c, z, y, x = image.shape
+    check(load().rx_aug_pointwise(_ptr(image), _ptr(out), _ptr(scratch) if scratch is not None else None,
+                                  scratch.numel() * scratch.element_size() if scratch is not None else 0, b, c, z, y, x,
+                                  c_void_p(host_table.data_ptr()), _ptr(table), pool_words, stream_ptr()), "rx_aug_pointwise")
+
+
+def aug_filter_zy(scratch, out, host_table, table, pool_words):
+    """pass 2: the k x k (Z, Y) correlation or the downscale gather, then the dropout boxes, scratch -> out"""
+    b, c, z, y, x = out.shape
+    check(load().rx_aug_filter_zy(_ptr(scratch), _ptr(out), b, c, z, y, x, c_void_p(host_table.data_ptr()), _ptr(table), pool_words,
+                                  stream_ptr()), "rx_aug_filter_zy")
+
+
+def augment_batch(image, host_table, table, pool_words, any_group3):
+    """both passes -> a new batch (allocated on the current stream)"""
+    if not image.is_cuda:
+        raise _l.RxError("augment_batch: the image batch must be a device tensor")
+    out = torch.empty_like(image)
+    scratch = None
+    if any_group3:
+        b, c, z, y, x = image.shape
+        assert load().rx_aug_workspace(b, c, z, y, x) == image.numel() * 4
+        scratch = torch.empty_like(image)
+    aug_pointwise(image, out, scratch, host_table, table, pool_words)
+    if any_group3:
+        aug_filter_zy(scratch, out, host_table, table, pool_words)
+    return out
+
+
+def aug_philox_u32(key, n, device):
+    """test hook: the raw Philox4x32-10 outputs behind the noise of voxels 0..n-1 -> int64 tensor of the uint32 values"""
+    out = torch.empty(n, dtype=torch.int32, device=device)
+    check(load().rx_aug_philox_u32(int(key), n, _ptr(out), stream_ptr()), "rx_aug_philox_u32")
+    return out.to(torch.int64) & 0xFFFFFFFF
+
+
 # ---- bench.py's `hbm` block: the HBM-bound launches timed against their ALGORITHMIC bytes ---------------------------
 # (every operand tensor touched once at its storage type, SURVEY 8(d): a standalone statistics pass or the first pass of a
 # two-pass backward is extra TIME, not extra algorithmic bytes).  Wrappers cost one Python call when no profiler is set.

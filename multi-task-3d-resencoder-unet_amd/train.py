@@ -88,8 +88,9 @@ class DeviceFeeder:
     `batch["image"].to(device)`, train.py:199-203) the 33.5 MB of a cfg2 batch sit between two steps: 0.7 ms of a 17 ms step with
     the device idle (`scripts/step_timeline.py` on a `--through-trainer` trace: first kernel 707 us after the previous step's last)."""
 
-    def __init__(self, loader, device):
+    def __init__(self, loader, device, augmenter=None):
         self.loader, self.device = loader, device
+        self.augmenter = augmenter          # `DeviceAugmenter`: applied on the copy stream, under the running step like the copies
         self.stream = torch.cuda.Stream(device)
         ring = getattr(loader, "collate_fn", None)
         self.ring = ring if isinstance(ring, PinnedRingCollate) else None
@@ -106,6 +107,8 @@ class DeviceFeeder:
             dev = {k: v.to(self.device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
             if self.ring is not None:
                 self.ring.copied()          # (records on the copy stream: the pinned slot is free once THESE copies are done)
+            if self.augmenter is not None:
+                dev["image"] = self.augmenter(dev["image"])
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return dev, ev
@@ -271,9 +274,19 @@ class BaseTrainer:
         stepper = (StreamedOptimizerStep(optimizer, engine_model)
                    if isinstance(engine_model, NetworkFromConfig) and os.environ.get("RX_STREAMED_STEP", "0") == "1" else None)
 
+        # dataset_config.augment: "device" -- the dataset hands out raw patches and the stack runs as HIP kernels on the batch:
+        # behind the feeder's copies for the batches it stages, here for every other batch (RX_DEVICE_FEEDER=0, and validation:
+        # the reference augments validation items too, both loaders share the dataset)
+        augmenter = None
+        if getattr(dataset, "device_augment", False):
+            from .dataloading.augment_device import DeviceAugmenter
+            augmenter = DeviceAugmenter(rank=self.rank)
+
         def forward_loss(batch, train_mode):
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
             x = batch["image"].to(device, dtype=torch.float32, non_blocking=True)
+            if augmenter is not None and not staged:
+                x = augmenter(x)
             targets = {k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items() if k != "image"}
             ring = getattr(train_loader, "collate_fn", None)
             if train_mode and not staged and isinstance(ring, PinnedRingCollate):
@@ -298,7 +311,7 @@ class BaseTrainer:
             steps, patches = 0, 0
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
-            feeder = (DeviceFeeder(train_loader, device)
+            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter)
                       if device.type == "cuda" and os.environ.get("RX_DEVICE_FEEDER", "1") != "0" else train_loader)
             for i, batch in enumerate(feeder):
                 if i >= self.mgr.max_steps_per_epoch:
