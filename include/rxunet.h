@@ -390,6 +390,26 @@ int rx_aug_filter_zy(const float* scratch, float* out, int batch, int c, int z, 
 /* test hook: the raw Philox outputs behind the noise of the first n voxels of a patch, out[i] = philox(key, i / 4)[i % 4] */
 int rx_aug_philox_u32(uint64_t key, long n, uint32_t* out, void* stream);
 
+/* ---- axis flips and 90-degree rotations on the device, with the component rule of a 3-vector field (reference
+ *      training/transforms/geometric/geometry.py; host side dataloading/geometry_device.py).  One gather pass per tensor:
+ *        out[b][c][o] = (+/-) in[b][cs(c)][i],   i[src_axis[d]] = flip[d] ? n_d - 1 - o_d : o_d   (d = 0, 1, 2 = z, y, x)
+ *      cs(c) = ch_src[c] with the sign bit flipped where ch_neg[c] for a vector tensor (`vector` != 0, needs c == 3); cs(c) = c
+ *      and no sign change otherwise.  Any chain of flips and rotations is one such record (they compose on the host).  A negated
+ *      0.0 is -0.0 (the sign bit is XORed; nothing is multiplied). */
+typedef struct {        /* one sample's transform, 48 bytes */
+  int32_t src_axis[3];  /* output axis d (0=z,1=y,2=x) reads input axis src_axis[d]            */
+  int32_t flip[3];      /* ... at coordinate flip[d] ? n_d-1-o_d : o_d                         */
+  int32_t ch_src[3];    /* vector tensors: output component c reads input component ch_src[c] */
+  int32_t ch_neg[3];    /* ... with its sign bit flipped if ch_neg[c]                          */
+} rx_geom_sample;
+/* in / out: contiguous fp32 (batch, c, z, y, x), distinct buffers.  `host_table`: `batch` records in HOST memory, read during
+ * the call and handed to the kernels by value (16 samples per launch): no device table, copy, allocation or synchronisation.
+ * RX_EINVAL before anything is launched: null pointers, in == out, src_axis or ch_src not a permutation of 0..2, a permutation
+ * that would change the shape (extent[src_axis[d]] != extent[d]), vector with c != 3, z * y * x >= 2^31, z or y > 65535,
+ * c > 4095.  One read and one write of the tensor for every record. */
+int rx_geom_apply(const float* in, float* out, int batch, int c, int z, int y, int x, const rx_geom_sample* host_table,
+                  int vector, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

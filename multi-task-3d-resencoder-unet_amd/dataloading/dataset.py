@@ -7,7 +7,11 @@ constructor, valid-patch search, cache file, dtype scaling and item layout as th
 albumentations / volumentations (absent): `dataloading/augment.py` restates the stack in numpy (parity unpinned) and is applied
 by default with ONE warning saying so (`dataset_config.augment: "restated"` acknowledges it, `false` feeds raw patches, `"device"`
 feeds raw patches and leaves the stack to the HIP kernels behind `augment_device.DeviceAugmenter`); remote
-(http) stores are refused (no network)."""
+(http) stores are refused (no network).
+
+`dataset_config.geometric` (absent: off) adds axis flips and 90-degree rotations that move the image and every target together
+and keep a normals target consistent (`geometry_device.py`): `where: device` leaves the items alone (the trainer applies
+`DeviceGeometry` to the staged batch), `where: host` runs the host classes inside `__getitem__`, before the intensity stack."""
 import json
 import os
 import warnings
@@ -36,6 +40,10 @@ class SyntheticPatchDataset(Dataset):
         self.seed = seed
         self.pool = int(mgr.dataset_config.get("synthetic_pool", 16))
         self._cache = {}
+        from .geometry_device import parse_geometric
+        self.geometric = parse_geometric(mgr.dataset_config, self.patch, self.tasks)
+        if self.geometric is not None and self.geometric["where"] != "device":
+            raise ValueError("dataset_config.geometric.where: \"host\" is served by the zarr dataset; synthetic patches take \"device\"")
 
     def __len__(self):
         return self.length
@@ -140,6 +148,11 @@ class ZarrSegmentationDataset3D(Dataset):
                           "(dataloading/augment.py: same structure and probabilities, the members' default parameters as "
                           "documented; not compared with albumentations).  Set dataset_config.augment: \"restated\" to "
                           "acknowledge, or false to feed raw patches.", RuntimeWarning, stacklevel=2)
+        # dataset_config.geometric: parsed and checked here; "device" is the trainer's business (`geometric` is what it reads)
+        from .geometry_device import host_transforms, parse_geometric
+        self.geometric = parse_geometric(getattr(mgr, "dataset_config", {}), self.patch_size, self.tasks)
+        self._host_geometry = (host_transforms(self.geometric)
+                               if self.geometric is not None and self.geometric["where"] == "host" else [])
         self.volumes = []
         for vol_idx, info in enumerate(self.volume_paths):
             vd = {"input_path": info["input"], "targets_path": {}, "ref_label_key": info.get("ref_label", "sheet")}
@@ -203,6 +216,8 @@ class ZarrSegmentationDataset3D(Dataset):
                     from scipy.ndimage import binary_dilation      # == skimage dilation(t > 0, ball(5)) on a 0/1 volume
                     t = binary_dilation(t > 0, structure=_ball(5)).astype(np.float32)
             item[task] = t
+        for transform in self._host_geometry:      # image and targets together; (Z, Y, X) and (C, Z, Y, X) arrays alike
+            item = transform(item)
         if self.augment:              # image only; targets untouched (dataset.py:200-205)
             from .augment import augment_image
             item["image"] = augment_image(item["image"])

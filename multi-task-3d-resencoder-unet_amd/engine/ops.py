@@ -8,6 +8,7 @@ torch's current stream.
 """
 from ctypes import byref, c_void_p
 
+import numpy as np
 import torch
 
 from . import lib as _l
@@ -656,6 +657,32 @@ def augment_batch(image, host_table, table, pool_words, any_group3):
     aug_pointwise(image, out, scratch, host_table, table, pool_words)
     if any_group3:
         aug_filter_zy(scratch, out, host_table, table, pool_words)
+    return out
+
+
+def geom_table(geom_ops):
+    """`geom_ops`: one record per sample -- objects with `.row()` (dataloading.geometry_device.GeomOp) or 12 integers
+    (src_axis, flip, ch_src, ch_neg) -> the (B, 12) int32 host image of `rx_geom_sample`"""
+    rows = [o.row() if hasattr(o, "row") else o for o in geom_ops]
+    table = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(len(rows), 12))
+    return table
+
+
+def geom_apply(tensor, geom_ops, vector):
+    """flips / 90-degree rotations of a float32 (B, C, Z, Y, X) device batch, one record of `geom_ops` per sample -> a new batch
+    (allocated on the current stream).  `vector`: the three channels are a vector field and follow the records' component rule."""
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise _l.RxError("geom_apply: the batch must be a device tensor (the host classes are training/transforms/geometric)")
+    if tensor.dim() != 5 or tensor.dtype != torch.float32:
+        raise _l.RxError(f"geom_apply: expected a float32 (B, C, Z, Y, X) batch, got {tensor.dtype} {tuple(tensor.shape)}")
+    tensor = tensor.contiguous()
+    table = geom_table(geom_ops)
+    b, c, z, y, x = tensor.shape
+    if table.shape[0] != b:
+        raise _l.RxError(f"geom_apply: {table.shape[0]} records for a batch of {b}")
+    out = torch.empty_like(tensor)
+    check(load().rx_geom_apply(_ptr(tensor), _ptr(out), b, c, z, y, x, table.ctypes.data, 1 if vector else 0, stream_ptr()),
+          "rx_geom_apply")
     return out
 
 

@@ -88,9 +88,10 @@ class DeviceFeeder:
     `batch["image"].to(device)`, train.py:199-203) the 33.5 MB of a cfg2 batch sit between two steps: 0.7 ms of a 17 ms step with
     the device idle (`scripts/step_timeline.py` on a `--through-trainer` trace: first kernel 707 us after the previous step's last)."""
 
-    def __init__(self, loader, device, augmenter=None):
+    def __init__(self, loader, device, augmenter=None, geometry=None):
         self.loader, self.device = loader, device
         self.augmenter = augmenter          # `DeviceAugmenter`: applied on the copy stream, under the running step like the copies
+        self.geometry = geometry            # `DeviceGeometry`: the whole staged dict, before the image augmenter
         self.stream = torch.cuda.Stream(device)
         ring = getattr(loader, "collate_fn", None)
         self.ring = ring if isinstance(ring, PinnedRingCollate) else None
@@ -107,6 +108,8 @@ class DeviceFeeder:
             dev = {k: v.to(self.device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
             if self.ring is not None:
                 self.ring.copied()          # (records on the copy stream: the pinned slot is free once THESE copies are done)
+            if self.geometry is not None:
+                dev = self.geometry(dev)
             if self.augmenter is not None:
                 dev["image"] = self.augmenter(dev["image"])
             ev = torch.cuda.Event()
@@ -281,9 +284,19 @@ class BaseTrainer:
         if getattr(dataset, "device_augment", False):
             from .dataloading.augment_device import DeviceAugmenter
             augmenter = DeviceAugmenter(rank=self.rank)
+        # dataset_config.geometric with where: device -- flips / 90-degree rotations of image AND targets (normals with their
+        # component rule) as one HIP pass per tensor, in the same two places and before the intensity stack
+        geometry = None
+        geo_cfg = getattr(dataset, "geometric", None)
+        if geo_cfg is not None and geo_cfg["where"] == "device":
+            from .dataloading.geometry_device import DeviceGeometry
+            geometry = DeviceGeometry(flip=geo_cfg["flip"], rot90=geo_cfg["rot90"], normal_keys=geo_cfg["normal_keys"], rank=self.rank)
+        self.device_geometry = geometry
 
         def forward_loss(batch, train_mode):
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
+            if geometry is not None and not staged:
+                batch = geometry({k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()})
             x = batch["image"].to(device, dtype=torch.float32, non_blocking=True)
             if augmenter is not None and not staged:
                 x = augmenter(x)
@@ -311,7 +324,7 @@ class BaseTrainer:
             steps, patches = 0, 0
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
-            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter)
+            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry)
                       if device.type == "cuda" and os.environ.get("RX_DEVICE_FEEDER", "1") != "0" else train_loader)
             for i, batch in enumerate(feeder):
                 if i >= self.mgr.max_steps_per_epoch:
