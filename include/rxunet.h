@@ -410,6 +410,25 @@ typedef struct {        /* one sample's transform, 48 bytes */
 int rx_geom_apply(const float* in, float* out, int batch, int c, int z, int y, int x, const rx_geom_sample* host_table,
                   int vector, void* stream);
 
+/* ---- test-time augmentation of streaming inference: the two entry points above with one rx_geom_sample per patch slot (`ops`:
+ *      `batch` records in HOST memory, handed to the kernels by value; no device table, copy or synchronisation).  Both use the
+ *      gather form of rx_geom_apply on the PATCH: out[o] = in[i(o)], i[src_axis[d]] = flip[d] ? n_d - 1 - o_d : o_d.
+ *      rx_sw_gather_geom: output voxel o of slot b is slab voxel origin_b + i(o) (z modulo the ring), scaled and standardised as
+ *      rx_sw_gather does; image channels are never permuted or negated.  With identity records it is rx_sw_gather, bit for bit.
+ *      rx_sw_accumulate_geom: `ops` are the records to APPLY to the prediction (a view's inverse).  Destination voxel l of slot b
+ *      adds weight[l] * q, q the activated logit at i(l) -- the activation runs over the view-frame channels first; with `vector`
+ *      (needs c == 3) destination channel ch takes activated channel ch_src[ch], its sign bit flipped where ch_neg[ch] (-0.0 is
+ *      kept).  The weight is indexed by the destination voxel.  Slots are added in slot order, no atomics; with identity records
+ *      it is rx_sw_accumulate, bit for bit.  RX_EINVAL before anything is launched: everything rx_sw_gather / rx_sw_accumulate
+ *      refuse, a null table, src_axis or ch_src not a permutation of 0..2, a permutation that would change the patch shape,
+ *      vector with c != 3. */
+int rx_sw_gather_geom(int in_dtype, const void* slab, int cin, int ring, int y, int x, int batch, const int32_t* origins,
+                      const rx_geom_sample* ops, int pz, int py, int px, int norm, float* out, void* ws, size_t ws_bytes,
+                      void* stream);
+int rx_sw_accumulate_geom(const float* logits, int batch, int valid, int c, int pz, int py, int px, const int32_t* origins,
+                          const rx_geom_sample* ops, int vector, int act, const float* weight, float* sum, float* wsum, int ring,
+                          int y, int x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,10 @@ class ConfigManager:
         self.infer_normalization = str(ic.get("normalization", "scale")).lower()
         gb = ic.get("max_device_gb", None)
         self.infer_max_device_gb = None if gb is None else float(gb)
+        # test-time augmentation: "flip" or {"flip": [axes], "rot90": [axes]} (inference.tta_views); absent / false: off
+        self.infer_tta = ic.get("tta", None)
+        nk = ic.get("tta_normal_keys", None)
+        self.infer_tta_normal_keys = None if nk is None else tuple(str(k) for k in ((nk,) if isinstance(nk, str) else nk))
         if verbose:
             self._print_summary()
 

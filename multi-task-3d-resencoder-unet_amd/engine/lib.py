@@ -141,6 +141,10 @@ _SIGNATURES = {
     "rx_aug_filter_zy": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
     "rx_aug_philox_u32": (c_int, [ctypes.c_uint64, c_long, c_void_p, c_void_p]),
     "rx_geom_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "rx_sw_gather_geom": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rx_sw_accumulate_geom": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -231,13 +231,101 @@ def _device_weights(kind: str, patch: Tuple[int, int, int], device) -> torch.Ten
     return w
 
 
+# ---- test-time augmentation: the views of a patch -------------------------------------------------------------------------
+TTA_MAX_VIEWS = 48          # the signed permutations of three axes: every flip / 90-degree rotation of a cube
+
+
+def default_normal_keys(tasks) -> tuple:
+    """the tasks whose predictions are surface normals: lower-case name `normals` and 3 channels (the rule of `_task_modes`)"""
+    return tuple(n for n, t in (tasks or {}).items() if str(n).lower() == "normals" and int(t.get("channels", 0)) == 3)
+
+
+def _tta_axes(owner, v):
+    axes = [str(a).lower() for a in (v if not isinstance(v, str) else list(v))] if v is not None else []
+    if any(a not in ("z", "y", "x") for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError(f"{owner}: {v!r} (a list of distinct axes out of z, y, x)")
+    return axes
+
+
+def tta_views(spec, patch, tasks=None, normal_keys=None) -> tuple:
+    """The views of test-time augmentation, a tuple of `GeomOp` (dataloading.geometry_device); pure, no device.
+
+    spec  None / False: off, `(GeomOp(),)`.  "flip": shorthand for {"flip": ["z", "y", "x"]}.
+          {"flip": [axes], "rot90": [axes]} (either key may be absent): for every flip combination -- binary counting order over
+          the listed axes, bit i = the i-th listed axis, combination 0 the identity -- every rotation chain, the first listed
+          rotation axis outermost and k = 0..3 quarter turns per axis (applied in the listed order); a view is
+          `compose(flip_combo, rot_chain)`.  Or an explicit sequence of `GeomOp` (Python only).
+          Duplicates are dropped (the first occurrence stays), so view 0 of a mapping is the identity; flips over z, y, x give 8
+          views, with rotations about z 16, with rotations about all three axes the whole group of 48.
+    Refused, with the offending key named: unknown keys, a rotation axis whose plane has unequal patch extents, an explicit op
+    that would change the patch shape, a task of `normal_keys` without 3 channels, more than 48 views.  `normal_keys`
+    (default: `default_normal_keys(tasks)`) names the tasks un-transformed with the component and sign rule."""
+    import itertools
+    from .dataloading.geometry_device import AXIS_OF, GeomOp, allowed_rot90_axes, compose, flip_op, rot90_op
+    patch = tuple(int(v) for v in patch)
+    if len(patch) != 3:
+        raise ValueError(f"tta: needs a 3-D patch, patch_size is {list(patch)}")
+    nk = default_normal_keys(tasks) if normal_keys is None else ((normal_keys,) if isinstance(normal_keys, str) else tuple(normal_keys))
+    for k in nk:
+        if tasks is not None and k not in tasks:
+            raise ValueError(f"tta normal_keys: {k!r} is not a task (tasks: {sorted(tasks)})")
+        if tasks is not None and int(tasks[k].get("channels", 0)) != 3:
+            raise ValueError(f"tta normal_keys: task {k!r} has channels = {tasks[k].get('channels')}, a normals prediction has 3")
+    if spec is None or spec is False:
+        return (GeomOp(),)
+    if isinstance(spec, str):
+        if spec.lower() != "flip":
+            raise ValueError(f"tta: {spec!r} (\"flip\", a mapping with the keys flip / rot90, or a sequence of GeomOp)")
+        spec = {"flip": ["z", "y", "x"]}
+    if isinstance(spec, dict):
+        unknown = set(spec) - {"flip", "rot90"}
+        if unknown:
+            raise ValueError(f"tta: unknown key(s) {sorted(str(k) for k in unknown)} (known: flip, rot90)")
+        flips, rots = _tta_axes("tta.flip", spec.get("flip")), _tta_axes("tta.rot90", spec.get("rot90"))
+        allowed = allowed_rot90_axes(patch)
+        wrong = [a for a in rots if a not in allowed]
+        if wrong:
+            raise ValueError(f"tta.rot90: a rotation about {wrong} turns a plane of unequal extents of the patch {list(patch)} and "
+                             f"would change its shape; axes this patch allows: {list(allowed)}")
+        views = []
+        for m in range(1 << len(flips)):
+            f = GeomOp()
+            for i, a in enumerate(flips):
+                if (m >> i) & 1:
+                    f = compose(f, flip_op(AXIS_OF[a]))
+            for ks in itertools.product(range(4), repeat=len(rots)):
+                r = GeomOp()
+                for a, k in zip(rots, ks):
+                    if k:
+                        r = compose(r, rot90_op(a, k))
+                views.append(compose(f, r))
+    else:
+        try:
+            views = list(spec)
+        except TypeError:
+            raise ValueError(f"tta: {spec!r} (\"flip\", a mapping with the keys flip / rot90, or a sequence of GeomOp)") from None
+        if not views or not all(isinstance(v, GeomOp) for v in views):
+            raise ValueError("tta: an explicit view list is a non-empty sequence of GeomOp")
+        for i, v in enumerate(views):
+            if not v.preserves(patch):
+                raise ValueError(f"tta: view {i} {v} would change the shape of the patch {list(patch)}; rotation axes this patch "
+                                 f"allows: {list(allowed_rot90_axes(patch))}")
+    out = tuple(dict.fromkeys(views))
+    if len(out) > TTA_MAX_VIEWS:
+        raise ValueError(f"tta: {len(out)} distinct views, at most {TTA_MAX_VIEWS}")
+    return out
+
+
 # ---- streaming schedule (pure: testable without a device) ------------------------------------------------------------------
 def stream_schedule(shape: Sequence[int], patch: Sequence[int], overlap: float, batch_size: int, cin: int = 1,
-                    in_itemsize: int = 1, acc_channels: int = 1, out_bytes_per_voxel: int = 0) -> dict:
+                    in_itemsize: int = 1, acc_channels: int = 1, out_bytes_per_voxel: int = 0, n_views: int = 1) -> dict:
     """Positions -> the order of work of `StreamingInferer`, one step per z-origin z_k (all_positions is z-major):
 
       load      input rows [lo, hi) to bring to the device (hi = z_k + pz; rows already there are not read again)
       batches   [(B positions, valid)] of the patches at z_k; the last is padded by repeating its last patch (one plan shape)
+      views     parallel to `batches`: per batch, the B view indices of its slots.  With `n_views` = V > 1 (test-time
+                augmentation) the slots of a z-row are its (position, view) pairs, position-major and view-minor, cut into
+                batches of B -- so `batches` repeats every position V times -- and the last batch repeats its last slot
       finalize  rows [lo, hi) no later patch touches (hi = z_{k+1}, the volume end at the last step): blended, cast, copied out
       write     output rows [lo, hi) whose chunk rows (chunk = patch) are now complete
 
@@ -249,24 +337,30 @@ def stream_schedule(shape: Sequence[int], patch: Sequence[int], overlap: float, 
     """
     Z, Y, X = (int(s) for s in shape)
     pz = int(patch[0])
+    V = int(n_views)
+    if V < 1:
+        raise ValueError(f"n_views must be at least 1, got {n_views!r}")
     pos = all_positions((Z, Y, X), patch, overlap)
-    B = max(1, min(int(batch_size), len(pos)))
+    B = max(1, min(int(batch_size), len(pos)))      # not a function of V: the device bytes are those of the run without views
     rows: Dict[int, list] = {}
     for p in pos:
         rows.setdefault(p[0], []).append(p)
     zs = sorted(rows)
     steps, loaded, fin, written = [], 0, 0, 0
     for k, zk in enumerate(zs):
-        batches = []
-        row = rows[zk]
-        for i in range(0, len(row), B):
-            chunk = row[i:i + B]
-            batches.append((tuple(chunk) + (chunk[-1],) * (B - len(chunk)), len(chunk)))
+        batches, views = [], []
+        slots = [(p, v) for p in rows[zk] for v in range(V)]
+        for i in range(0, len(slots), B):
+            chunk = slots[i:i + B]
+            chunk_p, chunk_v = [p for p, _ in chunk], [v for _, v in chunk]
+            batches.append((tuple(chunk_p) + (chunk_p[-1],) * (B - len(chunk)), len(chunk)))
+            views.append(tuple(chunk_v) + (chunk_v[-1],) * (B - len(chunk)))
         load = (max(loaded, zk), zk + pz)
         loaded = zk + pz
         f_hi = zs[k + 1] if k + 1 < len(zs) else Z
         w_hi = Z if f_hi == Z else (f_hi // pz) * pz
-        steps.append(dict(z=zk, load=load, batches=batches, finalize=(fin, f_hi), write=(written, max(written, w_hi))))
+        steps.append(dict(z=zk, load=load, batches=batches, views=views, finalize=(fin, f_hi),
+                          write=(written, max(written, w_hi))))
         fin, written = f_hi, max(written, w_hi)
     max_fin = max(s["finalize"][1] - s["finalize"][0] for s in steps)
     plane = Y * X
@@ -310,16 +404,32 @@ class StreamingInferer:
                    reference inference dataset's pytorch3dunet `Standardize(channelwise=False)` -- that package is not available
                    here, so this parity is UNPINNED; the statistics are summed in fp64 in a fixed order.
     max_device_bytes  refuse (before any launch) a volume whose slab, plan included, does not fit.  No Y/X tiling.
+    tta            test-time augmentation: None / False (default: off, the run is the one without this argument, bit for bit),
+                   "flip", {"flip": [axes], "rot90": [axes]} or a sequence of `GeomOp` -- see `tta_views`.  For every patch
+                   position p (all_positions order) and every view v with op g_v (view order; position-major, view-minor):
+                       x = apply_op(g_v, scaled_patch(p))            image channels: moved, never the vector rule
+                       P = act(forward_logits(x))                    the activation on the view-frame logits
+                       q = apply_op(g_v.inverse(), P, is_normal = task in normal_keys)
+                       sum[p-box] += w * q;  wsum[p-box] += w        w indexed by the destination voxel (the volume frame: the
+                                                                     Gaussian map is not mirror-symmetric for even extents)
+                   Finalize, blend and cast are unchanged, so `<t>_count` holds V x the patch count (uniform) or V x the Gaussian
+                   weight sum.  With zscore the statistics are taken on the transformed patch -- the same multiset of values.
+                   Device memory is the same with and without views.  Both ends are HIP (rx_sw_gather_geom,
+                   rx_sw_accumulate_geom): no extra pass and no extra buffer per view or task.
+    normal_keys    the tasks whose 3 channels are a vector field (components x, y, z) and follow the component and sign rule when
+                   a view is undone; default: the tasks named `normals` with 3 channels.
     source         a zarr path, a `zarr_lite` array, or any numpy-sliceable (Z, Y, X) / (C, Z, Y, X) array (e.g. a memmap) of
                    uint8 / uint16 / float32.
     The output store has `write_store`'s array set, dtypes, shapes and chunking (= patch), zlib or raw chunks.  Host work
     overlaps the device: the next slab is read on a worker thread; D2H results are assembled and compressed on a pool of at most
-    16 threads.
+    16 threads.  `last_timing` after a run: read_s, write_wait_s, total_s, patches (positions), views (V) and forwards (network
+    forward calls: batches of B (position, view) slots).
     """
 
     def __init__(self, model, targets: Optional[dict] = None, patch_size: Optional[Sequence[int]] = None, batch_size: int = 2,
                  overlap: float = 0.5, compute_dtype: Optional[torch.dtype] = torch.bfloat16, blend: str = "uniform",
-                 normalization: str = "scale", max_device_bytes: Optional[int] = None, device="cuda", io_threads: int = 16):
+                 normalization: str = "scale", max_device_bytes: Optional[int] = None, device="cuda", io_threads: int = 16,
+                 tta=None, normal_keys=None):
         self.model = model
         self.targets = dict(targets if targets is not None else model.tasks)
         self.patch = tuple(int(p) for p in (patch_size if patch_size is not None else model.patch_size))
@@ -339,6 +449,11 @@ class StreamingInferer:
         self.max_device_bytes = max_device_bytes
         self.device = torch.device(device)
         self.io_threads = max(1, min(16, int(io_threads)))
+        # test-time augmentation: everything that can be refused is refused here, before any device work
+        self.views = tta_views(tta, self.patch, self.targets, normal_keys)
+        self.normal_keys = default_normal_keys(self.targets) if normal_keys is None else \
+            ((normal_keys,) if isinstance(normal_keys, str) else tuple(normal_keys))
+        self.tta = not (tta is None or tta is False)
         self.last_schedule = None
         self.last_timing = None
 
@@ -352,7 +467,7 @@ class StreamingInferer:
     def schedule(self, shape, cin: int = 1, in_itemsize: int = 1) -> dict:
         sc = sum(int(t["channels"]) for t in self.targets.values())
         out_b = 4 + sum(int(t["channels"]) * (4 + (2 if n.lower() == "normals" else 1)) for n, t in self.targets.items())
-        return stream_schedule(shape, self.patch, self.overlap, self.batch_size, cin, in_itemsize, sc, out_b)
+        return stream_schedule(shape, self.patch, self.overlap, self.batch_size, cin, in_itemsize, sc, out_b, len(self.views))
 
     @torch.no_grad()
     def run(self, source, output_path: str, compressor: Optional[str] = "zlib") -> str:
@@ -428,6 +543,11 @@ class StreamingInferer:
         norm = L.RX_SW_ZSCORE if self.normalization == "zscore" else L.RX_SW_SCALE
         in_code = _IN_CODES[in_dt]
         O3 = ctypes.c_int32 * (3 * B)
+        G12 = ctypes.c_int32 * (12 * B)                       # B records of rx_geom_sample
+        fwd_rows = [v.row() for v in self.views]              # the view, applied to the patch
+        inv_rows = [v.inverse().row() for v in self.views]    # its inverse, applied to the prediction
+        for tk in tasks:
+            tk["vector"] = 1 if tk["name"] in self.normal_keys else 0
 
         # output store
         os.makedirs(store)
@@ -542,16 +662,28 @@ class StreamingInferer:
                     ev = torch.cuda.Event()
                     ev.record(stream)
                     in_ev[slot] = ev
-                for chunk, valid in st["batches"]:
+                for (chunk, valid), vidx in zip(st["batches"], st["views"]):
                     org = O3(*[v for p in chunk for v in p])
-                    L.check(lib.rx_sw_gather(in_code, ring_in.data_ptr(), cin, R, Y, X, B, org, pz, py, px, norm, xb.data_ptr(),
-                                             ws.data_ptr(), ws_b, sp), "rx_sw_gather")
+                    if self.tta:      # the patch as its view sees it; the prediction is moved back by the view's inverse below
+                        fwd = G12(*[v for j in vidx for v in fwd_rows[j]])
+                        inv = G12(*[v for j in vidx for v in inv_rows[j]])
+                        L.check(lib.rx_sw_gather_geom(in_code, ring_in.data_ptr(), cin, R, Y, X, B, org, fwd, pz, py, px, norm,
+                                                      xb.data_ptr(), ws.data_ptr(), ws_b, sp), "rx_sw_gather_geom")
+                    else:
+                        L.check(lib.rx_sw_gather(in_code, ring_in.data_ptr(), cin, R, Y, X, B, org, pz, py, px, norm, xb.data_ptr(),
+                                                 ws.data_ptr(), ws_b, sp), "rx_sw_gather")
                     outs = plan.run_forward(xb, apply_act=False)     # the plan's own head buffers, read before the next forward
                     n_fwd += 1
                     for i, tk in enumerate(tasks):
-                        L.check(lib.rx_sw_accumulate(outs[tk["name"]].data_ptr(), B, valid, tk["c"], pz, py, px, org, tk["act"],
-                                                     weights.data_ptr(), tk["sum"].data_ptr(), wsum.data_ptr() if i == 0 else None,
-                                                     R, Y, X, sp), "rx_sw_accumulate")
+                        ws_p = wsum.data_ptr() if i == 0 else None
+                        if self.tta:
+                            L.check(lib.rx_sw_accumulate_geom(outs[tk["name"]].data_ptr(), B, valid, tk["c"], pz, py, px, org, inv,
+                                                              tk["vector"], tk["act"], weights.data_ptr(), tk["sum"].data_ptr(), ws_p,
+                                                              R, Y, X, sp), "rx_sw_accumulate_geom")
+                        else:
+                            L.check(lib.rx_sw_accumulate(outs[tk["name"]].data_ptr(), B, valid, tk["c"], pz, py, px, org, tk["act"],
+                                                         weights.data_ptr(), tk["sum"].data_ptr(), ws_p, R, Y, X, sp),
+                                    "rx_sw_accumulate")
                 f_lo, f_hi = st["finalize"]
                 n = f_hi - f_lo
                 if n > 0:
@@ -586,7 +718,7 @@ class StreamingInferer:
             reader.shutdown(wait=True)
             drainer.shutdown(wait=True)
             pool.shutdown(wait=True)
-        timing.update(total_s=time.perf_counter() - t_start, forwards=n_fwd, patches=len(sched["positions"]))
+        timing.update(total_s=time.perf_counter() - t_start, forwards=n_fwd, patches=len(sched["positions"]), views=len(self.views))
         self.last_timing = timing
         return store
 
@@ -626,7 +758,8 @@ def main(argv=None):
     gb = mgr.infer_max_device_gb
     runner = StreamingInferer(load_model(mgr), mgr.infer_targets, mgr.infer_patch_size, mgr.infer_batch_size, mgr.infer_overlap,
                               blend=mgr.infer_blend, normalization=mgr.infer_normalization,
-                              max_device_bytes=None if gb is None else int(gb * 2**30))
+                              max_device_bytes=None if gb is None else int(gb * 2**30), tta=mgr.infer_tta,
+                              normal_keys=mgr.infer_tta_normal_keys)
     store = runner.run(src, a.output_path or mgr.infer_output_path, compressor=None if a.compressor == "none" else "zlib")
     print(store, flush=True)
     return store

@@ -1,11 +1,15 @@
 """Streaming sliding-window inference (inference.StreamingInferer) against the HBM-resident SlidingWindowInferer on the same volume:
 the cfg2 network, bf16, 128^3 patches, overlap 0.5, a synthetic uint8 zarr of 256 x 768 x 768 (default) on local disk.
 
-    python scripts/bench_infer_stream.py [--z 256 --yx 768] [--runs 3] [--modes raw,zlib,resident] [--keep DIR]
+    python scripts/bench_infer_stream.py [--z 256 --yx 768] [--runs 3] [--modes raw,zlib,resident] [--tta SPEC ...] [--keep DIR]
 
 Alternates the modes run by run and prints one JSON line per run and a summary line: patches/s and Mvoxel/s of volume, and for the
 streaming runs where the host time went (slab reads, waits for the chunk writers).  `--modes raw --runs 1` under
-`rocprofv3 --kernel-trace --stats` gives the per-kernel times of rx_sw_gather / rx_sw_accumulate / rx_sw_finalize."""
+`rocprofv3 --kernel-trace --stats` gives the per-kernel times of rx_sw_gather / rx_sw_accumulate / rx_sw_finalize.
+
+`--tta SPEC` (repeatable) runs the streaming modes with test-time augmentation as well: SPEC is `off`, `flip` or a JSON mapping such
+as '{"flip":["z","y","x"],"rot90":["z"]}'.  Every (mode, SPEC) pair is a variant of its own, alternated run by run with the others;
+a variant with V views also reports view-forwards/s = V x patches / seconds.  Without the option only `off` runs."""
 import argparse
 import json
 import os
@@ -51,6 +55,8 @@ def main():
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--modes", default="raw,zlib,resident")
+    ap.add_argument("--tta", action="append", default=None, metavar="SPEC",
+                    help="off, flip or a JSON mapping {flip: [axes], rot90: [axes]}; repeatable, each is run alternated with the others")
     ap.add_argument("--keep", default=None, help="work directory to use (default: a temporary one, removed at the end)")
     a = ap.parse_args()
     patch = (128, 128, 128)
@@ -69,11 +75,15 @@ def main():
         n_pos = len(all_positions(shape, patch, 0.5))
         vox = float(np.prod(shape))
         resident = None
-        modes = a.modes.split(",")
-        results = {m: [] for m in modes}
+        specs = [(t, None if t == "off" else (json.loads(t) if t.lstrip().startswith("{") else t)) for t in (a.tta or ["off"])]
+        # a variant: (label, mode, tta); the resident inferer has no views
+        modes = [(m if t == "off" else f"{m}+tta:{t}", m, spec) for m in a.modes.split(",")
+                 for t, spec in (specs if m != "resident" else [("off", None)])]
+        results = {label: [] for label, _, _ in modes}
+        views = {label: 1 for label, _, _ in modes}
         # run 0 of each mode is a warm-up (plan build, lazy buffers, program recording); the modes alternate run by run
-        order = [(r, m) for r in range(a.runs + 1) for m in modes]
-        for r, m in order:
+        order = [(r, v) for r in range(a.runs + 1) for v in modes]
+        for r, (label, m, spec) in order:
             torch.cuda.synchronize()
             if m == "resident":
                 if resident is None:
@@ -86,22 +96,26 @@ def main():
                 del out
                 extra = {}
             else:
-                out_dir = os.path.join(work, f"out_{m}_{r}")
-                inf = StreamingInferer(net, targets, patch, batch_size=a.batch, overlap=0.5, compute_dtype=torch.bfloat16)
+                out_dir = os.path.join(work, f"out_{r}")
+                inf = StreamingInferer(net, targets, patch, batch_size=a.batch, overlap=0.5, compute_dtype=torch.bfloat16, tta=spec)
                 t = time.perf_counter()
                 inf.run(src, out_dir, compressor=None if m == "raw" else "zlib")
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t
                 tm = inf.last_timing
+                views[label] = tm["views"]
                 extra = {"read_s": round(tm["read_s"], 3), "write_wait_s": round(tm["write_wait_s"], 3),
-                         "device_MiB": round(inf.last_schedule["device_bytes"] / 2**20, 1)}
+                         "device_MiB": round(inf.last_schedule["device_bytes"] / 2**20, 1), "views": tm["views"],
+                         "view_forwards_per_s": round(tm["views"] * n_pos / dt, 2)}
                 shutil.rmtree(out_dir, ignore_errors=True)
-            rec = dict(mode=m, run=r, warmup=r == 0, seconds=round(dt, 3), patches_per_s=round(n_pos / dt, 2),
+            rec = dict(mode=label, run=r, warmup=r == 0, seconds=round(dt, 3), patches_per_s=round(n_pos / dt, 2),
                        mvoxel_per_s=round(vox / dt / 1e6, 2), **extra)
             print(json.dumps(rec), flush=True)
             if r > 0:
-                results[m].append(dt)
-        summ = {m: dict(median_s=round(float(np.median(v)), 3), patches_per_s=round(n_pos / float(np.median(v)), 2),
+                results[label].append(dt)
+        summ = {m: dict(median_s=round(float(np.median(v)), 3), min_s=round(min(v), 3), max_s=round(max(v), 3),
+                        patches_per_s=round(n_pos / float(np.median(v)), 2),
+                        view_forwards_per_s=round(views[m] * n_pos / float(np.median(v)), 2),
                         mvoxel_per_s=round(vox / float(np.median(v)) / 1e6, 2)) for m, v in results.items() if v}
         if "resident" in summ:
             for m in summ:
