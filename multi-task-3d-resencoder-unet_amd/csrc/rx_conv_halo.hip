@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "rx_common.h"
+#include "rx_internal.h"
 
 struct ConvHaloGeom {
   int N, Z, Y, X;

@@ -22,6 +22,7 @@
 // fragment registers + halo prefetch + accumulators do not fit 256 VGPRs (the compiler spilled ~200 registers, 271 us) --
 // it needs the weight fragments in AGPRs by hand, not attempted.
 #include "rx_common.h"
+#include "rx_internal.h"
 
 #define DS2_HZ 5
 #define DS2_HY 5

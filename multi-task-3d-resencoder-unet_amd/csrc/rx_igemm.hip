@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "rx_common.h"
+#include "rx_internal.h"
 
 
 // One launch covers up to 8 PHASES that share input / output / weights but differ in iteration grid, output
@@ -524,17 +525,6 @@ static int igemm_launch(rx_dtype dt, const void* in, const void* w, const float*
   return RX_OK;
 }
 
-// rx_conv_halo.hip
-int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip, int accumulate,
-                     hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks, const RxBwdStat* bs);
-void rx_inbwd_fused_finalize_launch(const float* partial, int N, int nchunks, int C, double V, const float* stats, float* m12, hipStream_t st);
-// rx_pointwise.hip
-int rx_pointwise_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, const int32_t stride[3],
-                     int accumulate, hipStream_t st);
-// rx_dgrad_s2.hip
-int rx_dgrad_s2_halo_try(rx_dtype dt, const rx_act* dy, const void* w_bwd, const rx_act* dx, int accumulate, hipStream_t st);
-// rx_elementwise.hip
-void rx_stats_finalize_launch(const float* partial, int N, int nchunks, int C, double V, float eps, float* stats, hipStream_t st);
 static bool is_333_s1(const int32_t k[3], const int32_t s[3]) {
   return k[0] == 3 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1;
 }

@@ -9,6 +9,7 @@
 // by 16 bytes: 16 consecutive rows hit 16 distinct 4-bank groups).  Per tap: Ci/16 MFMAs 32x32x16, then the 32 x 32 tile leaves
 // as 16-byte stores (rx_pair16).  Persistent over voxel tiles; HBM traffic = x once + y once.
 #include "rx_common.h"
+#include "rx_internal.h"
 
 struct PwGeom {
   int N, Zi, Yi, Xi, Ci, ldi;

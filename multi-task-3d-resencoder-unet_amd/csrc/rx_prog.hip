@@ -21,6 +21,7 @@
 #include <utility>
 
 #include "rx_common.h"
+#include "rx_internal.h"
 #include "rx_prog.h"
 
 struct RxCmd {
@@ -39,12 +40,8 @@ struct rx_prog {
 
 static thread_local rx_prog* g_rec = nullptr;
 static thread_local int g_depth = 0;
-static thread_local int g_note_seq = 0;          // bumped by rx_note_kernel_seq (see rx_elementwise.hip)
 static thread_local int g_scope_note0 = 0;
 static thread_local size_t g_scope_cmd = (size_t)-1;
-
-extern "C" const char* rx_last_conv_kernel(void);
-int rx_note_seq(void);
 
 RxRecScope::RxRecScope() {
   rec = g_rec != nullptr && g_depth == 0;

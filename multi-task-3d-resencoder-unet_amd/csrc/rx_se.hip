@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "rx_common.h"
+#include "rx_reduce.h"
 
 template <typename T>
 struct SeView {
@@ -594,14 +595,7 @@ static SePlan se_plan(const rx_act* y, int per16, int keep_x) {
   p.chunks = (p.rows + p.rows_per_chunk - 1) / p.rows_per_chunk;
   return p;
 }
-static int se_check(const rx_act* a, int dt, const char* who) {
-  const int per16 = dt == RX_F32 ? 4 : 8;
-  if (!rx_act_ok(a)) RX_FAIL(RX_EINVAL, "%s: bad activation descriptor", who);
-  if (a->c % per16 || a->ld % per16 || ((uintptr_t)a->ptr & 15)) RX_FAIL(RX_EUNSUPPORTED, "%s: channels/ld/ptr must be 16-byte multiples (c=%d ld=%d)", who, a->c, a->ld);
-  if (a->c > 2048) RX_FAIL(RX_EUNSUPPORTED, "%s: too many channels (%d)", who, a->c);
-  return RX_OK;
-}
-static int se_same(const rx_act* a, const rx_act* b) { return a->n == b->n && a->z == b->z && a->y == b->y && a->x == b->x && a->c == b->c; }
+#define RX_SE_MAX_C 2048   // most channels the SE kernels take, whatever the element type
 static inline size_t se_al(size_t v) { return (v + 63) & ~(size_t)63; }
 
 // workspace: line-sum partials (2 planes) | dz2 [N][L][C] | dhm [N][L][64] | line_m [N][L][2][C]
@@ -615,7 +609,7 @@ extern "C" size_t rx_se_workspace(const rx_act* y) {
 extern "C" int rx_se_gate_fwd(rx_dtype dt, const rx_act* y, const float* stats, const float* path_scale, const rx_se_params* se, float* pooled,
                               float* hidden, float* gate, float* mult, void* ws, size_t ws_bytes, void* stream) {
   RX_RECORD(stream, [=, y_ = RxActV(y), se_ = RxSeV(se)](void* s) { return rx_se_gate_fwd(dt, y_.p(), stats, path_scale, se_.p(), pooled, hidden, gate, mult, ws, ws_bytes, s); });
-  int rc = se_check(y, dt, "rx_se_gate_fwd(y)");
+  int rc = check_vec_channels(y, dt, "rx_se_gate_fwd(y)", RX_SE_MAX_C);
   if (rc) return rc;
   if (!mult) RX_FAIL(RX_EINVAL, "rx_se_gate_fwd: null mult");
   hipStream_t st = (hipStream_t)stream;
@@ -648,12 +642,12 @@ extern "C" int rx_instnorm_gate_act_fwd(rx_dtype dt, const rx_act* y, const floa
                                         const rx_act* out, float slope, void* stream) {
   RX_RECORD(stream, [=, y_ = RxActV(y), residual_ = RxActV(residual), out_ = RxActV(out)](void* s) { return rx_instnorm_gate_act_fwd(dt, y_.p(), stats, mult, keep_x, residual_.p(), out_.p(), slope, s); });
   int rc;
-  if ((rc = se_check(y, dt, "rx_instnorm_gate_act_fwd(y)"))) return rc;
-  if ((rc = se_check(out, dt, "rx_instnorm_gate_act_fwd(out)"))) return rc;
-  if (!stats || !mult || !se_same(y, out)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_fwd: bad arguments");
+  if ((rc = check_vec_channels(y, dt, "rx_instnorm_gate_act_fwd(y)", RX_SE_MAX_C))) return rc;
+  if ((rc = check_vec_channels(out, dt, "rx_instnorm_gate_act_fwd(out)", RX_SE_MAX_C))) return rc;
+  if (!stats || !mult || !same_geom(y, out)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_fwd: bad arguments");
   if (residual) {
-    if ((rc = se_check(residual, dt, "rx_instnorm_gate_act_fwd(residual)"))) return rc;
-    if (!se_same(y, residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_fwd: residual geometry mismatch");
+    if ((rc = check_vec_channels(residual, dt, "rx_instnorm_gate_act_fwd(residual)", RX_SE_MAX_C))) return rc;
+    if (!same_geom(y, residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_fwd: residual geometry mismatch");
   }
   const long V = rx_act_voxels(y);
   hipStream_t st = (hipStream_t)stream;
@@ -685,12 +679,12 @@ extern "C" int rx_se_gate_bwd(rx_dtype dt, const rx_act* g, const rx_act* y, con
                               size_t ws_bytes, void* stream) {
   RX_RECORD(stream, [=, g_ = RxActV(g), y_ = RxActV(y), out_ = RxActV(out), se_ = RxSeV(se)](void* s) { return rx_se_gate_bwd(dt, g_.p(), y_.p(), stats, out_.p(), slope, path_scale, se_.p(), pooled, hidden, gate, mult, dadd, m12, dw1, db1, dw2, db2, ws, ws_bytes, s); });
   int rc;
-  if ((rc = se_check(g, dt, "rx_se_gate_bwd(g)"))) return rc;
-  if ((rc = se_check(y, dt, "rx_se_gate_bwd(y)"))) return rc;
-  if (!se_same(g, y) || !stats || !mult || !dadd || !m12 || !ws) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: bad arguments");
+  if ((rc = check_vec_channels(g, dt, "rx_se_gate_bwd(g)", RX_SE_MAX_C))) return rc;
+  if ((rc = check_vec_channels(y, dt, "rx_se_gate_bwd(y)", RX_SE_MAX_C))) return rc;
+  if (!same_geom(g, y) || !stats || !mult || !dadd || !m12 || !ws) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: bad arguments");
   if (out) {
-    if ((rc = se_check(out, dt, "rx_se_gate_bwd(out)"))) return rc;
-    if (!se_same(out, y)) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: out geometry mismatch");
+    if ((rc = check_vec_channels(out, dt, "rx_se_gate_bwd(out)", RX_SE_MAX_C))) return rc;
+    if (!same_geom(out, y)) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: out geometry mismatch");
   }
   if (se && (!pooled || !hidden || !gate || !dw1 || !db1 || !dw2 || !db2 || !se->w1 || !se->w2)) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: null SE argument");
   if (se && (se->rd < 1 || se->rd > 64)) RX_FAIL(RX_EUNSUPPORTED, "rx_se_gate_bwd: reduction channels %d outside [1, 64]", se->rd);
@@ -739,17 +733,17 @@ extern "C" int rx_instnorm_gate_act_bwd(rx_dtype dt, const rx_act* g, const rx_a
                                         const rx_act* d_residual, int accumulate_residual, void* stream) {
   RX_RECORD(stream, [=, g_ = RxActV(g), y_ = RxActV(y), out_ = RxActV(out), dy_ = RxActV(dy), d_residual_ = RxActV(d_residual)](void* s) { return rx_instnorm_gate_act_bwd(dt, g_.p(), y_.p(), stats, out_.p(), slope, mult, dadd, m12, keep_x, dy_.p(), d_residual_.p(), accumulate_residual, s); });
   int rc;
-  if ((rc = se_check(g, dt, "rx_instnorm_gate_act_bwd(g)"))) return rc;
-  if ((rc = se_check(y, dt, "rx_instnorm_gate_act_bwd(y)"))) return rc;
-  if ((rc = se_check(dy, dt, "rx_instnorm_gate_act_bwd(dy)"))) return rc;
-  if (!se_same(g, y) || !se_same(dy, y) || !stats || !mult || !dadd || !m12) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: bad arguments");
+  if ((rc = check_vec_channels(g, dt, "rx_instnorm_gate_act_bwd(g)", RX_SE_MAX_C))) return rc;
+  if ((rc = check_vec_channels(y, dt, "rx_instnorm_gate_act_bwd(y)", RX_SE_MAX_C))) return rc;
+  if ((rc = check_vec_channels(dy, dt, "rx_instnorm_gate_act_bwd(dy)", RX_SE_MAX_C))) return rc;
+  if (!same_geom(g, y) || !same_geom(dy, y) || !stats || !mult || !dadd || !m12) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: bad arguments");
   if (out) {
-    if ((rc = se_check(out, dt, "rx_instnorm_gate_act_bwd(out)"))) return rc;
-    if (!se_same(out, y)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: out geometry mismatch");
+    if ((rc = check_vec_channels(out, dt, "rx_instnorm_gate_act_bwd(out)", RX_SE_MAX_C))) return rc;
+    if (!same_geom(out, y)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: out geometry mismatch");
   }
   if (d_residual) {
-    if ((rc = se_check(d_residual, dt, "rx_instnorm_gate_act_bwd(d_residual)"))) return rc;
-    if (!se_same(d_residual, y)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: d_residual geometry mismatch");
+    if ((rc = check_vec_channels(d_residual, dt, "rx_instnorm_gate_act_bwd(d_residual)", RX_SE_MAX_C))) return rc;
+    if (!same_geom(d_residual, y)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: d_residual geometry mismatch");
   }
   const long V = rx_act_voxels(y);
   hipStream_t st = (hipStream_t)stream;

@@ -5,9 +5,10 @@
 // LDS tile [256 voxels][Cout] through ds_read_b64_tr_b16 (as in rx_wgrad_halo.hip); the B fragment of lane
 // (tap, k-half) is 8 consecutive x-values of the fp32 halo tile shifted by the tap, converted to the compute
 // dtype in registers.  Tile 4x4x16 voxels, 4 waves take 4 k-steps each, accumulators persist over all tiles of a
-// workgroup; partials [block][ci][slot=a*9+b*3+c][co] are summed by stem_wgrad_finalize (rx_elementwise.hip).
-// (fp32 mode keeps the exact VALU kernel of rx_elementwise.hip.)
+// workgroup; partials [block][ci][slot=a*9+b*3+c][co] are summed by stem_wgrad_finalize (rx_stem.hip).
+// (fp32 mode keeps the exact VALU kernel of rx_stem.hip.)
 #include "rx_common.h"
+#include "rx_internal.h"
 
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4_s;
 
@@ -181,7 +182,7 @@ int rx_stem_wgrad_mfma_try(rx_dtype dt, const float* x, int n, int cin, int z, i
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Stem FORWARD on MFMA (16-bit compute types, Cout = 32):  out[v][co] = bias[co] + sum_k W[co][k] * X[k][v],  k = (ci, tap).
-// The VALU kernel (rx_elementwise.hip: one thread per voxel, 864 FMAs and 216 LDS broadcast reads per voxel) runs at ~200 us
+// The VALU kernel (rx_stem.hip: one thread per voxel, 864 FMAs and 216 LDS broadcast reads per voxel) runs at ~200 us
 // for the cfg2 stem although it only has to write 268 MB; here a 32-voxel block is two MFMAs (K = 27 padded to 32 for one
 // input channel): A = the weights, converted once per workgroup and kept in registers; B = 8 consecutive k of the lane's voxel
 // gathered from the fp32 halo tile in LDS (tap offsets from a small LDS table) and converted in registers.  Tile 4x4x16.

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "rx_common.h"
+#include "rx_internal.h"
 
 
 struct WgradGeom {
@@ -277,8 +278,6 @@ static void wgrad_dispatch(int BR, int BC, dim3 grid, hipStream_t st, const void
 #undef RX_WG
 }
 
-void rx_wgrad_reduce_launch(const float* slab, int S, int T_, int R, int C, float* dw, hipStream_t st);
-
 static int wgrad_launch(rx_dtype dt, const void* gt, const void* xt, float* dw, WgradGeom& g, void* ws, size_t ws_bytes, hipStream_t st) {
   const int per16 = dt == RX_F32 ? 4 : 8;
   if (g.R % 32 || g.Cc % 32) RX_FAIL(RX_EUNSUPPORTED, "wgrad: channel counts must be multiples of 32 (R=%d C=%d)", g.R, g.Cc);
@@ -306,9 +305,6 @@ void rx_wgrad_reduce_launch(const float* slab, int S, int T_, int R, int C, floa
   else
     hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((RC + 255) / 256)), dim3(256), 0, st, slab, S, T_, R, C, dw);
 }
-size_t rx_wgrad_halo_ws_bytes(const rx_act* x, const rx_act* dy);
-int rx_wgrad_halo_try(rx_dtype dt, const rx_act* x, const rx_act* dy, const int32_t stride[3], float* dw, void* ws, size_t ws_bytes,
-                      hipStream_t st);
 
 extern "C" size_t rx_conv3d_bwd_weight_workspace(const rx_act* x, const rx_act* dy, const int32_t kernel[3]) {
   if (!rx_act_ok_planar(x) || !rx_act_ok(dy)) return 0;

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "rx_common.h"
+#include "rx_internal.h"
 
 struct WgHaloGeom {
   int N, Z, Y, X;
@@ -549,8 +550,6 @@ size_t rx_wgrad_halo_ws_bytes(const rx_act* x, const rx_act* dy) {
   long S = PP > 0 ? (512 + PP - 1) / PP : 1;
   return (size_t)S * 27 * dy->c * x->c * sizeof(float) + 256;
 }
-
-void rx_wgrad_reduce_launch(const float* slab, int S, int T_, int R, int C, float* dw, hipStream_t st);
 
 // called by rx_conv3d_bwd_weight; returns 1 if it handled the launch, 0 to fall through to the generic kernel,
 // negative on error
