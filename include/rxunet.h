@@ -264,6 +264,35 @@ int rx_masked_cosine_loss_fwd(const float* pred, const float* target, int n, int
 int rx_masked_cosine_loss_bwd(const float* pred, const float* target, int n, int c, long v, const float* coef,
                               const float* grad_loss, float* dpred, void* stream);
 
+/* ---- the other task losses of the reference's map (train.py:43-66), same pattern: single pass, device-scalar loss --------
+ * Element-wise family: loss = mean or sum over all N*C*V elements of l(x, t).
+ *   RX_LOSS_BCE_LOGITS  l = max(x,0) - x*ts + log1p(exp(-|x|)), ts = t*(1-2a) + a   (nn.BCEWithLogitsLoss: a = 0;
+ *                       BCEWithLogitsLossLabelSmoothing, losses.py:217-238: a = smoothing; BCEWithLogitsLossZSmooth, :240-304:
+ *                       a = alpha_z[z], a DEVICE table of `z` floats indexed by (index inside the V-plane) / (V / z))
+ *   RX_LOSS_BCE_PROB    nn.BCELoss on probabilities, with torch's clamps (log >= -100 forward, x(1-x) >= 1e-12 backward)
+ *   RX_LOSS_MSE         (x - t)^2
+ * `alpha_z` may be NULL (then `smoothing` is the constant a and `z` is ignored); non-NULL needs kind BCE_LOGITS, z >= 1,
+ * V % z == 0, V < 2^31.  ws: rx_loss_workspace(n, c, v) bytes.  Nothing is carried from fwd to bwd.  N*C < 65536. */
+typedef enum { RX_LOSS_BCE_LOGITS = 0, RX_LOSS_BCE_PROB = 1, RX_LOSS_MSE = 2 } rx_elem_loss_kind;
+typedef enum { RX_REDUCE_MEAN = 0, RX_REDUCE_SUM = 1 } rx_reduction;
+int rx_elem_loss_fwd(int kind, const float* x, const float* target, int n, int c, long v, float smoothing,
+                     const float* alpha_z, int z, int reduction, float* loss, void* ws, size_t ws_bytes, void* stream);
+int rx_elem_loss_bwd(int kind, const float* x, const float* target, int n, int c, long v, float smoothing,
+                     const float* alpha_z, int z, int reduction, const float* grad_loss, float* dx, void* stream);
+/* nn.CrossEntropyLoss over the channel axis of (N, C, V) fp32 logits, 1 <= C <= 1024, N < 65536.  Exactly one of
+ * `target_prob` ((N, C, V) fp32 class probabilities; mean divides by N*V) and `target_index` ((N, V) int64 class indices;
+ * voxels equal to `ignore_index` -- or outside [0, C) -- contribute nothing; mean divides by the number of contributing
+ * voxels, and is NaN with a zero gradient when there is none) is non-NULL.  `saved`: 2*N*V floats (N*V suffice for index
+ * targets), the per-voxel log-sum-exp and target sum the backward reads; `coef`: 1 float, the backward's scale.
+ * ws: rx_cross_entropy_loss_workspace() bytes. */
+size_t rx_cross_entropy_loss_workspace(int n, int c, long v);
+int rx_cross_entropy_loss_fwd(const float* logits, const float* target_prob, const int64_t* target_index,
+                              int64_t ignore_index, int n, int c, long v, int reduction, float* loss, float* coef,
+                              float* saved, void* ws, size_t ws_bytes, void* stream);
+int rx_cross_entropy_loss_bwd(const float* logits, const float* target_prob, const int64_t* target_index,
+                              int64_t ignore_index, int n, int c, long v, const float* coef, const float* saved,
+                              const float* grad_loss, float* dlogits, void* stream);
+
 /* ---- optimizer step fused with the weight re-pack (torch.optim.AdamW arithmetic: decoupled weight decay, bias
  *      correction; train.py:69-86 selects AdamW) -- one pass over a conv / convT weight updates p, exp_avg, exp_avg_sq
  *      and rewrites both packed copies.  `clip` is an optional DEVICE scalar multiplied into the gradient

@@ -20,6 +20,8 @@ RX_SW_CAST_U8, RX_SW_CAST_U16 = 0, 1
 RX_AUG_PW_NONE, RX_AUG_PW_AFFINE, RX_AUG_PW_PLANE, RX_AUG_PW_NOISE = 0, 1, 2, 3
 RX_AUG_G3_NONE, RX_AUG_G3_FILTER, RX_AUG_G3_DOWNSCALE = 0, 1, 2
 RX_AUG_MAX_K, RX_AUG_MAX_BOXES = 21, 4
+RX_LOSS_BCE_LOGITS, RX_LOSS_BCE_PROB, RX_LOSS_MSE = 0, 1, 2
+RX_REDUCE_MEAN, RX_REDUCE_SUM = 0, 1
 
 
 class RxError(RuntimeError):
@@ -108,6 +110,15 @@ _SIGNATURES = {
     "rx_masked_cosine_loss_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]),
     "rx_masked_cosine_loss_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rx_elem_loss_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_long, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
+    "rx_elem_loss_bwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_long, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p]),
+    "rx_cross_entropy_loss_workspace": (c_size_t, [c_int, c_int, c_long]),
+    "rx_cross_entropy_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_long, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rx_cross_entropy_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_long, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
     "rx_adamw_pack": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_double,
                               c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rx_adamw_flat_multi": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,

@@ -6,7 +6,14 @@ arguments and arithmetic as the reference so `_build_loss` (train.py:43-66) maps
 read + one write backward, loss value and upstream gradient kept as device scalars (the torch formulation makes 5-8
 passes per direction).  On a HIP device a missing librxunet.so is an error, not a fallback; tensors that live on the
 CPU (the host-side unit tests of the trainer plumbing) take the torch formulation, which is also what the GPU tests
-compare the kernels against.  The remaining losses of the reference's map are plain torch modules."""
+compare the kernels against.
+
+The other six names of the map run natively as well, on two more kernel families of the same file: the element-wise family
+(`_ElemLossFn`: `BCEWithLogitsLoss`, `BCEWithLogitsLossLabelSmoothing`, `BCEWithLogitsLossZSmooth`, `BCELoss`, `MSELoss`) and
+cross entropy over the channel axis (`_CrossEntropyFn`: `CrossEntropyLoss`, probability or class-index targets).  The four
+`torch.nn` names are subclasses of the torch classes (same constructor, `isinstance` holds); they take the HIP branch for
+device tensors with `reduction` "mean" or "sum" and none of `weight` / `pos_weight` / `label_smoothing`, and call
+`super().forward` for everything else (CPU tensors, `reduction="none"`, those keyword arguments)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -59,6 +66,59 @@ class _MaskedCosineFn(torch.autograd.Function):
         return (d if ctx.dtype == torch.float32 else d.to(ctx.dtype)), None
 
 
+class _ElemLossFn(torch.autograd.Function):
+    """mean / sum of a per-element term (csrc/rx_loss.hip, element-wise family); nothing but the inputs is saved"""
+
+    @staticmethod
+    def forward(ctx, pred, target, kind, reduction, smoothing, alpha_z):
+        from ...engine import ops
+        x, t = _as_f32c(pred.detach()), _as_f32c(target.detach())
+        loss = ops.elem_loss_fwd(kind, x, t, reduction, smoothing, alpha_z)
+        ctx.save_for_backward(x, t)
+        ctx.hp = (kind, reduction, smoothing, alpha_z, pred.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        from ...engine import ops
+        x, t = ctx.saved_tensors
+        kind, reduction, smoothing, alpha_z, dtype = ctx.hp
+        d = ops.elem_loss_bwd(kind, x, t, _as_f32c(g), reduction, smoothing, alpha_z)
+        return (d if dtype == torch.float32 else d.to(dtype)), None, None, None, None, None
+
+
+class _CrossEntropyFn(torch.autograd.Function):
+    """cross entropy over dim 1; the forward leaves the per-voxel log-sum-exp (and target sum) for the backward"""
+
+    @staticmethod
+    def forward(ctx, logits, target, reduction, ignore_index):
+        from ...engine import ops
+        x = _as_f32c(logits.detach())
+        t = target.detach()
+        t = t.contiguous() if t.dtype == torch.int64 else _as_f32c(t)
+        loss, coef, saved = ops.cross_entropy_loss_fwd(x, t, reduction, ignore_index)
+        ctx.save_for_backward(x, t, coef, saved)
+        ctx.hp = (ignore_index, logits.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        from ...engine import ops
+        x, t, coef, saved = ctx.saved_tensors
+        ignore_index, dtype = ctx.hp
+        d = ops.cross_entropy_loss_bwd(x, t, coef, saved, _as_f32c(g), ignore_index)
+        return (d if dtype == torch.float32 else d.to(dtype)), None, None, None
+
+
+_BCE_LOGITS, _BCE_PROB, _MSE = 0, 1, 2      # engine/lib.py RX_LOSS_*
+_CE_MAX_CLASSES = 1024
+
+
+def _elem_eligible(pred, target, reduction):
+    # a target that wants a gradient of its own (nn.MSELoss gives one) keeps torch's graph
+    return reduction in ("mean", "sum") and _hip_eligible(pred, target) and not target.requires_grad
+
+
 def flatten(tensor):
     """(N, C, *spatial) -> (C, N * prod(spatial))   (losses.py:321-333)"""
     c = tensor.size(1)
@@ -101,9 +161,21 @@ class BCEWithLogitsLossLabelSmoothing(nn.Module):
         self.smoothing, self.reduction = smoothing, reduction
 
     def forward(self, logits, targets):
+        if _elem_eligible(logits, targets, self.reduction):
+            return _ElemLossFn.apply(logits, targets, _BCE_LOGITS, self.reduction, float(self.smoothing), None)
         with torch.no_grad():
             smoothed = targets * (1.0 - 2.0 * self.smoothing) + self.smoothing
         return F.binary_cross_entropy_with_logits(logits, smoothed, reduction=self.reduction)
+
+
+_ZSMOOTH_TABLES = {}
+
+
+def _zsmooth_table(d, center, edge, device, dtype=torch.float32):
+    """per-slice smoothing, the reference's own expression (losses.py:277-288)"""
+    z = torch.arange(d, device=device, dtype=dtype)
+    ratio = (z - (d - 1) / 2.0).abs() / (d // 2)
+    return center + (edge - center) * ratio
 
 
 class BCEWithLogitsLossZSmooth(nn.Module):
@@ -116,11 +188,62 @@ class BCEWithLogitsLossZSmooth(nn.Module):
     def forward(self, logits, targets):
         assert logits.shape == targets.shape, "Logits and targets must match in shape."
         d = logits.shape[2]
-        z = torch.arange(d, device=logits.device, dtype=logits.dtype)
-        ratio = (z - (d - 1) / 2.0).abs() / (d // 2)
-        alpha = (self.center_smoothing + (self.edge_smoothing - self.center_smoothing) * ratio).view(1, 1, d, 1, 1)
+        if logits.dim() == 5 and d >= 2 and _elem_eligible(logits, targets, self.reduction):
+            key = (d, self.center_smoothing, self.edge_smoothing, logits.device)
+            table = _ZSMOOTH_TABLES.get(key)
+            if table is None:       # fp32 torch expression, evaluated once per (Z, center, edge, device)
+                table = _ZSMOOTH_TABLES[key] = _zsmooth_table(d, self.center_smoothing, self.edge_smoothing, logits.device).contiguous()
+            return _ElemLossFn.apply(logits, targets, _BCE_LOGITS, self.reduction, 0.0, table)
+        alpha = _zsmooth_table(d, self.center_smoothing, self.edge_smoothing, logits.device, logits.dtype).view(1, 1, d, 1, 1)
         return F.binary_cross_entropy_with_logits(logits, targets * (1.0 - 2.0 * alpha) + alpha,
                                                   reduction=self.reduction)
+
+
+class BCEWithLogitsLoss(nn.BCEWithLogitsLoss):
+    """nn.BCEWithLogitsLoss; without `weight` / `pos_weight` the element-wise HIP kernel on device tensors"""
+
+    def forward(self, input, target):
+        if self.weight is None and self.pos_weight is None and _elem_eligible(input, target, self.reduction):
+            return _ElemLossFn.apply(input, target, _BCE_LOGITS, self.reduction, 0.0, None)
+        return super().forward(input, target)
+
+
+class BCELoss(nn.BCELoss):
+    """nn.BCELoss (probabilities in, torch's -100 / 1e-12 clamps); without `weight` the element-wise HIP kernel"""
+
+    def forward(self, input, target):
+        if self.weight is None and _elem_eligible(input, target, self.reduction):
+            return _ElemLossFn.apply(input, target, _BCE_PROB, self.reduction, 0.0, None)
+        return super().forward(input, target)
+
+
+class MSELoss(nn.MSELoss):
+    """nn.MSELoss; the element-wise HIP kernel on device tensors"""
+
+    def forward(self, input, target):
+        if _elem_eligible(input, target, self.reduction):
+            return _ElemLossFn.apply(input, target, _MSE, self.reduction, 0.0, None)
+        return super().forward(input, target)
+
+
+class CrossEntropyLoss(nn.CrossEntropyLoss):
+    """nn.CrossEntropyLoss over dim 1.  HIP kernel for device tensors with float targets of the logits' shape (class
+    probabilities -- what the trainer's float32 cast of a multi-channel mask gives) or int64 targets (N, *spatial), when
+    `weight is None`, `label_smoothing == 0`, C <= 1024 and reduction is mean / sum"""
+
+    def _hip(self, input, target):
+        if not (input.is_cuda and target.is_cuda and input.dim() >= 3 and self.reduction in ("mean", "sum")) or target.requires_grad:
+            return False
+        if self.weight is not None or self.label_smoothing != 0.0 or input.shape[1] > _CE_MAX_CLASSES or input.numel() == 0:
+            return False
+        if target.dtype == torch.int64:
+            return target.shape == input.shape[:1] + input.shape[2:]
+        return target.is_floating_point() and target.shape == input.shape
+
+    def forward(self, input, target):
+        if self._hip(input, target):
+            return _CrossEntropyFn.apply(input, target, self.reduction, int(self.ignore_index))
+        return super().forward(input, target)
 
 
 class BCEDiceLoss(nn.Module):
@@ -154,9 +277,9 @@ LOSS_FN_MAP = {
     "BCEDiceLoss": BCEDiceLoss,
     "BCEWithLogitsLossLabelSmoothing": BCEWithLogitsLossLabelSmoothing,
     "BCEWithLogitsLossZSmooth": BCEWithLogitsLossZSmooth,
-    "BCEWithLogitsLoss": nn.BCEWithLogitsLoss,
-    "BCELoss": nn.BCELoss,
-    "CrossEntropyLoss": nn.CrossEntropyLoss,
-    "MSELoss": nn.MSELoss,
+    "BCEWithLogitsLoss": BCEWithLogitsLoss,
+    "BCELoss": BCELoss,
+    "CrossEntropyLoss": CrossEntropyLoss,
+    "MSELoss": MSELoss,
     "MaskedCosineLoss": MaskedCosineLoss,
 }
