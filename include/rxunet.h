@@ -458,6 +458,20 @@ int rx_sw_accumulate_geom(const float* logits, int batch, int valid, int c, int 
                           const rx_geom_sample* ops, int vector, int act, const float* weight, float* sum, float* wsum, int ring,
                           int y, int x, void* stream);
 
+/* ---- label dilation on the device (reference dataloading/dataset.py: `dilate_label`, dilation(t > 0, ball(5)); host side
+ *      dataloading/dilate_device.py).  Every (sample, channel) volume of a contiguous fp32 (batch, c, z, y, x) tensor on its own:
+ *        out[v] = 1.0f if some voxel u with in[u] > 0.0f lies within |u - v|^2 <= radius^2, else +0.0f
+ *      (a float compare: NaN, -0.0 and negatives are off).  Nothing outside the volume is on: no wrap, no reflection, the border
+ *      rule of skimage's dilation and of scipy's binary_dilation.  The input is packed to one bit per voxel in `scratch` first
+ *      (64 voxels of an x row to a word) and read nowhere else, so out == in is allowed.  One fp32 read and one fp32 write. */
+size_t rx_dilate_workspace(int batch, int c, int z, int y, int x);
+    /* bytes of scratch: batch*c*z*y*ceil(x/64) 64-bit words (0 on invalid sizes) */
+/* radius 1..8; any positive z, y, x (extents below the radius and x % 64 != 0 included), z * y * x < 2^31 per sample; `scratch`
+ * 8-byte aligned.  RX_EINVAL before anything is launched: null pointers, non-positive sizes, a radius out of range;
+ * RX_EWORKSPACE: scratch_bytes below rx_dilate_workspace(...). */
+int rx_label_dilate(const float* in, float* out, void* scratch, size_t scratch_bytes, int batch, int c, int z, int y, int x,
+                    int radius, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

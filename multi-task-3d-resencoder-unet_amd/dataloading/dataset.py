@@ -11,7 +11,11 @@ feeds raw patches and leaves the stack to the HIP kernels behind `augment_device
 
 `dataset_config.geometric` (absent: off) adds axis flips and 90-degree rotations that move the image and every target together
 and keep a normals target consistent (`geometry_device.py`): `where: device` leaves the items alone (the trainer applies
-`DeviceGeometry` to the staged batch), `where: host` runs the host classes inside `__getitem__`, before the intensity stack."""
+`DeviceGeometry` to the staged batch), `where: host` runs the host classes inside `__getitem__`, before the intensity stack.
+
+`tr_setup.dilate_label` dilates every target that is not `normals` with a ball; `dataset_config.dilate` (absent: `{where: host,
+radius: 5}`, the reference's behaviour) says where: `host` is scipy's `binary_dilation` inside `__getitem__`, `device` hands out
+the scaled raw label and leaves the dilation to `dilate_device.DeviceDilate` (the trainer reads `device_dilate`)."""
 import json
 import os
 import warnings
@@ -153,6 +157,10 @@ class ZarrSegmentationDataset3D(Dataset):
         self.geometric = parse_geometric(getattr(mgr, "dataset_config", {}), self.patch_size, self.tasks)
         self._host_geometry = (host_transforms(self.geometric)
                                if self.geometric is not None and self.geometric["where"] == "host" else [])
+        # dataset_config.dilate under tr_setup.dilate_label: "host" dilates in __getitem__, "device" is the trainer's business
+        from .dilate_device import parse_dilate
+        self.dilate = parse_dilate(getattr(mgr, "dataset_config", {}), self.dilate_label, self.tasks)
+        self.device_dilate = self.dilate if self.dilate is not None and self.dilate["where"] == "device" else None
         self.volumes = []
         for vol_idx, info in enumerate(self.volume_paths):
             vd = {"input_path": info["input"], "targets_path": {}, "ref_label_key": info.get("ref_label", "sheet")}
@@ -212,9 +220,9 @@ class ZarrSegmentationDataset3D(Dataset):
                     t /= 255.0
                 elif t_arr.dtype == np.uint16:
                     t /= 65535.0
-                if self.dilate_label:
-                    from scipy.ndimage import binary_dilation      # == skimage dilation(t > 0, ball(5)) on a 0/1 volume
-                    t = binary_dilation(t > 0, structure=_ball(5)).astype(np.float32)
+                if self.dilate is not None and self.dilate["where"] == "host":
+                    from scipy.ndimage import binary_dilation      # == skimage dilation(t > 0, ball(r)) on a 0/1 volume
+                    t = binary_dilation(t > 0, structure=_ball(self.dilate["radius"])).astype(np.float32)
             item[task] = t
         for transform in self._host_geometry:      # image and targets together; (Z, Y, X) and (C, Z, Y, X) arrays alike
             item = transform(item)

@@ -736,6 +736,31 @@ def geom_apply(tensor, geom_ops, vector):
     return out
 
 
+def label_dilate(tensor, radius=5, out=None):
+    """binary dilation with the ball of `radius` (1..8) of a float32 (B, C, Z, Y, X) device batch, every (sample, channel) volume
+    on its own: 1.0 where a voxel > 0 lies within the radius, else 0.0 (dataloading.dilate_device.dilate_numpy is the statement).
+    `out=None`: in place, returns `tensor`; the bit scratch comes from the caching allocator on the current stream."""
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise _l.RxError("label_dilate: the batch must be a device tensor (the host path is scipy's binary_dilation in the dataset)")
+    if tensor.dim() != 5 or tensor.dtype != torch.float32:
+        raise _l.RxError(f"label_dilate: expected a float32 (B, C, Z, Y, X) batch, got {tensor.dtype} {tuple(tensor.shape)}")
+    src = tensor.contiguous()
+    if out is None:
+        out = src
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.shape != src.shape
+          or not out.is_contiguous()):
+        raise _l.RxError(f"label_dilate: `out` must be a contiguous float32 device tensor of shape {tuple(src.shape)}")
+    b, c, z, y, x = src.shape
+    nbytes = load().rx_dilate_workspace(b, c, z, y, x)
+    scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=src.device)
+    check(load().rx_label_dilate(_ptr(src), _ptr(out), _ptr(scratch), nbytes, b, c, z, y, x, int(radius), stream_ptr()),
+          "rx_label_dilate")
+    if out is src and src is not tensor:      # a non-contiguous batch dilated "in place": hand the values back to its own storage
+        tensor.copy_(src)
+        return tensor
+    return out
+
+
 def aug_philox_u32(key, n, device):
     """test hook: the raw Philox4x32-10 outputs behind the noise of voxels 0..n-1 -> int64 tensor of the uint32 values"""
     out = torch.empty(n, dtype=torch.int32, device=device)

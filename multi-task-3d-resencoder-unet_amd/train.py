@@ -88,8 +88,9 @@ class DeviceFeeder:
     `batch["image"].to(device)`, train.py:199-203) the 33.5 MB of a cfg2 batch sit between two steps: 0.7 ms of a 17 ms step with
     the device idle (`scripts/step_timeline.py` on a `--through-trainer` trace: first kernel 707 us after the previous step's last)."""
 
-    def __init__(self, loader, device, augmenter=None, geometry=None):
+    def __init__(self, loader, device, augmenter=None, geometry=None, dilate=None):
         self.loader, self.device = loader, device
+        self.dilate = dilate                # `DeviceDilate`: the label targets, in place, before geometry (the host order)
         self.augmenter = augmenter          # `DeviceAugmenter`: applied on the copy stream, under the running step like the copies
         self.geometry = geometry            # `DeviceGeometry`: the whole staged dict, before the image augmenter
         self.stream = torch.cuda.Stream(device)
@@ -108,6 +109,8 @@ class DeviceFeeder:
             dev = {k: v.to(self.device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
             if self.ring is not None:
                 self.ring.copied()          # (records on the copy stream: the pinned slot is free once THESE copies are done)
+            if self.dilate is not None:
+                dev = self.dilate(dev)
             if self.geometry is not None:
                 dev = self.geometry(dev)
             if self.augmenter is not None:
@@ -292,11 +295,23 @@ class BaseTrainer:
             from .dataloading.geometry_device import DeviceGeometry
             geometry = DeviceGeometry(flip=geo_cfg["flip"], rot90=geo_cfg["rot90"], normal_keys=geo_cfg["normal_keys"], rank=self.rank)
         self.device_geometry = geometry
+        # tr_setup.dilate_label with dataset_config.dilate.where: device -- the dataset hands out raw labels and the ball dilation
+        # runs as a HIP pass on the targets, in the same two places and before geometry (the host order; the stages commute)
+        dilate = None
+        dil_cfg = getattr(dataset, "device_dilate", None)
+        if dil_cfg is not None:
+            from .dataloading.dilate_device import DeviceDilate
+            dilate = DeviceDilate(dil_cfg["keys"], dil_cfg["radius"])
+        self.device_dilate = dilate
 
         def forward_loss(batch, train_mode):
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
-            if geometry is not None and not staged:
-                batch = geometry({k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()})
+            if (dilate is not None or geometry is not None) and not staged:
+                batch = {k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
+                if dilate is not None:      # (the copies above are fresh device tensors: dilating them in place touches nothing else)
+                    batch = dilate(batch)
+                if geometry is not None:
+                    batch = geometry(batch)
             x = batch["image"].to(device, dtype=torch.float32, non_blocking=True)
             if augmenter is not None and not staged:
                 x = augmenter(x)
@@ -324,7 +339,7 @@ class BaseTrainer:
             steps, patches = 0, 0
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
-            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry)
+            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry, dilate=dilate)
                       if device.type == "cuda" and os.environ.get("RX_DEVICE_FEEDER", "1") != "0" else train_loader)
             for i, batch in enumerate(feeder):
                 if i >= self.mgr.max_steps_per_epoch:
