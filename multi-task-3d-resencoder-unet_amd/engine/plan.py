@@ -17,10 +17,10 @@ Layout decisions:
   * per-parameter packed copies ([tap][Co][Ci] and [tap][Ci][Co], compute dtype) are refreshed only
     when the parameter's version counter moved.
 """
-from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional
-
+import contextlib
 import os
+from dataclasses import dataclass
+from typing import Callable, ClassVar, Dict, List, NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -48,14 +48,6 @@ def side_stream(device):
     return st
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 @dataclass(eq=False)
 class AT:
     """an activation tensor of the plan and (training plans) the buffer of its gradient"""
@@ -64,12 +56,186 @@ class AT:
     gact: Optional[Act] = None
     written: bool = False      # plan-build-time tracking: has some backward step initialised gact?
     needs_grad: bool = True
+    # concat buffers: (weight range start, length, buffer start) of each half; set by _build, read by _emit_cdnr
+    segs: Optional[list] = None
+    # the record whose backward step wrote gact LAST (plan-build order = run order); set by _claim_grad, read by _bwd_inact
+    last_writer: Optional[object] = None
+    # gradient of the AvgPool that reads this block output, handed to the block's InstanceNorm backward instead of
+    # accumulated in a pass of its own; set by _bwd_pool, taken by _bwd_inact
+    pool_pending: Optional["PendingPool"] = None
+
+
+class PendingPool(NamedTuple):
+    gy: Act
+    gx: Act
+    stride: list
 
 
 @dataclass(eq=False)
-class Rec:
-    kind: str
-    a: dict = field(default_factory=dict)
+class SE:
+    """SqueezeExcite of one residual block: fc parameters as the kernels read them (padded shadows where needed)"""
+    rd: int
+    keep_x: int
+    w1: torch.Tensor
+    b1: torch.Tensor
+    w2: torch.Tensor
+    b2: torch.Tensor
+    idx: List[int]             # parameter indices of fc1.weight, fc1.bias, fc2.weight, fc2.bias
+
+    def args(self):
+        return dict(w1=self.w1, b1=self.b1, w2=self.w2, b2=self.b2, rd=self.rd, keep_x=self.keep_x)
+
+
+@dataclass(eq=False)
+class Gate:
+    """SqueezeExcite / DropPath state of one residual block (csrc/rx_se.hip); the per-(n, line, c) tensors live for the whole step"""
+    keep_x: int
+    drop_p: float
+    mult: torch.Tensor
+    dadd: torch.Tensor
+    m12: torch.Tensor
+    se: Optional[SE] = None
+    scale: Optional[torch.Tensor] = None        # DropPath: per-sample factor storage (None without DropPath)
+    pooled: Optional[torch.Tensor] = None
+    hidden: Optional[torch.Tensor] = None
+    gate: Optional[torch.Tensor] = None
+    scale_now: Optional[torch.Tensor] = None    # this step's DropPath factors: `scale` in training, None in eval (_forward_pre)
+
+    def se_args(self):
+        return self.se.args() if self.se is not None else None
+
+
+@dataclass(eq=False)
+class Drop:
+    """channel dropout in front of one InstanceNorm"""
+    p: float
+    keep: torch.Tensor         # this step's kept (n, c) planes, 1 / 0 (_draw_dropout)
+    eps: float
+    eps_now: float             # eps * (1-p)^2 in training, eps in eval (_forward_pre)
+    active: bool = False       # follows net.training (_forward_pre)
+
+    def __getitem__(self, name):
+        """d["keep"]: replacements of `Plan._draw_dropout` written when these entries of `plan._drops` were dicts keep working"""
+        return getattr(self, name)
+
+
+# ---- the tape: one record per layer.  Fields without a default are the layer itself (set by the emitters in _build);
+# ---- fields with a default are FUSION LINKS, set by the passes named in their comment and read by the step builders.
+@dataclass(eq=False)
+class StemRec:
+    """first conv of the net, reading the NCDHW fp32 image"""
+    kind: ClassVar[str] = "stem"
+    y: AT
+    w: torch.Tensor
+    b: Optional[torch.Tensor]
+    widx: int
+    bidx: Optional[int]
+    kernel: list
+    stats_to: Optional["InactRec"] = None       # set by _fuse_stem_stats; _fwd_stem leaves (mean, rstd) of y there
+
+
+@dataclass(eq=False)
+class ImageRec:
+    """NCDHW fp32 image -> channels-last compute type (identity 1x1x1 first-layer conv; a constant, not a parameter)"""
+    kind: ClassVar[str] = "image"
+    y: AT
+    w: torch.Tensor
+
+
+@dataclass(eq=False)
+class ConvRec:
+    kind: ClassVar[str] = "conv"
+    x: AT
+    y: AT
+    pk: dict
+    b: Optional[torch.Tensor]
+    widx: int
+    bidx: Optional[int]
+    kernel: list
+    stride: list
+    stats_to: Optional["InactRec"] = None       # set by _fuse_conv_stats; _fwd_conv leaves (mean, rstd) of y there
+    instats_for: Optional["InactRec"] = None    # set by _bwd_inact; this conv's backward-data step also fills that layer's m12
+
+
+@dataclass(eq=False)
+class ConvTRec:
+    kind: ClassVar[str] = "convT"
+    x: AT
+    y: AT
+    pk: dict
+    b: Optional[torch.Tensor]
+    widx: int
+    bidx: Optional[int]
+    stride: list
+    cat: AT
+
+
+@dataclass(eq=False)
+class InactRec:
+    """InstanceNorm + nonlinearity (+ residual add, + SE gate / DropPath, + channel dropout) behind a conv"""
+    kind: ClassVar[str] = "inact"
+    y: AT
+    stats: torch.Tensor
+    eps: float
+    res: Optional[AT]
+    out: AT
+    slope: float
+    gate: Optional[Gate]
+    drop: Optional[Drop]
+    stats_done: bool = False                    # set by _fuse_conv_stats / _fuse_stem_stats; _fwd_inact skips its statistics pass
+    pool_to: Optional["PoolRec"] = None         # set by _fuse_block_pool; _fwd_inact also writes that pool's output
+    head_to: Optional["HeadRec"] = None         # set by _fuse_head; _fwd_inact also computes that head's logits
+    head_src: Optional["HeadRec"] = None        # set by _bwd_inact; its step rebuilds the output gradient from that head's dlogits
+    head_dw_fused: bool = False                 # set by _bwd_inact; its step also produces the head's dw / db, _fwd_inact does not store out
+    m12: Optional[torch.Tensor] = None          # set by _bwd_inact; the two backward means, filled by ConvRec.instats_for's owner
+    m12_valid: bool = False                     # per step: set by that conv's backward-data step, cleared by this layer's
+    m12x: Optional[torch.Tensor] = None         # RX_SKIP=inbwd_reduce only: zeros standing in for m12 (allocated on first use)
+
+
+@dataclass(eq=False)
+class PoolRec:
+    kind: ClassVar[str] = "pool"
+    x: AT
+    y: AT
+    stride: list
+    fused: bool = False                         # set by _fuse_block_pool; the producer of x writes y, _fwd_pool emits nothing
+
+
+@dataclass(eq=False)
+class CopyRec:
+    """encoder skip -> second half of a further decoder's concat buffer"""
+    kind: ClassVar[str] = "copy"
+    x: AT
+    y: AT
+    cat: AT
+
+
+@dataclass(eq=False)
+class HeadRec:
+    kind: ClassVar[str] = "head"
+    x: AT
+    w: torch.Tensor
+    b: torch.Tensor
+    widx: int
+    bidx: int
+    k: int
+    name: str
+    out: torch.Tensor
+    act: int
+    fwd_fused: bool = False                     # set by _fuse_head; the layer below computes the logits, _fwd_head emits nothing
+    dx_fused: bool = False                      # set by _bwd_inact (with its head_src); _bwd_head's step writes no data gradient
+    dw_fused: bool = False                      # set by _bwd_inact (with its head_dw_fused); _bwd_head's step launches nothing
+
+
+def _above_single_launch(act):
+    """above the size the single-launch InstanceNorm kernel takes: beyond it the norm is a statistics pass plus an apply pass, and
+    either can be fused into a neighbouring launch"""
+    return act.voxels > 512
+
+
+def _halo_x_ok(act):
+    """the 3x3x3 stride-1 LDS-halo kernels (whose epilogues carry the fused statistics) work on 4 x 4 x 16 tiles: x extent >= 16"""
+    return act.dims[3] >= 16
 
 
 def _slope_of(nonlin):
@@ -111,8 +277,8 @@ class Plan:
         self.params: List[nn.Parameter] = []
         self._pidx: Dict[int, int] = {}
         self.packs: List[dict] = []          # {param, kind, w_fwd, w_bwd, version}
-        self.enc_tape: List[Rec] = []
-        self.dec_tapes: List[List[Rec]] = []
+        self.enc_tape: list = []             # records (StemRec ... HeadRec) of the encoder, forward order
+        self.dec_tapes: List[list] = []      # ... and of each task decoder
         self.fwd: List[Callable] = []
         self.bwd: List[Callable] = []
         self.dy_pool: Dict[tuple, Act] = {}
@@ -124,7 +290,6 @@ class Plan:
         self._grads: List[Optional[torch.Tensor]] = []
         self.grad_order: List[int] = []       # parameter indices in the order their gradients become ready
         self.grad_sync = None                 # optional engine.ddp.GradSync
-        import os
         # weight gradients on a side HIP stream (off the dependency chain); RX_OVERLAP_WGRAD=0 keeps one stream
         self.overlap_wgrad = os.environ.get("RX_OVERLAP_WGRAD", "1") != "0"
         # dy slots per shape: with 2 the main stream stalls whenever the side stream is more than one layer behind
@@ -140,8 +305,8 @@ class Plan:
         self._ev_fork = None                      # main -> side
         self._ev_join = None                      # side -> main
         self._pack_groups = None                  # [(entries, event slot)] in first-use order (static per plan)
-        self._gates: List[dict] = []              # SqueezeExcite / DropPath state of every gated block, forward order
-        self._drops: List[dict] = []              # channel-dropout layers (dropout_op_kwargs p > 0), forward order
+        self._gates: List[Gate] = []              # SqueezeExcite / DropPath state of every gated block, forward order
+        self._drops: List[Drop] = []              # channel-dropout layers (dropout_op_kwargs p > 0), forward order
         # Channel counts that are not a multiple of the kernels' K tile (features_per_stage is free in the reference,
         # build_network_from_config.py:85-148): every activation buffer is PADDED to the next multiple, and each parameter that
         # touches a padded extent gets a zero-padded fp32 SHADOW that the kernels read instead (refreshed from the real
@@ -180,6 +345,9 @@ class Plan:
         self._x_static = None
         self._dl_static: Dict[str, torch.Tensor] = {}
         self._image_t = None                      # channels-last copy of an image with > 16 channels (see _image_act)
+        self._image_at = None                     # the image in the engine's layout, once some layer needed it (_image_act)
+        self._cat_written: Dict[int, bool] = {}   # backward build: concat gradient buffers a full-buffer write has initialised
+        self._skip = frozenset()                  # RX_SKIP timing ablations (_gen_backward)
         self._pack_delay_at = None                # forward-list index behind the full-resolution encoder stage (deferred weight packs)
         self._pack_deferred = None
         self._build()
@@ -352,18 +520,17 @@ class Plan:
         b_k = self._shadow(conv.bias, (cout_p,), [((slice(0, cout),), (slice(None),))])
         if first_of_net:
             w_k = self._shadow(conv.weight, (cout_p, cin, *kshape), [((slice(0, cout),), (slice(None),))])
-            tape.append(Rec("stem", dict(y=y, w=w_k, b=b_k, widx=widx, bidx=bidx, kernel=kernel)))
+            tape.append(StemRec(y=y, w=w_k, b=b_k, widx=widx, bidx=bidx, kernel=kernel))
         else:
             # input-channel ranges of the weight -> where they sit in the (padded) input buffer; a decoder conv reads the concat
             # [upsampled C | skip C], whose halves are padded separately
-            segs = getattr(x, "segs", None) or [(0, cin, 0)]
+            segs = x.segs or [(0, cin, 0)]
             if sum(L for _, L, _ in segs) != cin:
                 raise RuntimeError("plan bug: input-channel segments do not add up")
             w_k = self._shadow(conv.weight, (cout_p, x.act.c, *kshape),
                                [((slice(0, cout), slice(d, d + L)), (slice(None), slice(s0, s0 + L))) for s0, L, d in segs])
             pk = self._pack(w_k, "conv")
-            tape.append(Rec("conv", dict(x=x, y=y, pk=pk, b=b_k, widx=widx, bidx=bidx, kernel=kernel,
-                                         stride=stride)))
+            tape.append(ConvRec(x=x, y=y, pk=pk, b=b_k, widx=widx, bidx=bidx, kernel=kernel, stride=stride))
         gate = None
         if se is not None or drop_p > 0.0:
             gate = self._gate_buffers(odims, cout_p, se, drop_p)
@@ -372,14 +539,13 @@ class Plan:
             # channel dropout in front of the InstanceNorm = the norm with eps * (1-p)^2 for the kept (n, c) planes and rstd = 0 for
             # the dropped ones (rx_instnorm_stats_mask): no pass over y, forward or backward.  keep: this step's draw (torch RNG, on
             # the device, forward order); eps_now / active follow net.training (_forward_pre).
-            drop = dict(p=p_drop, keep=torch.ones((self.B, cout_p), dtype=torch.float32, device=self.device), eps=eps,
-                        eps_now=eps, active=False)
+            drop = Drop(p=p_drop, keep=torch.ones((self.B, cout_p), dtype=torch.float32, device=self.device), eps=eps, eps_now=eps)
             self._drops.append(drop)
-        tape.append(Rec("inact", dict(y=y, stats=stats, eps=eps, res=residual, out=out, slope=slope, gate=gate, drop=drop)))
+        tape.append(InactRec(y=y, stats=stats, eps=eps, res=residual, out=out, slope=slope, gate=gate, drop=drop))
         return out
 
     def _image_act(self, tape):
-        if getattr(self, "_image_at", None) is not None:
+        if self._image_at is not None:
             return self._image_at
         cin = self.Cin
         cp = self._cp(cin)
@@ -396,13 +562,13 @@ class Plan:
         eye = torch.zeros((cp, cin, 1, 1, 1), dtype=torch.float32, device=self.device)
         if self.device.type != "meta":
             eye[torch.arange(cin), torch.arange(cin)] = 1.0
-        tape.append(Rec("image", dict(y=y, w=eye)))
+        tape.append(ImageRec(y=y, w=eye))
         self._image_at = y
         return y
 
     def _draw_dropout(self, d):
         """this step's kept (n, c) planes of one dropout layer: 1 / 0, in place (bernoulli(1 - p) as torch's feature dropout)"""
-        d["keep"].bernoulli_(1.0 - d["p"])
+        d.keep.bernoulli_(1.0 - d.p)
 
     def _gate_buffers(self, odims, c, se, drop_p):
         """SqueezeExcite / DropPath state of one residual block (csrc/rx_se.hip): the fc parameters are read raw (fp32),
@@ -410,61 +576,50 @@ class Plan:
         keep_x = 0 if (se is not None and self.two_d) else 1      # x.mean((2, 3)) of a 4-D tensor pools every spatial axis
         L = odims[2] if keep_x else 1
         f32 = dict(dtype=torch.float32, device=self.device)
-        g = dict(keep_x=keep_x, drop_p=float(drop_p), se=None, scale=None,
-                 mult=torch.empty((self.B, L, c), **f32), dadd=torch.empty((self.B, L, c), **f32),
-                 m12=torch.empty((self.B, c, 2), **f32), pooled=None, hidden=None, gate=None)
+        g = Gate(keep_x=keep_x, drop_p=float(drop_p), mult=torch.empty((self.B, L, c), **f32), dadd=torch.empty((self.B, L, c), **f32),
+                 m12=torch.empty((self.B, c, 2), **f32))
         if drop_p > 0.0:
-            g["scale"] = torch.ones(self.B, **f32)
+            g.scale = torch.ones(self.B, **f32)
         if se is not None:
             rd = se.fc1.out_channels
             if rd > 64:
                 raise UnsupportedConfig(f"SqueezeExcite with {rd} reduction channels (the gate kernel holds <= 64)")
             c_real = se.fc2.out_channels
             ones = tuple(se.fc1.weight.shape[2:])
-            g["se"] = dict(rd=rd, keep_x=keep_x,
-                           w1=self._shadow(se.fc1.weight, (rd, c, *ones), [((slice(None), slice(0, c_real)), (slice(None), slice(None)))]),
-                           b1=se.fc1.bias,
-                           w2=self._shadow(se.fc2.weight, (c, rd, *ones), [((slice(0, c_real),), (slice(None),))]),
-                           b2=self._shadow(se.fc2.bias, (c,), [((slice(0, c_real),), (slice(None),))]),
-                           idx=[self._param(se.fc1.weight), self._param(se.fc1.bias), self._param(se.fc2.weight),
-                                self._param(se.fc2.bias)])
-            g["pooled"] = torch.empty((self.B, L, c), **f32)
-            g["hidden"] = torch.empty((self.B, L, rd), **f32)
-            g["gate"] = torch.empty((self.B, L, c), **f32)
+            g.se = SE(rd=rd, keep_x=keep_x,
+                      w1=self._shadow(se.fc1.weight, (rd, c, *ones), [((slice(None), slice(0, c_real)), (slice(None), slice(None)))]),
+                      b1=se.fc1.bias,
+                      w2=self._shadow(se.fc2.weight, (c, rd, *ones), [((slice(0, c_real),), (slice(None),))]),
+                      b2=self._shadow(se.fc2.bias, (c,), [((slice(0, c_real),), (slice(None),))]),
+                      idx=[self._param(se.fc1.weight), self._param(se.fc1.bias), self._param(se.fc2.weight),
+                           self._param(se.fc2.bias)])
+            g.pooled = torch.empty((self.B, L, c), **f32)
+            g.hidden = torch.empty((self.B, L, rd), **f32)
+            g.gate = torch.empty((self.B, L, c), **f32)
         if self.device.type == "cuda":
             need = 4 * (self.B * 256 * 2 * odims[2] * c + self.B * odims[2] * (3 * c + 64)) + 1024
             ops.workspace(need, self.device)
-        g["scale_now"] = None
         self._gates.append(g)
         return g
 
     @staticmethod
-    def _se_args(g):
-        se = g["se"]
-        if se is None:
-            return None
-        return dict(w1=se["w1"], b1=se["b1"], w2=se["w2"], b2=se["b2"], rd=se["rd"], keep_x=se["keep_x"])
+    def _eps_now(r: InactRec):
+        return r.drop.eps_now if r.drop is not None else r.eps
 
     @staticmethod
-    def _eps_now(ia):
-        d = ia.get("drop")
-        return d["eps_now"] if d is not None else ia["eps"]
-
-    @staticmethod
-    def _mask_dropped(ia):
-        d = ia.get("drop")
-        if d is not None and d["active"]:
-            ops.instnorm_stats_mask(ia["stats"], d["keep"])
+    def _mask_dropped(r: InactRec):
+        if r.drop is not None and r.drop.active:
+            ops.instnorm_stats_mask(r.stats, r.drop.keep)
 
     def _draw_path_scale(self, g):
         """DropPath: per-sample bernoulli(keep)/keep in training, None (identity) in eval"""
-        if g["scale"] is None or not self.net.training:
+        if g.scale is None or not self.net.training:
             return None
-        keep = 1.0 - g["drop_p"]
-        g["scale"].bernoulli_(keep)
+        keep = 1.0 - g.drop_p
+        g.scale.bernoulli_(keep)
         if keep > 0.0:
-            g["scale"].div_(keep)
-        return g["scale"]
+            g.scale.div_(keep)
+        return g.scale
 
     def _emit_block(self, tape, blk, x: AT, out: Optional[AT] = None):
         """BasicBlockD / BottleneckD: skip path, main path, fused `nonlin(IN(conv_k(..)) + skip)`."""
@@ -478,7 +633,7 @@ class Plan:
                 st = self._k3(op.stride if isinstance(op.stride, (list, tuple)) else [op.stride] * (2 if self.two_d else 3))
                 odims = tuple(d // s for d, s in zip(r.act.dims[1:], st))
                 p = self._new(odims, r.act.c, f"pool:{len(tape)}", needs_grad=r.needs_grad)
-                tape.append(Rec("pool", dict(x=r, y=p, stride=st)))
+                tape.append(PoolRec(x=r, y=p, stride=st))
                 r = p
             else:
                 r = self._emit_cdnr(tape, op, r)        # 1x1 conv -> IN (no nonlin: slope 1)
@@ -559,7 +714,6 @@ class Plan:
         self.enc_skips = [(at, feats[i]) for i, at in enumerate(skips)]      # (activation, real channel count) per stage
 
         # ---- decoders
-        self.head_recs = []
         for d, name in enumerate(tasks):
             dec = net.task_decoders[name]
             tape = []
@@ -583,11 +737,10 @@ class Plan:
                 pk = self._pack(w_k, "convT")
                 widx = self._param(tconv.weight)
                 bidx = self._param(tconv.bias) if tconv.bias is not None else None
-                tape.append(Rec("convT", dict(x=low, y=up, pk=pk, b=b_k, widx=widx, bidx=bidx, stride=stride,
-                                              cat=cat)))
+                tape.append(ConvTRec(x=low, y=up, pk=pk, b=b_k, widx=widx, bidx=bidx, stride=stride, cat=cat))
                 if d > 0:
                     dst = AT(cat.act.slice(c, c), f"skipcopy{d}.{j}")
-                    tape.append(Rec("copy", dict(x=skips[es], y=dst, cat=cat)))
+                    tape.append(CopyRec(x=skips[es], y=dst, cat=cat))
                 st_mod = dec.stages[j]
                 h = cat
                 if hasattr(st_mod, "blocks"):
@@ -611,149 +764,164 @@ class Plan:
                 act_code = _l.RX_ACT_SOFTMAX
             hw_k = self._shadow(head.weight, (k, low.act.c, *head.weight.shape[2:]),
                                 [((slice(None), slice(0, head.in_channels)), (slice(None), slice(None)))])
-            tape.append(Rec("head", dict(x=low, w=hw_k, b=head.bias, widx=self._param(head.weight),
-                                         bidx=self._param(head.bias), k=k, name=name, out=out, act=act_code)))
+            tape.append(HeadRec(x=low, w=hw_k, b=head.bias, widx=self._param(head.weight), bidx=self._param(head.bias), k=k,
+                                name=name, out=out, act=act_code))
 
         self._gen_forward()
         if self.needs_grad:
             self._gen_backward()
 
-    # ------------------------------------------------------------------ launch lists
+    # ------------------------------------------------------------------ forward: fusion passes (they only set links)
+    def _fuse_conv_stats(self, tape):
+        """conv -> InstanceNorm pairs whose statistics come out of the conv epilogue (rx_conv3d_fwd_stats): 3x3x3 stride-1
+        layers in a 16-bit compute type, on the halo kernels, above the single-launch InstanceNorm size"""
+        for rec, nxt in zip(tape, tape[1:]):
+            if (rec.kind == "conv" and nxt.kind == "inact" and nxt.y is rec.y and self.dtype != torch.float32
+                    and list(rec.kernel) == [3, 3, 3] and list(rec.stride) == [1, 1, 1]
+                    and _above_single_launch(rec.y.act) and _halo_x_ok(rec.y.act)):
+                rec.stats_to, nxt.stats_done = nxt, True
+
+    def _fuse_stem_stats(self, tape):
+        """stem -> InstanceNorm: the same out of the first-layer kernel (rx_stem_conv_fwd_stats); no x-extent condition"""
+        for rec, nxt in zip(tape, tape[1:]):
+            if (rec.kind == "stem" and nxt.kind == "inact" and nxt.y is rec.y and self.dtype != torch.float32
+                    and _above_single_launch(rec.y.act)):
+                rec.stats_to, nxt.stats_done = nxt, True
+
+    def _fuse_block_pool(self, tape):
+        """un-gated block output -> AvgPool of the next block's skip path: one pass (rx_instnorm_act_pool_fwd) above the
+        single-launch InstanceNorm size; one pool per producer"""
+        producers = {id(r.out): r for r in tape if r.kind == "inact" and r.gate is None}
+        for rec in tape:
+            if rec.kind == "pool" and id(rec.x) in producers and _above_single_launch(rec.x.act):
+                src = producers[id(rec.x)]
+                if src.pool_to is None:
+                    src.pool_to, rec.fused = rec, True
+
+    def _fuse_head(self, tape):
+        """the layer under a task head (16-bit compute type, K <= 4, plain InstanceNorm: no gate, residual or fused pool):
+        InstanceNorm apply + LeakyReLU + the head's 1x1x1 conv in one pass (the activated output is written for the backward
+        but not re-read by a separate head kernel)"""
+        if self.dtype == torch.float32:
+            return
+        for rec in tape:
+            if rec.kind != "head" or rec.k > 4:
+                continue
+            prods = [r for r in tape if r.kind == "inact" and r.out is rec.x]
+            if len(prods) != 1:
+                continue
+            p = prods[0]
+            c = p.out.act.c
+            if (p.gate is None and p.res is None and p.pool_to is None and _above_single_launch(p.out.act)
+                    and c % 8 == 0 and 64 % (c // 8) == 0):
+                p.head_to, rec.fwd_fused = rec, True
+
+    # ------------------------------------------------------------------ forward: one step builder per record kind
+    def _fwd_stem(self, r: StemRec):
+        def step():
+            st = r.stats_to
+            if st is not None:
+                ops.stem_conv_fwd_stats(self._x, r.w, r.b, r.y.act, r.kernel, st.stats, self._eps_now(st))
+                self._mask_dropped(st)
+            else:
+                ops.stem_conv_fwd(self._x, r.w, r.b, r.y.act, r.kernel)
+        return [step]
+
+    def _fwd_image(self, r: ImageRec):
+        return [lambda: ops.stem_conv_fwd(self._x, r.w, None, r.y.act, [1, 1, 1])]
+
+    def _fwd_conv(self, r: ConvRec):
+        def step():
+            self._await_pack(r.pk)
+            st = r.stats_to
+            if st is not None:
+                ops.conv3d_fwd_stats(r.x.act, r.pk["w_fwd"], r.b, r.y.act, r.kernel, r.stride, st.stats, self._eps_now(st))
+                self._mask_dropped(st)
+            else:
+                ops.conv3d_fwd(r.x.act, r.pk["w_fwd"], r.b, r.y.act, r.kernel, r.stride)
+        return [step]
+
+    def _fwd_convT(self, r: ConvTRec):
+        def step():
+            self._await_pack(r.pk)
+            ops.convT3d_fwd(r.x.act, r.pk["w_fwd"], r.b, r.y.act, r.stride)
+        return [step]
+
+    def _fwd_inact(self, r: InactRec):
+        res = r.res.act if r.res is not None else None
+        g, head, pool = r.gate, r.head_to, r.pool_to
+
+        def stats_pass():
+            if not r.stats_done:
+                ops.instnorm_stats(r.y.act, r.stats, self._eps_now(r))
+                self._mask_dropped(r)
+
+        def gated():
+            # g.scale_now: this step's DropPath factors, drawn at the start of the forward (_forward_pre)
+            if g.se is None and g.scale_now is None:        # DropPath in eval: the plain block
+                ops.instnorm_fwd(r.y.act, r.stats, r.out.act, r.slope, res, r.eps)
+                return
+            if not r.stats_done:
+                ops.instnorm_stats(r.y.act, r.stats, r.eps)
+            ops.se_gate_fwd(r.y.act, r.stats, g.se_args(), g.pooled, g.hidden, g.gate, g.mult, g.scale_now)
+            ops.instnorm_gate_act_fwd(r.y.act, r.stats, g.mult, g.keep_x, r.out.act, r.slope, res)
+
+        def with_head():
+            stats_pass()
+            # the activated output is stored only if somebody will read it: a training plan whose backward rebuilds the
+            # head's gradients from y (r.head_dw_fused, set by _bwd_inact) and an inference plan do not
+            keep = self.needs_grad and not r.head_dw_fused
+            ops.instnorm_act_head_fwd(r.y.act, r.stats, r.out.act if keep else None, head.w.view(head.k, -1), head.b, head.out,
+                                      head.act if self._apply_act else _l.RX_ACT_NONE, r.slope)
+
+        def with_pool():
+            stats_pass()
+            ops.instnorm_act_pool_fwd(r.y.act, r.stats, r.out.act, pool.y.act, pool.stride, r.slope, res)
+
+        def plain():
+            if r.stats_done:     # the producing conv left (mean, rstd) behind
+                ops.instnorm_act_fwd(r.y.act, r.stats, r.out.act, r.slope, res)
+            elif r.drop is not None and r.drop.active:     # statistics, dropped planes, apply
+                stats_pass()
+                ops.instnorm_act_fwd(r.y.act, r.stats, r.out.act, r.slope, res)
+            else:
+                ops.instnorm_fwd(r.y.act, r.stats, r.out.act, r.slope, res, r.eps)
+        if g is not None:
+            return [gated]
+        return [with_head if head is not None else with_pool if pool is not None else plain]
+
+    def _fwd_pool(self, r: PoolRec):
+        return [] if r.fused else [lambda: ops.avgpool_fwd(r.x.act, r.y.act, r.stride)]
+
+    def _fwd_copy(self, r: CopyRec):
+        return [lambda: ops.avgpool_fwd(r.x.act, r.y.act, (1, 1, 1))]
+
+    def _fwd_head(self, r: HeadRec):
+        if r.fwd_fused:          # computed by the InstanceNorm step of the layer below
+            return []
+        return [lambda: ops.head_fwd(r.x.act, r.w.view(r.k, -1), r.b, r.out, r.act if self._apply_act else _l.RX_ACT_NONE)]
+
     def _gen_forward(self):
-        P = self
         f = self.fwd
         self.n_fwd_enc = None                 # number of forward steps that belong to the encoder tape (run_encoder)
         self.fwd_dec_start = []               # first forward step of each decoder tape (run_decoder)
+        build = {StemRec: self._fwd_stem, ImageRec: self._fwd_image, ConvRec: self._fwd_conv, ConvTRec: self._fwd_convT,
+                 InactRec: self._fwd_inact, PoolRec: self._fwd_pool, CopyRec: self._fwd_copy, HeadRec: self._fwd_head}
+        full_res = self.spatial[0] * self.spatial[1] * self.spatial[2]
         for tape in [self.enc_tape] + self.dec_tapes:
-            if tape is not self.enc_tape and self.n_fwd_enc is None:
-                self.n_fwd_enc = len(f)
             if tape is not self.enc_tape:
+                if self.n_fwd_enc is None:
+                    self.n_fwd_enc = len(f)
                 self.fwd_dec_start.append(len(f))
-            # conv -> InstanceNorm pairs whose statistics can come out of the conv epilogue (rx_conv3d_fwd_stats): 3x3x3
-            # stride-1 layers in a 16-bit compute type, above the size the single-launch InstanceNorm kernel takes
-            for i, rec in enumerate(tape[:-1]):
-                nxt = tape[i + 1]
-                if (rec.kind == "conv" and nxt.kind == "inact" and nxt.a["y"] is rec.a["y"] and self.dtype != torch.float32
-                        and list(rec.a["kernel"]) == [3, 3, 3] and list(rec.a["stride"]) == [1, 1, 1]
-                        and rec.a["y"].act.voxels > 512 and rec.a["y"].act.dims[3] >= 16):
-                    rec.a["stats_to"] = nxt.a
-                    nxt.a["stats_done"] = True
-                if (rec.kind == "stem" and nxt.kind == "inact" and nxt.a["y"] is rec.a["y"] and self.dtype != torch.float32
-                        and rec.a["y"].act.voxels > 512):      # rx_stem_conv_fwd_stats
-                    rec.a["stats_to"] = nxt.a
-                    nxt.a["stats_done"] = True
-            # block output -> AvgPool of the next block's skip path: one pass (rx_instnorm_act_pool_fwd) above the size the
-            # single-launch InstanceNorm kernel takes
-            producers = {id(r.a["out"]): r for r in tape if r.kind == "inact" and r.a["gate"] is None}
+            self._fuse_conv_stats(tape)
+            self._fuse_stem_stats(tape)
+            self._fuse_block_pool(tape)
+            self._fuse_head(tape)
             for rec in tape:
-                if rec.kind == "pool" and id(rec.a["x"]) in producers and rec.a["x"].act.voxels > 512:
-                    src = producers[id(rec.a["x"])]
-                    if "pool_to" not in src.a:
-                        src.a["pool_to"] = rec.a
-                        rec.a["fused"] = True
-            # the layer under a task head: InstanceNorm apply + LeakyReLU + the head's 1x1x1 conv in one pass (the activated
-            # output is written for the backward but not re-read by a separate head kernel)
-            if self.dtype != torch.float32:
-                for rec in tape:
-                    if rec.kind != "head" or rec.a["k"] > 4:
-                        continue
-                    prods = [r for r in tape if r.kind == "inact" and r.a["out"] is rec.a["x"]]
-                    if len(prods) != 1:
-                        continue
-                    pa = prods[0].a
-                    c = pa["out"].act.c
-                    if (pa["gate"] is None and pa["res"] is None and "pool_to" not in pa and not pa.get("norm_done")
-                            and pa["out"].act.voxels > 512 and c % 8 == 0 and 64 % (c // 8) == 0):
-                        pa["head_to"] = rec.a
-                        rec.a["fwd_fused"] = True
-            for rec in tape:
-                a = rec.a
                 if (tape is self.enc_tape and self._pack_delay_at is None and rec.kind in ("conv", "pool")
-                        and rec.a["y"].act.voxels < self.spatial[0] * self.spatial[1] * self.spatial[2]):
+                        and rec.y.act.voxels < full_res):
                     self._pack_delay_at = len(f)          # the first layer below full resolution
-                if rec.kind == "stem":
-                    def sstep(a=a):
-                        st = a.get("stats_to")
-                        if st is not None:
-                            ops.stem_conv_fwd_stats(P._x, a["w"], a["b"], a["y"].act, a["kernel"], st["stats"], P._eps_now(st))
-                            P._mask_dropped(st)
-                        else:
-                            ops.stem_conv_fwd(P._x, a["w"], a["b"], a["y"].act, a["kernel"])
-                    f.append(sstep)
-                elif rec.kind == "image":        # NCDHW fp32 image -> channels-last compute type (identity 1x1x1 first-layer conv)
-                    f.append(lambda a=a: ops.stem_conv_fwd(P._x, a["w"], None, a["y"].act, [1, 1, 1]))
-                elif rec.kind == "conv":
-                    def cstep(a=a):
-                        P._await_pack(a["pk"])
-                        st = a.get("stats_to")
-                        if st is not None:
-                            ops.conv3d_fwd_stats(a["x"].act, a["pk"]["w_fwd"], a["b"], a["y"].act, a["kernel"], a["stride"],
-                                                 st["stats"], P._eps_now(st))
-                            P._mask_dropped(st)
-                        else:
-                            ops.conv3d_fwd(a["x"].act, a["pk"]["w_fwd"], a["b"], a["y"].act, a["kernel"], a["stride"])
-                    f.append(cstep)
-                elif rec.kind == "convT":
-                    def tstep(a=a):
-                        P._await_pack(a["pk"])
-                        ops.convT3d_fwd(a["x"].act, a["pk"]["w_fwd"], a["b"], a["y"].act, a["stride"])
-                    f.append(tstep)
-                elif rec.kind == "inact" and a["gate"] is not None:
-                    def gstep(a=a):
-                        g = a["gate"]
-                        res = a["res"].act if a["res"] is not None else None
-                        # g["scale_now"]: this step's DropPath factors, drawn at the start of the forward (_forward_body)
-                        if g["se"] is None and g["scale_now"] is None:        # DropPath in eval: the plain block
-                            ops.instnorm_fwd(a["y"].act, a["stats"], a["out"].act, a["slope"], res, a["eps"])
-                            return
-                        if not a.get("stats_done"):
-                            ops.instnorm_stats(a["y"].act, a["stats"], a["eps"])
-                        ops.se_gate_fwd(a["y"].act, a["stats"], P._se_args(g), g["pooled"], g["hidden"], g["gate"], g["mult"],
-                                        g["scale_now"])
-                        ops.instnorm_gate_act_fwd(a["y"].act, a["stats"], g["mult"], g["keep_x"], a["out"].act, a["slope"], res)
-                    f.append(gstep)
-                elif rec.kind == "inact":
-                    def step(a=a):
-                        res = a["res"].act if a["res"] is not None else None
-                        head = a.get("head_to")
-                        if head is not None:
-                            if not a.get("stats_done"):
-                                ops.instnorm_stats(a["y"].act, a["stats"], P._eps_now(a))
-                                P._mask_dropped(a)
-                            # the activated output is stored only if somebody will read it: a training plan whose backward
-                            # rebuilds the head's gradients from y (a["head_src"], set by _gen_backward) and an inference plan do not
-                            keep = P.needs_grad and not a.get("head_dw_fused")
-                            ops.instnorm_act_head_fwd(a["y"].act, a["stats"], a["out"].act if keep else None, head["w"].view(head["k"], -1),
-                                                      head["b"], head["out"], head["act"] if P._apply_act else _l.RX_ACT_NONE, a["slope"])
-                            return
-                        pool = a.get("pool_to")
-                        if pool is not None:
-                            if not a.get("stats_done"):
-                                ops.instnorm_stats(a["y"].act, a["stats"], P._eps_now(a))
-                                P._mask_dropped(a)
-                            ops.instnorm_act_pool_fwd(a["y"].act, a["stats"], a["out"].act, pool["y"].act, pool["stride"], a["slope"], res)
-                        elif a.get("stats_done"):     # the producing conv left (mean, rstd) behind
-                            ops.instnorm_act_fwd(a["y"].act, a["stats"], a["out"].act, a["slope"], res)
-                        elif a["drop"] is not None and a["drop"]["active"]:     # statistics, dropped planes, apply
-                            ops.instnorm_stats(a["y"].act, a["stats"], P._eps_now(a))
-                            P._mask_dropped(a)
-                            ops.instnorm_act_fwd(a["y"].act, a["stats"], a["out"].act, a["slope"], res)
-                        else:
-                            ops.instnorm_fwd(a["y"].act, a["stats"], a["out"].act, a["slope"], res, a["eps"])
-                    f.append(step)
-                elif rec.kind == "pool":
-                    if not a.get("fused"):
-                        f.append(lambda a=a: ops.avgpool_fwd(a["x"].act, a["y"].act, a["stride"]))
-                elif rec.kind == "copy":
-                    f.append(lambda a=a: ops.avgpool_fwd(a["x"].act, a["y"].act, (1, 1, 1)))
-                elif rec.kind == "head":
-                    if a.get("fwd_fused"):          # computed by the InstanceNorm step of the layer below
-                        continue
-
-                    def step(a=a):
-                        w2 = a["w"].view(a["k"], -1)
-                        ops.head_fwd(a["x"].act, w2, a["b"], a["out"], a["act"] if P._apply_act else _l.RX_ACT_NONE)
-                    f.append(step)
+                f += build[type(rec)](rec)
 
     def _dy_for(self, y: AT):
         """scratch buffer for dL/dy of a conv output.  Two per shape, used alternately: the weight-gradient kernel
@@ -768,309 +936,283 @@ class Plan:
             self.dy_pool[slot] = Act(t)
         return self.dy_pool[slot]
 
-    def _gen_backward(self):
-        P = self
-        b = self.bwd
-        cat_written = {}
+    # ------------------------------------------------------------------ backward: what the steps call while they run
+    def _new_grad(self, idx):
+        """a FRESH tensor every backward (autograd may keep / accumulate into what we return); a gradient synchroniser may
+        hand out views of its flat buckets instead (engine/ddp.py)"""
+        ent = self._pad_idx.get(idx)
+        if ent is not None:                 # padded parameter: the kernels write the padded gradient, _backward_finish slices it
+            if ent["gpad"] is None:
+                ent["gpad"] = torch.empty(tuple(ent["sh"].shape), dtype=torch.float32, device=self.device)
+            self._pad_done.append(idx)
+            return ent["gpad"]
+        if self.grad_sync is not None:
+            g = self.grad_sync.alloc(idx)
+        elif self._use_gstore:             # program mode: the same storage every backward (see _grad_store)
+            g = self._gviews[idx]
+        else:
+            g = torch.empty_like(self.params[idx], memory_format=torch.contiguous_format)
+        self._grads[idx] = g
+        return g
 
-        def mark_cat(cat):
-            cat_written[cat.act.key] = True
+    def _grad_done(self, idx):
+        if idx in self._pad_idx:               # completed (and announced to a gradient synchroniser) in _backward_finish
+            return
+        if self._recording is not None:        # while a program is recorded: where in the command list the gradient is complete
+            self._marks.append((len(self._recording), idx, self._on_side))
+        if self.grad_sync is not None:
+            self.grad_sync.ready(idx)
 
-        def view_written(at):
-            return at.written or cat_written.get(at.act.key, False)
+    def _side_run(self, fn, dy_act):
+        """run `fn` (weight-gradient launches reading dy_act) on the side stream, ordered after everything the main stream has
+        enqueued so far.  An event guards dy_act: the side stream's last reader of a dy slot must be done before the main
+        stream writes that slot again (_before_dy_write)"""
+        if not (self.overlap_wgrad and self._side is not None):
+            fn(ops.workspace())
+            return
+        ops.event_record(self._ev_fork)              # main (current) stream
+        ops.stream_wait(self._ev_fork, self._side)
+        key = id(dy_act.t)
+        slot = self._dy_ev.get(key)
+        if slot is None:
+            slot = self._dy_ev[key] = ops.event_new()
+        self._on_side = True
+        try:
+            with torch.cuda.stream(self._side):
+                fn(self._ws2)
+                ops.event_record(slot)
+        finally:
+            self._on_side = False
+        self._dy_free[key] = slot
 
-        def new_grad(idx):
-            # a FRESH tensor every backward (autograd may keep / accumulate into what we return); a gradient
-            # synchroniser may hand out views of its flat buckets instead (engine/ddp.py)
-            sync = P.grad_sync
-            ent = P._pad_idx.get(idx)
-            if ent is not None:                 # padded parameter: the kernels write the padded gradient, _backward_finish slices it
-                if ent["gpad"] is None:
-                    ent["gpad"] = torch.empty(tuple(ent["sh"].shape), dtype=torch.float32, device=P.device)
-                P._pad_done.append(idx)
-                return ent["gpad"]
-            if sync is not None:
-                g = sync.alloc(idx)
-            elif P._use_gstore:             # program mode: the same storage every backward (see _grad_store)
-                g = P._gviews[idx]
+    def _before_dy_write(self, dy_act):
+        slot = self._dy_free.pop(id(dy_act.t), None)
+        if slot is not None:
+            ops.stream_wait(slot)
+
+    def _wgrad_step(self, r, dy, weight_launch):
+        """dw (`weight_launch(dw, ws)`) and db = sum(dy) of a conv-like record, on the side stream"""
+        def step():
+            dw = self._new_grad(r.widx)
+            db = self._new_grad(r.bidx) if r.bidx is not None else None
+
+            def launches(ws):
+                weight_launch(dw, ws)
+                self._grad_done(r.widx)
+                if db is not None:
+                    ops.channel_sum(dy, db, ws)
+                    self._grad_done(r.bidx)
+            self._side_run(launches, dy)
+        self.grad_order += [r.widx] + ([r.bidx] if r.bidx is not None else [])
+        return step
+
+    # ------------------------------------------------------------------ backward: build-time bookkeeping (order-dependent)
+    def _view_written(self, at: AT):
+        return at.written or self._cat_written.get(at.act.key, False)
+
+    def _claim_grad(self, at: AT, rec):
+        """`rec`'s backward step writes the gradient of `at`: its buffer, and whether an earlier step initialised it (accumulate)"""
+        g = self._grad_buf(at)
+        acc = self._view_written(at)
+        at.written, at.last_writer = True, rec
+        return g, acc
+
+    def _cat_grad(self, r):
+        """the view of the concat gradient that mirrors r.y (the upsampled / the copied half)"""
+        return r.y.act.like(r.cat.gact.root if r.cat.gact.root is not None else r.cat.gact.t)
+
+    # ------------------------------------------------------------------ backward: one step builder per record kind
+    def _bwd_head(self, r: HeadRec, tape, i):
+        assert not self._view_written(r.x)
+        gx, _ = self._claim_grad(r.x, r)
+
+        def step():
+            dl = self._dlogits.get(r.name)
+            if dl is None:      # this task did not take part in the loss
+                gx.t.zero_()
+                if self.grad_sync is not None:     # collectives need every rank to fill every bucket
+                    for j in (r.widx, r.bidx):
+                        self._new_grad(j).zero_()
+                        self._grad_done(j)
+                return
+            if r.dw_fused:      # dw / db come out of the InstanceNorm backward's reduce pass (next step)
+                return
+            dw, db = self._new_grad(r.widx), self._new_grad(r.bidx)
+            ops.head_bwd(dl, r.x.act, r.w.view(r.k, -1), None if r.dx_fused else gx, dw, db)
+            self._grad_done(r.widx)
+            self._grad_done(r.bidx)
+        self.grad_order += [r.widx, r.bidx]
+        return [step]
+
+    def _bwd_inact(self, r: InactRec, tape, i):
+        out, y, res = r.out, r.y, r.res
+        gout = self._grad_buf(out)
+        if not self._view_written(out):
+            raise RuntimeError(f"plan bug: gradient of {out.name} is consumed before it is produced")
+        dy = y.gact = self._dy_for(y)
+        gres, acc = None, False
+        if res is not None and res.needs_grad:        # (the converted image of a stem-less net needs no gradient)
+            gres, acc = self._claim_grad(res, r)
+        plain16 = r.gate is None and res is None and self.dtype != torch.float32 and _above_single_launch(out.act)
+        last = out.last_writer
+        # the layer under a task head (no residual): its output gradient is rank K -- rebuilt from the logit gradient
+        # inside both InstanceNorm passes instead of written by the head and read back twice
+        if plain16 and isinstance(last, HeadRec):
+            heads = [h for h in tape if h.kind == "head" and h.x is out]
+            if len(heads) == 1 and heads[0].k <= 4:
+                r.head_src, last.dx_fused = heads[0], True
+                # ... and the head's own dw / db from the same reduce pass (the activation is recomputed from y): no
+                # head_bwd launch, and the forward does not store this layer's activated output at all.  Needs the
+                # forward's fused head (the un-fused head kernel reads the stored output) and an un-padded head weight.
+                if heads[0].fwd_fused and heads[0].w is self.params[heads[0].widx]:
+                    r.head_dw_fused, last.dw_fused = True, True
+        # the output gradient is completed by a 3x3x3 backward-data launch: that launch accumulates this layer's two
+        # backward sums in its epilogue (rx_conv3d_bwd_data_instats) and the reduce pass over (g, y) disappears
+        if (plain16 and isinstance(last, ConvRec) and out.act.full_buffer and out.act.root is None and out.act.c % 32 == 0
+                and _halo_x_ok(out.act)):
+            r.m12 = torch.empty((self.B, out.act.c, 2), dtype=torch.float32, device=self.device)
+            last.instats_for = r
+        if r.gate is not None:
+            return [self._bwd_inact_gated(r, gout, dy, gres, acc)]
+        # residual-block epilogue whose residual gradient starts here: the masked gradient g' is written ONCE (by the
+        # reduce pass, into gres) and the apply pass reads (g', y) only -- rx_instnorm_act_bwd_res, 7 tensor passes
+        # instead of 8; if the AvgPool of the next stage's skip path was the last writer of gout, its gradient is
+        # added on the fly and that pass (1R 1W over the full-resolution gradient) is gone too
+        pend, out.pool_pending = out.pool_pending, None
+        if gres is not None and not acc and _above_single_launch(y.act):
+            return [self._bwd_inact_res(r, gout, dy, gres, pend)]
+        steps = []
+        if pend is not None:        # the deferred pool gradient runs as its own pass after all
+            steps.append(lambda: ops.avgpool_bwd(pend.gy, pend.gx, pend.stride, True))
+        return steps + [self._bwd_inact_plain(r, gout, dy, gres, acc)]
+
+    def _bwd_inact_gated(self, r, gout, dy, gres, acc):
+        g = r.gate
+
+        def step():
+            self._before_dy_write(dy)
+            if g.se is None and g.scale_now is None:
+                ops.instnorm_act_bwd(gout, r.y.act, r.stats, r.out.act if (r.slope != 1.0 and r.res is not None) else None, dy,
+                                     r.slope, gres, acc)
+                return
+            grads = [self._new_grad(j) for j in g.se.idx] if g.se is not None else [None] * 4
+            ops.se_gate_bwd(gout, r.y.act, r.stats, r.out.act, r.slope, g.se_args(), g.pooled, g.hidden, g.gate, g.mult, g.dadd,
+                            g.m12, *grads, path_scale=g.scale_now)
+            ops.instnorm_gate_act_bwd(gout, r.y.act, r.stats, r.out.act, r.slope, g.mult, g.dadd, g.m12, g.keep_x, dy, gres, acc)
+            if g.se is not None:
+                for j in g.se.idx:
+                    self._grad_done(j)
+        if g.se is not None:
+            self.grad_order += g.se.idx
+        return step
+
+    def _bwd_inact_res(self, r, gout, dy, gres, pend):
+        def step():
+            self._before_dy_write(dy)
+            ops.instnorm_act_bwd_res(gout, r.y.act, r.stats, r.out.act, dy, gres, r.slope,
+                                     pool_dy=pend.gy if pend is not None else None,
+                                     pool_stride=pend.stride if pend is not None else (1, 1, 1))
+        return step
+
+    def _bwd_inact_plain(self, r, gout, dy, gres, acc):
+        # the saved output is only needed for the mask of residual blocks (sign(out) != sign(xhat) there)
+        mask_out = r.out.act if (r.slope != 1.0 and r.res is not None) else None
+        hs = r.head_src
+
+        def step():
+            self._before_dy_write(dy)
+            dl = self._dlogits.get(hs.name) if hs is not None else None   # None: task outside the loss, gout was zeroed
+            if dl is not None and r.head_dw_fused:
+                dw, db = self._new_grad(hs.widx), self._new_grad(hs.bidx)
+                ops.instnorm_act_bwd_head(dl, hs.w.view(hs.k, -1), r.y.act, r.stats, dy, r.slope, dw=dw.view(hs.k, -1), db=db)
+                self._grad_done(hs.widx)
+                self._grad_done(hs.bidx)
+            elif dl is not None:
+                ops.instnorm_act_bwd_head(dl, hs.w.view(hs.k, -1), r.y.act, r.stats, dy, r.slope)
+            elif r.m12_valid:      # the two means came out of the backward-data kernel that completed gout
+                r.m12_valid = False
+                ops.instnorm_act_bwd_apply(gout, r.y.act, r.stats, mask_out, dy, r.m12, r.slope, gres, acc)
+            elif "inbwd_reduce" in self._skip and _above_single_launch(r.y.act):
+                if r.m12x is None:
+                    r.m12x = torch.zeros((self.B, r.y.act.c, 2), dtype=torch.float32, device=self.device)
+                ops.instnorm_act_bwd_apply(gout, r.y.act, r.stats, mask_out, dy, r.m12x, r.slope, gres, acc)
             else:
-                g = torch.empty_like(P.params[idx], memory_format=torch.contiguous_format)
-            P._grads[idx] = g
-            return g
+                ops.instnorm_act_bwd(gout, r.y.act, r.stats, mask_out, dy, r.slope, gres, acc)
+        return step
 
+    def _bwd_conv(self, r, tape, i):
+        """ConvRec / StemRec: weight + bias gradient on the side stream; (conv with an input gradient) data gradient on the main"""
+        dy = r.y.gact
+
+        def wlaunch(dw, ws):
+            if r.kind == "stem":
+                ops.stem_conv_bwd_weight(self._x, dy, dw, r.kernel, ws)
+            elif "wgrad" not in self._skip:
+                ops.conv3d_bwd_weight(r.x.act, dy, dw, r.kernel, r.stride, ws)
+        steps = [self._wgrad_step(r, dy, wlaunch)]
+        if r.kind == "conv" and r.x.needs_grad:
+            gx, acc = self._claim_grad(r.x, r)
+            if r.x.act.full_buffer:
+                self._cat_written[r.x.act.key] = True     # a full-buffer write initialises every channel view of it
+
+            def dstep():
+                if "dgrad" in self._skip:
+                    return
+                ia = r.instats_for
+                if ia is None:
+                    ops.conv3d_bwd_data(dy, r.pk["w_bwd"], gx, r.kernel, r.stride, acc)
+                else:
+                    ia.m12_valid = ops.conv3d_bwd_data_instats(dy, r.pk["w_bwd"], gx, r.kernel, r.stride, acc, ia.y.act, ia.stats,
+                                                               ia.slope, ia.m12)
+            steps.append(dstep)
+        return steps
+
+    def _bwd_convT(self, r: ConvTRec, tape, i):
+        if not self._view_written(r.y):
+            raise RuntimeError("plan bug: concat gradient not initialised before the transposed conv")
+        gy = self._cat_grad(r)
+        gx, acc = self._claim_grad(r.x, r)
+        # weight gradient on the side stream (gy is a gradient buffer that is not rewritten in this backward), then the data gradient
+        wstep = self._wgrad_step(r, gy, lambda dw, ws: ops.convT3d_bwd_weight(r.x.act, gy, dw, r.stride, ws))
+
+        def step():
+            wstep()
+            ops.convT3d_bwd_data(gy, r.pk["w_bwd"], gx, r.stride, acc)
+        return [step]
+
+    def _bwd_pool(self, r: PoolRec, tape, i):
+        x = r.x
+        if not x.needs_grad:
+            return []
+        gx, acc = self._claim_grad(x, r)
+        gy = r.y.gact
+        assert gy is not None, "plan bug: pooled tensor has no gradient"
+        # the pool opens a stage's skip path; x is the previous stage's last block output, whose InstanceNorm backward
+        # is the very next step: hand the pool gradient to it instead of accumulating it in a pass of its own
+        prev = tape[i - 1] if i > 0 else None
+        if (acc and prev is not None and prev.kind == "inact" and prev.out is x and prev.res is not None and prev.gate is None
+                and _above_single_launch(x.act)):
+            x.pool_pending = PendingPool(gy, gx, r.stride)
+            return []
+        return [lambda: ops.avgpool_bwd(gy, gx, r.stride, acc)]
+
+    def _bwd_copy(self, r: CopyRec, tape, i):
+        gy = self._cat_grad(r)
+        gx, acc = self._claim_grad(r.x, r)
+        return [lambda: ops.avgpool_bwd(gy, gx, (1, 1, 1), acc)]
+
+    def _gen_backward(self):
         # TIMING ABLATIONS ONLY (wrong results): honoured only together with RX_ABLATION=1, anything else is an error (ADVICE r2)
-        skip = set(filter(None, os.environ.get("RX_SKIP", "").split(",")))
-        if skip and os.environ.get("RX_ABLATION", "0") != "1":
+        self._skip = frozenset(filter(None, os.environ.get("RX_SKIP", "").split(",")))
+        if self._skip and os.environ.get("RX_ABLATION", "0") != "1":
             raise _l.RxError("RX_SKIP drops launches from the backward pass (timing ablations, wrong gradients): "
                              "set RX_ABLATION=1 as well to confirm, or unset RX_SKIP")
-
-        def done(idx):
-            if idx in P._pad_idx:               # completed (and announced to a gradient synchroniser) in _backward_finish
-                return
-            if P._recording is not None:        # while a program is recorded: where in the command list the gradient is complete
-                P._marks.append((len(P._recording), idx, P._on_side))
-            if P.grad_sync is not None:
-                P.grad_sync.ready(idx)
-
-        # events guarding the dy slots of every shape: the side stream's last reader of a slot must be done
-        # before the main stream writes that slot again
-        dy_free = self._dy_free
-
-        def side_run(fn, dy_act):
-            """run `fn` (weight-gradient launches reading dy_act) on the side stream, ordered after everything the
-            main stream has enqueued so far"""
-            if not (P.overlap_wgrad and P._side is not None):
-                fn(ops.workspace())
-                return
-            ops.event_record(P._ev_fork)              # main (current) stream
-            ops.stream_wait(P._ev_fork, P._side)
-            key = id(dy_act.t)
-            slot = P._dy_ev.get(key)
-            if slot is None:
-                slot = P._dy_ev[key] = ops.event_new()
-            P._on_side = True
-            try:
-                with torch.cuda.stream(P._side):
-                    fn(P._ws2)
-                    ops.event_record(slot)
-            finally:
-                P._on_side = False
-            dy_free[key] = slot
-
-        def before_dy_write(dy_act):
-            slot = dy_free.pop(id(dy_act.t), None)
-            if slot is not None:
-                ops.stream_wait(slot)
-
-        order = self.grad_order
-
-        # who wrote an activation's gradient LAST (plan-build order = run order): when the output gradient of an InstanceNorm
-        # layer WITHOUT residual is completed by a 3x3x3 backward-data launch, that launch can accumulate the layer's two
-        # backward sums in its epilogue (rx_conv3d_bwd_data_instats) and the reduce pass over (g, y) disappears
-        def wrote(at, kind, info=None):
-            at._gw = (kind, info)
-
+        build = {HeadRec: self._bwd_head, InactRec: self._bwd_inact, ConvRec: self._bwd_conv, StemRec: self._bwd_conv,
+                 ConvTRec: self._bwd_convT, PoolRec: self._bwd_pool, CopyRec: self._bwd_copy, ImageRec: lambda r, tape, i: []}
+        # ONE reverse walk: `written` / accumulate / last-writer are decided in run order, step by step
         for tape in self.dec_tapes + [self.enc_tape]:
-            for rec in reversed(tape):
-                a = rec.a
-                if rec.kind == "head":
-                    x = a["x"]
-                    assert not view_written(x)
-                    gx = self._grad_buf(x)
-                    x.written = True
-                    hinfo = {"fused": False}      # set by the InstanceNorm step below when it rebuilds the head's data gradient itself
-                    wrote(x, "head", hinfo)
-                    a["hinfo"] = hinfo
-
-                    def step(a=a, gx=gx, hinfo=hinfo):
-                        dl = P._dlogits.get(a["name"])
-                        if dl is None:      # this task did not take part in the loss
-                            gx.t.zero_()
-                            if P.grad_sync is not None:     # collectives need every rank to fill every bucket
-                                for i in (a["widx"], a["bidx"]):
-                                    new_grad(i).zero_()
-                                    done(i)
-                            return
-                        if hinfo.get("dw_fused"):     # dw / db come out of the InstanceNorm backward's reduce pass (next step)
-                            return
-                        dw, db = new_grad(a["widx"]), new_grad(a["bidx"])
-                        ops.head_bwd(dl, a["x"].act, a["w"].view(a["k"], -1), None if hinfo["fused"] else gx, dw, db)
-                        done(a["widx"])
-                        done(a["bidx"])
-                    order += [a["widx"], a["bidx"]]
-                    b.append(step)
-                elif rec.kind == "inact":
-                    out, y, res = a["out"], a["y"], a["res"]
-                    gout = self._grad_buf(out) if out.gact is None else out.gact
-                    if not view_written(out):
-                        raise RuntimeError(f"plan bug: gradient of {out.name} is consumed before it is produced")
-                    dy = self._dy_for(y)
-                    y.gact = dy
-                    gres, acc = None, False
-                    if res is not None and res.needs_grad:        # (the converted image of a stem-less net needs no gradient)
-                        gres = self._grad_buf(res)
-                        acc = view_written(res)
-                        res.written = True
-                        wrote(res, "gres")
-                    gw = getattr(out, "_gw", (None, None))
-                    # the layer under a task head (no residual): its output gradient is rank K -- rebuilt from the logit gradient
-                    # inside both InstanceNorm passes instead of written by the head and read back twice
-                    if (gw[0] == "head" and a["gate"] is None and res is None and self.dtype != torch.float32
-                            and out.act.voxels > 512):
-                        heads = [r.a for r in tape if r.kind == "head" and r.a["x"] is out]
-                        if len(heads) == 1 and heads[0]["k"] <= 4:
-                            a["head_src"] = heads[0]
-                            gw[1]["fused"] = True
-                            # ... and the head's own dw / db from the same reduce pass (the activation is recomputed from y): no
-                            # head_bwd launch, and the forward does not store this layer's activated output at all.  Needs the
-                            # forward's fused head (the un-fused head kernel reads the stored output) and an un-padded head weight.
-                            if heads[0].get("fwd_fused") and heads[0]["w"] is self.params[heads[0]["widx"]]:
-                                a["head_dw_fused"] = True
-                                gw[1]["dw_fused"] = True
-                    if (gw[0] == "conv" and a["gate"] is None and res is None and self.dtype != torch.float32
-                            and out.act.full_buffer and out.act.root is None and out.act.c % 32 == 0 and out.act.voxels > 512
-                            and out.act.dims[3] >= 16):
-                        a["m12"] = torch.empty((self.B, out.act.c, 2), dtype=torch.float32, device=self.device)
-                        a["m12_valid"] = False
-                        gw[1]["inact"] = a          # that conv's backward-data step now also fills a["m12"]
-                    def gistep(a=a, gout=gout, dy=dy, gres=gres, acc=acc):
-                        g = a["gate"]
-                        before_dy_write(dy)
-                        if g["se"] is None and g.get("scale_now") is None:
-                            ops.instnorm_act_bwd(gout, a["y"].act, a["stats"],
-                                                 a["out"].act if (a["slope"] != 1.0 and a["res"] is not None) else None, dy,
-                                                 a["slope"], gres, acc)
-                            return
-                        grads = [new_grad(i) for i in g["se"]["idx"]] if g["se"] is not None else [None] * 4
-                        ops.se_gate_bwd(gout, a["y"].act, a["stats"], a["out"].act, a["slope"], P._se_args(g), g["pooled"],
-                                        g["hidden"], g["gate"], g["mult"], g["dadd"], g["m12"], *grads,
-                                        path_scale=g.get("scale_now"))
-                        ops.instnorm_gate_act_bwd(gout, a["y"].act, a["stats"], a["out"].act, a["slope"], g["mult"], g["dadd"],
-                                                  g["m12"], g["keep_x"], dy, gres, acc)
-                        if g["se"] is not None:
-                            for i in g["se"]["idx"]:
-                                done(i)
-                    if a["gate"] is not None:
-                        if a["gate"]["se"] is not None:
-                            order += a["gate"]["se"]["idx"]
-                        b.append(gistep)
-                        continue
-
-                    # residual-block epilogue whose residual gradient starts here: the masked gradient g' is written ONCE (by the
-                    # reduce pass, into gres) and the apply pass reads (g', y) only -- rx_instnorm_act_bwd_res, 7 tensor passes
-                    # instead of 8; if the AvgPool of the next stage's skip path was the last writer of gout, its gradient is
-                    # added on the fly and that pass (1R 1W over the full-resolution gradient) is gone too
-                    pend = getattr(out, "_pool_pending", None)
-                    out._pool_pending = None
-                    fuse_res = gres is not None and not acc and res is not None and y.act.voxels > 512
-                    if pend is not None and not fuse_res:        # the deferred pool gradient runs as its own pass after all
-                        b.append(lambda pend=pend: ops.avgpool_bwd(pend["gy"], pend["gx"], pend["stride"], True))
-                        pend = None
-                    if fuse_res:
-                        def rstep(a=a, gout=gout, dy=dy, gres=gres, pend=pend):
-                            before_dy_write(dy)
-                            ops.instnorm_act_bwd_res(gout, a["y"].act, a["stats"], a["out"].act, dy, gres, a["slope"],
-                                                     pool_dy=pend["gy"] if pend is not None else None,
-                                                     pool_stride=pend["stride"] if pend is not None else (1, 1, 1))
-                        b.append(rstep)
-                        continue
-
-                    def istep(a=a, gout=gout, dy=dy, gres=gres, acc=acc):
-                        before_dy_write(dy)
-                        # the saved output is only needed for the mask of residual blocks (sign(out) != sign(xhat) there)
-                        mask_out = a["out"].act if (a["slope"] != 1.0 and a["res"] is not None) else None
-                        hs = a.get("head_src")
-                        dl = P._dlogits.get(hs["name"]) if hs is not None else None   # None: task outside the loss, gout was zeroed
-                        if dl is not None and a.get("head_dw_fused"):
-                            dw, db = new_grad(hs["widx"]), new_grad(hs["bidx"])
-                            ops.instnorm_act_bwd_head(dl, hs["w"].view(hs["k"], -1), a["y"].act, a["stats"], dy, a["slope"],
-                                                      dw=dw.view(hs["k"], -1), db=db)
-                            done(hs["widx"])
-                            done(hs["bidx"])
-                        elif dl is not None:
-                            ops.instnorm_act_bwd_head(dl, hs["w"].view(hs["k"], -1), a["y"].act, a["stats"], dy, a["slope"])
-                        elif a.get("m12_valid"):      # the two means came out of the backward-data kernel that completed gout
-                            a["m12_valid"] = False
-                            ops.instnorm_act_bwd_apply(gout, a["y"].act, a["stats"], mask_out, dy, a["m12"], a["slope"], gres, acc)
-                        elif "inbwd_reduce" in skip and a["y"].act.voxels > 512:
-                            if "m12x" not in a:
-                                a["m12x"] = torch.zeros((self.B, a["y"].act.c, 2), dtype=torch.float32, device=self.device)
-                            ops.instnorm_act_bwd_apply(gout, a["y"].act, a["stats"], mask_out, dy, a["m12x"], a["slope"], gres, acc)
-                        else:
-                            ops.instnorm_act_bwd(gout, a["y"].act, a["stats"], mask_out, dy, a["slope"], gres, acc)
-                    b.append(istep)
-                elif rec.kind in ("conv", "stem"):
-                    y = a["y"]
-                    dy = y.gact
-
-                    def wstep(a=a, dy=dy, kind=rec.kind):
-                        dw = new_grad(a["widx"])
-                        db = new_grad(a["bidx"]) if a["bidx"] is not None else None
-
-                        def launches(ws):
-                            if "wgrad" in skip and kind != "stem":
-                                pass
-                            elif kind == "stem":
-                                ops.stem_conv_bwd_weight(P._x, dy, dw, a["kernel"], ws)
-                            else:
-                                ops.conv3d_bwd_weight(a["x"].act, dy, dw, a["kernel"], a["stride"], ws)
-                            done(a["widx"])
-                            if db is not None:
-                                ops.channel_sum(dy, db, ws)
-                                done(a["bidx"])
-                        side_run(launches, dy)
-                    order += [a["widx"]] + ([a["bidx"]] if a["bidx"] is not None else [])
-                    b.append(wstep)
-                    if rec.kind == "conv" and a["x"].needs_grad:
-                        x = a["x"]
-                        gx = self._grad_buf(x)
-                        acc = view_written(x)
-                        x.written = True
-                        if x.act.full_buffer:
-                            mark_cat(x)     # a full-buffer write initialises every channel view of it
-                        bsinfo = {"inact": None}
-                        wrote(x, "conv", bsinfo)
-
-                        def dstep(a=a, dy=dy, gx=gx, acc=acc, bsinfo=bsinfo):
-                            if "dgrad" in skip:
-                                return
-                            ia = bsinfo["inact"]
-                            if ia is None:
-                                ops.conv3d_bwd_data(dy, a["pk"]["w_bwd"], gx, a["kernel"], a["stride"], acc)
-                            else:
-                                ia["m12_valid"] = ops.conv3d_bwd_data_instats(dy, a["pk"]["w_bwd"], gx, a["kernel"], a["stride"], acc,
-                                                                              ia["y"].act, ia["stats"], ia["slope"], ia["m12"])
-                        b.append(dstep)
-                elif rec.kind == "convT":
-                    x, y = a["x"], a["y"]
-                    if not view_written(y):
-                        raise RuntimeError("plan bug: concat gradient not initialised before the transposed conv")
-                    gy = y.act.like(a["cat"].gact.root if a["cat"].gact.root is not None else a["cat"].gact.t)
-                    gx = self._grad_buf(x)
-                    acc = view_written(x)
-                    x.written = True
-                    wrote(x, "convT")
-
-                    def step(a=a, gy=gy, gx=gx, acc=acc):
-                        dw = new_grad(a["widx"])
-                        db = new_grad(a["bidx"]) if a["bidx"] is not None else None
-
-                        def launches(ws):
-                            ops.convT3d_bwd_weight(a["x"].act, gy, dw, a["stride"], ws)
-                            done(a["widx"])
-                            if db is not None:
-                                ops.channel_sum(gy, db, ws)
-                                done(a["bidx"])
-                        side_run(launches, gy)      # gy is a gradient buffer that is not rewritten in this backward
-                        ops.convT3d_bwd_data(gy, a["pk"]["w_bwd"], gx, a["stride"], acc)
-                    order += [a["widx"]] + ([a["bidx"]] if a["bidx"] is not None else [])
-                    b.append(step)
-                elif rec.kind == "pool":
-                    x, y = a["x"], a["y"]
-                    if not x.needs_grad:
-                        continue
-                    gx = self._grad_buf(x)
-                    acc = view_written(x)
-                    x.written = True
-                    wrote(x, "pool")
-                    assert y.gact is not None, "plan bug: pooled tensor has no gradient"
-                    # the pool opens a stage's skip path; x is the previous stage's last block output, whose InstanceNorm backward
-                    # is the very next step: hand the pool gradient to it instead of accumulating it in a pass of its own (above)
-                    ti = next(i for i, r in enumerate(tape) if r is rec)
-                    prev = tape[ti - 1] if ti > 0 else None
-                    if (acc and prev is not None and prev.kind == "inact" and prev.a["out"] is x and prev.a["res"] is not None
-                            and prev.a["gate"] is None and x.act.voxels > 512):
-                        x._pool_pending = dict(gy=y.gact, gx=gx, stride=a["stride"])
-                        continue
-                    b.append(lambda a=a, gy=y.gact, gx=gx, acc=acc: ops.avgpool_bwd(gy, gx, a["stride"], acc))
-                elif rec.kind == "copy":
-                    x, y = a["x"], a["y"]
-                    gy = y.act.like(a["cat"].gact.root if a["cat"].gact.root is not None else a["cat"].gact.t)
-                    gx = self._grad_buf(x)
-                    acc = view_written(x)
-                    x.written = True
-                    wrote(x, "copy")
-                    b.append(lambda gy=gy, gx=gx, acc=acc: ops.avgpool_bwd(gy, gx, (1, 1, 1), acc))
+            for i in reversed(range(len(tape))):
+                self.bwd += build[type(tape[i])](tape[i], tape, i)
 
     def _grad_buf(self, at: AT):
         """gradient buffer of an activation; channel views of one buffer share one gradient buffer"""
@@ -1166,8 +1308,7 @@ class Plan:
         self._pack_groups_now(groups, side, 0)
 
     def _pack_groups_now(self, groups, side, gi0):
-        ctx = torch.cuda.stream(side) if side is not None else _NullCtx()
-        with ctx:
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             for gi, grp in enumerate(groups, gi0):
                 items = []
                 for ent in grp:
@@ -1200,7 +1341,7 @@ class Plan:
     # ---- launch programs -------------------------------------------------------------------------------------
     def _programs_on(self):
         return (self.use_programs and not self.use_graphs and self.device.type == "cuda" and ops._PROF is None
-                and not getattr(self, "_unstable_params", False))
+                and not self._unstable_params)
 
     def _streams(self):
         main = torch.cuda.current_stream()
@@ -1303,13 +1444,13 @@ class Plan:
             torch.cuda.current_stream().wait_event(ev)
             self._raw_seen = ev
         for g in self._gates:                               # DropPath: this step's per-sample factors (torch RNG)
-            g["scale_now"] = self._draw_path_scale(g)
+            g.scale_now = self._draw_path_scale(g)
         if self._shadows:                                   # padded channel extents: zero-padded copies of the parameters
             self._refresh_shadows()
         training = bool(self.net.training)
         for d in self._drops:                               # channel dropout: this step's kept planes, in forward order
-            d["active"] = training
-            d["eps_now"] = d["eps"] * (1.0 - d["p"]) ** 2 if training else d["eps"]
+            d.active = training
+            d.eps_now = d.eps * (1.0 - d.p) ** 2 if training else d.eps
             if training:
                 self._draw_dropout(d)
 
@@ -1319,8 +1460,13 @@ class Plan:
             if i == self._pack_delay_at:
                 self._issue_deferred_packs()
             step()
+        self._finish_packs()
+
+    def _finish_packs(self):
+        """issue the pack groups still held back, then wait for every pack (parameters of unused branches included: never leave
+        a pack in flight)"""
         self._issue_deferred_packs()
-        for ent in self.packs:          # parameters of unused branches: never leave a pack in flight
+        for ent in self.packs:
             self._await_pack(ent)
 
     def _mark_packs_fresh(self):
@@ -1329,20 +1475,32 @@ class Plan:
             ent["version"], ent["ptr"], ent["event"] = ent["param"]._version, ent["param"].data_ptr(), None
             ent["epoch"] = epoch
 
-    def run_forward(self, x, apply_act):
+    def _as_input(self, x):
+        """the caller's image as the first-layer kernels read it: detached, fp32, contiguous, of the shape the plan was built for"""
         if tuple(x.shape) != self.in_shape:
             raise ValueError(f"plan built for input {self.in_shape}, got {tuple(x.shape)}")
         x = x.detach()
         if x.dtype != torch.float32 or not x.is_contiguous():
             x = x.float().contiguous()
+        return x
+
+    def _set_input(self, x, static=False):
+        """make x this step's image; `static`: through a persistent copy (a graph / program reads a fixed address)"""
+        if static:
+            if self._x_static is None:
+                self._x_static = torch.empty(self.in_shape, dtype=torch.float32, device=self.device)
+            self._x_static.copy_(x)
+            x = self._x_static
+        self._x = x.unsqueeze(2) if self.two_d else x
+        if self._image_t is not None:
+            self._image_t.act.t[..., :self.Cin].copy_(self._x.permute(0, 2, 3, 4, 1))
+
+    def run_forward(self, x, apply_act):
+        x = self._as_input(x)
         self._apply_act = apply_act
         self._forward_pre()
         if self._graphs_on():
-            if self._x_static is None:
-                self._x_static = torch.empty(self.in_shape, dtype=torch.float32, device=self.device)
-            self._x_static.copy_(x)                 # the graph reads a fixed address
-            self._x = self._x_static.unsqueeze(2) if self.two_d else self._x_static
-            self._fill_image_t()
+            self._set_input(x, static=True)
             st = self._gstate.get(("f", apply_act))
             capturing = st is not None and st.get("graph") is None and st["calls"] >= 2
             self._graphed(("f", apply_act), lambda: self._forward_body(force_packs=capturing))
@@ -1351,21 +1509,16 @@ class Plan:
                 self._mark_packs_fresh()
         elif self._programs_on():
             self._ensure_side()
-            if self._x_static is None:
-                self._x_static = torch.empty(self.in_shape, dtype=torch.float32, device=self.device)
-            self._x_static.copy_(x)                 # the program reads a fixed address
-            self._x = self._x_static.unsqueeze(2) if self.two_d else self._x_static
-            self._fill_image_t()
+            self._set_input(x, static=True)
             stale = bool(self._packs_stale())
-            dropping = any(g["scale_now"] is not None for g in self._gates) or any(d["active"] for d in self._drops)
+            dropping = any(g.scale_now is not None for g in self._gates) or any(d.active for d in self._drops)
             # one program per launch-list VARIANT: with / without the weight re-pack, with / without DropPath factors
             key = ("f", apply_act, stale, dropping, self.overlap_wgrad)
             _, replayed = self._programmed(key, lambda: self._forward_body(force_packs=stale))
             if replayed and stale:
                 self._mark_packs_fresh()
         else:
-            self._x = x.unsqueeze(2) if self.two_d else x
-            self._fill_image_t()
+            self._set_input(x)
             self._forward_body(force_packs=False)
         self.generation += 1
         outs = {}
@@ -1373,29 +1526,18 @@ class Plan:
             outs[k] = v.squeeze(2) if self.two_d else v
         return outs
 
-    def _fill_image_t(self):
-        if self._image_t is not None:
-            self._image_t.act.t[..., :self.Cin].copy_(self._x.permute(0, 2, 3, 4, 1))
-
     def run_encoder(self, x):
         """the encoder part of the forward list alone (eager launches): the per-stage outputs (`Encoder.forward`'s skips) as NCDHW
         fp32 tensors.  Stage outputs that live inside a decoder's concat buffer are read through their channel view."""
-        if tuple(x.shape) != self.in_shape:
-            raise ValueError(f"plan built for input {self.in_shape}, got {tuple(x.shape)}")
-        x = x.detach()
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
+        x = self._as_input(x)
         self._apply_act = False
         self._forward_pre()
-        self._x = x.unsqueeze(2) if self.two_d else x
-        self._fill_image_t()
+        self._set_input(x)
         self.refresh_packs(force=False)
         n = self.n_fwd_enc if self.n_fwd_enc is not None else len(self.fwd)
         for step in self.fwd[:n]:
             step()
-        self._issue_deferred_packs()
-        for ent in self.packs:
-            self._await_pack(ent)
+        self._finish_packs()
         outs = []
         for at, c in self.enc_skips:
             t = at.act.to_ncdhw()[:, :c].float()
@@ -1412,9 +1554,7 @@ class Plan:
         self._apply_act = False
         self._forward_pre()
         self.refresh_packs(force=False)
-        self._issue_deferred_packs()
-        for ent in self.packs:
-            self._await_pack(ent)
+        self._finish_packs()
         for (at, c), t in zip(self.enc_skips, skips):
             t = t.detach()
             if self.two_d:

@@ -37,14 +37,13 @@ def work(tag, passes):
         items = []
         for ti, tape in enumerate([plan.enc_tape] + plan.dec_tapes):
             for ri, rec in enumerate(tape):
-                a = rec.a
                 if rec.kind in ("conv", "stem", "convT"):
-                    items.append((f"t{ti}.{ri}:{rec.kind}:y{tuple(a['y'].act.t.shape)}", a["y"].act.tensor()))
+                    items.append((f"t{ti}.{ri}:{rec.kind}:y{tuple(rec.y.act.t.shape)}", rec.y.act.tensor()))
                 elif rec.kind == "inact":
-                    items.append((f"t{ti}.{ri}:stats", a["stats"]))
-                    items.append((f"t{ti}.{ri}:inact:out{tuple(a['out'].act.t.shape)}", a["out"].act.tensor()))
+                    items.append((f"t{ti}.{ri}:stats", rec.stats))
+                    items.append((f"t{ti}.{ri}:inact:out{tuple(rec.out.act.t.shape)}", rec.out.act.tensor()))
                 elif rec.kind == "pool":
-                    items.append((f"t{ti}.{ri}:pool", a["y"].act.tensor()))
+                    items.append((f"t{ti}.{ri}:pool", rec.y.act.tensor()))
         items.append(("logits(clone taken by the autograd function)", out["sheet"]))
         items.append(("logits(engine buffer, read after the device sync)", plan.outputs["sheet"].clone()))
         if ref is None:

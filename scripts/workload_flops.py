@@ -19,14 +19,13 @@ for item in args:
         for rec in tape:
             if rec.kind not in ("conv", "convT", "stem"):
                 continue
-            a = rec.a
-            y = a["y"].act
+            y = rec.y.act
             vol = 1
             for d in y.dims:
                 vol *= d
-            ci = a["x"].act.c if "x" in a else w["in_channels"]
+            ci = rec.x.act.c if rec.kind != "stem" else w["in_channels"]
             taps = 1
-            for t in (a["kernel"] if rec.kind != "convT" else (1, 1, 1)):
+            for t in (rec.kernel if rec.kind != "convT" else (1, 1, 1)):
                 taps *= t
             f = 2 * vol * y.c * ci * taps
             fl += f

@@ -28,4 +28,4 @@ for n in pr:
     if b.norm() < 1e-9: continue
     print(f"{n:70s} cos {(a @ b / (a.norm() * b.norm())).item():.6f} ratio {(a.norm() / b.norm()).item():.4f} |ref| {b.norm().item():.3e} shape {tuple(pr[n].shape)}")
 plan = next(iter(net._plans.values()))
-print([ (r.kind, tuple(r.a['y'].act.dims), r.a['y'].act.c) if 'y' in r.a else r.kind for r in plan.enc_tape[:10]])
+print([ (r.kind, tuple(r.y.act.dims), r.y.act.c) if hasattr(r, 'y') else r.kind for r in plan.enc_tape[:10]])

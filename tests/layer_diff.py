@@ -26,11 +26,11 @@ for d in (torch.float32, dt):
     for tape in [plan.enc_tape] + plan.dec_tapes:
         for r in tape:
             if r.kind in ("conv", "stem", "convT"):
-                rows.append((r.kind + ":y", r.a["y"].act.tensor().float().clone(), plan.fwd and None))
+                rows.append((r.kind + ":y", r.y.act.tensor().float().clone(), plan.fwd and None))
             elif r.kind == "inact":
-                rows.append(("inact:out", r.a["out"].act.tensor().float().clone(), r.a["stats"].clone()))
+                rows.append(("inact:out", r.out.act.tensor().float().clone(), r.stats.clone()))
             elif r.kind == "pool":
-                rows.append(("pool:y", r.a["y"].act.tensor().float().clone(), None))
+                rows.append(("pool:y", r.y.act.tensor().float().clone(), None))
     acts[d] = (rows, {k: v.clone() for k, v in out.items()})
 ra, rb = acts[torch.float32][0], acts[dt][0]
 for j, ((ka, ta, sa), (kb, tb, sb)) in enumerate(zip(ra, rb)):

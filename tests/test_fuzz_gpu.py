@@ -350,8 +350,8 @@ def test_random_config_with_channel_dropout(NetworkFromConfig, i):
     def draw_mask(self, d):
         j = next(k for k, e in enumerate(self._drops) if e is d)
         if j not in masks:
-            masks[j] = torch.bernoulli(torch.full(tuple(d["keep"].shape), 1 - p), generator=gen)
-        d["keep"].copy_(masks[j])
+            masks[j] = torch.bernoulli(torch.full(tuple(d.keep.shape), 1 - p), generator=gen)
+        d.keep.copy_(masks[j])
     orig = plan_mod.Plan._draw_dropout
     plan_mod.Plan._draw_dropout = draw_mask
     try:

@@ -370,9 +370,9 @@ def test_planar_concat_plan_matches_interleaved_plan(monkeypatch):
         loss = oracle.train_loss(out, {k: v.cuda() for k, v in t.items()}, tasks)
         loss.backward()
         plan = next(iter(net._plans.values()))
-        cats = [r.a["cat"].act for r in plan.dec_tapes[0] if r.kind == "convT"]
+        cats = [r.cat.act for r in plan.dec_tapes[0] if r.kind == "convT"]
         assert any(c.is_planar_cat for c in cats) == (mode == "1")
-        assert all(c.is_planar_cat == (mode == "1") for tape in plan.dec_tapes for c in [r.a["cat"].act for r in tape if r.kind == "convT"][-1:])
+        assert all(c.is_planar_cat == (mode == "1") for tape in plan.dec_tapes for c in [r.cat.act for r in tape if r.kind == "convT"][-1:])
         res[mode] = (torch.cat([out["sheet"], out["normals"]], 1).detach().clone(),
                      {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None})
     assert torch.equal(res["0"][0], res["1"][0])
@@ -557,11 +557,11 @@ def test_channel_dropout_on_the_fused_paths(NetworkFromConfig):
     def draw(self, d):
         i = next(j for j, e in enumerate(self._drops) if e is d)
         if i not in masks:
-            mk = torch.bernoulli(torch.full(tuple(d["keep"].shape), 1 - p), generator=gen)
+            mk = torch.bernoulli(torch.full(tuple(d.keep.shape), 1 - p), generator=gen)
             if i == 1:
                 mk[:, 3] = 0            # one channel of the first block's conv1 dropped in BOTH samples
             masks[i] = mk
-        d["keep"].copy_(masks[i])
+        d.keep.copy_(masks[i])
     orig = plan_mod.Plan._draw_dropout
     plan_mod.Plan._draw_dropout = draw
     try:
@@ -581,11 +581,11 @@ def test_channel_dropout_on_the_fused_paths(NetworkFromConfig):
             plan = [pl for pl in net._plans.values() if pl.dtype == dt and pl.needs_grad][0]
             assert len(plan._drops) == len(masks)
             # the activations after a dropped plane's InstanceNorm are exactly zero
-            inacts = [r for tape in [plan.enc_tape] + plan.dec_tapes for r in tape if r.kind == "inact" and r.a["drop"] is not None]
+            inacts = [r for tape in [plan.enc_tape] + plan.dec_tapes for r in tape if r.kind == "inact" and r.drop is not None]
             for i, r in enumerate(inacts):
-                if r.a.get("head_dw_fused"):                 # the layer under a task head does not store its activated output (round 3)
+                if r.head_dw_fused:                 # the layer under a task head does not store its activated output (round 3)
                     continue
-                a = r.a["out"].act.tensor().float()          # (N, Z, Y, X, C)
+                a = r.out.act.tensor().float()          # (N, Z, Y, X, C)
                 dropped = masks[i] == 0
                 if dropped.any():
                     planes = a.abs().amax(dim=(1, 2, 3))      # (N, C)
@@ -609,7 +609,7 @@ def test_channel_dropout_on_the_fused_paths(NetworkFromConfig):
         e1 = net(x)["sheet"].clone()
         for pl in net._plans.values():
             for d in pl._drops:
-                d["keep"].zero_()
+                d.keep.zero_()
         e2 = net(x)["sheet"].clone()
     assert torch.equal(e1, e2) and e1.abs().sum() > 0
     # free-running masks: ~(1 - p) kept, different from step to step
@@ -619,7 +619,7 @@ def test_channel_dropout_on_the_fused_paths(NetworkFromConfig):
     for _ in range(2):
         net(x)
         plan = [pl for pl in net._plans.values() if pl.dtype == torch.bfloat16 and pl.needs_grad][0]
-        fr.append(torch.cat([d["keep"].flatten() for d in plan._drops]).clone())
+        fr.append(torch.cat([d.keep.flatten() for d in plan._drops]).clone())
     assert not torch.equal(fr[0], fr[1]) and set(fr[0].unique().tolist()) <= {0.0, 1.0}
     assert abs(fr[0].mean().item() - (1 - p)) < 0.05
 

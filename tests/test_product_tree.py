@@ -80,7 +80,7 @@ def test_no_cpu_fallback_and_loud_rejections():
         Plan(NetworkFromConfig(mgr).to("meta"), (1, 1, 16, 16, 16), torch.float32, "meta", True)
     mgr = oracle.make_mgr((16, 16, 16), {"a": {"channels": 1}}, model_config={"dropout_op_kwargs": {"p": 0.5}})
     plan = Plan(NetworkFromConfig(mgr).to("meta"), (1, 1, 16, 16, 16), torch.float32, "meta", True)
-    assert len(plan._drops) >= 5 and all(d["keep"].shape[0] == 1 for d in plan._drops)
+    assert len(plan._drops) >= 5 and all(d.keep.shape[0] == 1 for d in plan._drops)
 
 
 def test_yaml_string_blocks_do_not_crash_like_the_reference():
@@ -110,9 +110,9 @@ def test_squeeze_excite_and_droppath_containers_match_the_oracle_tree():
     blk = net.shared_encoder.stages[1].blocks[0]
     assert blk.apply_se and blk.apply_stochastic_depth and blk.squeeze_excitation.rd_channels == 8
     plan = Plan(net.to("meta"), (2, 1, 16, 16, 16), torch.float32, "meta", True)
-    gated = [r for r in plan.enc_tape if r.kind == "inact" and r.a["gate"] is not None]
+    gated = [r for r in plan.enc_tape if r.kind == "inact" and r.gate is not None]
     n_blocks = sum(len(st.blocks) for st in net.shared_encoder.stages)
-    assert len(gated) == n_blocks and all(g.a["gate"]["se"] is not None and g.a["gate"]["keep_x"] == 1 for g in gated)
+    assert len(gated) == n_blocks and all(g.gate.se is not None and g.gate.keep_x == 1 for g in gated)
     fc = {id(p) for n, p in net.named_parameters() if "squeeze_excitation" in n}
     assert fc <= {id(p) for p in plan.params}
 

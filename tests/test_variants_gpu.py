@@ -111,13 +111,13 @@ def test_droppath_training_and_eval(NetworkFromConfig):
     blocks_r = [m for m in ref.modules() if isinstance(m, oracle.DropPath)]
 
     def draw(self, g):
-        if g["scale"] is None or not self.net.training:
+        if g.scale is None or not self.net.training:
             return None
         i = len(forced)
         v = torch.tensor([0.0, 1.25] if i == 0 else [1.25, 1.25], dtype=torch.float32)
         forced.append(v)
-        g["scale"].copy_(v)
-        return g["scale"]
+        g.scale.copy_(v)
+        return g.scale
     orig = plan_mod.Plan._draw_path_scale
     plan_mod.Plan._draw_path_scale = draw
     try:
@@ -144,7 +144,7 @@ def test_droppath_training_and_eval(NetworkFromConfig):
     # the random draw itself: per-sample values in {0, 1/keep}
     net(x.cuda())
     plan = next(iter(net._plans.values()))
-    scales = [r.a["gate"]["scale"] for r in plan.enc_tape if r.kind == "inact" and r.a["gate"] is not None]
+    scales = [r.gate.scale for r in plan.enc_tape if r.kind == "inact" and r.gate is not None]
     assert len(scales) == len(blocks_r)
     for sc in scales:
         assert all(abs(v) < 1e-6 or abs(v - 1.25) < 1e-6 for v in sc.cpu().tolist())
