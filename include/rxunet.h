@@ -472,6 +472,30 @@ size_t rx_dilate_workspace(int batch, int c, int z, int y, int x);
 int rx_label_dilate(const float* in, float* out, void* scratch, size_t scratch_bytes, int batch, int c, int z, int y, int x,
                     int radius, void* stream);
 
+/* ---- box statistics on the device: what the valid-patch search asks of every candidate patch (reference helpers.py:
+ *      _check_patch_chunk, find_label_bounding_box; host side dataloading/patch_search_device.py).  `vol` is a contiguous
+ *      (z, y, x) device array of `dtype` (rx_sw_in_dtype: RX_SW_U8, RX_SW_U16, RX_SW_F32; anything else is RX_EINVAL), aligned
+ *      to its element size.  `host_boxes` holds n_boxes records (z0, y0, x0, dz, dy, dx) in HOST memory; per box i
+ *        count[i] = the number of voxels != 0 (np.count_nonzero: a NaN and a negative count, -0.0 does not)
+ *        ext[i]   = (minz, maxz, miny, maxy, minx, maxx) of the voxels > 0 in BOX-LOCAL coordinates (NaN, negatives and -0.0
+ *                   do not extend it); (dz, -1, dy, -1, dx, -1) when the box has no voxel > 0, the reference's empty record.
+ *      For the integer dtypes the two predicates are the same.  The global bounding box of a volume is the call with one box
+ *      that covers it.  The table is copied into `workspace` on `stream` (host_boxes must stay valid and unchanged until the
+ *      stream is synchronised), and count / ext are initialised on the stream by the call, not by the caller.
+ *      A box is cut along z -- and below a plane along y -- into chunks of whole x-rows, one workgroup each, so one volume-sized
+ *      box and thousands of patch-sized ones both fill the device; a launch gives every box the chunk grid of its largest box,
+ *      so keep the boxes of one call of similar size.  Rows are read with 16-byte loads between a scalar head and tail (x0 is
+ *      arbitrary), reduced per lane, wave and workgroup, then merged with one integer atomic per workgroup and output word
+ *      (add on the 64-bit count, min / max on the extents): the result does not depend on arrival order, a launch is
+ *      bit-reproducible, and there is no floating-point arithmetic.  Voxel offsets are 64-bit: z * y * x may exceed 2^31, only
+ *      z, y and x themselves are int32.  Overlapping and duplicate boxes are allowed; every box reads its own voxels.
+ *      RX_EINVAL before anything is launched or copied: null pointers, non-positive z / y / x, n_boxes <= 0, an unknown dtype,
+ *      a box with a non-positive extent or one that leaves the volume, vol not aligned to its element, workspace not 16-byte,
+ *      count not 8-byte or ext not 4-byte aligned; RX_EWORKSPACE: workspace_bytes below rx_box_stats_workspace(n_boxes). */
+size_t rx_box_stats_workspace(int n_boxes); /* bytes of the device box table, a multiple of 16 (0 for n_boxes <= 0) */
+int rx_box_stats(const void* vol, int dtype, int z, int y, int x, const int32_t* host_boxes, int n_boxes, void* workspace,
+                 size_t workspace_bytes, uint64_t* count, int32_t* ext, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

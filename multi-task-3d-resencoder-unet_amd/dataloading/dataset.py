@@ -15,7 +15,11 @@ and keep a normals target consistent (`geometry_device.py`): `where: device` lea
 
 `tr_setup.dilate_label` dilates every target that is not `normals` with a ball; `dataset_config.dilate` (absent: `{where: host,
 radius: 5}`, the reference's behaviour) says where: `host` is scipy's `binary_dilation` inside `__getitem__`, `device` hands out
-the scaled raw label and leaves the dilation to `dilate_device.DeviceDilate` (the trainer reads `device_dilate`)."""
+the scaled raw label and leaves the dilation to `dilate_device.DeviceDilate` (the trainer reads `device_dilate`).
+
+`dataset_config.patch_search` (absent: `{where: host}`, `find_valid_patches` below) says where the valid-patch search of the
+constructor runs: `device` hands each volume's reference label to `patch_search_device.find_valid_patches_device` (HIP box
+statistics, the same list and the same cache file; no device is an error, not a fallback)."""
 import json
 import os
 import warnings
@@ -161,6 +165,9 @@ class ZarrSegmentationDataset3D(Dataset):
         from .dilate_device import parse_dilate
         self.dilate = parse_dilate(getattr(mgr, "dataset_config", {}), self.dilate_label, self.tasks)
         self.device_dilate = self.dilate if self.dilate is not None and self.dilate["where"] == "device" else None
+        # dataset_config.patch_search: where the valid-patch search below runs (the list and the cache file are the same)
+        from .patch_search_device import find_valid_patches_device, parse_patch_search
+        self.patch_search = parse_patch_search(getattr(mgr, "dataset_config", {}))
         self.volumes = []
         for vol_idx, info in enumerate(self.volume_paths):
             vd = {"input_path": info["input"], "targets_path": {}, "ref_label_key": info.get("ref_label", "sheet")}
@@ -181,7 +188,11 @@ class ZarrSegmentationDataset3D(Dataset):
         else:
             for vol_idx, vd in enumerate(self.volumes):
                 ref = zarr_lite.open(vd["targets_path"][vd["ref_label_key"]])
-                found = find_valid_patches(ref, ps, self.min_bbox_percent, self.min_labeled_ratio)
+                if self.patch_search["where"] == "device":
+                    found = find_valid_patches_device(ref, ps, self.min_bbox_percent, self.min_labeled_ratio,
+                                                      max_device_bytes=self.patch_search["max_device_bytes"])
+                else:
+                    found = find_valid_patches(ref, ps, self.min_bbox_percent, self.min_labeled_ratio)
                 for p in found:
                     p["volume_idx"] = vol_idx
                 self.all_valid_patches.extend(found)

@@ -158,6 +158,8 @@ _SIGNATURES = {
                                       c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "rx_dilate_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rx_label_dilate": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rx_box_stats_workspace": (c_size_t, [c_int]),
+    "rx_box_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -761,6 +761,41 @@ def label_dilate(tensor, radius=5, out=None):
     return out
 
 
+def box_stats(vol, boxes):
+    """per box (z0, y0, x0, dz, dy, dx) of a contiguous (Z, Y, X) device tensor -- uint8, float32, or uint16 (int16 is read as the
+    uint16 bits it holds) -- the count of voxels != 0 and the box-local (minz, maxz, miny, maxy, minx, maxx) of the voxels > 0,
+    (dz, -1, dy, -1, dx, -1) where there is none (dataloading.patch_search_device.box_stats_numpy is the statement).  Returns
+    (count np.uint64 [N], ext np.int32 [N, 6]) after synchronising the current stream."""
+    codes = {torch.uint8: _l.RX_SW_U8, torch.int16: _l.RX_SW_U16, torch.float32: _l.RX_SW_F32}
+    if hasattr(torch, "uint16"):
+        codes[torch.uint16] = _l.RX_SW_U16
+    if not isinstance(vol, torch.Tensor) or not vol.is_cuda:
+        raise _l.RxError("box_stats: the volume must be a device tensor (the host statement is patch_search_device.box_stats_numpy)")
+    if vol.dtype not in codes:
+        raise _l.RxError(f"box_stats: dtype {vol.dtype} (uint8, uint16 / int16 or float32)")
+    if vol.dim() != 3 or not vol.is_contiguous():
+        raise _l.RxError(f"box_stats: expected a contiguous (Z, Y, X) tensor, got {tuple(vol.shape)} with strides {tuple(vol.stride())}")
+    if max(vol.shape) >= (1 << 31):
+        raise _l.RxError(f"box_stats: an extent of {tuple(vol.shape)} is beyond int32 (only z * y * x may exceed 2^31)")
+    table = np.asarray(boxes)
+    if table.ndim != 2 or table.shape[1] != 6 or table.shape[0] < 1 or table.dtype.kind not in "iu":
+        raise _l.RxError(f"box_stats: boxes must be an (N, 6) integer array with N >= 1, got {table.dtype} {table.shape}")
+    if table.min() < -(1 << 31) or table.max() >= (1 << 31):
+        raise _l.RxError("box_stats: a box entry is beyond int32")
+    table = np.ascontiguousarray(table, dtype=np.int32)      # read by the copy engine until the synchronise below
+    n = len(table)
+    z, y, x = vol.shape
+    with torch.cuda.device(vol.device):
+        nbytes = load().rx_box_stats_workspace(n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+        count = torch.empty(n, dtype=torch.int64, device=vol.device)
+        ext = torch.empty((n, 6), dtype=torch.int32, device=vol.device)
+        check(load().rx_box_stats(_ptr(vol), codes[vol.dtype], z, y, x, table.ctypes.data, n, _ptr(ws), nbytes, _ptr(count), _ptr(ext),
+                                  stream_ptr()), "rx_box_stats")
+        torch.cuda.current_stream().synchronize()
+        return count.cpu().numpy().view(np.uint64), ext.cpu().numpy()
+
+
 def aug_philox_u32(key, n, device):
     """test hook: the raw Philox4x32-10 outputs behind the noise of voxels 0..n-1 -> int64 tensor of the uint32 values"""
     out = torch.empty(n, dtype=torch.int32, device=device)
