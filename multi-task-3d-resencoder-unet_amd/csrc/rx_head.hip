@@ -5,6 +5,7 @@
 #include "rx_common.h"
 #include "rx_internal.h"
 #include "rx_reduce.h"
+#include "rx_instnorm_core.h"
 
 // ---- task head: 1x1x1 conv with bias (forward: accumulator arrays sized 8 / 16 / 32 / 64, K <= 8 keeps the lean kernel, more
 // than 64 classes run in chunks of 64 with the eval-mode softmax as a separate pass over the logits; backward: weight / bias
@@ -82,26 +83,17 @@ extern "C" int rx_head_fwd(rx_dtype dt, const rx_act* x, const float* w, const f
   if (k < 1 || k > RX_HEAD_MAXK) RX_FAIL(RX_EUNSUPPORTED, "rx_head_fwd: 1 <= K <= %d (got %d)", RX_HEAD_MAXK, k);
   const long V = rx_act_voxels(x);
   hipStream_t st = (hipStream_t)stream;
-#define RX_LAUNCH_HEAD_FWD(MK)                                                                                                        \
-  hipLaunchKernelGGL((head_fwd_kernel<T, MK>), dim3(G, x->n), dim3(256), (size_t)kc * x->c * sizeof(float), st, (const T*)x->ptr, x->ld, \
-                     V * x->ld, w, b, kc, k0, k, out_ncdhw, (int)V, x->c, act_here)
   RX_DISPATCH_DTYPE(dt, T, {
     int G = (int)((V + 255) / 256 > 4096 ? 4096 : (V + 255) / 256);
     const int act_here = (k > 64 && act == RX_ACT_SOFTMAX) ? (int)RX_ACT_NONE : act;      // softmax needs every class: second pass
     for (int k0 = 0; k0 < k; k0 += 64) {
       const int kc = k - k0 < 64 ? k - k0 : 64;
-      if (kc <= 8)
-        RX_LAUNCH_HEAD_FWD(8);
-      else if (kc <= 16)
-        RX_LAUNCH_HEAD_FWD(16);
-      else if (kc <= 32)
-        RX_LAUNCH_HEAD_FWD(32);
-      else
-        RX_LAUNCH_HEAD_FWD(64);
+      auto kern = kc <= 8 ? head_fwd_kernel<T, 8> : kc <= 16 ? head_fwd_kernel<T, 16> : kc <= 32 ? head_fwd_kernel<T, 32> : head_fwd_kernel<T, 64>;
+      hipLaunchKernelGGL(kern, dim3(G, x->n), dim3(256), (size_t)kc * x->c * sizeof(float), st, (const T*)x->ptr, x->ld, V * x->ld, w, b, kc, k0, k,
+                         out_ncdhw, (int)V, x->c, act_here);
     }
     if (k > 64 && act == RX_ACT_SOFTMAX) hipLaunchKernelGGL(softmax_ncdhw_kernel, dim3(G, x->n), dim3(256), 0, st, out_ncdhw, k, V);
   });
-#undef RX_LAUNCH_HEAD_FWD
   RX_CHECK_LAUNCH("rx_head_fwd");
   return RX_OK;
 }
@@ -242,6 +234,14 @@ extern "C" int rx_head_bwd(rx_dtype dt, const float* dout_ncdhw, const rx_act* x
 }
 
 #define RX_HEADG_MAXK 4
+// the head's weights for a thread's channel vector: w[k][j] = hw[k][c0 + j], 0 past K
+template <int P>
+__device__ inline void load_head_w(const float* hw, int K, int C, int c0, float (&w)[RX_HEADG_MAXK][P]) {
+#pragma unroll
+  for (int j = 0; j < P; ++j)
+#pragma unroll
+    for (int k = 0; k < RX_HEADG_MAXK; ++k) w[k][j] = k < K ? hw[k * C + c0 + j] : 0.f;
+}
 // ---- InstanceNorm + LeakyReLU of the layer under a task head, with the head's 1x1x1 conv in the same pass -----------
 // rx_head_fwd re-read the activated output (268 MB at cfg2) to form K logits per voxel.  Here the CV lanes that hold one voxel's
 // channel vectors pass the running sums along (lane cv adds the partial dot product of its 8 channels to what lane cv-1 holds, from
@@ -253,35 +253,24 @@ __global__ __launch_bounds__(256) void in_act_head_fwd_kernel(const T* __restric
                                                               const float* __restrict__ hw, const float* __restrict__ hb, int K,
                                                               float* __restrict__ logits, int act) {
   constexpr int P = Elem<T>::PER16;
-  const int CV = C / P;
-  const int n = blockIdx.y;
-  const long total = (long)V * CV;
-  long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long step = (long)gridDim.x * 256;
-  const int cv = (int)(i % CV);
+  Sweep<P> sw(V, C);
+  const int CV = sw.CV, n = sw.n, cv = sw.cv;
   float mean[P], rstd[P], w[RX_HEADG_MAXK][P], b[RX_HEADG_MAXK];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    mean[j] = stats[2 * ((size_t)n * C + cv * P + j)];
-    rstd[j] = stats[2 * ((size_t)n * C + cv * P + j) + 1];
-#pragma unroll
-    for (int k = 0; k < RX_HEADG_MAXK; ++k) w[k][j] = k < K ? hw[k * C + cv * P + j] : 0.f;
-  }
+  load_pair(stats, n, C, cv * P, mean, rstd);
+  load_head_w(hw, K, C, cv * P, w);
 #pragma unroll
   for (int k = 0; k < RX_HEADG_MAXK; ++k) b[k] = k < K ? hb[k] : 0.f;
   const T* yn = y + n * sy;
   T* on = out ? out + n * so : nullptr;
-  for (; i < total; i += step) {
-    long v = i / CV;
+  for (; sw.more(); sw.next()) {
+    const long v = sw.v();
     Vec16<T> a = ld16(yn + v * ldy + cv * P);
     Vec16<T> o;
     float of[P];
 #pragma unroll
     for (int j = 0; j < P; ++j) {
-      float f = (Elem<T>::to_f(a.v[j]) - mean[j]) * rstd[j];
-      f = f > 0.f ? f : f * slope;
-      o.v[j] = Elem<T>::from_f(f);
-      of[j] = Elem<T>::to_f(o.v[j]);
+      o.v[j] = in_fwd_elem<T, false>(a.v[j], mean[j], rstd[j], a.v[j], slope);
+      of[j] = Elem<T>::to_f(o.v[j]);      // logits from the output AS STORED
     }
     if (on) st16(on + v * ldo + cv * P, o);      // (out == NULL: nobody reads the activated output -- see rx_instnorm_act_bwd_head's dw / db)
     // The CV lanes of a voxel each form the partial dot products of THEIR 8 channels, then hand a running sum along in channel
@@ -347,12 +336,10 @@ extern "C" int rx_instnorm_act_head_fwd(rx_dtype dt, const rx_act* y, const floa
   const long V = rx_act_voxels(y);
   hipStream_t st = (hipStream_t)stream;
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    int CV = y->c / P;
-    int G = sweep_grid(V * CV, CV);
-    hipLaunchKernelGGL((in_act_head_fwd_kernel<T>), dim3(G, y->n), dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld, stats,
-                       out ? (T*)out->ptr : (T*)nullptr, out ? out->ld : 0, out ? V * out->ld : 0L, (int)V, y->c, slope, head_w, head_b, k,
-                       out_ncdhw, act);
+    const int CV = y->c / Elem<T>::PER16, G = sweep_grid(V * CV, CV);
+    const ActView<T> o = make_view<T>(out);
+    hipLaunchKernelGGL((in_act_head_fwd_kernel<T>), dim3(G, y->n), dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld, stats, (T*)o.ptr, o.ld,
+                       o.sample_stride, (int)V, y->c, slope, head_w, head_b, k, out_ncdhw, act);
   });
   RX_CHECK_LAUNCH("rx_instnorm_act_head_fwd");
   return RX_OK;
@@ -377,37 +364,22 @@ struct InBwdHeadOp {
   const float* hw;    // (K, C)
   int C, K, V;
   float slope;
-  bool mask_xhat;
+  InMask mask;   // IN_MASK_XHAT or IN_MASK_NONE: the layer under a head has no residual
   float mean[Elem<T>::PER16], rstd[Elem<T>::PER16], w[RX_HEADG_MAXK][Elem<T>::PER16];
   __device__ inline void prepare(int n, int c0) {
-#pragma unroll
-    for (int j = 0; j < Elem<T>::PER16; ++j) {
-      mean[j] = stats[2 * ((size_t)n * C + c0 + j)];
-      rstd[j] = stats[2 * ((size_t)n * C + c0 + j) + 1];
-#pragma unroll
-      for (int k = 0; k < RX_HEADG_MAXK; ++k) w[k][j] = k < K ? hw[k * C + c0 + j] : 0.f;
-    }
+    load_pair(stats, n, C, c0, mean, rstd);
+    load_head_w(hw, K, C, c0, w);
   }
   __device__ inline void accumulate(int n, int v, int c0, float (&acc)[KW ? KW + 3 : 2][Elem<T>::PER16]) const {
     constexpr int P = Elem<T>::PER16;
     Vec16<T> yv = ld16(y.at(n, v, c0));
     float d[P], gk[RX_HEADG_MAXK];
-#pragma unroll
-    for (int j = 0; j < P; ++j) d[j] = 0.f;
-#pragma unroll
-    for (int k = 0; k < RX_HEADG_MAXK; ++k) {
-      gk[k] = 0.f;
-      if (k < K) {
-        gk[k] = dout[((size_t)n * K + k) * V + v];
-#pragma unroll
-        for (int j = 0; j < P; ++j) d[j] += gk[k] * w[k][j];
-      }
-    }
+    head_grad_vec(dout, n, K, V, v, w, d, gk);
 #pragma unroll
     for (int j = 0; j < P; ++j) {
-      float gg = Elem<T>::to_f(Elem<T>::from_f(d[j]));
-      float xh = (Elem<T>::to_f(yv.v[j]) - mean[j]) * rstd[j];
-      if (mask_xhat && !(xh > 0.f)) gg *= slope;
+      const float xh = in_xhat(yv.v[j], mean[j], rstd[j]);
+      float gg = Elem<T>::to_f(Elem<T>::from_f(d[j]));      // g rounded to T BEFORE the mask
+      in_bwd_gprime(gg, xh, mask, slope);
       acc[0][j] += gg;
       acc[1][j] += gg * xh;
       if (KW) {
@@ -451,98 +423,73 @@ __global__ __launch_bounds__(256) void in_act_bwd_apply_head_kernel(const float*
                                                                     const T* __restrict__ y, int ldy, long sy,
                                                                     const float* __restrict__ stats, const float* __restrict__ m12,
                                                                     T* __restrict__ dy, int lddy, long sdy, int V, int C, float slope,
-                                                                    int mask_xhat) {
+                                                                    InMask mask) {
   constexpr int P = Elem<T>::PER16;
-  const int CV = C / P;
-  const int n = blockIdx.y;
-  const long total = (long)V * CV;
-  long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long step = (long)gridDim.x * 256;
-  const int cv = (int)(i % CV);
+  Sweep<P> s(V, C);
+  const int n = s.n, c0 = s.cv * P;
   float mean[P], rstd[P], m1[P], m2[P], w[RX_HEADG_MAXK][P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    size_t k = (size_t)n * C + cv * P + j;
-    mean[j] = stats[2 * k];
-    rstd[j] = stats[2 * k + 1];
-    m1[j] = m12[2 * k];
-    m2[j] = m12[2 * k + 1];
-#pragma unroll
-    for (int q = 0; q < RX_HEADG_MAXK; ++q) w[q][j] = q < K ? hw[q * C + cv * P + j] : 0.f;
-  }
-  for (; i < total; i += step) {
-    long v = i / CV;
-    Vec16<T> yv = ld16(y + n * sy + v * ldy + cv * P);
-    float d[P];
-#pragma unroll
-    for (int j = 0; j < P; ++j) d[j] = 0.f;
-#pragma unroll
-    for (int q = 0; q < RX_HEADG_MAXK; ++q)
-      if (q < K) {
-        const float gk = dout[((size_t)n * K + q) * V + v];
-#pragma unroll
-        for (int j = 0; j < P; ++j) d[j] += gk * w[q][j];
-      }
+  load_pair(stats, n, C, c0, mean, rstd);
+  load_pair(m12, n, C, c0, m1, m2);
+  load_head_w(hw, K, C, c0, w);
+  for (; s.more(); s.next()) {
+    const long v = s.v();
+    Vec16<T> yv = ld16(y + n * sy + v * ldy + c0);
+    float d[P], gk[RX_HEADG_MAXK];
+    head_grad_vec(dout, n, K, V, v, w, d, gk);
     Vec16<T> dv;
 #pragma unroll
     for (int j = 0; j < P; ++j) {
+      const float xh = in_xhat(yv.v[j], mean[j], rstd[j]);
       float gg = Elem<T>::to_f(Elem<T>::from_f(d[j]));
-      float xh = (Elem<T>::to_f(yv.v[j]) - mean[j]) * rstd[j];
-      if (mask_xhat && !(xh > 0.f)) gg *= slope;
-      dv.v[j] = Elem<T>::from_f(rstd[j] * (gg - m1[j] - xh * m2[j]));
+      in_bwd_gprime(gg, xh, mask, slope);
+      dv.v[j] = Elem<T>::from_f(in_bwd_dy(gg, xh, rstd[j], m1[j], m2[j]));
     }
-    st16(dy + n * sdy + v * lddy + cv * P, dv);
+    st16(dy + n * sdy + v * lddy + c0, dv);
   }
 }
 
 // dy = InstanceNorm+LeakyReLU backward of a layer WITHOUT residual whose output gradient is the data gradient of a 1x1x1 head:
 // g = dout (N,K,Z,Y,X fp32) x head_w (K,C), never materialised.  Same result as rx_head_bwd(dx = g) + rx_instnorm_act_bwd(g, ...,
 // out = NULL).  K <= 4.
-#define RX_HEAD_REDUCE(KW_)                                                                                                              \
-  do {                                                                                                                                   \
-    InBwdHeadOp<T, KW_> op{make_view<T>(y), stats, dout_ncdhw, head_w, C, k, (int)V, slope, mask_xhat, {}, {}, {}};                       \
-    hipLaunchKernelGGL((colreduce_kernel<T, (KW_ ? KW_ + 3 : 2), InBwdHeadOp<T, KW_>>), dim3(p.nchunks, N), dim3(256), lds, st, op, (int)V, C, \
-                       p.chunk_vox, partial);                                                                                            \
-  } while (0)
+template <typename T, int KW>
+static ReducePlan launch_head_reduce(const rx_act* y, const float* stats, const float* dout, const float* hw, int k, float slope, InMask mask,
+                                     float* partial, hipStream_t st) {
+  const long V = rx_act_voxels(y);
+  InBwdHeadOp<T, KW> op{make_view<T>(y), stats, dout, hw, y->c, k, (int)V, slope, mask, {}, {}, {}};
+  return launch_colreduce<T, (KW ? KW + 3 : 2)>(op, y->n, V, y->c, partial, st);
+}
 extern "C" int rx_instnorm_act_bwd_head(rx_dtype dt, const float* dout_ncdhw, int k, const float* head_w, const rx_act* y,
                                         const float* stats, float slope, const rx_act* dy, float* head_dw, float* head_db, void* ws,
                                         size_t ws_bytes, void* stream) {
   RX_RECORD(stream, [=, y_ = RxActV(y), dy_ = RxActV(dy)](void* s) { return rx_instnorm_act_bwd_head(dt, dout_ncdhw, k, head_w, y_.p(), stats, slope, dy_.p(), head_dw, head_db, ws, ws_bytes, s); });
-  int rc;
-  if ((rc = check_vec_channels(y, dt, "rx_instnorm_act_bwd_head(y)"))) return rc;
-  if ((rc = check_vec_channels(dy, dt, "rx_instnorm_act_bwd_head(dy)"))) return rc;
-  if (!dout_ncdhw || !head_w || !stats || !ws || k < 1 || k > RX_HEADG_MAXK || !same_geom(y, dy))
+  int rc = check_acts(dt, "rx_instnorm_act_bwd_head", y, {{"y", y, true}, {"dy", dy, true}});
+  if (rc) return rc;
+  if (!dout_ncdhw || !head_w || !stats || !ws || k < 1 || k > RX_HEADG_MAXK)
     RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_head: bad arguments (K must be 1..%d)", RX_HEADG_MAXK);
   const long V = rx_act_voxels(y);
   const int N = y->n, C = y->c;
   if (V > 0x7fffffffL) RX_FAIL(RX_EUNSUPPORTED, "rx_instnorm_act_bwd_head: volume too large");
   if ((head_dw == nullptr) != (head_db == nullptr)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_head: head_dw and head_db come together");
   const int nacc = head_dw ? k + 3 : 2;
-  size_t need = rx_reduce_ws_bytes(N, V, C, nacc) + (size_t)N * C * 2 * sizeof(float);
-  if (ws_bytes < need) RX_FAIL(RX_EWORKSPACE, "rx_instnorm_act_bwd_head: workspace too small (%zu < %zu)", ws_bytes, need);
-  float* partial = (float*)ws;
-  float* m12 = (float*)((char*)ws + rx_align_up(rx_reduce_ws_bytes(N, V, C, nacc) - 256, 256));
+  const ReduceWs w = reduce_ws(ws, N, V, C, nacc);
+  if (ws_bytes < w.need) RX_FAIL(RX_EWORKSPACE, "rx_instnorm_act_bwd_head: workspace too small (%zu < %zu)", ws_bytes, w.need);
   hipStream_t st = (hipStream_t)stream;
-  const bool mask_xhat = slope != 1.0f;
+  const InMask mask = in_mask_of(slope, nullptr);
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    ReducePlan p = rx_reduce_plan(V, C, P);
-    int CV = C / P, VP = 256 / CV;
-    size_t lds = (size_t)nacc * (VP > 4 ? VP : 4) * C * sizeof(float);
-    if (!head_dw) {
-      RX_HEAD_REDUCE(0);
-      rx_colreduce_finalize_launch(st, (const float*)partial, N, p.nchunks, 2, C, (double)V, 0.f, (int)FIN_MEAN2, m12);
-    } else {
-      if (k == 1) RX_HEAD_REDUCE(1);
-      else if (k == 2) RX_HEAD_REDUCE(2);
-      else if (k == 3) RX_HEAD_REDUCE(3);
-      else RX_HEAD_REDUCE(4);
-      hipLaunchKernelGGL(inbwd_head_finalize, dim3(N * C + k * C + k), dim3(256), 0, st, (const float*)partial, N, p.nchunks, nacc, C, k,
-                         (double)V, m12, head_dw, head_db);
-    }
-    int G = sweep_grid(V * CV, CV);
+    auto reduce = !head_dw ? launch_head_reduce<T, 0>
+                  : k == 1 ? launch_head_reduce<T, 1>
+                  : k == 2 ? launch_head_reduce<T, 2>
+                  : k == 3 ? launch_head_reduce<T, 3>
+                           : launch_head_reduce<T, 4>;
+    const ReducePlan p = reduce(y, stats, dout_ncdhw, head_w, k, slope, mask, w.partial, st);
+    if (!head_dw)
+      rx_colreduce_finalize_launch(st, w.partial, N, p.nchunks, 2, C, (double)V, 0.f, (int)FIN_MEAN2, w.m12);
+    else
+      hipLaunchKernelGGL(inbwd_head_finalize, dim3(N * C + k * C + k), dim3(256), 0, st, (const float*)w.partial, N, p.nchunks, nacc, C, k,
+                         (double)V, w.m12, head_dw, head_db);
+    const int CV = C / Elem<T>::PER16, G = sweep_grid(V * CV, CV);
     hipLaunchKernelGGL((in_act_bwd_apply_head_kernel<T>), dim3(G, N), dim3(256), 0, st, dout_ncdhw, k, head_w, (const T*)y->ptr, y->ld,
-                       V * y->ld, stats, (const float*)m12, (T*)dy->ptr, dy->ld, V * dy->ld, (int)V, C, slope, mask_xhat ? 1 : 0);
+                       V * y->ld, stats, (const float*)w.m12, (T*)dy->ptr, dy->ld, V * dy->ld, (int)V, C, slope, mask);
   });
   RX_CHECK_LAUNCH("rx_instnorm_act_bwd_head");
   return RX_OK;

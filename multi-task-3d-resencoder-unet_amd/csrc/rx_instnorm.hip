@@ -9,6 +9,7 @@
 #include "rx_common.h"
 #include "rx_internal.h"
 #include "rx_reduce.h"
+#include "rx_instnorm_core.h"
 
 __global__ __launch_bounds__(256) void colreduce_finalize(const float* __restrict__ partial, int N, int nchunks, int nacc, int C, double V,
                                                           float eps, int mode, float* __restrict__ out) {
@@ -72,16 +73,8 @@ extern "C" int rx_instnorm_stats(rx_dtype dt, const rx_act* y, float eps, float*
   const long V = rx_act_voxels(y);
   hipStream_t st = (hipStream_t)stream;
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    ReducePlan p = rx_reduce_plan(V, y->c, P);
-    int CV = y->c / P, VP = 256 / CV;
-    StatsOp<T> op{make_view<T>(y)};
-    size_t lds = (size_t)2 * (VP > 4 ? VP : 4) * y->c * sizeof(float);
-    hipLaunchKernelGGL((colreduce_kernel<T, 2, StatsOp<T>>), dim3(p.nchunks, y->n), dim3(256), lds, st, op, (int)V, y->c,
-                       p.chunk_vox, (float*)ws);
-    int tot = y->n * y->c;
-    rx_colreduce_finalize_launch(st, (const float*)ws, y->n, p.nchunks, 2,
-                       y->c, (double)V, eps, (int)FIN_STATS, stats);
+    ReducePlan p = launch_colreduce<T, 2>(StatsOp<T>{make_view<T>(y)}, y->n, V, y->c, (float*)ws, st);
+    rx_colreduce_finalize_launch(st, (const float*)ws, y->n, p.nchunks, 2, y->c, (double)V, eps, (int)FIN_STATS, stats);
   });
   RX_CHECK_LAUNCH("rx_instnorm_stats");
   return RX_OK;
@@ -137,15 +130,8 @@ extern "C" int rx_channel_sum(rx_dtype dt, const rx_act* x, float* out, void* ws
   const long V = rx_act_voxels(x);
   hipStream_t st = (hipStream_t)stream;
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    ReducePlan p = rx_reduce_plan(V, x->c, P);
-    int CV = x->c / P, VP = 256 / CV;
-    SumOp<T> op{make_view<T>(x)};
-    size_t lds = (size_t)(VP > 4 ? VP : 4) * x->c * sizeof(float);
-    hipLaunchKernelGGL((colreduce_kernel<T, 1, SumOp<T>>), dim3(p.nchunks, x->n), dim3(256), lds, st, op, (int)V, x->c,
-                       p.chunk_vox, (float*)ws);
-    rx_colreduce_finalize_launch(st, (const float*)ws, x->n, p.nchunks, 1,
-                       x->c, (double)V, 0.f, (int)FIN_SUM_OVER_N, out);
+    ReducePlan p = launch_colreduce<T, 1>(SumOp<T>{make_view<T>(x)}, x->n, V, x->c, (float*)ws, st);
+    rx_colreduce_finalize_launch(st, (const float*)ws, x->n, p.nchunks, 1, x->c, (double)V, 0.f, (int)FIN_SUM_OVER_N, out);
   });
   RX_CHECK_LAUNCH("rx_channel_sum");
   return RX_OK;
@@ -159,64 +145,38 @@ __global__ __launch_bounds__(256) void in_act_fwd_kernel(const T* __restrict__ y
                                                          const T* __restrict__ res, int ldr, long sr, T* __restrict__ out, int ldo,
                                                          long so, int V, int C, float slope) {
   constexpr int P = Elem<T>::PER16;
-  const int CV = C / P;
-  const int n = blockIdx.y;
-  const long total = (long)V * CV;
-  long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long step = (long)gridDim.x * 256;
-  const int cv = (int)(i % CV);
+  Sweep<P> s(V, C);
+  const int n = s.n, c0 = s.cv * P;
   float mean[P], rstd[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    mean[j] = stats[2 * ((size_t)n * C + cv * P + j)];
-    rstd[j] = stats[2 * ((size_t)n * C + cv * P + j) + 1];
-  }
+  load_pair(stats, n, C, c0, mean, rstd);
   const T* yn = y + n * sy;
   const T* rn = HAS_RES ? res + n * sr : nullptr;
   T* on = out + n * so;
-  for (; i < total; i += step) {
-    long v = i / CV;
-    Vec16<T> a = ld16(yn + v * ldy + cv * P);
+  for (; s.more(); s.next()) {
+    const long v = s.v();
+    Vec16<T> a = ld16(yn + v * ldy + c0);
     Vec16<T> r;
-    if (HAS_RES) r = ld16(rn + v * ldr + cv * P);
+    if (HAS_RES) r = ld16(rn + v * ldr + c0);
     Vec16<T> o;
 #pragma unroll
-    for (int j = 0; j < P; ++j) {
-      float f = (Elem<T>::to_f(a.v[j]) - mean[j]) * rstd[j];
-      if (HAS_RES) f += Elem<T>::to_f(r.v[j]);
-      f = f > 0.f ? f : f * slope;
-      o.v[j] = Elem<T>::from_f(f);
-    }
-    st16(on + v * ldo + cv * P, o);
+    for (int j = 0; j < P; ++j) o.v[j] = in_fwd_elem<T, HAS_RES>(a.v[j], mean[j], rstd[j], r.v[j], slope);
+    st16(on + v * ldo + c0, o);
   }
 }
 
 extern "C" int rx_instnorm_act_fwd(rx_dtype dt, const rx_act* y, const float* stats, const rx_act* residual,
                                    const rx_act* out, float slope, void* stream) {
   RX_RECORD(stream, [=, y_ = RxActV(y), residual_ = RxActV(residual), out_ = RxActV(out)](void* s) { return rx_instnorm_act_fwd(dt, y_.p(), stats, residual_.p(), out_.p(), slope, s); });
-  int rc = check_vec_channels(y, dt, "rx_instnorm_act_fwd(y)");
+  int rc = check_acts(dt, "rx_instnorm_act_fwd", y, {{"y", y, true}, {"out", out, true}, {"residual", residual, false}});
   if (rc) return rc;
-  rc = check_vec_channels(out, dt, "rx_instnorm_act_fwd(out)");
-  if (rc) return rc;
-  if (!stats || !same_geom(y, out)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_fwd: geometry mismatch / null stats");
-  if (residual) {
-    rc = check_vec_channels(residual, dt, "rx_instnorm_act_fwd(residual)");
-    if (rc) return rc;
-    if (!same_geom(y, residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_fwd: residual geometry mismatch");
-  }
+  if (!stats) RX_FAIL(RX_EINVAL, "rx_instnorm_act_fwd: null stats");
   const long V = rx_act_voxels(y);
   hipStream_t st = (hipStream_t)stream;
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    int CV = y->c / P;
-    int G = sweep_grid(V * CV, CV);
-    if (residual)
-      hipLaunchKernelGGL((in_act_fwd_kernel<T, true>), dim3(G, y->n), dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld, stats,
-                         (const T*)residual->ptr, residual->ld, V * residual->ld, (T*)out->ptr, out->ld, V * out->ld, (int)V,
-                         y->c, slope);
-    else
-      hipLaunchKernelGGL((in_act_fwd_kernel<T, false>), dim3(G, y->n), dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld, stats,
-                         (const T*)nullptr, 0, 0L, (T*)out->ptr, out->ld, V * out->ld, (int)V, y->c, slope);
+    const int CV = y->c / Elem<T>::PER16, G = sweep_grid(V * CV, CV);
+    const ActView<T> r = make_view<T>(residual);
+    hipLaunchKernelGGL((residual ? in_act_fwd_kernel<T, true> : in_act_fwd_kernel<T, false>), dim3(G, y->n), dim3(256), 0, st, (const T*)y->ptr,
+                       y->ld, V * y->ld, stats, r.ptr, r.ld, r.sample_stride, (T*)out->ptr, out->ld, V * out->ld, (int)V, y->c, slope);
   });
   RX_CHECK_LAUNCH("rx_instnorm_act_fwd");
   return RX_OK;
@@ -231,28 +191,20 @@ struct InBwdOp {
   const float* stats;
   int C;
   float slope;
-  bool use_mask;   // LeakyReLU mask from the sign of the saved output (residual blocks)
-  bool mask_xhat;  // no residual: out > 0 <=> xhat > 0, the output tensor is not read at all
+  InMask mask;
   float mean[Elem<T>::PER16], rstd[Elem<T>::PER16];
-  __device__ inline void prepare(int n, int c0) {
-#pragma unroll
-    for (int j = 0; j < Elem<T>::PER16; ++j) {
-      mean[j] = stats[2 * ((size_t)n * C + c0 + j)];
-      rstd[j] = stats[2 * ((size_t)n * C + c0 + j) + 1];
-    }
-  }
+  __device__ inline void prepare(int n, int c0) { load_pair(stats, n, C, c0, mean, rstd); }
   __device__ inline void accumulate(int n, int v, int c0, float (&acc)[2][Elem<T>::PER16]) const {
     constexpr int P = Elem<T>::PER16;
     Vec16<T> gv = ld16(g.at(n, v, c0));
     Vec16<T> yv = ld16(y.at(n, v, c0));
     Vec16<T> ov;
-    if (use_mask) ov = ld16(out.at(n, v, c0));
+    if (mask == IN_MASK_OUT) ov = ld16(out.at(n, v, c0));
 #pragma unroll
     for (int j = 0; j < P; ++j) {
+      const float xh = in_xhat(yv.v[j], mean[j], rstd[j]);
       float gg = Elem<T>::to_f(gv.v[j]);
-      float xh = (Elem<T>::to_f(yv.v[j]) - mean[j]) * rstd[j];
-      if (use_mask && !(Elem<T>::to_f(ov.v[j]) > 0.f)) gg *= slope;
-      if (mask_xhat && !(xh > 0.f)) gg *= slope;
+      in_bwd_gprime(gg, xh, mask, ov.v[j], slope);
       acc[0][j] += gg;
       acc[1][j] += gg * xh;
     }
@@ -264,54 +216,50 @@ __global__ __launch_bounds__(256) void in_act_bwd_apply_kernel(const T* __restri
                                                                long sy, const T* __restrict__ out, int ldo, long so,
                                                                const float* __restrict__ stats, const float* __restrict__ m12,
                                                                T* __restrict__ dy, int lddy, long sdy, T* __restrict__ dres, int lddr,
-                                                               long sdr, int V, int C, float slope, int use_mask) {
+                                                               long sdr, int V, int C, float slope, InMask mask) {
   constexpr int P = Elem<T>::PER16;
-  const int CV = C / P;
-  const int n = blockIdx.y;
-  const long total = (long)V * CV;
-  long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long step = (long)gridDim.x * 256;
-  const int cv = (int)(i % CV);
+  Sweep<P> s(V, C);
+  const int n = s.n, c0 = s.cv * P;
   float mean[P], rstd[P], m1[P], m2[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    size_t k = (size_t)n * C + cv * P + j;
-    mean[j] = stats[2 * k];
-    rstd[j] = stats[2 * k + 1];
-    m1[j] = m12[2 * k];
-    m2[j] = m12[2 * k + 1];
-  }
-  for (; i < total; i += step) {
-    long v = i / CV;
-    Vec16<T> gv = ld16(g + n * sg + v * ldg + cv * P);
-    Vec16<T> yv = ld16(y + n * sy + v * ldy + cv * P);
+  load_pair(stats, n, C, c0, mean, rstd);
+  load_pair(m12, n, C, c0, m1, m2);
+  for (; s.more(); s.next()) {
+    const long v = s.v();
+    Vec16<T> gv = ld16(g + n * sg + v * ldg + c0);
+    Vec16<T> yv = ld16(y + n * sy + v * ldy + c0);
     Vec16<T> ov;
-    if (use_mask == 1) ov = ld16(out + n * so + v * ldo + cv * P);
+    if (mask == IN_MASK_OUT) ov = ld16(out + n * so + v * ldo + c0);
     Vec16<T> dv, rv;
-    if (HAS_DRES && ACC_DRES) rv = ld16(dres + n * sdr + v * lddr + cv * P);
+    if (HAS_DRES && ACC_DRES) rv = ld16(dres + n * sdr + v * lddr + c0);
 #pragma unroll
     for (int j = 0; j < P; ++j) {
+      const float xh = in_xhat(yv.v[j], mean[j], rstd[j]);
       float gg = Elem<T>::to_f(gv.v[j]);
-      float xh = (Elem<T>::to_f(yv.v[j]) - mean[j]) * rstd[j];
-      if (use_mask == 1 && !(Elem<T>::to_f(ov.v[j]) > 0.f)) gg *= slope;
-      if (use_mask == 2 && !(xh > 0.f)) gg *= slope;
-      dv.v[j] = Elem<T>::from_f(rstd[j] * (gg - m1[j] - xh * m2[j]));
+      in_bwd_gprime(gg, xh, mask, ov.v[j], slope);
+      dv.v[j] = Elem<T>::from_f(in_bwd_dy(gg, xh, rstd[j], m1[j], m2[j]));
       if (HAS_DRES) {
         float r = gg;
         if (ACC_DRES) r += Elem<T>::to_f(rv.v[j]);
         rv.v[j] = Elem<T>::from_f(r);
       }
     }
-    st16(dy + n * sdy + v * lddy + cv * P, dv);
-    if (HAS_DRES) st16(dres + n * sdr + v * lddr + cv * P, rv);
+    st16(dy + n * sdy + v * lddy + c0, dv);
+    if (HAS_DRES) st16(dres + n * sdr + v * lddr + c0, rv);
   }
 }
 
-#define RX_LAUNCH_APPLY(HD, AD)                                                                                                   \
-  hipLaunchKernelGGL((in_act_bwd_apply_kernel<T, HD, AD>), dim3(G, N), dim3(256), 0, st, (const T*)g->ptr, g->ld, V * g->ld,     \
-                     (const T*)y->ptr, y->ld, V * y->ld, outp, ldo, V * ldo, stats, (const float*)m12, (T*)dy->ptr, dy->ld,       \
-                     V * dy->ld, d_residual ? (T*)d_residual->ptr : (T*)nullptr, d_residual ? d_residual->ld : 0,                 \
-                     d_residual ? V * d_residual->ld : 0L, (int)V, C, slope, use_mask ? 1 : (mask_xhat ? 2 : 0))
+// apply pass on (g, y[, out]) -> dy[, d_residual]; `out` is passed on only under IN_MASK_OUT
+template <typename T>
+static void launch_bwd_apply(const rx_act* g, const rx_act* y, const float* stats, const rx_act* out, float slope, InMask mask, const float* m12,
+                             const rx_act* dy, const rx_act* d_residual, int accumulate_residual, hipStream_t st) {
+  const long V = rx_act_voxels(y);
+  const int CV = y->c / Elem<T>::PER16, G = sweep_grid(V * CV, CV);
+  const ActView<T> o = make_view<T>(mask == IN_MASK_OUT ? out : nullptr), dr = make_view<T>(d_residual);
+  auto kern = !d_residual ? in_act_bwd_apply_kernel<T, false, false>
+                          : (accumulate_residual ? in_act_bwd_apply_kernel<T, true, true> : in_act_bwd_apply_kernel<T, true, false>);
+  hipLaunchKernelGGL(kern, dim3(G, y->n), dim3(256), 0, st, (const T*)g->ptr, g->ld, V * g->ld, (const T*)y->ptr, y->ld, V * y->ld, o.ptr, o.ld,
+                     o.sample_stride, stats, m12, (T*)dy->ptr, dy->ld, V * dy->ld, (T*)dr.ptr, dr.ld, dr.sample_stride, (int)V, y->c, slope, mask);
+}
 
 // ---- single-launch InstanceNorm forward / backward for SMALL tensors (low-resolution stages) ---------------------
 // At 8^3 and below (measured: 16^3 is already better off with the chip-filling three-launch path; narrower 8-channel
@@ -327,7 +275,7 @@ __global__ __launch_bounds__(256) void in_small_fwd_kernel(const T* __restrict__
   constexpr int CPG = G / P;  // 16-byte chunks per G-channel group
   __shared__ double red[4][2][G];
   __shared__ float mr[2][G];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int n = blockIdx.y, c0 = blockIdx.x * G;
   const int ck = tid % CPG, vl = tid / CPG;
   const int VL = 256 / CPG;
@@ -344,24 +292,9 @@ __global__ __launch_bounds__(256) void in_small_fwd_kernel(const T* __restrict__
       q[j] += f * f;
     }
   }
-  for (int o = CPG; o < 64; o <<= 1) {
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      s[j] += __shfl_xor(s[j], o, 64);
-      q[j] += __shfl_xor(q[j], o, 64);
-    }
-  }
-  if (lane < CPG) {
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      red[wave][0][lane * P + j] = (double)s[j];
-      red[wave][1][lane * P + j] = (double)q[j];
-    }
-  }
-  __syncthreads();
+  in_small_reduce<G>(s, q, red);
   if (tid < G) {
-    double s0 = red[0][0][tid] + red[1][0][tid] + red[2][0][tid] + red[3][0][tid];
-    double s1 = red[0][1][tid] + red[1][1][tid] + red[2][1][tid] + red[3][1][tid];
+    double s0 = in_small_total(red, 0, tid), s1 = in_small_total(red, 1, tid);
     double mean = s0 / V, var = s1 / V - mean * mean;
     if (var < 0.0) var = 0.0;
     float m = (float)mean, r = (float)(1.0 / sqrt(var + (double)eps));
@@ -385,48 +318,37 @@ __global__ __launch_bounds__(256) void in_small_fwd_kernel(const T* __restrict__
     if (HAS_RES) r = ld16(rn + (long)v * ldr);
     Vec16<T> o;
 #pragma unroll
-    for (int j = 0; j < P; ++j) {
-      float f = (Elem<T>::to_f(a.v[j]) - mean[j]) * rstd[j];
-      if (HAS_RES) f += Elem<T>::to_f(r.v[j]);
-      f = f > 0.f ? f : f * slope;
-      o.v[j] = Elem<T>::from_f(f);
-    }
+    for (int j = 0; j < P; ++j) o.v[j] = in_fwd_elem<T, HAS_RES>(a.v[j], mean[j], rstd[j], r.v[j], slope);
     st16(on + (long)v * ldo, o);
   }
 }
 
-// mask_mode: 0 none, 1 sign of `out`, 2 sign of xhat
 template <typename T, int G>
 __global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__ g, int ldg, long sg, const T* __restrict__ y, int ldy, long sy,
                                                            const T* __restrict__ out, int ldo, long so, const float* __restrict__ stats,
                                                            T* __restrict__ dy, int lddy, long sdy, T* __restrict__ dres, int lddr, long sdr,
-                                                           int acc_res, int V, int C, float slope, int mask_mode) {
+                                                           int acc_res, int V, int C, float slope, InMask mask) {
   constexpr int P = Elem<T>::PER16;
   constexpr int CPG = G / P;
   __shared__ double red[4][2][G];
   __shared__ float mm[2][G];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int n = blockIdx.y, c0 = blockIdx.x * G;
   const int ck = tid % CPG, vl = tid / CPG;
   const int VL = 256 / CPG;
   const long co = c0 + ck * P;
   float mean[P], rstd[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    mean[j] = stats[2 * ((size_t)n * C + co + j)];
-    rstd[j] = stats[2 * ((size_t)n * C + co + j) + 1];
-  }
+  load_pair(stats, n, C, c0 + ck * P, mean, rstd);
   auto gprime = [&](int v, float (&gg)[P], float (&xh)[P]) {
     Vec16<T> gv = ld16(g + n * sg + (long)v * ldg + co);
     Vec16<T> yv = ld16(y + n * sy + (long)v * ldy + co);
     Vec16<T> ov;
-    if (mask_mode == 1) ov = ld16(out + n * so + (long)v * ldo + co);
+    if (mask == IN_MASK_OUT) ov = ld16(out + n * so + (long)v * ldo + co);
 #pragma unroll
     for (int j = 0; j < P; ++j) {
+      xh[j] = in_xhat(yv.v[j], mean[j], rstd[j]);
       gg[j] = Elem<T>::to_f(gv.v[j]);
-      xh[j] = (Elem<T>::to_f(yv.v[j]) - mean[j]) * rstd[j];
-      if (mask_mode == 1 && !(Elem<T>::to_f(ov.v[j]) > 0.f)) gg[j] *= slope;
-      if (mask_mode == 2 && !(xh[j] > 0.f)) gg[j] *= slope;
+      in_bwd_gprime(gg[j], xh[j], mask, ov.v[j], slope);
     }
   };
   float s[P], q[P];
@@ -441,24 +363,10 @@ __global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__
       q[j] += gg[j] * xh[j];
     }
   }
-  for (int o = CPG; o < 64; o <<= 1) {
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      s[j] += __shfl_xor(s[j], o, 64);
-      q[j] += __shfl_xor(q[j], o, 64);
-    }
-  }
-  if (lane < CPG) {
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      red[wave][0][lane * P + j] = (double)s[j];
-      red[wave][1][lane * P + j] = (double)q[j];
-    }
-  }
-  __syncthreads();
+  in_small_reduce<G>(s, q, red);
   if (tid < G) {
-    mm[0][tid] = (float)((red[0][0][tid] + red[1][0][tid] + red[2][0][tid] + red[3][0][tid]) / V);
-    mm[1][tid] = (float)((red[0][1][tid] + red[1][1][tid] + red[2][1][tid] + red[3][1][tid]) / V);
+    mm[0][tid] = (float)(in_small_total(red, 0, tid) / V);
+    mm[1][tid] = (float)(in_small_total(red, 1, tid) / V);
   }
   __syncthreads();
   float m1[P], m2[P];
@@ -474,7 +382,7 @@ __global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__
     if (dres && acc_res) rv = ld16(dres + n * sdr + (long)v * lddr + co);
 #pragma unroll
     for (int j = 0; j < P; ++j) {
-      dv.v[j] = Elem<T>::from_f(rstd[j] * (gg[j] - m1[j] - xh[j] * m2[j]));
+      dv.v[j] = Elem<T>::from_f(in_bwd_dy(gg[j], xh[j], rstd[j], m1[j], m2[j]));
       if (dres) {
         float r = gg[j];
         if (acc_res) r += Elem<T>::to_f(rv.v[j]);
@@ -497,66 +405,33 @@ extern "C" int rx_instnorm_act_bwd(rx_dtype dt, const rx_act* g, const rx_act* y
                                    float slope, const rx_act* dy, const rx_act* d_residual, int accumulate_residual, void* ws,
                                    size_t ws_bytes, void* stream) {
   RX_RECORD(stream, [=, g_ = RxActV(g), y_ = RxActV(y), out_ = RxActV(out), dy_ = RxActV(dy), d_residual_ = RxActV(d_residual)](void* s) { return rx_instnorm_act_bwd(dt, g_.p(), y_.p(), stats, out_.p(), slope, dy_.p(), d_residual_.p(), accumulate_residual, ws, ws_bytes, s); });
-  int rc;
-  if ((rc = check_vec_channels(g, dt, "rx_instnorm_act_bwd(g)"))) return rc;
-  if ((rc = check_vec_channels(y, dt, "rx_instnorm_act_bwd(y)"))) return rc;
-  if ((rc = check_vec_channels(dy, dt, "rx_instnorm_act_bwd(dy)"))) return rc;
-  // mask source: none (slope 1) | sign of xhat (no residual: `out` may be NULL and is never read) | saved output
-  const bool mask_xhat = slope != 1.0f && out == nullptr;
-  const bool use_mask = slope != 1.0f && out != nullptr;
-  if (use_mask) {
-    if ((rc = check_vec_channels(out, dt, "rx_instnorm_act_bwd(out)"))) return rc;
-    if (!same_geom(y, out)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd: out geometry mismatch");
-  }
-  if (d_residual) {
-    if ((rc = check_vec_channels(d_residual, dt, "rx_instnorm_act_bwd(d_residual)"))) return rc;
-    if (!same_geom(y, d_residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd: d_residual geometry mismatch");
-  }
-  if (!stats || !ws || !same_geom(y, g) || !same_geom(y, dy)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd: bad arguments");
+  // `out` may be NULL (no residual) and is read only where its sign is the mask
+  const InMask mask = in_mask_of(slope, out);
+  int rc = check_acts(dt, "rx_instnorm_act_bwd", y, {{"y", y, true}, {"g", g, true}, {"dy", dy, true},
+                      {"out", mask == IN_MASK_OUT ? out : nullptr, false}, {"d_residual", d_residual, false}});
+  if (rc) return rc;
+  if (!stats || !ws) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd: bad arguments");
   const long V = rx_act_voxels(y);
   const int N = y->n, C = y->c;
+  hipStream_t st = (hipStream_t)stream;
   if (V <= RX_IN_SMALL_MAX_VOXELS && C % 32 == 0) {   // low-resolution stages: one launch instead of three
-    hipStream_t st1 = (hipStream_t)stream;
-    const int mode = use_mask ? 1 : (mask_xhat ? 2 : 0);
     const bool narrow = dt != RX_F32 && V >= RX_IN_SMALL_NARROW_VOXELS;   // (fp32 = parity mode: the summation order the goldens' seeds were screened with)
-    dim3 grid1(narrow ? C / 8 : C / 32, N);
-#define RX_LAUNCH_IN_SMALL_BWD(G)                                                                                                     \
-  hipLaunchKernelGGL((in_small_bwd_kernel<T, G>), grid1, dim3(256), 0, st1, (const T*)g->ptr, g->ld, V * g->ld, (const T*)y->ptr, y->ld, \
-                     V * y->ld, use_mask ? (const T*)out->ptr : (const T*)nullptr, use_mask ? out->ld : 0,                           \
-                     use_mask ? V * out->ld : 0L, stats, (T*)dy->ptr, dy->ld, V * dy->ld,                                             \
-                     d_residual ? (T*)d_residual->ptr : (T*)nullptr, d_residual ? d_residual->ld : 0,                                 \
-                     d_residual ? V * d_residual->ld : 0L, accumulate_residual, (int)V, C, slope, mode)
     RX_DISPATCH_DTYPE(dt, T, {
-      if (narrow) RX_LAUNCH_IN_SMALL_BWD(8);
-      else RX_LAUNCH_IN_SMALL_BWD(32);
+      const ActView<T> o = make_view<T>(mask == IN_MASK_OUT ? out : nullptr), dr = make_view<T>(d_residual);
+      hipLaunchKernelGGL((narrow ? in_small_bwd_kernel<T, 8> : in_small_bwd_kernel<T, 32>), dim3(narrow ? C / 8 : C / 32, N), dim3(256), 0, st,
+                         (const T*)g->ptr, g->ld, V * g->ld, (const T*)y->ptr, y->ld, V * y->ld, o.ptr, o.ld, o.sample_stride, stats, (T*)dy->ptr,
+                         dy->ld, V * dy->ld, (T*)dr.ptr, dr.ld, dr.sample_stride, accumulate_residual, (int)V, C, slope, mask);
     });
     RX_CHECK_LAUNCH("rx_instnorm_act_bwd(small)");
     return RX_OK;
   }
-  size_t need = rx_reduce_ws_bytes(N, V, C, 2) + (size_t)N * C * 2 * sizeof(float);
-  if (ws_bytes < need) RX_FAIL(RX_EWORKSPACE, "rx_instnorm_act_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
-  float* partial = (float*)ws;
-  float* m12 = (float*)((char*)ws + rx_align_up(rx_reduce_ws_bytes(N, V, C, 2) - 256, 256));
-  hipStream_t st = (hipStream_t)stream;
+  const ReduceWs w = reduce_ws(ws, N, V, C, 2);
+  if (ws_bytes < w.need) RX_FAIL(RX_EWORKSPACE, "rx_instnorm_act_bwd: workspace too small (%zu < %zu)", ws_bytes, w.need);
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    ReducePlan p = rx_reduce_plan(V, C, P);
-    int CV = C / P, VP = 256 / CV;
-    InBwdOp<T> op{make_view<T>(g), make_view<T>(y), use_mask ? make_view<T>(out) : make_view<T>(y), stats, C, slope, use_mask, mask_xhat, {}, {}};
-    size_t lds = (size_t)2 * (VP > 4 ? VP : 4) * C * sizeof(float);
-    hipLaunchKernelGGL((colreduce_kernel<T, 2, InBwdOp<T>>), dim3(p.nchunks, N), dim3(256), lds, st, op, (int)V, C, p.chunk_vox,
-                       partial);
-    rx_colreduce_finalize_launch(st, (const float*)partial, N, p.nchunks, 2, C,
-                       (double)V, 0.f, (int)FIN_MEAN2, m12);
-    int G = sweep_grid(V * CV, CV);
-    const T* outp = use_mask ? (const T*)out->ptr : nullptr;
-    int ldo = use_mask ? out->ld : 0;
-    if (!d_residual)
-      RX_LAUNCH_APPLY(false, false);
-    else if (accumulate_residual)
-      RX_LAUNCH_APPLY(true, true);
-    else
-      RX_LAUNCH_APPLY(true, false);
+    InBwdOp<T> op{make_view<T>(g), make_view<T>(y), make_view<T>(mask == IN_MASK_OUT ? out : y), stats, C, slope, mask, {}, {}};
+    ReducePlan p = launch_colreduce<T, 2>(op, N, V, C, w.partial, st);
+    rx_colreduce_finalize_launch(st, w.partial, N, p.nchunks, 2, C, (double)V, 0.f, (int)FIN_MEAN2, w.m12);
+    launch_bwd_apply<T>(g, y, stats, out, slope, mask, w.m12, dy, d_residual, accumulate_residual, st);
   });
   RX_CHECK_LAUNCH("rx_instnorm_act_bwd");
   return RX_OK;
@@ -584,13 +459,7 @@ struct InBwdResOp {
   int Yi, Xi, Yo, Xo, fz, fy, fx;
   float inv;
   float mean[Elem<T>::PER16], rstd[Elem<T>::PER16];
-  __device__ inline void prepare(int n, int c0) {
-#pragma unroll
-    for (int j = 0; j < Elem<T>::PER16; ++j) {
-      mean[j] = stats[2 * ((size_t)n * C + c0 + j)];
-      rstd[j] = stats[2 * ((size_t)n * C + c0 + j) + 1];
-    }
-  }
+  __device__ inline void prepare(int n, int c0) { load_pair(stats, n, C, c0, mean, rstd); }
   __device__ inline void accumulate(int n, int v, int c0, float (&acc)[2][Elem<T>::PER16]) const {
     constexpr int P = Elem<T>::PER16;
     Vec16<T> gv = ld16(g.at(n, v, c0));
@@ -608,10 +477,10 @@ struct InBwdResOp {
     for (int j = 0; j < P; ++j) {
       float gg = Elem<T>::to_f(gv.v[j]);
       if (POOL) gg += Elem<T>::to_f(pv.v[j]) * inv;
-      if (!(Elem<T>::to_f(ov.v[j]) > 0.f)) gg *= slope;
+      const float xh = in_xhat(yv.v[j], mean[j], rstd[j]);
+      in_bwd_gprime(gg, xh, IN_MASK_OUT, ov.v[j], slope);
       w.v[j] = Elem<T>::from_f(gg);
-      gg = Elem<T>::to_f(w.v[j]);
-      const float xh = (Elem<T>::to_f(yv.v[j]) - mean[j]) * rstd[j];
+      gg = Elem<T>::to_f(w.v[j]);      // summed AS STORED
       acc[0][j] += gg;
       acc[1][j] += gg * xh;
     }
@@ -625,14 +494,10 @@ extern "C" int rx_instnorm_act_bwd_res(rx_dtype dt, const rx_act* g, const rx_ac
   static const int32_t one3[3] = {1, 1, 1};
   if (!pool_stride) pool_stride = one3;
   RX_RECORD(stream, [=, g_ = RxActV(g), y_ = RxActV(y), out_ = RxActV(out), pool_dy_ = RxActV(pool_dy), pool_stride_ = RxI3V(pool_stride), d_residual_ = RxActV(d_residual), dy_ = RxActV(dy)](void* s) { return rx_instnorm_act_bwd_res(dt, g_.p(), y_.p(), stats, out_.p(), slope, pool_dy_.p(), pool_stride_.v, d_residual_.p(), dy_.p(), ws, ws_bytes, s); });
-  int rc;
-  if ((rc = check_vec_channels(g, dt, "rx_instnorm_act_bwd_res(g)"))) return rc;
-  if ((rc = check_vec_channels(y, dt, "rx_instnorm_act_bwd_res(y)"))) return rc;
-  if ((rc = check_vec_channels(out, dt, "rx_instnorm_act_bwd_res(out)"))) return rc;
-  if ((rc = check_vec_channels(dy, dt, "rx_instnorm_act_bwd_res(dy)"))) return rc;
-  if ((rc = check_vec_channels(d_residual, dt, "rx_instnorm_act_bwd_res(d_residual)"))) return rc;
-  if (!stats || !ws || !same_geom(y, g) || !same_geom(y, dy) || !same_geom(y, out) || !same_geom(y, d_residual))
-    RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_res: bad arguments");
+  int rc = check_acts(dt, "rx_instnorm_act_bwd_res", y, {{"y", y, true}, {"g", g, true}, {"out", out, true}, {"dy", dy, true},
+                      {"d_residual", d_residual, true}});
+  if (rc) return rc;
+  if (!stats || !ws) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_res: bad arguments");
   if (d_residual->ptr == dy->ptr) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_res: d_residual and dy must be different buffers");
   if (pool_dy) {
     if ((rc = check_vec_channels(pool_dy, dt, "rx_instnorm_act_bwd_res(pool_dy)"))) return rc;
@@ -640,32 +505,24 @@ extern "C" int rx_instnorm_act_bwd_res(rx_dtype dt, const rx_act* g, const rx_ac
   }
   const long V = rx_act_voxels(y);
   const int N = y->n, C = y->c;
-  size_t need = rx_reduce_ws_bytes(N, V, C, 2) + (size_t)N * C * 2 * sizeof(float);
-  if (ws_bytes < need) RX_FAIL(RX_EWORKSPACE, "rx_instnorm_act_bwd_res: workspace too small (%zu < %zu)", ws_bytes, need);
-  float* partial = (float*)ws;
-  float* m12 = (float*)((char*)ws + rx_align_up(rx_reduce_ws_bytes(N, V, C, 2) - 256, 256));
+  const ReduceWs w = reduce_ws(ws, N, V, C, 2);
+  if (ws_bytes < w.need) RX_FAIL(RX_EWORKSPACE, "rx_instnorm_act_bwd_res: workspace too small (%zu < %zu)", ws_bytes, w.need);
   hipStream_t st = (hipStream_t)stream;
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    ReducePlan p = rx_reduce_plan(V, C, P);
-    int CV = C / P, VP = 256 / CV;
-    size_t lds = (size_t)2 * (VP > 4 ? VP : 4) * C * sizeof(float);
+    ReducePlan p;
     if (pool_dy) {
       InBwdResOp<T, true> op{make_view<T>(g), make_view<T>(y), make_view<T>(out), make_view<T>(pool_dy), (T*)d_residual->ptr,
                              V * (long)d_residual->ld, d_residual->ld, stats, C, slope, y->y, y->x, pool_dy->y, pool_dy->x,
                              pool_stride[0], pool_stride[1], pool_stride[2], 1.f / (float)(pool_stride[0] * pool_stride[1] * pool_stride[2]), {}, {}};
-      hipLaunchKernelGGL((colreduce_kernel<T, 2, InBwdResOp<T, true>>), dim3(p.nchunks, N), dim3(256), lds, st, op, (int)V, C, p.chunk_vox, partial);
+      p = launch_colreduce<T, 2>(op, N, V, C, w.partial, st);
     } else {
       InBwdResOp<T, false> op{make_view<T>(g), make_view<T>(y), make_view<T>(out), make_view<T>(y), (T*)d_residual->ptr,
                               V * (long)d_residual->ld, d_residual->ld, stats, C, slope, y->y, y->x, 1, 1, 1, 1, 1, 1.f, {}, {}};
-      hipLaunchKernelGGL((colreduce_kernel<T, 2, InBwdResOp<T, false>>), dim3(p.nchunks, N), dim3(256), lds, st, op, (int)V, C, p.chunk_vox, partial);
+      p = launch_colreduce<T, 2>(op, N, V, C, w.partial, st);
     }
-    rx_colreduce_finalize_launch(st, (const float*)partial, N, p.nchunks, 2, C, (double)V, 0.f, (int)FIN_MEAN2, m12);
-    int G = sweep_grid(V * CV, CV);
+    rx_colreduce_finalize_launch(st, w.partial, N, p.nchunks, 2, C, (double)V, 0.f, (int)FIN_MEAN2, w.m12);
     // apply: dy = rstd * (g' - m1 - xhat * m2) from (g', y) alone -- no mask, no residual output
-    hipLaunchKernelGGL((in_act_bwd_apply_kernel<T, false, false>), dim3(G, N), dim3(256), 0, st, (const T*)d_residual->ptr, d_residual->ld,
-                       V * d_residual->ld, (const T*)y->ptr, y->ld, V * y->ld, (const T*)nullptr, 0, 0L, stats, (const float*)m12,
-                       (T*)dy->ptr, dy->ld, V * dy->ld, (T*)nullptr, 0, 0L, (int)V, C, slope, 0);
+    launch_bwd_apply<T>(d_residual, y, stats, nullptr, slope, IN_MASK_NONE, w.m12, dy, nullptr, 0, st);
   });
   RX_CHECK_LAUNCH("rx_instnorm_act_bwd_res");
   return RX_OK;
@@ -699,37 +556,12 @@ extern "C" int rx_instnorm_act_bwd_apply(rx_dtype dt, const rx_act* g, const rx_
                                          const float* m12, const rx_act* dy, const rx_act* d_residual, int accumulate_residual,
                                          void* stream) {
   RX_RECORD(stream, [=, g_ = RxActV(g), y_ = RxActV(y), out_ = RxActV(out), dy_ = RxActV(dy), d_residual_ = RxActV(d_residual)](void* s) { return rx_instnorm_act_bwd_apply(dt, g_.p(), y_.p(), stats, out_.p(), slope, m12, dy_.p(), d_residual_.p(), accumulate_residual, s); });
-  int rc;
-  if ((rc = check_vec_channels(g, dt, "rx_instnorm_act_bwd_apply(g)"))) return rc;
-  if ((rc = check_vec_channels(y, dt, "rx_instnorm_act_bwd_apply(y)"))) return rc;
-  if ((rc = check_vec_channels(dy, dt, "rx_instnorm_act_bwd_apply(dy)"))) return rc;
-  const bool mask_xhat = slope != 1.0f && out == nullptr;
-  const bool use_mask = slope != 1.0f && out != nullptr;
-  if (use_mask) {
-    if ((rc = check_vec_channels(out, dt, "rx_instnorm_act_bwd_apply(out)"))) return rc;
-    if (!same_geom(y, out)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_apply: out geometry mismatch");
-  }
-  if (d_residual) {
-    if ((rc = check_vec_channels(d_residual, dt, "rx_instnorm_act_bwd_apply(d_residual)"))) return rc;
-    if (!same_geom(y, d_residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_apply: d_residual geometry mismatch");
-  }
-  if (!stats || !m12 || !same_geom(y, g) || !same_geom(y, dy)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_apply: bad arguments");
-  const long V = rx_act_voxels(y);
-  const int N = y->n, C = y->c;
-  hipStream_t st = (hipStream_t)stream;
-  RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    int CV = C / P;
-    int G = sweep_grid(V * CV, CV);
-    const T* outp = use_mask ? (const T*)out->ptr : nullptr;
-    int ldo = use_mask ? out->ld : 0;
-    if (!d_residual)
-      RX_LAUNCH_APPLY(false, false);
-    else if (accumulate_residual)
-      RX_LAUNCH_APPLY(true, true);
-    else
-      RX_LAUNCH_APPLY(true, false);
-  });
+  const InMask mask = in_mask_of(slope, out);
+  int rc = check_acts(dt, "rx_instnorm_act_bwd_apply", y, {{"y", y, true}, {"g", g, true}, {"dy", dy, true},
+                      {"out", mask == IN_MASK_OUT ? out : nullptr, false}, {"d_residual", d_residual, false}});
+  if (rc) return rc;
+  if (!stats || !m12) RX_FAIL(RX_EINVAL, "rx_instnorm_act_bwd_apply: bad arguments");
+  RX_DISPATCH_DTYPE(dt, T, { launch_bwd_apply<T>(g, y, stats, out, slope, mask, m12, dy, d_residual, accumulate_residual, (hipStream_t)stream); });
   RX_CHECK_LAUNCH("rx_instnorm_act_bwd_apply");
   return RX_OK;
 }
@@ -744,24 +576,16 @@ extern "C" int rx_instnorm_fwd(rx_dtype dt, const rx_act* y, float eps, float* s
     if ((rc = rx_instnorm_stats(dt, y, eps, stats, ws, ws_bytes, stream))) return rc;
     return rx_instnorm_act_fwd(dt, y, stats, residual, out, slope, stream);
   }
-  if ((rc = check_vec_channels(out, dt, "rx_instnorm_fwd(out)"))) return rc;
-  if (!stats || !same_geom(y, out)) RX_FAIL(RX_EINVAL, "rx_instnorm_fwd: geometry mismatch / null stats");
-  if (residual) {
-    if ((rc = check_vec_channels(residual, dt, "rx_instnorm_fwd(residual)"))) return rc;
-    if (!same_geom(y, residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_fwd: residual geometry mismatch");
-  }
+  if ((rc = check_acts(dt, "rx_instnorm_fwd", y, {{"out", out, true}, {"residual", residual, false}}))) return rc;
+  if (!stats) RX_FAIL(RX_EINVAL, "rx_instnorm_fwd: null stats");
   hipStream_t st = (hipStream_t)stream;
   const bool narrow = dt != RX_F32 && V >= RX_IN_SMALL_NARROW_VOXELS;   // (fp32 = parity mode: the summation order the goldens' seeds were screened with)
-  dim3 grid(narrow ? y->c / 8 : y->c / 32, y->n);
-#define RX_LAUNCH_IN_SMALL_FWD(G, RES)                                                                                              \
-  hipLaunchKernelGGL((in_small_fwd_kernel<T, G, RES>), grid, dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld,                  \
-                     RES ? (const T*)residual->ptr : (const T*)nullptr, RES ? residual->ld : 0, RES ? V * residual->ld : 0L,         \
-                     (T*)out->ptr, out->ld, V * out->ld, stats, (int)V, y->c, eps, slope)
   RX_DISPATCH_DTYPE(dt, T, {
-    if (residual && narrow) RX_LAUNCH_IN_SMALL_FWD(8, true);
-    else if (residual) RX_LAUNCH_IN_SMALL_FWD(32, true);
-    else if (narrow) RX_LAUNCH_IN_SMALL_FWD(8, false);
-    else RX_LAUNCH_IN_SMALL_FWD(32, false);
+    auto kern = residual ? (narrow ? in_small_fwd_kernel<T, 8, true> : in_small_fwd_kernel<T, 32, true>)
+                         : (narrow ? in_small_fwd_kernel<T, 8, false> : in_small_fwd_kernel<T, 32, false>);
+    const ActView<T> r = make_view<T>(residual);
+    hipLaunchKernelGGL(kern, dim3(narrow ? y->c / 8 : y->c / 32, y->n), dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld, r.ptr, r.ld,
+                       r.sample_stride, (T*)out->ptr, out->ld, V * out->ld, stats, (int)V, y->c, eps, slope);
   });
   RX_CHECK_LAUNCH("rx_instnorm_fwd");
   return RX_OK;
@@ -856,19 +680,13 @@ __global__ __launch_bounds__(256) void in_act_pool_fwd_kernel(const T* __restric
                                                               T* __restrict__ pooled, int ldp, long sp, int Zo, int Yo, int Xo, int Yi, int Xi,
                                                               int C, int fz, int fy, int fx, float slope) {
   constexpr int P = Elem<T>::PER16;
-  const int CV = C / P, n = blockIdx.y;
-  const long total = (long)Zo * Yo * Xo * CV, step = (long)gridDim.x * 256;
-  long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const int cv = (int)(i % CV);
+  Sweep<P> s((long)Zo * Yo * Xo, C);
+  const int n = s.n, c0 = s.cv * P;
   float mean[P], rstd[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    mean[j] = stats[2 * ((size_t)n * C + cv * P + j)];
-    rstd[j] = stats[2 * ((size_t)n * C + cv * P + j) + 1];
-  }
+  load_pair(stats, n, C, c0, mean, rstd);
   const float inv = 1.f / (float)(fz * fy * fx);
-  for (; i < total; i += step) {
-    const long vo = i / CV;
+  for (; s.more(); s.next()) {
+    const long vo = s.v();
     const int xo = (int)(vo % Xo), yo = (int)((vo / Xo) % Yo), zo = (int)(vo / ((long)Xo * Yo));
     float acc[P];
 #pragma unroll
@@ -877,53 +695,40 @@ __global__ __launch_bounds__(256) void in_act_pool_fwd_kernel(const T* __restric
       for (int b = 0; b < fy; ++b)
         for (int c = 0; c < fx; ++c) {
           const long vi = ((long)(zo * fz + a) * Yi + (yo * fy + b)) * Xi + (xo * fx + c);
-          Vec16<T> t = ld16(y + n * sy + vi * ldy + cv * P), r, o;
-          if (HAS_RES) r = ld16(res + n * sr + vi * ldr + cv * P);
+          Vec16<T> t = ld16(y + n * sy + vi * ldy + c0), r, o;
+          if (HAS_RES) r = ld16(res + n * sr + vi * ldr + c0);
 #pragma unroll
           for (int j = 0; j < P; ++j) {
-            float f = (Elem<T>::to_f(t.v[j]) - mean[j]) * rstd[j];
-            if (HAS_RES) f += Elem<T>::to_f(r.v[j]);
-            f = f > 0.f ? f : f * slope;
-            o.v[j] = Elem<T>::from_f(f);
-            acc[j] += Elem<T>::to_f(o.v[j]);
+            o.v[j] = in_fwd_elem<T, HAS_RES>(t.v[j], mean[j], rstd[j], r.v[j], slope);
+            acc[j] += Elem<T>::to_f(o.v[j]);      // averaged AS STORED
           }
-          st16(out + n * so + vi * ldo + cv * P, o);
+          st16(out + n * so + vi * ldo + c0, o);
         }
     Vec16<T> p;
 #pragma unroll
     for (int j = 0; j < P; ++j) p.v[j] = Elem<T>::from_f(acc[j] * inv);
-    st16(pooled + n * sp + vo * ldp + cv * P, p);
+    st16(pooled + n * sp + vo * ldp + c0, p);
   }
 }
 
 extern "C" int rx_instnorm_act_pool_fwd(rx_dtype dt, const rx_act* y, const float* stats, const rx_act* residual, const rx_act* out,
                                         const rx_act* pooled, const int32_t stride[3], float slope, void* stream) {
   RX_RECORD(stream, [=, y_ = RxActV(y), residual_ = RxActV(residual), out_ = RxActV(out), pooled_ = RxActV(pooled), stride_ = RxI3V(stride)](void* s) { return rx_instnorm_act_pool_fwd(dt, y_.p(), stats, residual_.p(), out_.p(), pooled_.p(), stride_.v, slope, s); });
-  int rc;
-  if ((rc = check_vec_channels(y, dt, "rx_instnorm_act_pool_fwd(y)"))) return rc;
-  if ((rc = check_vec_channels(out, dt, "rx_instnorm_act_pool_fwd(out)"))) return rc;
+  int rc = check_acts(dt, "rx_instnorm_act_pool_fwd", y, {{"y", y, true}, {"out", out, true}, {"residual", residual, false}});
+  if (rc) return rc;
   if ((rc = check_vec_channels(pooled, dt, "rx_instnorm_act_pool_fwd(pooled)"))) return rc;
-  if (!stats || !same_geom(y, out)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_pool_fwd: geometry mismatch / null stats");
+  if (!stats) RX_FAIL(RX_EINVAL, "rx_instnorm_act_pool_fwd: null stats");
   if ((rc = check_pool(out, pooled, stride, "rx_instnorm_act_pool_fwd"))) return rc;
-  if (residual) {
-    if ((rc = check_vec_channels(residual, dt, "rx_instnorm_act_pool_fwd(residual)"))) return rc;
-    if (!same_geom(y, residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_act_pool_fwd: residual geometry mismatch");
-  }
   const long V = rx_act_voxels(y), Vp = rx_act_voxels(pooled);
   hipStream_t st = (hipStream_t)stream;
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    const int CV = y->c / P;
+    const int CV = y->c / Elem<T>::PER16;
     const int G = sweep_grid(Vp * CV * 4, CV);      // a thread produces up to 8 outputs: 4x the blocks of a plain sweep of Vp
-    if (residual)
-      hipLaunchKernelGGL((in_act_pool_fwd_kernel<T, true>), dim3(G, y->n), dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld, stats,
-                         (const T*)residual->ptr, residual->ld, V * residual->ld, (T*)out->ptr, out->ld, V * out->ld, (T*)pooled->ptr,
-                         pooled->ld, Vp * pooled->ld, pooled->z, pooled->y, pooled->x, y->y, y->x, y->c, stride[0], stride[1], stride[2],
-                         slope);
-    else
-      hipLaunchKernelGGL((in_act_pool_fwd_kernel<T, false>), dim3(G, y->n), dim3(256), 0, st, (const T*)y->ptr, y->ld, V * y->ld, stats,
-                         (const T*)nullptr, 0, 0L, (T*)out->ptr, out->ld, V * out->ld, (T*)pooled->ptr, pooled->ld, Vp * pooled->ld,
-                         pooled->z, pooled->y, pooled->x, y->y, y->x, y->c, stride[0], stride[1], stride[2], slope);
+    const ActView<T> r = make_view<T>(residual);
+    hipLaunchKernelGGL((residual ? in_act_pool_fwd_kernel<T, true> : in_act_pool_fwd_kernel<T, false>), dim3(G, y->n), dim3(256), 0, st,
+                       (const T*)y->ptr, y->ld, V * y->ld, stats, r.ptr, r.ld, r.sample_stride, (T*)out->ptr, out->ld, V * out->ld,
+                       (T*)pooled->ptr, pooled->ld, Vp * pooled->ld, pooled->z, pooled->y, pooled->x, y->y, y->x, y->c, stride[0], stride[1],
+                       stride[2], slope);
   });
   RX_CHECK_LAUNCH("rx_instnorm_act_pool_fwd");
   return RX_OK;

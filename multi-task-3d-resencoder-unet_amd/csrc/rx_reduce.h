@@ -1,6 +1,8 @@
 // rx_reduce.h -- what the channels-last elementwise files (rx_instnorm.hip, rx_head.hip, rx_stem.hip, rx_se.hip) share: the
 // deterministic two-stage column reduction, the activation view its operators read through, and the host-side descriptor checks.
 #pragma once
+#include <initializer_list>
+
 #include "rx_common.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -128,15 +130,37 @@ struct ActView {
   const T* ptr;
   long sample_stride;  // elements
   int ld;
-  __device__ inline const T* at(int n, int v, int c) const { return ptr + n * sample_stride + (long)v * ld + c; }
+  __device__ inline const T* at(int n, long v, int c) const { return ptr + n * sample_stride + v * ld + c; }
 };
 template <typename T>
-static inline ActView<T> make_view(const rx_act* a) {
-  ActView<T> r;
-  r.ptr = (const T*)a->ptr;
-  r.ld = a->ld;
-  r.sample_stride = rx_act_voxels(a) * (long)a->ld;
-  return r;
+static inline ActView<T> make_view(const rx_act* a) {   // a == NULL: the null view (ptr == nullptr)
+  if (!a) return ActView<T>{nullptr, 0, 0};
+  return ActView<T>{(const T*)a->ptr, rx_act_voxels(a) * (long)a->ld, a->ld};
+}
+
+// ---- one host path for the two-stage reductions ------------------------------------------------
+// Workspace of a backward entry point: the colreduce partials, then the (m1, m2) table of N*C pairs.  rx_reduce_ws_bytes is
+// payload + 256 spare bytes; m12 starts at the payload rounded up to 256 (hence `- 256`: at most 255 bytes past the payload,
+// inside the spare), so partial and m12 never overlap and `need` = partials + table covers both.
+struct ReduceWs {
+  float* partial;
+  float* m12;
+  size_t need;
+};
+static inline ReduceWs reduce_ws(void* ws, int N, long V, int C, int nacc) {
+  const size_t part = rx_reduce_ws_bytes(N, V, C, nacc);
+  return ReduceWs{(float*)ws, (float*)((char*)ws + rx_align_up(part - 256, 256)), part + (size_t)N * C * 2 * sizeof(float)};
+}
+
+// first stage of a column reduction: plan, LDS rows (4 on the shuffle path, VP otherwise) and launch
+template <typename T, int NACC, typename Op>
+static inline ReducePlan launch_colreduce(const Op& op, int N, long V, int C, float* partial, hipStream_t st) {
+  constexpr int P = Elem<T>::PER16;
+  const ReducePlan p = rx_reduce_plan(V, C, P);
+  const int VP = 256 / (C / P);
+  const size_t lds = (size_t)NACC * (VP > 4 ? VP : 4) * C * sizeof(float);
+  hipLaunchKernelGGL((colreduce_kernel<T, NACC, Op>), dim3(p.nchunks, N), dim3(256), lds, st, op, (int)V, C, p.chunk_vox, partial);
+  return p;
 }
 
 // ---- descriptor checks and sweep geometry (host) ---------------------------------------------
@@ -166,6 +190,25 @@ static inline int sweep_grid(long total_vec, int CV) {
 
 static inline int same_geom(const rx_act* a, const rx_act* b) {
   return a->n == b->n && a->z == b->z && a->y == b->y && a->x == b->x && a->c == b->c;
+}
+
+// The validation preamble of an entry point `fn`: every listed activation passes check_vec_channels and has the geometry of
+// `ref` (list `ref` itself first, so it is validated before it is compared against).  An absent optional one is skipped.
+struct ActArg {
+  const char* name;
+  const rx_act* act;
+  bool required;
+};
+static inline int check_acts(int dt, const char* fn, const rx_act* ref, std::initializer_list<ActArg> acts, int max_c = 0) {
+  for (const ActArg& a : acts) {
+    if (!a.act && !a.required) continue;
+    char who[96];
+    snprintf(who, sizeof who, "%s(%s)", fn, a.name);
+    int rc = check_vec_channels(a.act, dt, who, max_c);
+    if (rc) return rc;
+    if (!same_geom(ref, a.act)) RX_FAIL(RX_EINVAL, "%s: %s geometry mismatch", fn, a.name);
+  }
+  return RX_OK;
 }
 
 static inline int check_pool(const rx_act* big, const rx_act* small, const int32_t f[3], const char* who) {

@@ -23,25 +23,13 @@
 
 #include "rx_common.h"
 #include "rx_reduce.h"
-
-template <typename T>
-struct SeView {
-  const T* ptr;
-  long ss;
-  int ld;
-};
-template <typename T>
-static inline SeView<T> se_view(const rx_act* a) {
-  SeView<T> v;
-  v.ptr = (const T*)a->ptr, v.ld = a->ld, v.ss = rx_act_voxels(a) * (long)a->ld;
-  return v;
-}
+#include "rx_instnorm_core.h"
 
 // ---- line sums ------------------------------------------------------------------------------------------------------
 // grid = (row chunks, x segments, N); thread = one (x, 16-byte channel vector) pair of the segment: every row of the chunk
 // is one contiguous, fully coalesced run.  part[((n*chunks + chunk)*NACC + a)*X*C + x*C + c]
 template <typename T, bool BWD>
-__global__ __launch_bounds__(256) void se_linesum_kernel(SeView<T> y, SeView<T> g, SeView<T> out, const float* __restrict__ stats, int rows, int X,
+__global__ __launch_bounds__(256) void se_linesum_kernel(ActView<T> y, ActView<T> g, ActView<T> out, const float* __restrict__ stats, int rows, int X,
                                                          int C, int rows_per_chunk, float slope, float* __restrict__ part) {
   constexpr int P = Elem<T>::PER16;
   constexpr int NACC = BWD ? 2 : 1;
@@ -49,14 +37,9 @@ __global__ __launch_bounds__(256) void se_linesum_kernel(SeView<T> y, SeView<T> 
   const int pair = blockIdx.y * 256 + threadIdx.x;
   if (pair >= X * CV) return;
   const int x = pair / CV, cv = pair - x * CV, n = blockIdx.z;
+  const InMask mask = out.ptr ? IN_MASK_OUT : IN_MASK_NONE;
   float mean[P], rstd[P];
-  if (BWD) {
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      mean[j] = stats[2 * ((size_t)n * C + cv * P + j)];
-      rstd[j] = stats[2 * ((size_t)n * C + cv * P + j) + 1];
-    }
-  }
+  if (BWD) load_pair(stats, n, C, cv * P, mean, rstd);
   float acc[NACC][P];
 #pragma unroll
   for (int a = 0; a < NACC; ++a)
@@ -66,19 +49,19 @@ __global__ __launch_bounds__(256) void se_linesum_kernel(SeView<T> y, SeView<T> 
 #pragma unroll 4
   for (int r = r0; r < r1; ++r) {
     const long v = (long)r * X + x;
-    Vec16<T> yv = ld16(y.ptr + n * y.ss + v * y.ld + cv * P);
+    Vec16<T> yv = ld16(y.at(n, v, cv * P));
     if (!BWD) {
 #pragma unroll
       for (int j = 0; j < P; ++j) acc[0][j] += Elem<T>::to_f(yv.v[j]);
     } else {
-      Vec16<T> gv = ld16(g.ptr + n * g.ss + v * g.ld + cv * P);
+      Vec16<T> gv = ld16(g.at(n, v, cv * P));
       Vec16<T> ov;
-      if (out.ptr) ov = ld16(out.ptr + n * out.ss + v * out.ld + cv * P);
+      if (mask == IN_MASK_OUT) ov = ld16(out.at(n, v, cv * P));
 #pragma unroll
       for (int j = 0; j < P; ++j) {
+        const float xh = in_xhat(yv.v[j], mean[j], rstd[j]);
         float gg = Elem<T>::to_f(gv.v[j]);
-        const float xh = (Elem<T>::to_f(yv.v[j]) - mean[j]) * rstd[j];
-        if (out.ptr && !(Elem<T>::to_f(ov.v[j]) > 0.f)) gg *= slope;
+        in_bwd_gprime(gg, xh, mask, ov.v[j], slope);
         acc[0][j] += gg;
         acc[NACC - 1][j] += gg * xh;
       }
@@ -499,78 +482,62 @@ __global__ __launch_bounds__(256) void se_param_grad_kernel(const float* __restr
 
 // ---- gated apply passes ---------------------------------------------------------------------------------------------
 template <typename T, bool HAS_RES>
-__global__ __launch_bounds__(256) void in_gate_act_fwd_kernel(SeView<T> y, const float* __restrict__ stats, const float* __restrict__ mult, int L, int X,
-                                                              SeView<T> res, T* __restrict__ out, int ldo, long so, int V, int C, float slope) {
+__global__ __launch_bounds__(256) void in_gate_act_fwd_kernel(ActView<T> y, const float* __restrict__ stats, const float* __restrict__ mult, int L, int X,
+                                                              ActView<T> res, T* __restrict__ out, int ldo, long so, int V, int C, float slope) {
   constexpr int P = Elem<T>::PER16;
-  const int CV = C / P, n = blockIdx.y;
-  const long total = (long)V * CV, step = (long)gridDim.x * 256;
-  long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const int cv = (int)(i % CV);
+  Sweep<P> s(V, C);
+  const int n = s.n, c0 = s.cv * P;
   float mean[P], rstd[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    mean[j] = stats[2 * ((size_t)n * C + cv * P + j)];
-    rstd[j] = stats[2 * ((size_t)n * C + cv * P + j) + 1];
-  }
-  for (; i < total; i += step) {
-    const long v = i / CV;
+  load_pair(stats, n, C, c0, mean, rstd);
+  for (; s.more(); s.next()) {
+    const long v = s.v();
     const int line = L == 1 ? 0 : (int)(v % X);
-    const float* mp = mult + ((size_t)n * L + line) * C + cv * P;
-    Vec16<T> a = ld16(y.ptr + n * y.ss + v * y.ld + cv * P), r, o;
-    if (HAS_RES) r = ld16(res.ptr + n * res.ss + v * res.ld + cv * P);
+    const float* mp = mult + ((size_t)n * L + line) * C + c0;
+    Vec16<T> a = ld16(y.at(n, v, c0)), r, o;
+    if (HAS_RES) r = ld16(res.at(n, v, c0));
 #pragma unroll
-    for (int j = 0; j < P; ++j) {
-      float f = (Elem<T>::to_f(a.v[j]) - mean[j]) * rstd[j] * mp[j];
-      if (HAS_RES) f += Elem<T>::to_f(r.v[j]);
-      f = f > 0.f ? f : f * slope;
-      o.v[j] = Elem<T>::from_f(f);
-    }
-    st16(out + n * so + v * ldo + cv * P, o);
+    for (int j = 0; j < P; ++j) o.v[j] = in_fwd_elem<T, HAS_RES, true>(a.v[j], mean[j], rstd[j], r.v[j], slope, mp[j]);
+    st16(out + n * so + v * ldo + c0, o);
   }
 }
 
 template <typename T, bool HAS_DRES, bool ACC_DRES>
-__global__ __launch_bounds__(256) void in_gate_act_bwd_kernel(SeView<T> g, SeView<T> y, SeView<T> out, const float* __restrict__ stats,
+__global__ __launch_bounds__(256) void in_gate_act_bwd_kernel(ActView<T> g, ActView<T> y, ActView<T> out, const float* __restrict__ stats,
                                                               const float* __restrict__ mult, const float* __restrict__ dadd,
                                                               const float* __restrict__ m12, int L, int X, T* __restrict__ dy, int lddy, long sdy,
                                                               T* __restrict__ dres, int lddr, long sdr, int V, int C, float slope) {
   constexpr int P = Elem<T>::PER16;
-  const int CV = C / P, n = blockIdx.y;
-  const long total = (long)V * CV, step = (long)gridDim.x * 256;
-  long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const int cv = (int)(i % CV);
+  Sweep<P> s(V, C);
+  const int n = s.n, c0 = s.cv * P;
+  const InMask mask = out.ptr ? IN_MASK_OUT : IN_MASK_NONE;
   float mean[P], rstd[P], m1[P], m2[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const size_t k = (size_t)n * C + cv * P + j;
-    mean[j] = stats[2 * k], rstd[j] = stats[2 * k + 1];
-    m1[j] = m12[2 * k], m2[j] = m12[2 * k + 1];
-  }
-  for (; i < total; i += step) {
-    const long v = i / CV;
+  load_pair(stats, n, C, c0, mean, rstd);
+  load_pair(m12, n, C, c0, m1, m2);
+  for (; s.more(); s.next()) {
+    const long v = s.v();
     const int line = L == 1 ? 0 : (int)(v % X);
-    const float* mp = mult + ((size_t)n * L + line) * C + cv * P;
-    const float* dp = dadd + ((size_t)n * L + line) * C + cv * P;
-    Vec16<T> gv = ld16(g.ptr + n * g.ss + v * g.ld + cv * P);
-    Vec16<T> yv = ld16(y.ptr + n * y.ss + v * y.ld + cv * P);
+    const float* mp = mult + ((size_t)n * L + line) * C + c0;
+    const float* dp = dadd + ((size_t)n * L + line) * C + c0;
+    Vec16<T> gv = ld16(g.at(n, v, c0));
+    Vec16<T> yv = ld16(y.at(n, v, c0));
     Vec16<T> ov, dv, rv;
-    if (out.ptr) ov = ld16(out.ptr + n * out.ss + v * out.ld + cv * P);
-    if (HAS_DRES && ACC_DRES) rv = ld16(dres + n * sdr + v * lddr + cv * P);
+    if (mask == IN_MASK_OUT) ov = ld16(out.at(n, v, c0));
+    if (HAS_DRES && ACC_DRES) rv = ld16(dres + n * sdr + v * lddr + c0);
 #pragma unroll
     for (int j = 0; j < P; ++j) {
+      const float xh = in_xhat(yv.v[j], mean[j], rstd[j]);
       float gg = Elem<T>::to_f(gv.v[j]);
-      const float xh = (Elem<T>::to_f(yv.v[j]) - mean[j]) * rstd[j];
-      if (out.ptr && !(Elem<T>::to_f(ov.v[j]) > 0.f)) gg *= slope;
+      in_bwd_gprime(gg, xh, mask, ov.v[j], slope);
       const float dx = gg * mp[j] + dp[j];
-      dv.v[j] = Elem<T>::from_f(rstd[j] * (dx - m1[j] - xh * m2[j]));
+      dv.v[j] = Elem<T>::from_f(in_bwd_dy(dx, xh, rstd[j], m1[j], m2[j]));
       if (HAS_DRES) {
         float r = gg;
         if (ACC_DRES) r += Elem<T>::to_f(rv.v[j]);
         rv.v[j] = Elem<T>::from_f(r);
       }
     }
-    st16(dy + n * sdy + v * lddy + cv * P, dv);
-    if (HAS_DRES) st16(dres + n * sdr + v * lddr + cv * P, rv);
+    st16(dy + n * sdy + v * lddy + c0, dv);
+    if (HAS_DRES) st16(dres + n * sdr + v * lddr + c0, rv);
   }
 }
 
@@ -627,8 +594,8 @@ extern "C" int rx_se_gate_fwd(rx_dtype dt, const rx_act* y, const float* stats, 
   const SePlan p = se_plan(y, per16, se->keep_x);
   float* part = (float*)ws;
   RX_DISPATCH_DTYPE(dt, T, {
-    SeView<T> yv = se_view<T>(y), none{nullptr, 0, 0};
-    hipLaunchKernelGGL((se_linesum_kernel<T, false>), dim3(p.chunks, p.segs, y->n), dim3(256), 0, st, yv, none, none, stats, p.rows, p.X, y->c,
+    const ActView<T> none = make_view<T>(nullptr);
+    hipLaunchKernelGGL((se_linesum_kernel<T, false>), dim3(p.chunks, p.segs, y->n), dim3(256), 0, st, make_view<T>(y), none, none, stats, p.rows, p.X, y->c,
                        p.rows_per_chunk, 1.f, part);
   });
   const size_t lds = (size_t)(y->c + 64 + 256) * sizeof(float);
@@ -641,33 +608,16 @@ extern "C" int rx_se_gate_fwd(rx_dtype dt, const rx_act* y, const float* stats, 
 extern "C" int rx_instnorm_gate_act_fwd(rx_dtype dt, const rx_act* y, const float* stats, const float* mult, int keep_x, const rx_act* residual,
                                         const rx_act* out, float slope, void* stream) {
   RX_RECORD(stream, [=, y_ = RxActV(y), residual_ = RxActV(residual), out_ = RxActV(out)](void* s) { return rx_instnorm_gate_act_fwd(dt, y_.p(), stats, mult, keep_x, residual_.p(), out_.p(), slope, s); });
-  int rc;
-  if ((rc = check_vec_channels(y, dt, "rx_instnorm_gate_act_fwd(y)", RX_SE_MAX_C))) return rc;
-  if ((rc = check_vec_channels(out, dt, "rx_instnorm_gate_act_fwd(out)", RX_SE_MAX_C))) return rc;
-  if (!stats || !mult || !same_geom(y, out)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_fwd: bad arguments");
-  if (residual) {
-    if ((rc = check_vec_channels(residual, dt, "rx_instnorm_gate_act_fwd(residual)", RX_SE_MAX_C))) return rc;
-    if (!same_geom(y, residual)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_fwd: residual geometry mismatch");
-  }
+  int rc = check_acts(dt, "rx_instnorm_gate_act_fwd", y, {{"y", y, true}, {"out", out, true}, {"residual", residual, false}}, RX_SE_MAX_C);
+  if (rc) return rc;
+  if (!stats || !mult) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_fwd: bad arguments");
   const long V = rx_act_voxels(y);
   hipStream_t st = (hipStream_t)stream;
   const int L = keep_x ? y->x : 1;
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    const int CV = y->c / P;
-    long want = (V * CV + 2047) / 2048;
-    int gq = CV;                                                 // G * 256 % CV == 0: a thread keeps one channel vector
-    for (int d = 256; gq % 2 == 0 && d > 1; d /= 2) gq /= 2;
-    if (want < 1) want = 1;
-    if (want > 2048) want = 2048;
-    const int G = (int)((want + gq - 1) / gq * gq);
-    SeView<T> yv = se_view<T>(y);
-    if (residual)
-      hipLaunchKernelGGL((in_gate_act_fwd_kernel<T, true>), dim3(G, y->n), dim3(256), 0, st, yv, stats, mult, L, y->x, se_view<T>(residual),
-                         (T*)out->ptr, out->ld, V * out->ld, (int)V, y->c, slope);
-    else
-      hipLaunchKernelGGL((in_gate_act_fwd_kernel<T, false>), dim3(G, y->n), dim3(256), 0, st, yv, stats, mult, L, y->x, SeView<T>{nullptr, 0, 0},
-                         (T*)out->ptr, out->ld, V * out->ld, (int)V, y->c, slope);
+    const int CV = y->c / Elem<T>::PER16, G = sweep_grid(V * CV, CV);
+    hipLaunchKernelGGL((residual ? in_gate_act_fwd_kernel<T, true> : in_gate_act_fwd_kernel<T, false>), dim3(G, y->n), dim3(256), 0, st,
+                       make_view<T>(y), stats, mult, L, y->x, make_view<T>(residual), (T*)out->ptr, out->ld, V * out->ld, (int)V, y->c, slope);
   });
   RX_CHECK_LAUNCH("rx_instnorm_gate_act_fwd");
   return RX_OK;
@@ -678,14 +628,9 @@ extern "C" int rx_se_gate_bwd(rx_dtype dt, const rx_act* g, const rx_act* y, con
                               const float* mult, float* dadd, float* m12, float* dw1, float* db1, float* dw2, float* db2, void* ws,
                               size_t ws_bytes, void* stream) {
   RX_RECORD(stream, [=, g_ = RxActV(g), y_ = RxActV(y), out_ = RxActV(out), se_ = RxSeV(se)](void* s) { return rx_se_gate_bwd(dt, g_.p(), y_.p(), stats, out_.p(), slope, path_scale, se_.p(), pooled, hidden, gate, mult, dadd, m12, dw1, db1, dw2, db2, ws, ws_bytes, s); });
-  int rc;
-  if ((rc = check_vec_channels(g, dt, "rx_se_gate_bwd(g)", RX_SE_MAX_C))) return rc;
-  if ((rc = check_vec_channels(y, dt, "rx_se_gate_bwd(y)", RX_SE_MAX_C))) return rc;
-  if (!same_geom(g, y) || !stats || !mult || !dadd || !m12 || !ws) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: bad arguments");
-  if (out) {
-    if ((rc = check_vec_channels(out, dt, "rx_se_gate_bwd(out)", RX_SE_MAX_C))) return rc;
-    if (!same_geom(out, y)) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: out geometry mismatch");
-  }
+  int rc = check_acts(dt, "rx_se_gate_bwd", y, {{"y", y, true}, {"g", g, true}, {"out", out, false}}, RX_SE_MAX_C);
+  if (rc) return rc;
+  if (!stats || !mult || !dadd || !m12 || !ws) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: bad arguments");
   if (se && (!pooled || !hidden || !gate || !dw1 || !db1 || !dw2 || !db2 || !se->w1 || !se->w2)) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: null SE argument");
   if (se && (se->rd < 1 || se->rd > 64)) RX_FAIL(RX_EUNSUPPORTED, "rx_se_gate_bwd: reduction channels %d outside [1, 64]", se->rd);
   if (ws_bytes < rx_se_workspace(y)) RX_FAIL(RX_EWORKSPACE, "rx_se_gate_bwd: workspace too small");
@@ -704,9 +649,8 @@ extern "C" int rx_se_gate_bwd(rx_dtype dt, const rx_act* g, const rx_act* y, con
   hipStream_t st = (hipStream_t)stream;
   const bool masked = out && slope != 1.f;
   RX_DISPATCH_DTYPE(dt, T, {
-    SeView<T> ov = masked ? se_view<T>(out) : SeView<T>{nullptr, 0, 0};
-    hipLaunchKernelGGL((se_linesum_kernel<T, true>), dim3(p.chunks, p.segs, y->n), dim3(256), 0, st, se_view<T>(y), se_view<T>(g), ov, stats, p.rows,
-                       p.X, y->c, p.rows_per_chunk, slope, part);
+    hipLaunchKernelGGL((se_linesum_kernel<T, true>), dim3(p.chunks, p.segs, y->n), dim3(256), 0, st, make_view<T>(y), make_view<T>(g),
+                       make_view<T>(masked ? out : nullptr), stats, p.rows, p.X, y->c, p.rows_per_chunk, slope, part);
   });
   const size_t lds = (size_t)(3 * C + 64 + 512) * sizeof(float);
   if (se && se->w1 && y->c <= 512 && se->rd <= 32 && se->rd % 4 == 0 && !((uintptr_t)se->w2 & 15))
@@ -732,45 +676,21 @@ extern "C" int rx_instnorm_gate_act_bwd(rx_dtype dt, const rx_act* g, const rx_a
                                         const float* mult, const float* dadd, const float* m12, int keep_x, const rx_act* dy,
                                         const rx_act* d_residual, int accumulate_residual, void* stream) {
   RX_RECORD(stream, [=, g_ = RxActV(g), y_ = RxActV(y), out_ = RxActV(out), dy_ = RxActV(dy), d_residual_ = RxActV(d_residual)](void* s) { return rx_instnorm_gate_act_bwd(dt, g_.p(), y_.p(), stats, out_.p(), slope, mult, dadd, m12, keep_x, dy_.p(), d_residual_.p(), accumulate_residual, s); });
-  int rc;
-  if ((rc = check_vec_channels(g, dt, "rx_instnorm_gate_act_bwd(g)", RX_SE_MAX_C))) return rc;
-  if ((rc = check_vec_channels(y, dt, "rx_instnorm_gate_act_bwd(y)", RX_SE_MAX_C))) return rc;
-  if ((rc = check_vec_channels(dy, dt, "rx_instnorm_gate_act_bwd(dy)", RX_SE_MAX_C))) return rc;
-  if (!same_geom(g, y) || !same_geom(dy, y) || !stats || !mult || !dadd || !m12) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: bad arguments");
-  if (out) {
-    if ((rc = check_vec_channels(out, dt, "rx_instnorm_gate_act_bwd(out)", RX_SE_MAX_C))) return rc;
-    if (!same_geom(out, y)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: out geometry mismatch");
-  }
-  if (d_residual) {
-    if ((rc = check_vec_channels(d_residual, dt, "rx_instnorm_gate_act_bwd(d_residual)", RX_SE_MAX_C))) return rc;
-    if (!same_geom(d_residual, y)) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: d_residual geometry mismatch");
-  }
+  int rc = check_acts(dt, "rx_instnorm_gate_act_bwd", y, {{"y", y, true}, {"g", g, true}, {"dy", dy, true}, {"out", out, false},
+                      {"d_residual", d_residual, false}}, RX_SE_MAX_C);
+  if (rc) return rc;
+  if (!stats || !mult || !dadd || !m12) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: bad arguments");
   const long V = rx_act_voxels(y);
   hipStream_t st = (hipStream_t)stream;
   const int L = keep_x ? y->x : 1;
   const bool masked = out && slope != 1.f;
   RX_DISPATCH_DTYPE(dt, T, {
-    constexpr int P = Elem<T>::PER16;
-    const int CV = y->c / P;
-    long want = (V * CV + 2047) / 2048;
-    int gq = CV;
-    for (int d = 256; gq % 2 == 0 && d > 1; d /= 2) gq /= 2;
-    if (want < 1) want = 1;
-    if (want > 2048) want = 2048;
-    const int G = (int)((want + gq - 1) / gq * gq);
-    SeView<T> ov = masked ? se_view<T>(out) : SeView<T>{nullptr, 0, 0};
-    T* dr = d_residual ? (T*)d_residual->ptr : (T*)nullptr;
-    const int lddr = d_residual ? d_residual->ld : 0;
-    const long sdr = d_residual ? V * d_residual->ld : 0L;
-    if (!d_residual)
-      hipLaunchKernelGGL((in_gate_act_bwd_kernel<T, false, false>), dim3(G, y->n), dim3(256), 0, st, se_view<T>(g), se_view<T>(y), ov, stats, mult, dadd,
-                         m12, L, y->x, (T*)dy->ptr, dy->ld, V * dy->ld, dr, lddr, sdr, (int)V, y->c, slope);
-    else if (accumulate_residual)
-      hipLaunchKernelGGL((in_gate_act_bwd_kernel<T, true, true>), dim3(G, y->n), dim3(256), 0, st, se_view<T>(g), se_view<T>(y), ov, stats, mult, dadd,
-                         m12, L, y->x, (T*)dy->ptr, dy->ld, V * dy->ld, dr, lddr, sdr, (int)V, y->c, slope);
-    else
-      hipLaunchKernelGGL((in_gate_act_bwd_kernel<T, true, false>), dim3(G, y->n), dim3(256), 0, st, se_view<T>(g), se_view<T>(y), ov, stats, mult, dadd,
-                         m12, L, y->x, (T*)dy->ptr, dy->ld, V * dy->ld, dr, lddr, sdr, (int)V, y->c, slope);
+    const int CV = y->c / Elem<T>::PER16, G = sweep_grid(V * CV, CV);
+    const ActView<T> dr = make_view<T>(d_residual);
+    auto kern = !d_residual ? in_gate_act_bwd_kernel<T, false, false>
+                            : (accumulate_residual ? in_gate_act_bwd_kernel<T, true, true> : in_gate_act_bwd_kernel<T, true, false>);
+    hipLaunchKernelGGL(kern, dim3(G, y->n), dim3(256), 0, st, make_view<T>(g), make_view<T>(y), make_view<T>(masked ? out : nullptr), stats, mult,
+                       dadd, m12, L, y->x, (T*)dy->ptr, dy->ld, V * dy->ld, (T*)dr.ptr, dr.ld, dr.sample_stride, (int)V, y->c, slope);
   });
   RX_CHECK_LAUNCH("rx_instnorm_gate_act_bwd");
   return RX_OK;
