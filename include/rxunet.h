@@ -496,6 +496,28 @@ size_t rx_box_stats_workspace(int n_boxes); /* bytes of the device box table, a 
 int rx_box_stats(const void* vol, int dtype, int z, int y, int x, const int32_t* host_boxes, int n_boxes, void* workspace,
                  size_t workspace_bytes, uint64_t* count, int32_t* ext, void* stream);
 
+/* ---- raw patches -> the float32, channel-first training batch (reference dataloading/dataset.py __getitem__: astype(float32), the
+ *      dtype scaling, and transpose(3, 0, 1, 2) of a channels-last normals store; host side dataloading/ingest_device.py).  `in`
+ *      holds `batch` contiguous samples of `dtype` (rx_sw_in_dtype), each (z, y, x) for c == 1 or channels-last (z, y, x, c) for
+ *      1 < c <= 8; `out` is contiguous fp32 (batch, c, z, y, x).  One rule per call, in float32 as numpy evaluates it (true IEEE
+ *      division; the result has the bits of ingest_device.ingest_numpy):
+ *        RX_INGEST_COPY         v                      (a float32 input is copied bit for bit: -0.0, NaN payloads, denormals)
+ *        RX_INGEST_DIV255       v / 255                RX_INGEST_DIV65535     v / 65535
+ *        RX_INGEST_NORMAL_U16   v / 32767.5 - 1        RX_INGEST_NORMAL_MUL2  v * 2 - 1
+ *      Every rule takes every dtype.  One read of the input at its storage width and one fp32 write: 16-byte loads and stores
+ *      between a scalar head and tail per sample (samples need no alignment beyond their element); c > 1 goes through LDS, a
+ *      contiguous run of voxels in, one coalesced run per plane out.  No workspace, no copy, no synchronisation.
+ *      RX_EINVAL before anything is launched: null pointers, in == out, an unknown dtype or rule, non-positive batch or extents,
+ *      c > 8, z * y * x * c >= 2^31, `in` not aligned to its element or `out` not 4-byte aligned. */
+typedef enum {
+  RX_INGEST_COPY = 0,
+  RX_INGEST_DIV255 = 1,
+  RX_INGEST_DIV65535 = 2,
+  RX_INGEST_NORMAL_U16 = 3,
+  RX_INGEST_NORMAL_MUL2 = 4
+} rx_ingest_rule;
+int rx_ingest(const void* in, int dtype, float* out, int batch, int z, int y, int x, int c, int rule, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

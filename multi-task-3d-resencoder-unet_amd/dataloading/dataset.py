@@ -19,7 +19,12 @@ the scaled raw label and leaves the dilation to `dilate_device.DeviceDilate` (th
 
 `dataset_config.patch_search` (absent: `{where: host}`, `find_valid_patches` below) says where the valid-patch search of the
 constructor runs: `device` hands each volume's reference label to `patch_search_device.find_valid_patches_device` (HIP box
-statistics, the same list and the same cache file; no device is an error, not a fallback)."""
+statistics, the same list and the same cache file; no device is an error, not a fallback).
+
+`dataset_config.ingest` (absent: `{where: host}`, every item as described above) says where the float32 conversion, the dtype
+scaling and the channels-last transpose of `__getitem__` run: `device` hands out `torch.from_numpy` of the raw slices -- uint8,
+uint16 or float32, (Z, Y, X) or (Z, Y, X, C), no channel axis added -- and leaves the rest to `ingest_device.DeviceIngest` (the
+trainer reads `device_ingest`, {key: rule}); it needs every host stage that works on scaled floats off or on the device."""
 import json
 import os
 import warnings
@@ -168,6 +173,12 @@ class ZarrSegmentationDataset3D(Dataset):
         # dataset_config.patch_search: where the valid-patch search below runs (the list and the cache file are the same)
         from .patch_search_device import find_valid_patches_device, parse_patch_search
         self.patch_search = parse_patch_search(getattr(mgr, "dataset_config", {}))
+        # dataset_config.ingest: "device" hands out what the store holds; the scaling is the trainer's business (`device_ingest`)
+        from .ingest_device import check_host_stages, parse_ingest
+        self.ingest = parse_ingest(getattr(mgr, "dataset_config", {}))
+        self.device_ingest = None
+        if self.ingest["where"] == "device":
+            check_host_stages(self.augment, self.geometric, self.dilate)
         self.volumes = []
         for vol_idx, info in enumerate(self.volume_paths):
             vd = {"input_path": info["input"], "targets_path": {}, "ref_label_key": info.get("ref_label", "sheet")}
@@ -179,6 +190,8 @@ class ZarrSegmentationDataset3D(Dataset):
                 if str(pth).startswith("http"):
                     raise ValueError(f"remote zarr store {pth}: no network in this environment, mirror it locally")
             self.volumes.append(vd)
+        if self.ingest["where"] == "device":
+            self.device_ingest = self._ingest_rules()
         ps = self.patch_size
         self.cache_file = Path(f"{self.cache_folder}/{self.model_name}_{ps[0]}_{ps[1]}_{ps[2]}_cache.json")
         self.all_valid_patches = []
@@ -201,6 +214,26 @@ class ZarrSegmentationDataset3D(Dataset):
                 with open(self.cache_file, "w") as f:
                     json.dump(self.all_valid_patches, f)
 
+    def _ingest_rules(self):
+        """opens every volume's input and target stores once: {key: rule} for `DeviceIngest`.  One rule and one layout per key, so
+        a key's dtype and dimensionality must agree across volumes."""
+        from .ingest_device import DTYPES, MAX_CHANNELS, ingest_rule
+        seen = {}
+        for vol_idx, vd in enumerate(self.volumes):
+            for key, path in [("image", vd["input_path"]), *vd["targets_path"].items()]:
+                arr = zarr_lite.open(path)
+                dt, nd = np.dtype(arr.dtype), len(arr.shape)
+                if dt not in DTYPES:
+                    raise ValueError(f"dataset_config.ingest.where: device: '{key}' of volume {vol_idx} is {dt} (uint8, uint16 or float32)")
+                if nd != 3 and not (nd == 4 and key.lower() == "normals" and 1 <= arr.shape[3] <= MAX_CHANNELS):
+                    raise ValueError(f"dataset_config.ingest.where: device: '{key}' of volume {vol_idx} has shape {tuple(arr.shape)} "
+                                     f"((Z, Y, X), or channels-last (Z, Y, X, C <= {MAX_CHANNELS}) for normals)")
+                if key in seen and seen[key][:2] != (dt, nd):
+                    raise ValueError(f"dataset_config.ingest.where: device: '{key}' is {seen[key][0]} with {seen[key][1]} dimensions in "
+                                     f"volume {seen[key][2]} and {dt} with {nd} in volume {vol_idx}")
+                seen.setdefault(key, (dt, nd, vol_idx))
+        return {key: ingest_rule(key, dt) for key, (dt, _, _) in seen.items()}
+
     def __len__(self):
         return len(self.all_valid_patches)
 
@@ -210,6 +243,11 @@ class ZarrSegmentationDataset3D(Dataset):
         dz, dy, dx = self.patch_size
         sl = np.s_[z0:z0 + dz, y0:y0 + dy, x0:x0 + dx]
         vd = self.volumes[info["volume_idx"]]
+        if self.device_ingest is not None:      # what the store holds: no astype, no scaling, no transpose, no channel axis
+            item = {"image": torch.from_numpy(np.ascontiguousarray(zarr_lite.open(vd["input_path"])[sl]))}
+            for task, path in vd["targets_path"].items():
+                item[task] = torch.from_numpy(np.ascontiguousarray(zarr_lite.open(path)[sl]))
+            return item
         arr = zarr_lite.open(vd["input_path"])
         img = arr[sl]
         og = img.dtype

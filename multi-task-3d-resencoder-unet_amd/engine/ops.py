@@ -796,6 +796,38 @@ def box_stats(vol, boxes):
         return count.cpu().numpy().view(np.uint64), ext.cpu().numpy()
 
 
+def ingest(tensor, rule, out=None):
+    """raw patches -> the float32 channel-first batch: a uint8, uint16 or float32 device tensor, (B, Z, Y, X) or channels-last
+    (B, Z, Y, X, C) with C <= 8, scaled by `rule` (a name of dataloading.ingest_device.RULES or its code; `ingest_numpy` is the
+    statement) into a new (B, C, Z, Y, X) float32 tensor on the current stream (C = 1 for a 4-D input), or into `out`.  A
+    non-contiguous input is made contiguous first."""
+    from ..dataloading.ingest_device import RULES, rule_code
+    codes = {torch.uint8: _l.RX_SW_U8, torch.float32: _l.RX_SW_F32}
+    if hasattr(torch, "uint16"):
+        codes[torch.uint16] = _l.RX_SW_U16
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise _l.RxError("ingest: the batch must be a device tensor (the host statement is ingest_device.ingest_numpy)")
+    if tensor.dtype not in codes:
+        raise _l.RxError(f"ingest: dtype {tensor.dtype} (uint8, uint16 or float32)")
+    if tensor.dim() not in (4, 5):
+        raise _l.RxError(f"ingest: expected (B, Z, Y, X) or channels-last (B, Z, Y, X, C), got {tuple(tensor.shape)}")
+    try:
+        code = rule_code(rule)
+    except ValueError as e:
+        raise _l.RxError(str(e)) from None
+    src = tensor.contiguous()
+    b, z, y, x = src.shape[:4]
+    c = src.shape[4] if src.dim() == 5 else 1
+    shape = (b, c, z, y, x)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != shape
+          or not out.is_contiguous()):
+        raise _l.RxError(f"ingest: `out` must be a contiguous float32 device tensor of shape {shape}")
+    check(load().rx_ingest(_ptr(src), codes[src.dtype], _ptr(out), b, z, y, x, c, code, stream_ptr()), f"rx_ingest ({RULES[code]})")
+    return out
+
+
 def aug_philox_u32(key, n, device):
     """test hook: the raw Philox4x32-10 outputs behind the noise of voxels 0..n-1 -> int64 tensor of the uint32 values"""
     out = torch.empty(n, dtype=torch.int32, device=device)

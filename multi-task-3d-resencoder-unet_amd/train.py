@@ -88,8 +88,9 @@ class DeviceFeeder:
     `batch["image"].to(device)`, train.py:199-203) the 33.5 MB of a cfg2 batch sit between two steps: 0.7 ms of a 17 ms step with
     the device idle (`scripts/step_timeline.py` on a `--through-trainer` trace: first kernel 707 us after the previous step's last)."""
 
-    def __init__(self, loader, device, augmenter=None, geometry=None, dilate=None):
+    def __init__(self, loader, device, augmenter=None, geometry=None, dilate=None, ingest=None):
         self.loader, self.device = loader, device
+        self.ingest = ingest                # `DeviceIngest`: raw batches are copied in the store's dtype and scaled here, first
         self.dilate = dilate                # `DeviceDilate`: the label targets, in place, before geometry (the host order)
         self.augmenter = augmenter          # `DeviceAugmenter`: applied on the copy stream, under the running step like the copies
         self.geometry = geometry            # `DeviceGeometry`: the whole staged dict, before the image augmenter
@@ -106,9 +107,14 @@ class DeviceFeeder:
         except StopIteration:
             return None
         with torch.cuda.stream(self.stream):
-            dev = {k: v.to(self.device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
+            if self.ingest is not None:     # integers over the link, float32 (B, C, Z, Y, X) from one HIP pass per tensor
+                dev = {k: v.to(self.device, non_blocking=True) for k, v in batch.items()}
+            else:
+                dev = {k: v.to(self.device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
             if self.ring is not None:
                 self.ring.copied()          # (records on the copy stream: the pinned slot is free once THESE copies are done)
+            if self.ingest is not None:
+                dev = self.ingest(dev)
             if self.dilate is not None:
                 dev = self.dilate(dev)
             if self.geometry is not None:
@@ -303,10 +309,21 @@ class BaseTrainer:
             from .dataloading.dilate_device import DeviceDilate
             dilate = DeviceDilate(dil_cfg["keys"], dil_cfg["radius"])
         self.device_dilate = dilate
+        # dataset_config.ingest.where: device -- the dataset hands out what the store holds (uint8 / uint16 / float32, normals
+        # channels-last); the float32 conversion, the scaling and the transpose run as one HIP pass per tensor, in the same two
+        # places and first, so that dilation, geometry and the intensity stack see exactly the tensors they see today
+        ingest = None
+        ing_rules = getattr(dataset, "device_ingest", None)
+        if ing_rules is not None:
+            from .dataloading.ingest_device import DeviceIngest
+            ingest = DeviceIngest(ing_rules)
+        self.device_ingest = ingest
 
         def forward_loss(batch, train_mode):
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
-            if (dilate is not None or geometry is not None) and not staged:
+            if ingest is not None and not staged:    # each tensor in its own dtype; from here on the batch is what `where: host` gives
+                batch = ingest({k: v.to(device, non_blocking=True) for k, v in batch.items()})
+            if (dilate is not None or geometry is not None) and not staged:      # (after ingest: fresh device tensors already)
                 batch = {k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
                 if dilate is not None:      # (the copies above are fresh device tensors: dilating them in place touches nothing else)
                     batch = dilate(batch)
@@ -339,7 +356,7 @@ class BaseTrainer:
             steps, patches = 0, 0
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
-            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry, dilate=dilate)
+            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry, dilate=dilate, ingest=ingest)
                       if device.type == "cuda" and os.environ.get("RX_DEVICE_FEEDER", "1") != "0" else train_loader)
             for i, batch in enumerate(feeder):
                 if i >= self.mgr.max_steps_per_epoch:
