@@ -518,6 +518,32 @@ typedef enum {
 } rx_ingest_rule;
 int rx_ingest(const void* in, int dtype, float* out, int batch, int z, int y, int x, int c, int rule, void* stream);
 
+/* ---- rotation and isotropic scaling about the patch centre on the device, with the vector rule of a 3-component field (the
+ *      continuous counterpart of rx_geom_apply; host side dataloading/spatial_device.py, whose affine_numpy is the statement).
+ *      One resampling pass per tensor.  For output voxel o of sample b, per axis d in (z, y, x), all in float32, one rounding per
+ *      operation, nothing contracted into an fma, denormals kept:
+ *        c_d = (float)(n_d - 1) * 0.5          t_d = (float)o_d - c_d
+ *        p_d = ((point[3d] * t_z + point[3d+1] * t_y) + point[3d+2] * t_x) + c_d
+ *      RX_AFFINE_LINEAR:  i_d = floor(p_d), f_d = p_d - i_d, the eight corners i and i + 1, lerp(a, b, f) = a + f * (b - a) along
+ *                         x, then y, then z.      RX_AFFINE_NEAREST: the source index is floor(p_d + 0.5).
+ *      RX_AFFINE_CONSTANT: a corner / source voxel with an index outside [0, n_d - 1] has the value `fill`;
+ *      RX_AFFINE_CLAMP:    its index is clamped to [0, n_d - 1].
+ *      `vector` != 0 (needs c == 3): with s the three sampled components, out_k = (vector[3k] * s_0 + vector[3k+1] * s_1) +
+ *      vector[3k+2] * s_2; otherwise channels are sampled one by one.  All channels of a sample share one set of coordinates. */
+typedef enum { RX_AFFINE_LINEAR = 0, RX_AFFINE_NEAREST = 1 } rx_affine_interp;
+typedef enum { RX_AFFINE_CONSTANT = 0, RX_AFFINE_CLAMP = 1 } rx_affine_border;
+typedef struct {      /* one sample's transform, 72 bytes */
+  float point[9];     /* row-major 3 x 3, (z, y, x) axis order: output voxel offsets from the centre -> input voxel offsets */
+  float vector[9];    /* row-major 3 x 3, component order: the rotation of a vector tensor's three channels           */
+} rx_affine_sample;
+/* in / out: contiguous fp32 (batch, c, z, y, x), distinct buffers.  `host_table`: `batch` records in HOST memory, read during
+ * the call and handed to the kernels by value (16 samples per launch): no device table, copy, allocation or synchronisation.
+ * No load leaves a sample, whatever the matrices hold.  RX_EINVAL before anything is launched: null pointers, in == out, an
+ * unknown interp or border, vector with c != 3, a matrix entry that is not finite, z * y * x >= 2^31, z or y > 65535,
+ * x > 2^24 (float32 coordinates), c > 4095.  One write of the tensor; every source voxel a brick needs is read through L1 / L2. */
+int rx_affine_apply(const float* in, float* out, int batch, int c, int z, int y, int x, const rx_affine_sample* host_table,
+                    int interp, int border, float fill, int vector, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,11 @@ and keep a normals target consistent (`geometry_device.py`): `where: device` lea
 radius: 5}`, the reference's behaviour) says where: `host` is scipy's `binary_dilation` inside `__getitem__`, `device` hands out
 the scaled raw label and leaves the dilation to `dilate_device.DeviceDilate` (the trainer reads `device_dilate`).
 
+`dataset_config.spatial` (absent: off) adds small-angle rotation and mild isotropic scaling about the patch centre, image and
+targets together, a normals target turned with them (`spatial_device.py`): `where: device` leaves the items alone and exposes
+`device_spatial` (the trainer applies `DeviceSpatial` to the staged batch, after geometry), `where: host` draws one op per item
+and runs `affine_numpy` inside `__getitem__`, after the host geometric classes and before the intensity stack.
+
 `dataset_config.patch_search` (absent: `{where: host}`, `find_valid_patches` below) says where the valid-patch search of the
 constructor runs: `device` hands each volume's reference label to `patch_search_device.find_valid_patches_device` (HIP box
 statistics, the same list and the same cache file; no device is an error, not a fallback).
@@ -57,6 +62,12 @@ class SyntheticPatchDataset(Dataset):
         self.geometric = parse_geometric(mgr.dataset_config, self.patch, self.tasks)
         if self.geometric is not None and self.geometric["where"] != "device":
             raise ValueError("dataset_config.geometric.where: \"host\" is served by the zarr dataset; synthetic patches take \"device\"")
+        # dataset_config.spatial: "device" is the trainer's business (`device_spatial`); "host" resamples every item handed out,
+        # one draw per item from `spatial_rng` (None: the `random` module, which a DataLoader seeds per worker)
+        from .spatial_device import parse_spatial
+        self.spatial = parse_spatial(mgr.dataset_config, self.patch, self.tasks)
+        self.device_spatial = self.spatial if self.spatial is not None and self.spatial["where"] == "device" else None
+        self.spatial_rng, self.last_spatial_op = None, None
 
     def __len__(self):
         return self.length
@@ -66,8 +77,13 @@ class SyntheticPatchDataset(Dataset):
             key = int(idx) % self.pool
             if key not in self._cache:
                 self._cache[key] = self._make(key)
-            return dict(self._cache[key])
-        return self._make(idx)
+            return self._host_spatial(dict(self._cache[key]))
+        return self._host_spatial(self._make(idx))
+
+    def _host_spatial(self, item):
+        if self.spatial is None or self.spatial["where"] != "host":
+            return item
+        return _host_spatial(self, item)
 
     def _make(self, idx):
         g = torch.Generator().manual_seed(self.seed + int(idx))
@@ -81,6 +97,18 @@ class SyntheticPatchDataset(Dataset):
             else:
                 item[name] = seg.expand(c, *self.patch).contiguous()
         return item
+
+
+def _host_spatial(ds, item):
+    """`dataset_config.spatial.where: host`: one draw per item, `affine_numpy` on every array of it (an identity draw: untouched)"""
+    import random
+    from .spatial_device import apply_item_numpy, draw_affine
+    cfg = ds.spatial
+    op = draw_affine(ds.spatial_rng if ds.spatial_rng is not None else random, cfg["rotation"], cfg["scale"])
+    ds.last_spatial_op = op
+    if op.is_identity():
+        return item
+    return apply_item_numpy(op, item, cfg["normal_keys"], cfg["image_border"])
 
 
 def find_label_bounding_box(arr, chunk_shape=(192, 192, 192)):
@@ -179,6 +207,13 @@ class ZarrSegmentationDataset3D(Dataset):
         self.device_ingest = None
         if self.ingest["where"] == "device":
             check_host_stages(self.augment, self.geometric, self.dilate)
+        # dataset_config.spatial: "device" is the trainer's business (`device_spatial`); "host" resamples in __getitem__ and needs
+        # scaled float items with their labels already dilated
+        from .spatial_device import check_host_spatial, parse_spatial
+        self.spatial = parse_spatial(getattr(mgr, "dataset_config", {}), self.patch_size, self.tasks)
+        check_host_spatial(self.spatial, self.ingest, self.dilate)
+        self.device_spatial = self.spatial if self.spatial is not None and self.spatial["where"] == "device" else None
+        self.spatial_rng, self.last_spatial_op = None, None
         self.volumes = []
         for vol_idx, info in enumerate(self.volume_paths):
             vd = {"input_path": info["input"], "targets_path": {}, "ref_label_key": info.get("ref_label", "sheet")}
@@ -275,6 +310,8 @@ class ZarrSegmentationDataset3D(Dataset):
             item[task] = t
         for transform in self._host_geometry:      # image and targets together; (Z, Y, X) and (C, Z, Y, X) arrays alike
             item = transform(item)
+        if self.spatial is not None and self.spatial["where"] == "host":      # after the signed permutations, before the intensity stack
+            item = _host_spatial(self, item)
         if self.augment:              # image only; targets untouched (dataset.py:200-205)
             from .augment import augment_image
             item["image"] = augment_image(item["image"])

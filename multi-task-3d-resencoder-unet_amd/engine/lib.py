@@ -23,6 +23,8 @@ RX_AUG_MAX_K, RX_AUG_MAX_BOXES = 21, 4
 RX_LOSS_BCE_LOGITS, RX_LOSS_BCE_PROB, RX_LOSS_MSE = 0, 1, 2
 RX_REDUCE_MEAN, RX_REDUCE_SUM = 0, 1
 RX_INGEST_COPY, RX_INGEST_DIV255, RX_INGEST_DIV65535, RX_INGEST_NORMAL_U16, RX_INGEST_NORMAL_MUL2 = 0, 1, 2, 3, 4
+RX_AFFINE_LINEAR, RX_AFFINE_NEAREST = 0, 1
+RX_AFFINE_CONSTANT, RX_AFFINE_CLAMP = 0, 1
 
 
 class RxError(RuntimeError):
@@ -162,6 +164,7 @@ _SIGNATURES = {
     "rx_box_stats_workspace": (c_size_t, [c_int]),
     "rx_box_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "rx_ingest": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "rx_affine_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
 }
 
 _lib = None

@@ -736,6 +736,43 @@ def geom_apply(tensor, geom_ops, vector):
     return out
 
 
+def affine_table(affine_ops):
+    """`affine_ops`: one record per sample -- objects with `.row()` (dataloading.spatial_device.AffineOp) or 18 numbers (point,
+    then vector, row-major), or a (B, 18) array -> the (B, 18) float32 host image of `rx_affine_sample`"""
+    if isinstance(affine_ops, np.ndarray):
+        rows = affine_ops
+    else:
+        rows = [o.row() if hasattr(o, "row") else o for o in affine_ops]
+    return np.ascontiguousarray(np.asarray(rows, dtype=np.float32).reshape(len(rows), 18))
+
+
+def affine_apply(tensor, table, interp, border, fill=0.0, vector=False, out=None):
+    """rotation / scaling of a float32 (B, C, Z, Y, X) device batch, one record of `table` (`affine_table`, or what it takes) per
+    sample -> a new batch on the current stream, or `out` (a distinct contiguous float32 tensor of the same shape).  `interp`:
+    "linear" | "nearest"; `border`: "constant" (outside voxels are `fill`) | "clamp"; `vector`: the three channels are a vector
+    field and are turned by the records' `vector` matrices.  dataloading.spatial_device.affine_numpy is the statement."""
+    from ..dataloading.spatial_device import BORDER, INTERP
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise _l.RxError("affine_apply: the batch must be a device tensor (the host path is spatial_device.affine_numpy)")
+    if tensor.dim() != 5 or tensor.dtype != torch.float32:
+        raise _l.RxError(f"affine_apply: expected a float32 (B, C, Z, Y, X) batch, got {tensor.dtype} {tuple(tensor.shape)}")
+    if interp not in INTERP or border not in BORDER:
+        raise _l.RxError(f"affine_apply: interp {interp!r} (linear, nearest), border {border!r} (constant, clamp)")
+    src = tensor.contiguous()
+    table = affine_table(table)
+    b, c, z, y, x = src.shape
+    if table.shape[0] != b:
+        raise _l.RxError(f"affine_apply: {table.shape[0]} records for a batch of {b}")
+    if out is None:
+        out = torch.empty_like(src)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.shape != src.shape
+          or not out.is_contiguous()):
+        raise _l.RxError(f"affine_apply: `out` must be a contiguous float32 device tensor of shape {tuple(src.shape)}")
+    check(load().rx_affine_apply(_ptr(src), _ptr(out), b, c, z, y, x, table.ctypes.data, INTERP[interp], BORDER[border], float(fill),
+                                 1 if vector else 0, stream_ptr()), "rx_affine_apply")
+    return out
+
+
 def label_dilate(tensor, radius=5, out=None):
     """binary dilation with the ball of `radius` (1..8) of a float32 (B, C, Z, Y, X) device batch, every (sample, channel) volume
     on its own: 1.0 where a voxel > 0 lies within the radius, else 0.0 (dataloading.dilate_device.dilate_numpy is the statement).

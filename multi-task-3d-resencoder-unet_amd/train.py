@@ -88,12 +88,13 @@ class DeviceFeeder:
     `batch["image"].to(device)`, train.py:199-203) the 33.5 MB of a cfg2 batch sit between two steps: 0.7 ms of a 17 ms step with
     the device idle (`scripts/step_timeline.py` on a `--through-trainer` trace: first kernel 707 us after the previous step's last)."""
 
-    def __init__(self, loader, device, augmenter=None, geometry=None, dilate=None, ingest=None):
+    def __init__(self, loader, device, augmenter=None, geometry=None, dilate=None, ingest=None, spatial=None):
         self.loader, self.device = loader, device
         self.ingest = ingest                # `DeviceIngest`: raw batches are copied in the store's dtype and scaled here, first
         self.dilate = dilate                # `DeviceDilate`: the label targets, in place, before geometry (the host order)
         self.augmenter = augmenter          # `DeviceAugmenter`: applied on the copy stream, under the running step like the copies
         self.geometry = geometry            # `DeviceGeometry`: the whole staged dict, before the image augmenter
+        self.spatial = spatial              # `DeviceSpatial`: the whole staged dict, after geometry (the host order)
         self.stream = torch.cuda.Stream(device)
         ring = getattr(loader, "collate_fn", None)
         self.ring = ring if isinstance(ring, PinnedRingCollate) else None
@@ -119,6 +120,8 @@ class DeviceFeeder:
                 dev = self.dilate(dev)
             if self.geometry is not None:
                 dev = self.geometry(dev)
+            if self.spatial is not None:
+                dev = self.spatial(dev)
             if self.augmenter is not None:
                 dev["image"] = self.augmenter(dev["image"])
             ev = torch.cuda.Event()
@@ -301,6 +304,15 @@ class BaseTrainer:
             from .dataloading.geometry_device import DeviceGeometry
             geometry = DeviceGeometry(flip=geo_cfg["flip"], rot90=geo_cfg["rot90"], normal_keys=geo_cfg["normal_keys"], rank=self.rank)
         self.device_geometry = geometry
+        # dataset_config.spatial with where: device -- rotation / scaling of image AND targets (normals turned by the vector rule)
+        # as one HIP resampling pass per tensor, in the same two places, after geometry and before the intensity stack
+        spatial = None
+        spa_cfg = getattr(dataset, "device_spatial", None)
+        if spa_cfg is not None:
+            from .dataloading.spatial_device import DeviceSpatial
+            spatial = DeviceSpatial(rotation=spa_cfg["rotation"], scale=spa_cfg["scale"], normal_keys=spa_cfg["normal_keys"],
+                                    image_border=spa_cfg["image_border"], rank=self.rank)
+        self.device_spatial = spatial
         # tr_setup.dilate_label with dataset_config.dilate.where: device -- the dataset hands out raw labels and the ball dilation
         # runs as a HIP pass on the targets, in the same two places and before geometry (the host order; the stages commute)
         dilate = None
@@ -323,12 +335,14 @@ class BaseTrainer:
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
             if ingest is not None and not staged:    # each tensor in its own dtype; from here on the batch is what `where: host` gives
                 batch = ingest({k: v.to(device, non_blocking=True) for k, v in batch.items()})
-            if (dilate is not None or geometry is not None) and not staged:      # (after ingest: fresh device tensors already)
+            if (dilate is not None or geometry is not None or spatial is not None) and not staged:      # (after ingest: fresh device tensors already)
                 batch = {k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
                 if dilate is not None:      # (the copies above are fresh device tensors: dilating them in place touches nothing else)
                     batch = dilate(batch)
                 if geometry is not None:
                     batch = geometry(batch)
+                if spatial is not None:
+                    batch = spatial(batch)
             x = batch["image"].to(device, dtype=torch.float32, non_blocking=True)
             if augmenter is not None and not staged:
                 x = augmenter(x)
@@ -356,7 +370,7 @@ class BaseTrainer:
             steps, patches = 0, 0
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
-            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry, dilate=dilate, ingest=ingest)
+            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry, dilate=dilate, ingest=ingest, spatial=spatial)
                       if device.type == "cuda" and os.environ.get("RX_DEVICE_FEEDER", "1") != "0" else train_loader)
             for i, batch in enumerate(feeder):
                 if i >= self.mgr.max_steps_per_epoch:
