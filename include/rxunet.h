@@ -56,7 +56,9 @@ typedef struct {
 int rx_abi_version(void);
 const char* rx_last_error(void);
 int rx_device_arch_ok(void); /* 1 iff the current device is gfx950 */
-/* name of the kernel instantiation the last conv / convT entry point of this thread launched (bench attribution) */
+/* name of the kernel instantiation the last conv / convT entry point of this thread launched (bench attribution), or of
+ * the gate kernel the last rx_se_gate_fwd / rx_se_gate_bwd chose (se_gate_fwd_kernel, se_fill_mult_kernel,
+ * se_gate_bwd_small_kernel, se_gate_bwd_kernel) */
 const char* rx_last_conv_kernel(void);
 
 /* ---- parameter packing ------------------------------------------------------------------ */

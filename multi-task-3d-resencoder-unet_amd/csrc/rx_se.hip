@@ -584,6 +584,7 @@ extern "C" int rx_se_gate_fwd(rx_dtype dt, const rx_act* y, const float* stats, 
     const int L = y->x;   // mult is laid out [n][x][c] like the SE case (keep_x = 1)
     const long total = (long)y->n * L * y->c;
     hipLaunchKernelGGL(se_fill_mult_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, path_scale, L * y->c, total, mult);
+    rx_note_kernel("se_fill_mult_kernel");
     RX_CHECK_LAUNCH("rx_se_gate_fwd(fill)");
     return RX_OK;
   }
@@ -601,6 +602,7 @@ extern "C" int rx_se_gate_fwd(rx_dtype dt, const rx_act* y, const float* stats, 
   const size_t lds = (size_t)(y->c + 64 + 256) * sizeof(float);
   hipLaunchKernelGGL(se_gate_fwd_kernel, dim3(p.L, y->n), dim3(256), lds, st, (const float*)part, p.chunks, p.X, y->c, se->keep_x, p.R, stats,
                      path_scale, se->w1, se->b1, se->w2, se->b2, se->rd, pooled, hidden, gate, mult);
+  rx_note_kernel("se_gate_fwd_kernel");
   RX_CHECK_LAUNCH("rx_se_gate_fwd");
   return RX_OK;
 }
@@ -631,6 +633,7 @@ extern "C" int rx_se_gate_bwd(rx_dtype dt, const rx_act* g, const rx_act* y, con
   int rc = check_acts(dt, "rx_se_gate_bwd", y, {{"y", y, true}, {"g", g, true}, {"out", out, false}}, RX_SE_MAX_C);
   if (rc) return rc;
   if (!stats || !mult || !dadd || !m12 || !ws) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: bad arguments");
+  if (slope != 1.f && !out) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: slope %g without `out`: a gated block's LeakyReLU mask needs the saved output", (double)slope);
   if (se && (!pooled || !hidden || !gate || !dw1 || !db1 || !dw2 || !db2 || !se->w1 || !se->w2)) RX_FAIL(RX_EINVAL, "rx_se_gate_bwd: null SE argument");
   if (se && (se->rd < 1 || se->rd > 64)) RX_FAIL(RX_EUNSUPPORTED, "rx_se_gate_bwd: reduction channels %d outside [1, 64]", se->rd);
   if (ws_bytes < rx_se_workspace(y)) RX_FAIL(RX_EWORKSPACE, "rx_se_gate_bwd: workspace too small");
@@ -653,7 +656,9 @@ extern "C" int rx_se_gate_bwd(rx_dtype dt, const rx_act* g, const rx_act* y, con
                        make_view<T>(masked ? out : nullptr), stats, p.rows, p.X, y->c, p.rows_per_chunk, slope, part);
   });
   const size_t lds = (size_t)(3 * C + 64 + 512) * sizeof(float);
-  if (se && se->w1 && y->c <= 512 && se->rd <= 32 && se->rd % 4 == 0 && !((uintptr_t)se->w2 & 15))
+  const bool small = se && se->w1 && y->c <= 512 && se->rd <= 32 && se->rd % 4 == 0 && !((uintptr_t)se->w2 & 15);
+  rx_note_kernel(small ? "se_gate_bwd_small_kernel" : "se_gate_bwd_kernel");
+  if (small)
     hipLaunchKernelGGL(se_gate_bwd_small_kernel, dim3(p.L, y->n), dim3(256), lds, st, (const float*)part, p.chunks, p.X, y->c, keep_x, p.R, path_scale,
                      se ? se->w1 : (const float*)nullptr, se ? se->w2 : (const float*)nullptr, se ? se->rd : 0, pooled, hidden, gate, mult, dadd, dz2,
                      dhm, line_m);
@@ -680,6 +685,7 @@ extern "C" int rx_instnorm_gate_act_bwd(rx_dtype dt, const rx_act* g, const rx_a
                       {"d_residual", d_residual, false}}, RX_SE_MAX_C);
   if (rc) return rc;
   if (!stats || !mult || !dadd || !m12) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: bad arguments");
+  if (slope != 1.f && !out) RX_FAIL(RX_EINVAL, "rx_instnorm_gate_act_bwd: slope %g without `out`: a gated block's LeakyReLU mask needs the saved output", (double)slope);
   const long V = rx_act_voxels(y);
   hipStream_t st = (hipStream_t)stream;
   const int L = keep_x ? y->x : 1;

@@ -140,12 +140,13 @@ def child(path):
                     ops.instnorm_gate_act_fwd(y, stats, mult, keep_x, o, 0.01, r)
                     put(f"{tag} gate_act_fwd keep_x={keep_x} se={with_se} res={r is not None}", o)
                 for oo in (None, o):
-                    ops.se_gate_bwd(g, y, stats, oo, 0.01, se, pooled, hidden, gate, mult, dadd, m12g, *grads, path_scale=scale)
+                    sl = 0.01 if oo is not None else 1.0      # a gated block's mask needs the saved output: without it only slope 1
+                    ops.se_gate_bwd(g, y, stats, oo, sl, se, pooled, hidden, gate, mult, dadd, m12g, *grads, path_scale=scale)
                     put(f"{tag} se_gate_bwd keep_x={keep_x} se={with_se} out={oo is not None}", dadd, m12g, *([t for t in grads] if with_se else []))
                     for dres_mode in ("absent", "written", "accumulated"):
                         dy = like(y)
                         dr = None if dres_mode == "absent" else like(y, 0.25)
-                        ops.instnorm_gate_act_bwd(g, y, stats, oo, 0.01, mult, dadd, m12g, keep_x, dy, dr, dres_mode == "accumulated")
+                        ops.instnorm_gate_act_bwd(g, y, stats, oo, sl, mult, dadd, m12g, keep_x, dy, dr, dres_mode == "accumulated")
                         put(f"{tag} gate_act_bwd keep_x={keep_x} se={with_se} out={oo is not None} dres={dres_mode}", dy,
                             *([dr] if dr is not None else []))
     with open(path, "w") as f:
