@@ -546,6 +546,39 @@ typedef struct {      /* one sample's transform, 72 bytes */
 int rx_affine_apply(const float* in, float* out, int batch, int c, int z, int y, int x, const rx_affine_sample* host_table,
                     int interp, int border, float fill, int vector, void* stream);
 
+/* ---- validation metrics on the device (host side training/metrics/metrics.py, whose seg_counts_numpy, class_counts_numpy and
+ *      normal_stats_numpy are the statements).  Operands are contiguous (n, c, v) device arrays: `pred` of `pred_dtype` (rx_dtype),
+ *      aligned to its element, `target` fp32, 4-byte aligned (a base that is not 16-byte aligned is fine).  Every entry point ADDS
+ *      into its output buffers: the caller zeroes them once and accumulates over as many calls as it likes, with no extra kernel
+ *      and no synchronisation.  One read of each operand: a row is a scalar head up to the first 16-byte boundary of the
+ *      prediction, 16-byte vectors, a scalar tail; nothing outside [0, v) of a row is read; voxel offsets are 64-bit.  Integer
+ *      results are reduced per lane, wave and workgroup, then merged with one 64-bit atomic add per workgroup and output word, so
+ *      they do not depend on arrival order.  RX_EINVAL before anything is launched, for all of them: null pointers, non-positive
+ *      n / c / v, an unknown dtype, a misaligned pointer.
+ *      rx_seg_counts: binary confusion per (sample, channel).  Predicted positive is pred > thr_pred, labelled positive is
+ *        target > thr_target, both IEEE float32 comparisons (a NaN is negative; a NaN threshold is RX_EINVAL).
+ *        counts: int64 (n, c, 3) = (TP, FP, FN); TN is v minus their sum.
+ *      rx_class_counts: multi-class confusion by arg-max over the c channels, 2 <= c <= 64 (else RX_EINVAL).  The predicted class
+ *        is best = 0; for k = 1 .. c-1: if x[k] > x[best], or x[best] is a NaN and x[k] is not: best = k -- the first maximum wins
+ *        and a NaN is never chosen over a number.  The label is the same rule on the fp32 target_prob (n, c, v), or
+ *        target_index int64 (n, v), 8-byte aligned; exactly one of the two is non-null.  Voxels whose index equals ignore_index,
+ *        or is no class at all (outside [0, c)), are skipped.  counts: int64 (n, c, 3) = per-class (TP, FP, FN): a voxel with
+ *        label l predicted as p adds TP[l] if p == l, else FP[p] and FN[l].
+ *      rx_normal_stats: 3-channel vector fields (n, 3, v).  In float32, one rounding per operation: the mask is
+ *        sqrt((tx*tx + ty*ty) + tz*tz) > 1e-6 (the mask of MaskedCosineLoss); per masked voxel
+ *        cos = dot / (max(|p|, 1e-8) * max(|t|, 1e-8)) clamped to [-1, 1], deg = acos(cos) * (180 / pi).
+ *        count: int64 (n) += the masked voxels; sums: float64 (n, 2) += (sum of cos, sum of deg).  The float sums never go
+ *        through an atomic: per-workgroup fp64 partials in `ws` (8-byte aligned), then a finalize that adds a sample's partials in
+ *        index order, so two runs on the same input give the same bits.  RX_EWORKSPACE: ws_bytes below
+ *        rx_normal_stats_workspace(n, v). */
+int rx_seg_counts(const void* pred, int pred_dtype, const float* target, int n, int c, long v, float thr_pred, float thr_target,
+                  int64_t* counts, void* stream);
+int rx_class_counts(const void* pred, int pred_dtype, const float* target_prob, const int64_t* target_index, int64_t ignore_index,
+                    int n, int c, long v, int64_t* counts, void* stream);
+size_t rx_normal_stats_workspace(int n, long v); /* bytes of partials (0 for non-positive arguments) */
+int rx_normal_stats(const void* pred, int pred_dtype, const float* target, int n, long v, int64_t* count, double* sums, void* ws,
+                    size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,10 @@ _SIGNATURES = {
     "rx_box_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "rx_ingest": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rx_affine_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
+    "rx_seg_counts": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_long, c_float, c_float, c_void_p, c_void_p]),
+    "rx_class_counts": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "rx_normal_stats_workspace": (c_size_t, [c_int, c_long]),
+    "rx_normal_stats": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

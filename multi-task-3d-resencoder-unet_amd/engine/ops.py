@@ -865,6 +865,96 @@ def ingest(tensor, rule, out=None):
     return out
 
 
+# ---- validation metrics (training/metrics/metrics.py holds the numpy statements and `ValidationMetrics`) --------------------------
+def _metric_pred(fn, pred, min_dim=3):
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        raise _l.RxError(f"{fn}: the prediction must be a device tensor (the host statement is training.metrics.{fn}_numpy)")
+    if pred.dtype not in _l.DTYPE_CODE:
+        raise _l.RxError(f"{fn}: prediction dtype {pred.dtype} (float32, bfloat16 or float16)")
+    if pred.dim() < min_dim or pred.numel() == 0:
+        raise _l.RxError(f"{fn}: expected a non-empty (N, C, *spatial) prediction, got {tuple(pred.shape)}")
+    return pred.contiguous()
+
+
+def _metric_f32_target(fn, pred, target):
+    if not isinstance(target, torch.Tensor) or target.device != pred.device:
+        raise _l.RxError(f"{fn}: the target must be a tensor on the prediction's device")
+    if target.dtype != torch.float32:
+        raise _l.RxError(f"{fn}: target dtype {target.dtype} (float32)")
+    if target.shape != pred.shape:
+        raise _l.RxError(f"{fn}: target shape {tuple(target.shape)} against prediction shape {tuple(pred.shape)}")
+    return target.contiguous()
+
+
+def _metric_out(fn, name, out, shape, dtype, device):
+    if out is None:
+        return torch.zeros(shape, dtype=dtype, device=device)
+    if (not isinstance(out, torch.Tensor) or out.device != device or out.dtype != dtype or tuple(out.shape) != tuple(shape)
+            or not out.is_contiguous()):
+        raise _l.RxError(f"{fn}: `{name}` must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
+def seg_counts(pred, target, thr_pred=0.5, thr_target=0.5, out=None):
+    """binary confusion per (sample, channel) of a float32 / bfloat16 / float16 (N, C, *spatial) device prediction against a float32
+    target of the same shape: int64 (N, C, 3) = (TP, FP, FN) of `pred > thr_pred` against `target > thr_target`, float32 compares,
+    a NaN is negative (training.metrics.seg_counts_numpy is the statement).  ADDED into `out` when given (the caller zeroes it),
+    else returned in a fresh zeroed tensor; on the current stream, no synchronisation."""
+    p = _metric_pred("seg_counts", pred, 2)
+    t = _metric_f32_target("seg_counts", p, target)
+    n, c, v = _ncv(p)
+    out = _metric_out("seg_counts", "out", out, (n, c, 3), torch.int64, p.device)
+    timed_bytes("seg_counts", p.numel() * (p.element_size() + 4),
+                lambda: check(load().rx_seg_counts(_ptr(p), _code(p.dtype), _ptr(t), n, c, v, float(thr_pred), float(thr_target), _ptr(out),
+                                                   stream_ptr()), "rx_seg_counts"))
+    return out
+
+
+def class_counts(pred, target, ignore_index=-100, out=None):
+    """multi-class confusion by arg-max over the 2..64 channels of an (N, C, *spatial) device prediction; `target` is float32 class
+    probabilities of the same shape or int64 class indices (N, *spatial), where `ignore_index` voxels are skipped: int64 (N, C, 3)
+    = per-class (TP, FP, FN) (training.metrics.class_counts_numpy is the statement).  ADDED into `out` when given."""
+    p = _metric_pred("class_counts", pred)
+    n, c, v = _ncv(p)
+    if isinstance(target, torch.Tensor) and target.dtype == torch.int64:
+        if target.device != p.device or tuple(target.shape) != (n,) + tuple(p.shape[2:]):
+            raise _l.RxError(f"class_counts: index target {tuple(target.shape)} on {target.device} against prediction {tuple(p.shape)} "
+                             f"on {p.device}")
+        tp, ti, tbytes = None, target.contiguous(), n * v * 8
+    else:
+        tp, ti, tbytes = _metric_f32_target("class_counts", p, target), None, p.numel() * 4
+    out = _metric_out("class_counts", "out", out, (n, c, 3), torch.int64, p.device)
+    timed_bytes("class_counts", p.numel() * p.element_size() + tbytes,
+                lambda: check(load().rx_class_counts(_ptr(p), _code(p.dtype), _ptr(tp), _ptr(ti), int(ignore_index), n, c, v, _ptr(out),
+                                                     stream_ptr()), "rx_class_counts"))
+    return out
+
+
+def normal_stats(pred, target, out=None, ws=None):
+    """angular agreement of a 3-channel (N, 3, *spatial) device prediction with a float32 target over the voxels where |target| >
+    1e-6: (count int64 (N,), sums float64 (N, 2) = (sum of cos, sum of the angle in degrees)), float32 per voxel, float64 sums in a
+    fixed order (training.metrics.normal_stats_numpy is the statement).  ADDED into `out=(count, sums)` when given.  `ws`: a float64
+    device tensor of at least `rx_normal_stats_workspace(N, V) / 8` elements for the partials, else one is taken from the allocator."""
+    p = _metric_pred("normal_stats", pred)
+    t = _metric_f32_target("normal_stats", p, target)
+    n, c, v = _ncv(p)
+    if c != 3:
+        raise _l.RxError(f"normal_stats: expected 3 channels, got {tuple(p.shape)}")
+    if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+        raise _l.RxError("normal_stats: `out` must be the pair (count, sums)")
+    count = _metric_out("normal_stats", "out[0]", None if out is None else out[0], (n,), torch.int64, p.device)
+    sums = _metric_out("normal_stats", "out[1]", None if out is None else out[1], (n, 2), torch.float64, p.device)
+    nbytes = load().rx_normal_stats_workspace(n, v)
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=p.device)
+    elif not isinstance(ws, torch.Tensor) or ws.device != p.device or ws.dtype != torch.float64 or not ws.is_contiguous():
+        raise _l.RxError(f"normal_stats: `ws` must be a contiguous float64 tensor on {p.device}")
+    timed_bytes("normal_stats", p.numel() * (p.element_size() + 4),
+                lambda: check(load().rx_normal_stats(_ptr(p), _code(p.dtype), _ptr(t), n, v, _ptr(count), _ptr(sums), _ptr(ws), ws.numel() * 8,
+                                                     stream_ptr()), "rx_normal_stats"))
+    return count, sums
+
+
 def aug_philox_u32(key, n, device):
     """test hook: the raw Philox4x32-10 outputs behind the noise of voxels 0..n-1 -> int64 tensor of the uint32 values"""
     out = torch.empty(n, dtype=torch.int32, device=device)

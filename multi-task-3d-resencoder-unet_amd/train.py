@@ -14,7 +14,10 @@ CosineAnnealingLR stepped per epoch, final `<model_name>_final.pth`).  Differenc
   * launched under `torch.distributed.run` it becomes data parallel (RCCL all-reduce overlapped with backward,
     engine/ddp.py) -- the reference is single-GPU;
   * the CLI passes arguments by keyword (the reference swaps `verbose` / `debug_dataloader` positionally);
-  * TensorBoard / debug GIFs are optional extras and skipped when their packages are missing.
+  * TensorBoard / debug GIFs are optional extras and skipped when their packages are missing;
+  * `tr_config.val_metrics` (absent / false: off, and then nothing below differs) adds Dice / IoU / precision / recall of the
+    segmentation heads and the angular error of a normals head to the validation pass (training/metrics, HIP kernels, one host
+    copy per epoch), writes them and the validation losses to TensorBoard, and with `best` keeps `<model_name>.best.pth`.
 """
 import os
 import time
@@ -33,6 +36,7 @@ from .dataloading.dataset import SyntheticPatchDataset, ZarrSegmentationDataset3
 from .engine.ddp import GradSync, broadcast_parameters
 from .engine.streamed_step import StreamedOptimizerStep
 from .training.losses.losses import LOSS_FN_MAP
+from .training.metrics import ValidationMetrics, parse_config as parse_val_metrics
 from .training.optim import clip_and_step
 
 _AMP = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": None}
@@ -150,6 +154,10 @@ class BaseTrainer:
         self.rank = int(os.environ.get("RANK", 0))
         self.local_rank = int(os.environ.get("LOCAL_RANK", 0))
         self.last_patches_per_sec = None
+        # tr_config.val_metrics: checked here, so a typo stops the run before a model is built (ValueError naming the key)
+        self.val_metrics_config = parse_val_metrics(self.mgr.tr_configs.get("val_metrics"), self.mgr.tasks)
+        self.last_val_metrics = None
+        self.best_val_metric = None
 
     # ---- hooks ----------------------------------------------------------------------------------
     def _build_model(self):
@@ -229,6 +237,31 @@ class BaseTrainer:
     def _log(self, *a):
         if self.rank == 0:
             print(*a, flush=True)
+
+    def _report_val_metrics(self, metrics, vrun, vsteps, epoch, writer, best_cfg, ckpt_dir, checkpoint):
+        """rank 0 (every rank validates the same list): one log line per task and metric, `val/{task}_{metric}` and
+        `val/{task}_loss` to TensorBoard (nan skipped), and with `best` the epoch's checkpoint dict to `<model_name>.best.pth` when
+        the watched value improved (a nan never does)"""
+        self.last_val_metrics = metrics
+        if self.rank != 0:
+            return
+        for task, vals in metrics.items():
+            for name, v in vals.items():
+                self._log(f"Task '{task}', epoch {epoch + 1} val {name}: {v:.4f}")
+        if writer is not None:
+            for k in vrun:
+                writer.add_scalar(f"val/{k}_loss", vrun[k] / max(vsteps, 1), epoch)
+            for task, vals in metrics.items():
+                for name, v in vals.items():
+                    if v == v:
+                        writer.add_scalar(f"val/{task}_{name}", v, epoch)
+        if best_cfg is not None:
+            v = metrics[best_cfg["task"]][best_cfg["metric"]]
+            old = self.best_val_metric
+            if v == v and (old is None or (v > old if best_cfg["mode"] == "max" else v < old)):
+                self.best_val_metric = v
+                torch.save(checkpoint(), f"{ckpt_dir}/{self.mgr.model_name}.best.pth")
+                self._log(f"Best {best_cfg['task']} {best_cfg['metric']} so far ({v:.4f}): saved {self.mgr.model_name}.best.pth")
 
     # ---- training loop ----------------------------------------------------------------------------
     def train(self):
@@ -331,6 +364,10 @@ class BaseTrainer:
             ingest = DeviceIngest(ing_rules)
         self.device_ingest = ingest
 
+        # tr_config.val_metrics: counts and sums accumulate on the device over the validation loop
+        val_metrics = ValidationMetrics(self.mgr.tasks, self.val_metrics_config) if self.val_metrics_config is not None else None
+        best_cfg = self.val_metrics_config["best"] if self.val_metrics_config is not None else None
+
         def forward_loss(batch, train_mode):
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
             if ingest is not None and not staged:    # each tensor in its own dtype; from here on the batch is what `where: host` gives
@@ -362,6 +399,8 @@ class BaseTrainer:
                         l = l * self.mgr.tasks[name].get("weight", 1.0)
                     total = total + l
                     per[name] = l.detach()
+            if not train_mode and val_metrics is not None:
+                val_metrics.update(out, targets)      # kernels on this stream, no host sync; read out once after the loop
             return total, per, x.shape[0]
 
         for epoch in range(start_epoch, self.mgr.max_epoch):
@@ -408,11 +447,14 @@ class BaseTrainer:
                 torch.save({"model": model.state_dict(), "optimizer": optimizer.state_dict(),
                             "scheduler": scheduler.state_dict(), "epoch": epoch},
                            f"{ckpt_dir}/{self.mgr.model_name}_{epoch + 1}.pth")
+                # (`<model_name>.best.pth` of tr_config.val_metrics.best has a dot there on purpose: this glob must not match it)
                 ckpts = sorted(ckpt_dir.glob(f"{self.mgr.model_name}_*.pth"), key=lambda p: p.stat().st_mtime)
                 while len(ckpts) > 10:
                     ckpts.pop(0).unlink()
 
             model.eval()
+            if val_metrics is not None:
+                val_metrics.reset()
             with torch.no_grad():
                 vrun, vsteps = {t: 0.0 for t in self.mgr.tasks}, 0
                 for i, batch in enumerate(val_loader):
@@ -425,6 +467,10 @@ class BaseTrainer:
                 vrun = {k: float(v) for k, v in vrun.items()}
                 for k in vrun:
                     self._log(f"Task '{k}', epoch {epoch + 1} avg val loss: {vrun[k] / max(vsteps, 1):.4f}")
+                if val_metrics is not None:
+                    self._report_val_metrics(val_metrics.compute(), vrun, vsteps, epoch, writer, best_cfg, ckpt_dir,
+                                             lambda: {"model": model.state_dict(), "optimizer": optimizer.state_dict(),
+                                                      "scheduler": scheduler.state_dict(), "epoch": epoch})
             scheduler.step()
 
         self._log("Training Finished!")
