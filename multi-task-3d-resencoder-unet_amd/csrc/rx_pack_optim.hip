@@ -266,6 +266,15 @@ __device__ inline float adamw_update(float p, float g, float& m, float& v, const
   return p - (a.lr / a.bc1) * (m / denom);
 }
 
+// The packed copies must be the cast of the STORED fp32 weight -- what a later re-pack of that weight writes.  Left alone, the f16
+// kernel evaluates the last FMA of the update a second time as v_fma_mixlo_f16, which rounds the unrounded result to f16 once:
+// one f16 ulp away from the cast of the fp32 value wherever that value is a rounding tie (3 of 25920 elements of a 40 x 24 x 27
+// weight).  The empty statement makes the rounded fp32 value the only thing the conversion can see.
+__device__ __forceinline__ float stored_f32(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void adamw_pack_kernel(float* __restrict__ w, const float* __restrict__ grad, float* __restrict__ m,
                                                          float* __restrict__ v, const float* __restrict__ clip, const AdamArgs aa, int A,
@@ -287,7 +296,7 @@ __global__ __launch_bounds__(256) void adamw_pack_kernel(float* __restrict__ w, 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float mj = pm[j], vj = pv[j];
-        pw[j] = adamw_update(pw[j], pg[j] * cs, mj, vj, aa);
+        pw[j] = stored_f32(adamw_update(pw[j], pg[j] * cs, mj, vj, aa));
         pm[j] = mj, pv[j] = vj;
       }
       *reinterpret_cast<f32x4*>(w + off) = pw;
@@ -308,7 +317,7 @@ __global__ __launch_bounds__(256) void adamw_pack_kernel(float* __restrict__ w, 
       if (a0 + a < A && b0 + b < B) {
         const size_t off = ((size_t)(a0 + a) * B + b0) * TT + r;
         float mj = m[off], vj = v[off];
-        nw = adamw_update(w[off], grad[off] * cs, mj, vj, aa);
+        nw = stored_f32(adamw_update(w[off], grad[off] * cs, mj, vj, aa));
         w[off] = nw, m[off] = mj, v[off] = vj;
       }
       L[(t * 32 + a) * RX_PACK_PB + b] = Elem<T>::from_f(nw);

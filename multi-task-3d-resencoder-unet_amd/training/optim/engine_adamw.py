@@ -99,7 +99,9 @@ class EngineAdamW(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 st["step"] = int(st["step"]) + 1
                 ent = packed.get(id(p))
-                if ent is not None:
+                # (rx_adamw_pack holds a [taps][32][40] tile in LDS: up to 27 taps.  A 5- / 7-wide kernel or a stride-3 / -4
+                # transposed conv takes the flat update; its pack entry stays stale and the next forward re-packs it)
+                if ent is not None and p[0, 0].numel() <= 27:
                     kind = 0 if ent["kind"] == "conv" else 1
                     A, B = p.shape[0], p.shape[1]
                     taps = p[0, 0].numel()

@@ -920,6 +920,51 @@ def test_pack_multi_matches_reference_layouts(ops, dtype):
     assert torch.equal(wf2, wf)
 
 
+def _pack_refs(w, kind, dtype):
+    """(w_fwd [T][Co][Ci], w_bwd [T][Ci][Co]) as the plain permutation of a Conv3d (Co,Ci,k) / ConvTranspose3d (Ci,Co,k) weight"""
+    flat = w.reshape(w.shape[0], w.shape[1], -1)
+    same, swp = flat.permute(2, 0, 1).to(dtype).contiguous(), flat.permute(2, 1, 0).to(dtype).contiguous()
+    return (same, swp) if kind == 0 else (swp, same)
+
+
+# more than 27 taps go to pack_naive_kernel, one launch each, and the rest of the list to the table kernel: a mixed list (125, 343 and
+# -- a stride-4 transposed conv -- 64 taps between <= 27-tap entries), a list of such entries only, and one 64 x 64 x 343 weight
+# whose 1.4 M elements exceed the naive kernel's grid of 4096 x 256 threads (second trip of its grid-stride loop)
+BIG_TAP_LISTS = {
+    "mixed": [(0, 64, 32, (3, 3, 3)), (0, 32, 32, (5, 5, 5)), (1, 64, 32, (2, 2, 2)), (0, 33, 17, (7, 7, 7)), (0, 40, 24, (3, 3, 3)),
+              (1, 32, 64, (4, 4, 4)), (0, 64, 32, (1, 1, 1)), (1, 24, 40, (1, 4, 4))],
+    "all_big": [(0, 32, 32, (5, 5, 5)), (1, 32, 64, (4, 4, 4)), (0, 33, 17, (7, 7, 7)), (1, 17, 33, (1, 7, 7))],
+    "above_grid_cap": [(0, 64, 64, (7, 7, 7))],
+}
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("which", list(BIG_TAP_LISTS))
+def test_pack_multi_more_than_27_taps(ops, dtype, which):
+    """rx_pack_multi on lists with > 27-tap entries: every packed copy, NaN before the call, is bit for bit the permutation of the
+    weight (both kinds: the naive branch exchanges same / swap for a transposed conv itself), and equals the single-tensor entries"""
+    g = torch.Generator().manual_seed(17)
+    items, refs = [], []
+    for kind, a, b, k in BIG_TAP_LISTS[which]:
+        w = torch.randn((a, b, *k), generator=g).cuda()
+        rf, rb = _pack_refs(w, kind, dtype)
+        items.append((w, kind, poisoned(rf.shape, dtype), poisoned(rb.shape, dtype)))
+        refs.append((rf, rb))
+    if which == "above_grid_cap":
+        assert items[0][0].numel() > 4096 * 256
+    ops.pack_weights_multi(items, dtype)
+    for (w, kind, wf, wb), (rf, rb) in zip(items, refs):
+        assert not torch.isnan(wf).any() and not torch.isnan(wb).any(), (kind, tuple(w.shape))
+        assert torch.equal(wf, rf) and torch.equal(wb, rb), (kind, tuple(w.shape))
+        one = ops.pack_conv_weight(w, dtype) if kind == 0 else ops.pack_convT_weight(w, dtype)
+        assert torch.equal(one[0], wf) and torch.equal(one[1], wb)
+    # forward-only plans pack no bwd copy: the naive kernel with one NULL output
+    w, kind, wf, wb = items[-1]
+    wf2 = poisoned(wf.shape, dtype)
+    ops.pack_weights_multi([(w, kind, wf2, None)], dtype)
+    assert torch.equal(wf2, wf)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("pool", [None, (2, 2, 2), (1, 2, 2)])
 def test_instnorm_act_bwd_res_masked_gradient_written_once(ops, dtype, pool):

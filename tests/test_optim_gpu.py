@@ -6,16 +6,16 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import resenc_oracle as oracle
-from golden_cases import CASES
+from golden_cases import CASES, TASKS_SIGMOID_SHEET, _manual
 from helpers import rel_l2
 
 
-def _setup():
+def _setup(case="auto16_2head"):
     import mt3d_amd  # noqa: F401
     from mt3d_amd.builders.build_network_from_config import NetworkFromConfig
     from mt3d_amd.engine import lib
     lib.require_device()
-    c = CASES["auto16_2head"]
+    c = CASES[case] if isinstance(case, str) else case
     mgr = oracle.make_mgr(c["patch"], c["tasks"], c["in_channels"], c["batch"], c["autoconfigure"], c["model_config"])
     torch.manual_seed(c["seed"])
     net = NetworkFromConfig(mgr).cuda()
@@ -69,6 +69,81 @@ def test_engine_adamw_tracks_torch_adamw():
         assert torch.equal(o1[k], o2[k]), k
     plan = [p for p in net_b._plans.values() if p.needs_grad][0]
     assert all(e.get("event") is None for e in plan.packs)
+
+
+# Both golden cases with more than 27 taps (big_kernels, stride4_mixed) widen their 5-wide stem weight into a zero-padded shadow, and a
+# plan with shadows never takes the fused update-and-pack: EngineAdamW(model=net) steps them flat.  A plan WITHOUT shadows needs a
+# 3^3 stem; this one (smaller than either golden case) then holds 5^3 kernels (125 taps) and a stride-4 transposed conv (64 taps).
+WIDE_TAPS_NO_SHADOW = dict(patch=(16, 16, 16), batch=2, in_channels=1, tasks=TASKS_SIGMOID_SHEET, autoconfigure=False, seed=11,
+                           model_config=_manual(features_per_stage=[32, 64], num_stages=2, n_blocks_per_stage=[1, 2],
+                                                n_conv_per_stage_decoder=[1], kernel_sizes=[[3, 3, 3], [5, 5, 5]],
+                                                strides=[[1, 1, 1], [4, 4, 4]]))
+
+
+@pytest.mark.parametrize("case", ["big_kernels", "wide_taps_no_shadow"])
+def test_engine_adamw_steps_a_plan_with_more_than_27_taps(case):
+    """EngineAdamW(model=net) on a plan that holds weights of more than 27 taps (5^3 / 7^3 kernels; a stride-4 transposed conv).
+    rx_adamw_pack refuses those (RX_EINVAL), so in a plan that takes the fused path (wide_taps_no_shadow) they get the flat update
+    and their packs are left stale for the next forward; big_kernels has a shadow parameter and is stepped flat as a whole.  Every
+    parameter -- of this net and of a twin given the same gradients and stepped with model=None -- is per element within the fp32
+    bound of the fp64 AdamW (tests/adamw_ref.py), and the next forward equals that of a fresh module with the same state_dict."""
+    from adamw_ref import HYPERS, adam_args, check_step
+    from mt3d_amd.training.optim import EngineAdamW
+    net_a, c, mgr, x, targets, N = _setup(WIDE_TAPS_NO_SHADOW if case == "wide_taps_no_shadow" else case)
+    torch.manual_seed(c["seed"])
+    net_b = N(mgr).cuda()
+    pa, pb = [p for p in net_a.parameters()], [p for p in net_b.parameters()]
+    hyper = HYPERS[0]
+    kw = dict(lr=hyper[0], betas=hyper[1:3], eps=hyper[3], weight_decay=hyper[4])
+    oa, ob = EngineAdamW(pa, model=net_a, **kw), EngineAdamW(pb, model=None, **kw)
+    net_a.train()
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        out = net_a(x)
+    oracle.train_loss(out, targets, c["tasks"]).backward()
+    plans = [p for p in net_a._plans.values() if p.needs_grad]
+    assert len(plans) == 1
+    plan = plans[0]
+    fused = case == "wide_taps_no_shadow"
+    assert bool(plan._shadows) == (not fused) and (oa._plan() is plan) == fused
+    taps = {id(e["param"]): e["param"][0, 0].numel() for e in plan.packs}
+    big = {i for i, t in taps.items() if t > 27}
+    assert big and len(big) < len(taps), sorted(taps.values())
+    if fused:                                                     # a transposed conv among them (kind 1 of rx_adamw_pack's refusal)
+        assert any(e["kind"] == "convT" and e["param"][0, 0].numel() > 27 for e in plan.packs)
+    before = []
+    for a, b in zip(pa, pb):
+        assert torch.equal(a, b)
+        b.grad = None if a.grad is None else a.grad.clone()
+        before.append(a.detach().flatten().cpu())
+    na, nb = oa.clip_grad_norm(0.05), ob.clip_grad_norm(0.05)
+    clip = oa._clip.item()
+    assert na.item() == nb.item() and clip == ob._clip.item()
+    oa.step()                                                     # raised RX_EINVAL ("rx_adamw_pack: bad arguments") before the fix
+    ob.step()
+    torch.cuda.synchronize()
+    args = adam_args(*hyper, 1)
+    for (name, a), b, p0 in zip(net_a.named_parameters(), pb, before):
+        if a.grad is None:
+            assert torch.equal(a.detach().flatten().cpu(), p0), name
+            continue
+        zero = torch.zeros_like(p0)
+        for opt, p in ((oa, a), (ob, b)):
+            st = opt.state[p]
+            assert st["step"] == 1
+            check_step((p.detach().flatten(), st["exp_avg"].flatten(), st["exp_avg_sq"].flatten()), (p0, zero, zero), a.grad.flatten().cpu(),
+                       clip, args, f"engine_adamw plan: {case} {name} ({'fused' if opt is oa else 'flat'})")
+    stale = {id(e["param"]) for e in plan._packs_stale()}
+    assert stale == (big if fused else set(taps)), "exactly the weights that took the flat update wait for a re-pack"
+    fresh = N(mgr).cuda()
+    fresh.load_state_dict(net_a.state_dict())
+
+    def fwd(m):
+        m.train()
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            return m(x)
+    o1, o2 = fwd(net_a), fwd(fresh)
+    for k in o1:
+        assert torch.equal(o1[k], o2[k]), k
 
 
 def test_engine_adamw_trains_like_torch_over_several_steps():
