@@ -546,6 +546,41 @@ typedef struct {      /* one sample's transform, 72 bytes */
 int rx_affine_apply(const float* in, float* out, int batch, int c, int z, int y, int x, const rx_affine_sample* host_table,
                     int interp, int border, float fill, int vector, void* stream);
 
+/* ---- smooth non-rigid deformation on the device, with the vector rule of a 3-component normal field (host side
+ *      dataloading/elastic_device.py, whose displacement_numpy and elastic_numpy are the statement).  One resampling pass per
+ *      tensor: out(o) = in(o + D(o)), D a cubic B-spline displacement field over a node lattice of pitch `spacing`:
+ *      G_d = (n_d - 1) / s_d + 4 nodes along axis d of (z, y, x).  The output grid is regular, so each axis arrives as a table over
+ *      its voxel indices o: idx[o] = floor(o / s) (voxel o uses nodes idx[o] .. idx[o] + 3), w[o][0..3] the uniform cubic
+ *      B-spline weights at f = o / s - idx[o], dw[o][0..3] their derivatives with respect to o (evaluated in float64, rounded
+ *      once).  For component c of (z, y, x) at voxel (oz, oy, ox), all float32, one rounding per operation, nothing contracted
+ *      into an fma, denormals kept, every sum from its first product on, left to right:
+ *        L1[c][b][k] = sum_a w_z[oz][a] * nodes[c][iz+a][iy+b][ix+k]
+ *        L2[c][k]    = sum_b w_y[oy][b] * L1[c][b][k]
+ *        D_c         = sum_k w_x[ox][k] * L2[c][k]                 (z, then y, then x: an L2 line serves a whole x row)
+ *        E[d][e]     = the same three sums with dw on axis e and w on the other two          (dD_d / do_e)
+ *        p_d = (float)o_d + D_d
+ *      From p_d on the rules are rx_affine_apply's: RX_AFFINE_LINEAR / _NEAREST, RX_AFFINE_CONSTANT (`fill`) / _CLAMP, lerp along
+ *      x, then y, then z.  All channels of a sample share one set of coordinates.
+ *      `vector` != 0 (needs c == 3, channels (Nx, Ny, Nz)): with s the sampled components and (n_z, n_y, n_x) = (s_2, s_1, s_0),
+ *        t_e = n_e + ((E[z][e] * n_z + E[y][e] * n_y) + E[x][e] * n_x)                        (a normal is a covector)
+ *        q = (s_0*s_0 + s_1*s_1) + s_2*s_2     r = (t_x*t_x + t_y*t_y) + t_z*t_z     k = r > 0 ? sqrt(q / r) : 0
+ *      with correctly rounded sqrt and /; output channel j is t_(x, y, z)[j] * k: the sampled length is kept, zero stays zero. */
+typedef struct {         /* one axis, DEVICE pointers */
+  const int32_t* idx;    /* [n]    */
+  const float* w;        /* [n][4] */
+  const float* dw;       /* [n][4] */
+} rx_elastic_axis;
+typedef struct { rx_elastic_axis z, y, x; } rx_elastic_tables;
+/* in / out: contiguous fp32 (batch, c, z, y, x), distinct buffers.  `nodes`: DEVICE, fp32 (batch, 3, Gz, Gy, Gx).  `spacing` and
+ * `tables`: HOST, read during the call (the pointers inside `tables` are device pointers and ride in the kernel arguments).  No
+ * allocation, copy or synchronisation.  Device data cannot be validated here (the Python wrapper refuses nodes that are not
+ * finite before upload); whatever nodes and tables hold, every node load is clamped into the lattice and every source load into
+ * the sample.  RX_EINVAL before anything is launched: null pointers, in == out, an unknown interp or border, vector with
+ * c != 3, a spacing < 8, z * y * x >= 2^31, z or y > 65535, x > 2^24 (float32 coordinates), c > 4095, batch > 65535.  One
+ * write of the tensor; source voxels are read through L1 / L2; 3.2 KB of LDS whatever the lattice. */
+int rx_elastic_apply(const float* in, float* out, int batch, int c, int z, int y, int x, const float* nodes, const int32_t spacing[3],
+                     const rx_elastic_tables* tables, int interp, int border, float fill, int vector, void* stream);
+
 /* ---- validation metrics on the device (host side training/metrics/metrics.py, whose seg_counts_numpy, class_counts_numpy and
  *      normal_stats_numpy are the statements).  Operands are contiguous (n, c, v) device arrays: `pred` of `pred_dtype` (rx_dtype),
  *      aligned to its element, `target` fp32, 4-byte aligned (a base that is not 16-byte aligned is fine).  Every entry point ADDS

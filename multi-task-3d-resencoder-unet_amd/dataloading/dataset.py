@@ -22,6 +22,11 @@ targets together, a normals target turned with them (`spatial_device.py`): `wher
 `device_spatial` (the trainer applies `DeviceSpatial` to the staged batch, after geometry), `where: host` draws one op per item
 and runs `affine_numpy` inside `__getitem__`, after the host geometric classes and before the intensity stack.
 
+`dataset_config.elastic` (absent: off) adds a smooth B-spline deformation, image and targets together, a normals target carried
+as a covector (`elastic_device.py`): `where: device` leaves the items alone and exposes `device_elastic` (the trainer applies
+`DeviceElastic` to the staged batch, after spatial), `where: host` draws one field per item and runs `elastic_numpy` inside
+`__getitem__`, after the host spatial stage and before the intensity stack.
+
 `dataset_config.patch_search` (absent: `{where: host}`, `find_valid_patches` below) says where the valid-patch search of the
 constructor runs: `device` hands each volume's reference label to `patch_search_device.find_valid_patches_device` (HIP box
 statistics, the same list and the same cache file; no device is an error, not a fallback).
@@ -68,6 +73,11 @@ class SyntheticPatchDataset(Dataset):
         self.spatial = parse_spatial(mgr.dataset_config, self.patch, self.tasks)
         self.device_spatial = self.spatial if self.spatial is not None and self.spatial["where"] == "device" else None
         self.spatial_rng, self.last_spatial_op = None, None
+        # dataset_config.elastic: the same two places ("host": one field per item from `elastic_rng`, after the spatial stage)
+        from .elastic_device import parse_elastic
+        self.elastic = parse_elastic(mgr.dataset_config, self.patch, self.tasks)
+        self.device_elastic = self.elastic if self.elastic is not None and self.elastic["where"] == "device" else None
+        self.elastic_rng, self.last_elastic_field = None, None
 
     def __len__(self):
         return self.length
@@ -81,9 +91,11 @@ class SyntheticPatchDataset(Dataset):
         return self._host_spatial(self._make(idx))
 
     def _host_spatial(self, item):
-        if self.spatial is None or self.spatial["where"] != "host":
-            return item
-        return _host_spatial(self, item)
+        if self.spatial is not None and self.spatial["where"] == "host":
+            item = _host_spatial(self, item)
+        if self.elastic is not None and self.elastic["where"] == "host":
+            item = _host_elastic(self, item)
+        return item
 
     def _make(self, idx):
         g = torch.Generator().manual_seed(self.seed + int(idx))
@@ -109,6 +121,19 @@ def _host_spatial(ds, item):
     if op.is_identity():
         return item
     return apply_item_numpy(op, item, cfg["normal_keys"], cfg["image_border"])
+
+
+def _host_elastic(ds, item):
+    """`dataset_config.elastic.where: host`: one draw per item, `elastic_numpy` on every array of it (a zero field: untouched)"""
+    import random
+    from .elastic_device import apply_item_numpy, draw_elastic
+    cfg = ds.elastic
+    shape = tuple(int(v) for v in item["image"].shape[-3:])
+    field = draw_elastic(ds.elastic_rng if ds.elastic_rng is not None else random, shape, cfg["spacing"], cfg["magnitude"], cfg["p"])
+    ds.last_elastic_field = field
+    if field.is_identity():
+        return item
+    return apply_item_numpy(field, item, cfg["normal_keys"], cfg["image_border"])
 
 
 def find_label_bounding_box(arr, chunk_shape=(192, 192, 192)):
@@ -214,6 +239,12 @@ class ZarrSegmentationDataset3D(Dataset):
         check_host_spatial(self.spatial, self.ingest, self.dilate)
         self.device_spatial = self.spatial if self.spatial is not None and self.spatial["where"] == "device" else None
         self.spatial_rng, self.last_spatial_op = None, None
+        # dataset_config.elastic: as spatial ("host" needs scaled float items with their labels already dilated)
+        from .elastic_device import check_host_elastic, parse_elastic
+        self.elastic = parse_elastic(getattr(mgr, "dataset_config", {}), self.patch_size, self.tasks)
+        check_host_elastic(self.elastic, self.ingest, self.dilate)
+        self.device_elastic = self.elastic if self.elastic is not None and self.elastic["where"] == "device" else None
+        self.elastic_rng, self.last_elastic_field = None, None
         self.volumes = []
         for vol_idx, info in enumerate(self.volume_paths):
             vd = {"input_path": info["input"], "targets_path": {}, "ref_label_key": info.get("ref_label", "sheet")}
@@ -312,6 +343,8 @@ class ZarrSegmentationDataset3D(Dataset):
             item = transform(item)
         if self.spatial is not None and self.spatial["where"] == "host":      # after the signed permutations, before the intensity stack
             item = _host_spatial(self, item)
+        if self.elastic is not None and self.elastic["where"] == "host":      # after the host spatial stage, before the intensity stack
+            item = _host_elastic(self, item)
         if self.augment:              # image only; targets untouched (dataset.py:200-205)
             from .augment import augment_image
             item["image"] = augment_image(item["image"])

@@ -144,6 +144,52 @@ def _axis_index(v, n, lo):
     return np.fmax(np.fmin(v, np.float32(n)), np.float32(lo)).astype(np.int64)
 
 
+def sample_numpy(a, p, interp, border, fill=0.0):
+    """the sampling half of `affine_numpy`, from the coordinates on: `a` float32 (C, Z, Y, X), `p` = (p_z, p_y, p_x) float32 arrays
+    that broadcast to (Z, Y, X) -> the sampled (C, Z, Y, X) values under the interp / border rules stated there (the index
+    squashing and the lerp order included).  `elastic_device.elastic_numpy` samples through it with coordinates of its own."""
+    f32 = np.float32
+    n = a.shape[1:]
+    with np.errstate(over="ignore", invalid="ignore"):
+        fillv = f32(fill)
+        flat = a.reshape(a.shape[0], -1)
+        stride = (n[1] * n[2], n[2], 1)
+
+        def fetch(idx):
+            """idx: per axis (int64 index array, whole-number float array it came from) -> (C, Z, Y, X) values under the border rule"""
+            off, ok = 0, True
+            for d in range(3):
+                ii, fi = idx[d]
+                if border == "constant":
+                    ok = ok & (fi >= 0) & (fi <= f32(n[d] - 1))
+                off = off + np.clip(ii, 0, n[d] - 1) * stride[d]
+            v = flat[:, off]
+            return np.where(ok, v, fillv) if border == "constant" else v
+
+        if interp == "nearest":
+            r = [np.floor(p[d] + f32(0.5)) for d in range(3)]
+            s = fetch([(_axis_index(r[d], n[d], -1), r[d]) for d in range(3)])
+        else:
+            i0 = [np.floor(p[d]) for d in range(3)]
+            f = [p[d] - i0[d] for d in range(3)]
+            lo = [_axis_index(i0[d], n[d], -2) for d in range(3)]
+            # (index, the float it stands for): i + 1 of a clamped index is outside whenever i + 1 of the true one is
+            ax = [((lo[d], lo[d].astype(f32)), (lo[d] + 1, (lo[d] + 1).astype(f32))) for d in range(3)]
+
+            def lerp(u, w, fr):
+                return u + fr * (w - u)
+            zs = []
+            for kz in (0, 1):
+                ys = []
+                for ky in (0, 1):
+                    u = fetch([ax[0][kz], ax[1][ky], ax[2][0]])
+                    w = fetch([ax[0][kz], ax[1][ky], ax[2][1]])
+                    ys.append(lerp(u, w, f[2]))
+                zs.append(lerp(ys[0], ys[1], f[1]))
+            s = lerp(zs[0], zs[1], f[0])
+    return s
+
+
 def affine_numpy(op, arr, interp, border, fill=0.0, is_normal=False):
     """What rx_affine_apply computes, in numpy: (Z, Y, X) or (C, Z, Y, X) float32 in, a new contiguous float32 array out.  EVERY
     arithmetic step below is ONE float32 operation (round to nearest even, denormals kept), in the order written, so a kernel that
@@ -183,42 +229,7 @@ def affine_numpy(op, arr, interp, border, fill=0.0, is_normal=False):
     t = [(np.arange(n[d], dtype=f32) - c[d]).reshape(shp[d]) for d in range(3)]
     with np.errstate(over="ignore", invalid="ignore"):
         p = [((m[d, 0] * t[0] + m[d, 1] * t[1]) + m[d, 2] * t[2]) + c[d] for d in range(3)]
-        fillv = f32(fill)
-        flat = a.reshape(a.shape[0], -1)
-        stride = (n[1] * n[2], n[2], 1)
-
-        def fetch(idx):
-            """idx: per axis (int64 index array, whole-number float array it came from) -> (C, Z, Y, X) values under the border rule"""
-            off, ok = 0, True
-            for d in range(3):
-                ii, fi = idx[d]
-                if border == "constant":
-                    ok = ok & (fi >= 0) & (fi <= f32(n[d] - 1))
-                off = off + np.clip(ii, 0, n[d] - 1) * stride[d]
-            v = flat[:, off]
-            return np.where(ok, v, fillv) if border == "constant" else v
-
-        if interp == "nearest":
-            r = [np.floor(p[d] + f32(0.5)) for d in range(3)]
-            s = fetch([(_axis_index(r[d], n[d], -1), r[d]) for d in range(3)])
-        else:
-            i0 = [np.floor(p[d]) for d in range(3)]
-            f = [p[d] - i0[d] for d in range(3)]
-            lo = [_axis_index(i0[d], n[d], -2) for d in range(3)]
-            # (index, the float it stands for): i + 1 of a clamped index is outside whenever i + 1 of the true one is
-            ax = [((lo[d], lo[d].astype(f32)), (lo[d] + 1, (lo[d] + 1).astype(f32))) for d in range(3)]
-
-            def lerp(u, w, fr):
-                return u + fr * (w - u)
-            zs = []
-            for kz in (0, 1):
-                ys = []
-                for ky in (0, 1):
-                    u = fetch([ax[0][kz], ax[1][ky], ax[2][0]])
-                    w = fetch([ax[0][kz], ax[1][ky], ax[2][1]])
-                    ys.append(lerp(u, w, f[2]))
-                zs.append(lerp(ys[0], ys[1], f[1]))
-            s = lerp(zs[0], zs[1], f[0])
+        s = sample_numpy(a, p, interp, border, fill)
         if is_normal:
             v = op.vector
             s = np.stack([(v[k, 0] * s[0] + v[k, 1] * s[1]) + v[k, 2] * s[2] for k in range(3)])

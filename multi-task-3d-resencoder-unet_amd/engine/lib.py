@@ -43,6 +43,11 @@ class RxSeParams(ctypes.Structure):
                 ("keep_x", c_int32)]
 
 
+class RxElasticTables(ctypes.Structure):
+    """mirror of `rx_elastic_tables` (include/rxunet.h): per axis z, y, x the device pointers idx, w, dw"""
+    _fields_ = [(f"{a}_{n}", c_void_p) for a in "zyx" for n in ("idx", "w", "dw")]
+
+
 I3 = c_int32 * 3
 _P = POINTER(RxAct)
 _PSE = POINTER(RxSeParams)
@@ -165,6 +170,8 @@ _SIGNATURES = {
     "rx_box_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "rx_ingest": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rx_affine_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
+    "rx_elastic_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int,
+                                 c_void_p]),
     "rx_seg_counts": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_long, c_float, c_float, c_void_p, c_void_p]),
     "rx_class_counts": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_long, c_void_p, c_void_p]),
     "rx_normal_stats_workspace": (c_size_t, [c_int, c_long]),

@@ -773,6 +773,97 @@ def affine_apply(tensor, table, interp, border, fill=0.0, vector=False, out=None
     return out
 
 
+_ELASTIC_TABLES = {}
+
+
+def elastic_tables(shape, spacing, device=None):
+    """the per-axis B-spline tables of a (Z, Y, X) patch at `spacing` = (sz, sy, sx) (dataloading.elastic_device.bspline_tables) on
+    the device: ((idx_z, w_z, dw_z), (idx_y, ...), (idx_x, ...)), int32 [n] and float32 [n, 4] tensors.  Cached per (shape, spacing,
+    device): a trainer uploads them once."""
+    from ..dataloading.elastic_device import bspline_tables
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise _l.RxError(f"elastic_tables: {device} is not a device (the host path is elastic_device.elastic_numpy)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    shape, spacing = tuple(int(v) for v in shape), tuple(int(v) for v in spacing)
+    if len(shape) != 3 or len(spacing) != 3 or min(shape) < 1 or min(spacing) < 1:
+        raise _l.RxError(f"elastic_tables: shape {shape}, spacing {spacing} (three positive extents, three positive spacings)")
+    key = (shape, spacing, device)
+    if key not in _ELASTIC_TABLES:
+        _ELASTIC_TABLES[key] = tuple(tuple(torch.from_numpy(t).to(device) for t in bspline_tables(n, s)) for n, s in zip(shape, spacing))
+    return _ELASTIC_TABLES[key]
+
+
+def elastic_nodes(fields, device=None):
+    """`fields`: one `dataloading.elastic_device.ElasticField` per sample, all with one spacing and one lattice -> the
+    (B, 3, Gz, Gy, Gx) float32 device tensor of their nodes: staged in pinned host memory and uploaded with ONE non-blocking copy
+    on the current stream, no synchronisation.  Nodes that are not finite are refused here (the device cannot refuse them)."""
+    fields = list(fields)
+    if not fields or any(not hasattr(f, "nodes") or not hasattr(f, "spacing") for f in fields):
+        raise _l.RxError("elastic_nodes: expected a non-empty list of ElasticField")
+    sp, shp = tuple(fields[0].spacing), tuple(fields[0].nodes.shape)
+    for i, f in enumerate(fields):
+        if tuple(f.spacing) != sp or tuple(f.nodes.shape) != shp:
+            raise _l.RxError(f"elastic_nodes: field {i} has spacing {tuple(f.spacing)} and nodes {tuple(f.nodes.shape)}, field 0 has "
+                             f"{sp} and {shp}: one batch, one lattice")
+        if not np.isfinite(f.nodes).all():
+            raise _l.RxError(f"elastic_nodes: field {i} has nodes that are not finite")
+    host = torch.empty((len(fields),) + shp, dtype=torch.float32, pin_memory=True)
+    stage = host.numpy()
+    for i, f in enumerate(fields):
+        stage[i] = f.nodes
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    return host.to(device, non_blocking=True)
+
+
+def elastic_apply(tensor, nodes, tables, spacing, interp, border, fill=0.0, vector=False, out=None):
+    """B-spline deformation of a float32 (B, C, Z, Y, X) device batch: `nodes` (`elastic_nodes`) the (B, 3, Gz, Gy, Gx) float32
+    device lattice, `tables` (`elastic_tables`) for (Z, Y, X) at `spacing` = (sz, sy, sx), each >= 8 -> a new batch on the current
+    stream, or `out` (a distinct contiguous float32 tensor of the same shape).  `interp`: "linear" | "nearest"; `border`: "constant"
+    (outside voxels are `fill`) | "clamp"; `vector`: the three channels are a normal field (Nx, Ny, Nz) and take the covector
+    rule.  dataloading.elastic_device.elastic_numpy is the statement.  The fold guard is the config parser's: nodes of any finite
+    size are served, and no load leaves a sample."""
+    from ..dataloading.spatial_device import BORDER, INTERP
+    if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+        raise _l.RxError("elastic_apply: the batch must be a device tensor (the host path is elastic_device.elastic_numpy)")
+    if tensor.dim() != 5 or tensor.dtype != torch.float32:
+        raise _l.RxError(f"elastic_apply: expected a float32 (B, C, Z, Y, X) batch, got {tensor.dtype} {tuple(tensor.shape)}")
+    if interp not in INTERP or border not in BORDER:
+        raise _l.RxError(f"elastic_apply: interp {interp!r} (linear, nearest), border {border!r} (constant, clamp)")
+    src = tensor.contiguous()
+    b, c, z, y, x = src.shape
+    try:
+        sp = tuple(int(v) for v in spacing)
+    except (TypeError, ValueError):
+        sp = ()
+    if len(sp) != 3 or min(sp) < 1:
+        raise _l.RxError(f"elastic_apply: spacing {spacing!r} (three positive ints)")
+    want = (b, 3) + tuple((n - 1) // s + 4 for n, s in zip((z, y, x), sp))
+    if (not isinstance(nodes, torch.Tensor) or nodes.device != src.device or nodes.dtype != torch.float32 or tuple(nodes.shape) != want
+            or not nodes.is_contiguous()):
+        got = (nodes.dtype, tuple(nodes.shape), nodes.device) if isinstance(nodes, torch.Tensor) else type(nodes)
+        raise _l.RxError(f"elastic_apply: `nodes` must be a contiguous float32 tensor of shape {want} on {src.device}, got {got}")
+    ok = isinstance(tables, (tuple, list)) and len(tables) == 3
+    for n, ax in zip((z, y, x), tables if ok else ()):
+        ok = ok and isinstance(ax, (tuple, list)) and len(ax) == 3 and all(isinstance(t, torch.Tensor) and t.device == src.device
+                                                                            and t.is_contiguous() for t in ax)
+        ok = ok and ax[0].dtype == torch.int32 and tuple(ax[0].shape) == (n,) and all(t.dtype == torch.float32 and tuple(t.shape) == (n, 4)
+                                                                                      for t in ax[1:])
+    if not ok:
+        raise _l.RxError(f"elastic_apply: `tables` must be elastic_tables(({z}, {y}, {x}), spacing) on {src.device}")
+    if out is None:
+        out = torch.empty_like(src)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.shape != src.shape
+          or not out.is_contiguous()):
+        raise _l.RxError(f"elastic_apply: `out` must be a contiguous float32 device tensor of shape {tuple(src.shape)}")
+    rec = _l.RxElasticTables(*[t.data_ptr() for ax in tables for t in ax])
+    timed_bytes("elastic_apply", 2 * src.numel() * 4,
+                lambda: check(load().rx_elastic_apply(_ptr(src), _ptr(out), b, c, z, y, x, _ptr(nodes), I3(*sp), byref(rec), INTERP[interp],
+                                                      BORDER[border], float(fill), 1 if vector else 0, stream_ptr()), "rx_elastic_apply"))
+    return out
+
+
 def label_dilate(tensor, radius=5, out=None):
     """binary dilation with the ball of `radius` (1..8) of a float32 (B, C, Z, Y, X) device batch, every (sample, channel) volume
     on its own: 1.0 where a voxel > 0 lies within the radius, else 0.0 (dataloading.dilate_device.dilate_numpy is the statement).

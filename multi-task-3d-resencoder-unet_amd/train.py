@@ -92,13 +92,14 @@ class DeviceFeeder:
     `batch["image"].to(device)`, train.py:199-203) the 33.5 MB of a cfg2 batch sit between two steps: 0.7 ms of a 17 ms step with
     the device idle (`scripts/step_timeline.py` on a `--through-trainer` trace: first kernel 707 us after the previous step's last)."""
 
-    def __init__(self, loader, device, augmenter=None, geometry=None, dilate=None, ingest=None, spatial=None):
+    def __init__(self, loader, device, augmenter=None, geometry=None, dilate=None, ingest=None, spatial=None, elastic=None):
         self.loader, self.device = loader, device
         self.ingest = ingest                # `DeviceIngest`: raw batches are copied in the store's dtype and scaled here, first
         self.dilate = dilate                # `DeviceDilate`: the label targets, in place, before geometry (the host order)
         self.augmenter = augmenter          # `DeviceAugmenter`: applied on the copy stream, under the running step like the copies
         self.geometry = geometry            # `DeviceGeometry`: the whole staged dict, before the image augmenter
         self.spatial = spatial              # `DeviceSpatial`: the whole staged dict, after geometry (the host order)
+        self.elastic = elastic              # `DeviceElastic`: the whole staged dict, after spatial (the host order)
         self.stream = torch.cuda.Stream(device)
         ring = getattr(loader, "collate_fn", None)
         self.ring = ring if isinstance(ring, PinnedRingCollate) else None
@@ -126,6 +127,8 @@ class DeviceFeeder:
                 dev = self.geometry(dev)
             if self.spatial is not None:
                 dev = self.spatial(dev)
+            if self.elastic is not None:
+                dev = self.elastic(dev)
             if self.augmenter is not None:
                 dev["image"] = self.augmenter(dev["image"])
             ev = torch.cuda.Event()
@@ -346,6 +349,15 @@ class BaseTrainer:
             spatial = DeviceSpatial(rotation=spa_cfg["rotation"], scale=spa_cfg["scale"], normal_keys=spa_cfg["normal_keys"],
                                     image_border=spa_cfg["image_border"], rank=self.rank)
         self.device_spatial = spatial
+        # dataset_config.elastic with where: device -- a B-spline deformation of image AND targets (normals as covectors) as one
+        # HIP resampling pass per tensor, in the same two places, after spatial and before the intensity stack
+        elastic = None
+        ela_cfg = getattr(dataset, "device_elastic", None)
+        if ela_cfg is not None:
+            from .dataloading.elastic_device import DeviceElastic
+            elastic = DeviceElastic(spacing=ela_cfg["spacing"], magnitude=ela_cfg["magnitude"], p=ela_cfg["p"],
+                                    normal_keys=ela_cfg["normal_keys"], image_border=ela_cfg["image_border"], rank=self.rank)
+        self.device_elastic = elastic
         # tr_setup.dilate_label with dataset_config.dilate.where: device -- the dataset hands out raw labels and the ball dilation
         # runs as a HIP pass on the targets, in the same two places and before geometry (the host order; the stages commute)
         dilate = None
@@ -372,7 +384,7 @@ class BaseTrainer:
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
             if ingest is not None and not staged:    # each tensor in its own dtype; from here on the batch is what `where: host` gives
                 batch = ingest({k: v.to(device, non_blocking=True) for k, v in batch.items()})
-            if (dilate is not None or geometry is not None or spatial is not None) and not staged:      # (after ingest: fresh device tensors already)
+            if (dilate is not None or geometry is not None or spatial is not None or elastic is not None) and not staged:      # (after ingest: fresh device tensors already)
                 batch = {k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
                 if dilate is not None:      # (the copies above are fresh device tensors: dilating them in place touches nothing else)
                     batch = dilate(batch)
@@ -380,6 +392,8 @@ class BaseTrainer:
                     batch = geometry(batch)
                 if spatial is not None:
                     batch = spatial(batch)
+                if elastic is not None:
+                    batch = elastic(batch)
             x = batch["image"].to(device, dtype=torch.float32, non_blocking=True)
             if augmenter is not None and not staged:
                 x = augmenter(x)
@@ -409,7 +423,8 @@ class BaseTrainer:
             steps, patches = 0, 0
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
-            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry, dilate=dilate, ingest=ingest, spatial=spatial)
+            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry, dilate=dilate, ingest=ingest, spatial=spatial,
+                                   elastic=elastic)
                       if device.type == "cuda" and os.environ.get("RX_DEVICE_FEEDER", "1") != "0" else train_loader)
             for i, batch in enumerate(feeder):
                 if i >= self.mgr.max_steps_per_epoch:
