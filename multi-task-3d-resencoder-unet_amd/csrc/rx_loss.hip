@@ -44,7 +44,7 @@ __device__ inline float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
 // grid (chunks, N*C): plane nc = one (sample, channel) of V contiguous floats
 __global__ __launch_bounds__(RX_LOSS_BLOCK) void bce_dice_partial_kernel(const float* __restrict__ x, const float* __restrict__ t, long V,
-                                                                          float smoothing, float* __restrict__ partial) {
+                                                                          float smoothing, int aligned, float* __restrict__ partial) {
   const long plane = (long)blockIdx.y * V;
   const long begin = (long)blockIdx.x * RX_LOSS_ELEMS_PER_BLOCK;
   const long end = begin + RX_LOSS_ELEMS_PER_BLOCK < V ? begin + RX_LOSS_ELEMS_PER_BLOCK : V;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(RX_LOSS_BLOCK) void bce_dice_partial_kernel(const f
     acc[2] += p * p;
     acc[3] += tv * tv;
   };
-  const bool vec = ((plane & 3) == 0) && ((V & 3) == 0);
+  const bool vec = aligned && ((plane & 3) == 0) && ((V & 3) == 0);   // aligned: the base pointers, from the host
   if (vec) {
     for (long i = begin + 4 * threadIdx.x; i < end; i += 4 * RX_LOSS_BLOCK) {
       const f32x4 xv = *reinterpret_cast<const f32x4*>(x + plane + i);
@@ -113,19 +113,21 @@ __global__ __launch_bounds__(256) void bce_dice_finalize_kernel(const float* __r
 __global__ __launch_bounds__(RX_LOSS_BLOCK) void bce_dice_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, long V, int C,
                                                                       float smoothing, float k_bce, float k_dice,
                                                                       const float* __restrict__ coef, const float* __restrict__ gloss,
-                                                                      float* __restrict__ dx) {
+                                                                      int aligned, float* __restrict__ dx) {
   const int c = blockIdx.y % C;
   const long plane = (long)blockIdx.y * V;
   const long begin = (long)blockIdx.x * RX_LOSS_ELEMS_PER_BLOCK;
   const long end = begin + RX_LOSS_ELEMS_PER_BLOCK < V ? begin + RX_LOSS_ELEMS_PER_BLOCK : V;
   const float g = gloss ? *gloss : 1.f;
   const float a = coef[2 * c], b = coef[2 * c + 1];
+  // no contraction: the 16-byte and the scalar path must round alike, so that a misaligned call gives the aligned call's bits
   auto one = [&](float xv, float tv) {
+#pragma clang fp contract(off)
     const float ts = tv * (1.f - 2.f * smoothing) + smoothing;
     const float p = sigmoidf_(xv);
     return g * (k_bce * (p - ts) - k_dice * (a * tv - b * p) * p * (1.f - p));
   };
-  const bool vec = ((plane & 3) == 0) && ((V & 3) == 0);
+  const bool vec = aligned && ((plane & 3) == 0) && ((V & 3) == 0);   // aligned: the base pointers, from the host
   if (vec) {
     for (long i = begin + 4 * threadIdx.x; i < end; i += 4 * RX_LOSS_BLOCK) {
       const f32x4 xv = *reinterpret_cast<const f32x4*>(x + plane + i);
@@ -198,18 +200,24 @@ __global__ __launch_bounds__(RX_LOSS_BLOCK) void masked_cosine_bwd_kernel(const 
         pp += p[c] * p[c], tt += t[c] * t[c], pt += p[c] * t[c];
       }
     const float pn = sqrtf(pp), tn = sqrtf(tt);
-    // d cos / d pred = (t/|t| - cos * pred/|pred|) / |pred|   (the 1e-8 clamps of the forward are inactive wherever
-    // |pred| >= 1e-8; below that the torch graph's gradient is through the clamp constant -- zero direction term)
-    const bool on = tn > 1e-6f && pn >= 1e-8f;
-    const float inv_p = on ? 1.f / pn : 0.f, inv_t = on ? 1.f / tn : 0.f;
-    const float cs = pt * inv_p * inv_t;
+    // The graph of the host formulation, u = pred / pc with pc = max(|pred|, 1e-8), cos = (u . t) / (uc * |t|) with uc = max(|u|, 1e-8):
+    //   d cos / d pred = (t/|t| - cos * pred/|pred|) / (uc * pc)
+    // Where |pred| >= 1e-8 both clamps are inactive and uc * pc = |pred|.  Below that u = pred / 1e-8 is still linear in pred and the
+    // cosine is scale-invariant, so down to |pred| = 1e-16 (|u| = 1e-8) the product is |pred| again: the same expression.  Below
+    // 1e-16 the second clamp holds uc at 1e-8 and cos shrinks with |u|; at pred == 0 what is left is t/|t| * 1e16.
+    const bool on = tn > 1e-6f;
+    const float pc = fmaxf(pn, 1e-8f);
+    const float scale = pn >= 1e-8f ? 1.f / pn : 1.f / (fmaxf(pn / pc, 1e-8f) * pc);
+    const float inv_p = pn > 0.f ? 1.f / pn : 0.f, inv_t = on ? 1.f / tn : 0.f;
+    const float cs = pt * scale * inv_t;
 #pragma unroll
     for (int c = 0; c < RX_COS_MAXC; ++c)
-      if (c < C) dp[base + c * V + i] = on ? k * (t[c] * inv_t - cs * p[c] * inv_p) * inv_p : 0.f;
+      if (c < C) dp[base + c * V + i] = on ? k * (t[c] * inv_t - cs * p[c] * inv_p) * scale : 0.f;
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline int loss_chunks(long V) { return (int)((V + RX_LOSS_ELEMS_PER_BLOCK - 1) / RX_LOSS_ELEMS_PER_BLOCK); }
 
 extern "C" size_t rx_loss_workspace(int n, int c, long v) {
@@ -224,8 +232,9 @@ extern "C" int rx_bce_dice_loss_fwd(const float* logits, const float* target, in
   if (!loss_args_ok(logits, target, n, c, v) || !loss || !coef || !ws) RX_FAIL(RX_EINVAL, "rx_bce_dice_loss_fwd: bad arguments");
   if (ws_bytes < rx_loss_workspace(n, c, v)) RX_FAIL(RX_EWORKSPACE, "rx_bce_dice_loss_fwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int chunks = loss_chunks(v);
-  hipLaunchKernelGGL(bce_dice_partial_kernel, dim3(chunks, n * c), dim3(RX_LOSS_BLOCK), 0, st, logits, target, v, smoothing, (float*)ws);
+  const int chunks = loss_chunks(v), aligned = aligned16(logits) && aligned16(target);
+  hipLaunchKernelGGL(bce_dice_partial_kernel, dim3(chunks, n * c), dim3(RX_LOSS_BLOCK), 0, st, logits, target, v, smoothing, aligned,
+                     (float*)ws);
   hipLaunchKernelGGL(bce_dice_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, n, c, chunks, (double)n * c * (double)v, alpha,
                      beta, eps, loss, coef);
   RX_CHECK_LAUNCH("rx_bce_dice_loss_fwd");
@@ -237,8 +246,9 @@ extern "C" int rx_bce_dice_loss_bwd(const float* logits, const float* target, in
   if (!loss_args_ok(logits, target, n, c, v) || !coef || !dlogits) RX_FAIL(RX_EINVAL, "rx_bce_dice_loss_bwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   const float k_bce = (float)((double)alpha / ((double)n * c * (double)v)), k_dice = beta / c;
+  const int aligned = aligned16(logits) && aligned16(target) && aligned16(dlogits);
   hipLaunchKernelGGL(bce_dice_bwd_kernel, dim3(loss_chunks(v), n * c), dim3(RX_LOSS_BLOCK), 0, st, logits, target, v, c, smoothing, k_bce,
-                     k_dice, coef, grad_loss, dlogits);
+                     k_dice, coef, grad_loss, aligned, dlogits);
   RX_CHECK_LAUNCH("rx_bce_dice_loss_bwd");
   return RX_OK;
 }
@@ -520,8 +530,6 @@ __global__ __launch_bounds__(RX_LOSS_BLOCK) void ce_bwd_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static int elem_args_ok(int kind, const float* alpha_z, int z, int n, int c, long v, int reduction) {
   if (kind < RX_LOSS_BCE_LOGITS || kind > RX_LOSS_MSE) return 0;
   if (reduction != RX_REDUCE_MEAN && reduction != RX_REDUCE_SUM) return 0;

@@ -4,7 +4,11 @@
   * CPU (`-m "not gpu"`): the torch formulation shipped for host tensors reproduces the reference to fp32 round-off.
   * GPU (`-m gpu`): the single-pass HIP kernels (csrc/rx_loss.hip, through the C ABI) against the same vectors --
     tolerance 2e-6 absolute on the loss value (fp32 partial sums, fp64 combination) and 2e-5 rel-L2 on d(loss)/d(pred) --
-    and, at the BASELINE size (2,1,128^3), against the torch formulation evaluated on the device."""
+    and, at the BASELINE size (2,1,128^3), against the torch formulation evaluated on the device.
+
+These bounds judge a whole tensor.  The per-element checks of the same kernels -- every dispatch path, guarded and NaN-poisoned
+outputs, value edges, each gradient element against an fp64 reference -- are in tests/test_loss_ops_gpu.py (reference and bounds:
+tests/loss_ref.py)."""
 import os
 
 import numpy as np

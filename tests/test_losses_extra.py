@@ -8,7 +8,11 @@ MSELoss, CrossEntropyLoss -- against vectors produced by the reference's classes
     of tests/test_losses.py -- 2e-6 absolute on a mean-reduced loss, 2e-5 rel-L2 on the gradient.  A sum-reduced loss is judged
     relative to the float64 value of the fixture (`loss64`): within 4x the relative error of torch's own fp32 CPU result for
     that case (another summation order of the same fp32 terms), floor 2e-6.  Then the fallbacks, the dtype rule, and larger
-    shapes against the torch formulation evaluated on the device."""
+    shapes against the torch formulation evaluated on the device.
+
+These bounds judge a whole tensor.  The per-element checks of the same kernels -- every dispatch path, guarded and NaN-poisoned
+outputs, value edges, each gradient element against an fp64 reference -- are in tests/test_loss_ops_gpu.py (reference and bounds:
+tests/loss_ref.py)."""
 import ctypes
 import importlib.util
 import os
