@@ -11,7 +11,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from exact_ops import U32, assert_bits, assert_within, half_ulp, poisoned
+from exact_ops import U32, assert_bits, assert_exact_precondition, assert_within, exact_tensor, half_ulp, poisoned
 from test_ops_gpu import (TOL, check_norm_bwd, check_norm_fwd, check_stats, exact_conv_pass, exact_conv_ref, exact_convT_pass,
                           last_kernel, lrelu_mask, nan_act, norm_bwd_ref, out_dim, rel, rnd, to_act)
 
@@ -244,3 +244,68 @@ def test_random_fused_conv_norm_entry_points(ops, dtype, i):
         ops.avgpool_fwd(o1, p1, (2, 2, 2))
         ops.instnorm_act_pool_fwd(y1, s1, o2, p2, (2, 2, 2), 0.01, res)
         assert torch.equal(o1.t, o2.t) and torch.equal(p1.t, p2.t), (c, dims, n)
+
+
+# ---- stem / head: random widths, kernels, extents and layouts on exact integer data ----------------------------------------------
+def stem_draws(n=24):
+    rng = random.Random(int(os.environ.get("RX_FUZZ_SEED", "31337")) + 4)
+    out = []
+    while len(out) < n:
+        cin, co = rng.randint(1, 8), rng.choice([16, 32, 64])
+        k = tuple(rng.choice([1, 3]) for _ in range(3))
+        dims = tuple(rng.randint(3, 40) for _ in range(3))
+        nb = rng.choice([1, 2, 3])
+        if nb * dims[0] * dims[1] * dims[2] > 24000:               # the fp64 reference of a draw stays well under a second
+            continue
+        out.append((cin, co, k, dims, nb, rng.choice(["dense", "lo", "hi"])))
+    return out
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, torch.float16])
+@pytest.mark.parametrize("i", range(24))
+def test_random_stem(ops, dtype, i):
+    """rx_stem_conv_fwd / _fwd_stats / _bwd_weight on exact data: y rounded once (both entry points, the same bits), dw bit for bit"""
+    from test_stem_head_gpu import DW_NAMES, Out, in_layout, ncdhw
+    cin, co, k, dims, n, layout = stem_draws()[i]
+    what = f"stem draw {i}: {(cin, co, k, dims, n, layout)}"
+    sd, pad, V = 7000 + 10 * i, [(kk - 1) // 2 for kk in k], dims[0] * dims[1] * dims[2]
+    x = exact_tensor((n, cin, *dims), sd, -4, 4, 0.5, 2.0 ** -2)
+    w = exact_tensor((co, cin, *k), sd + 1, -4, 4, 0.5, 2.0 ** -3)
+    b = exact_tensor((co,), sd + 2, -16, 16, 1.0, 2.0 ** -5)
+    g = exact_tensor((n, co, *dims), sd + 3, -4, 4, 0.5, 2.0 ** -2)
+    assert_exact_precondition(None, (x, w), 2.0 ** -5, terms=cin * k[0] * k[1] * k[2], extra=b, what="stem y")
+    assert_exact_precondition(None, (x, g), 2.0 ** -4, terms=n * V, out16=False, what="stem dw")
+    y_ref = F.conv3d(x, w, b, padding=pad)
+    dw_ref = torch.nn.grad.conv3d_weight(x, tuple(w.shape), g, padding=pad)
+    xd, wd, bd = x.float().cuda().contiguous(), w.float().cuda(), b.float().cuda()
+    ya, yb = Out(ops, n, dims, co, dtype, layout), Out(ops, n, dims, co, dtype, layout)
+    ops.stem_conv_fwd(xd, wd, bd, ya.act, k)
+    ops.stem_conv_fwd_stats(xd, wd, bd, yb.act, k, poisoned((n, co, 2)))
+    for yy in (ya, yb):
+        yy.check(what)
+        assert_bits(ncdhw(yy.act), y_ref, dtype, f"{what} y")
+    dw = poisoned(tuple(w.shape))
+    ops.stem_conv_bwd_weight(xd, in_layout(ops, g, dtype, layout), dw, k)
+    assert_bits(dw, dw_ref, torch.float32, f"{what} dw", names=DW_NAMES)
+
+
+def head_draws(n=24):
+    rng = random.Random(int(os.environ.get("RX_FUZZ_SEED", "31337")) + 5)
+    out = []
+    while len(out) < n:
+        c, k = rng.choice([16, 32, 64]), rng.randint(1, 20)
+        dims = tuple(rng.randint(3, 40) for _ in range(3))
+        nb = rng.choice([1, 2, 3])
+        if nb * dims[0] * dims[1] * dims[2] > 24000:
+            continue
+        out.append((c, k, dims, nb, rng.choice(["dense", "lo", "hi"])))
+    return out
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, torch.float16])
+@pytest.mark.parametrize("i", range(24))
+def test_random_head(ops, dtype, i):
+    """rx_head_fwd / rx_head_bwd on exact data: logits, dw, db bit for bit, dx rounded once between guard channels"""
+    from test_stem_head_gpu import head_exact_pass, head_ref
+    c, k, dims, n, layout = head_draws()[i]
+    head_exact_pass(ops, head_ref(n, c, k, dims, exact_only=True), dtype, layout, f"head draw {i}: {(c, k, dims, n, layout)}")
