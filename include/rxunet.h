@@ -614,6 +614,29 @@ size_t rx_normal_stats_workspace(int n, long v); /* bytes of partials (0 for non
 int rx_normal_stats(const void* pred, int pred_dtype, const float* target, int n, long v, int64_t* count, double* sums, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ---- validation preview on the device: one panel of the debug GIF (host side training/visualization/preview.py, whose
+ *      panel_numpy and minmax_numpy are the statements).  `src` is ONE sample's contiguous (c, z, h, w) block of `dtype` (rx_dtype),
+ *      aligned to its element (a base that is not 16-byte aligned is fine).  c == 3 draws channels 0, 1, 2 into bytes 0, 1, 2 of
+ *      a pixel, each scaled by its own range; any other c draws channel 0 as grey (the same byte three times).  Kept slice j is
+ *      source slice j * z_step, j < z_kept = ceil(z / z_step).  Its h x w x 3 bytes go to
+ *        frames + j * frame_stride + (y0 + row) * row_stride + 3 * (x0 + col)
+ *      and nothing outside that rectangle is written; nothing outside the sample is read; every offset is 64-bit.
+ *      Per drawn channel and kept slice, in float32 with one rounding per operation, nothing contracted into an fma, IEEE
+ *      division: v = the element (`sigmoid` != 0: v = 1.0f / (1.0f + expf(-v)), the device's expf), lo = min v, hi = max v,
+ *      r = hi - lo; if every v is finite, r > 1e-6f and r is finite, the byte is trunc(((v - lo) / r) * 255.0f), else the whole
+ *      slice is 127 (= trunc(0.5 * 255): a flat slice, and by this library's own rule a slice that holds a NaN or an infinity).
+ *      `minmax` (nullable, 4-byte aligned): float32 (c_drawn, z_kept, 2) = (lo, hi), or (NaN, NaN) for a slice that holds a NaN
+ *      or an infinity.
+ *      One launch draws the panel: one workgroup per kept slice reduces lo / hi / "not finite" per lane, wave (shuffles) and
+ *      workgroup (LDS) -- no atomics, so nothing depends on arrival order -- then reads its slice again (from L2) and writes the
+ *      bytes.  Both passes read a scalar head up to the first 16-byte boundary of the slice of channel 0, 16-byte vectors, a scalar
+ *      tail.  The bytes are staged in LDS in pixel order and stored as whole dwords wherever a destination dword lies inside a
+ *      panel row (row_stride and 3 * x0 need not be multiples of 4; the rest are byte stores).  No allocation, copy or
+ *      synchronisation.  RX_EINVAL before anything is launched: null src or frames, non-positive c / z / h / w / z_step, an unknown
+ *      dtype, a misaligned src or minmax, negative y0 or x0, row_stride < 3 * (x0 + w), frame_stride < (y0 + h) * row_stride. */
+int rx_preview_panel(const void* src, int dtype, int c, int z, int h, int w, int z_step, int sigmoid, uint8_t* frames,
+                     long frame_stride, long row_stride, int y0, int x0, float* minmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

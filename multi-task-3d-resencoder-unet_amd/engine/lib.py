@@ -176,6 +176,8 @@ _SIGNATURES = {
     "rx_class_counts": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_long, c_void_p, c_void_p]),
     "rx_normal_stats_workspace": (c_size_t, [c_int, c_long]),
     "rx_normal_stats": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rx_preview_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int,
+                                 c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1046,6 +1046,102 @@ def normal_stats(pred, target, out=None, ws=None):
     return count, sums
 
 
+# ---- validation preview (training/visualization/preview.py holds the numpy statements, the config and the GIF writer) -------------
+def _preview_vol(fn, vol):
+    if not isinstance(vol, torch.Tensor) or not vol.is_cuda:
+        raise _l.RxError(f"{fn}: the volume must be a device tensor (the host statement is training.visualization.panel_numpy)")
+    if vol.dtype not in _l.DTYPE_CODE:
+        raise _l.RxError(f"{fn}: volume dtype {vol.dtype} (float32, bfloat16 or float16)")
+    if vol.dim() != 4 or vol.numel() == 0:
+        raise _l.RxError(f"{fn}: expected one sample's non-empty (C, Z, H, W) volume, got {tuple(vol.shape)}")
+    if not vol.is_contiguous():
+        raise _l.RxError(f"{fn}: the sample must be contiguous (strides {vol.stride()} for shape {tuple(vol.shape)})")
+    return vol
+
+
+def _preview_launch(vol, frames, y0, x0, z_step, sigmoid, minmax):
+    c, z, h, w = vol.shape
+    check(load().rx_preview_panel(_ptr(vol), _code(vol.dtype), c, z, h, w, z_step, 1 if sigmoid else 0, _ptr(frames), frames.stride(0),
+                                  frames.stride(1), y0, x0, _ptr(minmax), stream_ptr()), "rx_preview_panel")
+
+
+def _preview_bytes(vol, z_step):
+    c, z, h, w = vol.shape
+    zk = -(-z // z_step)
+    return zk * h * w * ((3 if c == 3 else 1) * vol.element_size() + 3)
+
+
+def preview_panel(vol4, frames, y0, x0, z_step=1, sigmoid=False, minmax=None):
+    """draws one sample's (C, Z, H, W) float32 / bfloat16 / float16 device volume into the uint8 device frames (Zf, Hf, Wf, 3) (rows and
+    pixels packed: strides (*, *, 3, 1)): the panel of kept slice j = source slice j * z_step occupies rows y0 .. y0 + H and
+    columns x0 .. x0 + W of frame j; nothing else is written.  Every slice of every drawn channel is scaled to its own range
+    (training.visualization.panel_numpy is the statement; `sigmoid` draws 1 / (1 + exp(-v))).  `minmax`: an optional contiguous
+    float32 (c_drawn, Zk, 2) device tensor that receives (lo, hi).  On the current stream, no synchronisation; returns `frames`."""
+    vol = _preview_vol("preview_panel", vol4)
+    c, z, h, w = vol.shape
+    z_step, y0, x0 = int(z_step), int(y0), int(x0)
+    if z_step < 1 or y0 < 0 or x0 < 0:
+        raise _l.RxError(f"preview_panel: z_step must be >= 1 and y0, x0 >= 0 (got z_step={z_step} y0={y0} x0={x0})")
+    zk = -(-z // z_step)
+    if (not isinstance(frames, torch.Tensor) or frames.device != vol.device or frames.dtype != torch.uint8 or frames.dim() != 4
+            or frames.shape[3] != 3 or frames.stride(3) != 1 or frames.stride(2) != 3):
+        raise _l.RxError(f"preview_panel: `frames` must be a uint8 (Z, H, W, 3) tensor with packed pixels on {vol.device}")
+    if frames.shape[0] < zk or frames.shape[1] < y0 + h or frames.shape[2] < x0 + w:
+        raise _l.RxError(f"preview_panel: a {zk} x {h} x {w} panel at (y0={y0}, x0={x0}) does not fit frames of shape {tuple(frames.shape)}")
+    if minmax is not None:
+        shape = (3 if c == 3 else 1, zk, 2)
+        if (not isinstance(minmax, torch.Tensor) or minmax.device != vol.device or minmax.dtype != torch.float32
+                or tuple(minmax.shape) != shape or not minmax.is_contiguous()):
+            raise _l.RxError(f"preview_panel: `minmax` must be a contiguous float32 tensor of shape {shape} on {vol.device}")
+    timed_bytes("preview_panel", _preview_bytes(vol, z_step), lambda: _preview_launch(vol, frames, y0, x0, z_step, sigmoid, minmax))
+    return frames
+
+
+def preview_frames(image, targets, preds, sample=0, every=1, sigmoid_tasks=(), out=None):
+    """the frames of the validation preview of one sample of a batch: image (B, C, Z, H, W), targets / preds {task: (B, C, Z, H, W)}
+    device tensors -> uint8 (Zk, 2H, (1 + T)W, 3) on the device, Zk = ceil(Z / every): the input panel and one target panel per task
+    (sorted by name) above a blank tile and the prediction panels (training.visualization.frames_numpy is the statement).  One
+    rx_preview_panel launch per panel on the current stream, no synchronisation.  The tensor is zeroed when it is created and the
+    blank tile is never written, so `out` -- a tensor an earlier call of the same shapes returned -- is reused as it is."""
+    names = sorted(targets)
+    vols = [("image", image, False)] + [(f"targets['{n}']", targets[n], False) for n in names]
+    for n in names:
+        if n not in preds:
+            raise _l.RxError(f"preview_frames: no prediction for task '{n}'")
+        vols.append((f"preds['{n}']", preds[n], None))
+    sample, every = int(sample), int(every)
+    if every < 1:
+        raise _l.RxError(f"preview_frames: every must be >= 1 (got {every})")
+    samples = []
+    for label, t, _ in vols:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _l.RxError(f"preview_frames: {label} must be a device tensor")
+        if t.dim() != 5:
+            raise _l.RxError(f"preview_frames: {label}: expected (B, C, Z, H, W), got {tuple(t.shape)} (2-D patches have no slices to page through)")
+        if not 0 <= sample < t.shape[0]:
+            raise _l.RxError(f"preview_frames: sample {sample} of a batch of {t.shape[0]}")
+        samples.append(_preview_vol("preview_frames", t[sample]))
+    z, h, w = samples[0].shape[1:]
+    for (label, _, _), s in zip(vols, samples):
+        if tuple(s.shape[1:]) != (z, h, w) or s.device != samples[0].device:
+            raise _l.RxError(f"preview_frames: {label} is {tuple(s.shape[1:])} on {s.device}, the image {(z, h, w)} on {samples[0].device}")
+    t_n = len(names)
+    shape = (-(-z // every), 2 * h, (1 + t_n) * w, 3)
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.uint8, device=samples[0].device)
+    elif (not isinstance(out, torch.Tensor) or out.device != samples[0].device or out.dtype != torch.uint8 or tuple(out.shape) != shape
+          or not out.is_contiguous()):
+        raise _l.RxError(f"preview_frames: `out` must be a contiguous uint8 tensor of shape {shape} on {samples[0].device}")
+
+    def run():
+        for i, s in enumerate(samples):
+            row, col = divmod(i, 1 + t_n) if i <= t_n else (1, i - t_n)
+            sig = i > t_n and names[i - t_n - 1] in sigmoid_tasks and s.shape[0] == 1
+            _preview_launch(s, out, row * h, col * w, every, sig, None)
+    timed_bytes("preview_frames", sum(_preview_bytes(s, every) for s in samples), run)
+    return out
+
+
 def aug_philox_u32(key, n, device):
     """test hook: the raw Philox4x32-10 outputs behind the noise of voxels 0..n-1 -> int64 tensor of the uint32 values"""
     out = torch.empty(n, dtype=torch.int32, device=device)

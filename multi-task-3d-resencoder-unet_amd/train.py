@@ -14,7 +14,11 @@ CosineAnnealingLR stepped per epoch, final `<model_name>_final.pth`).  Differenc
   * launched under `torch.distributed.run` it becomes data parallel (RCCL all-reduce overlapped with backward,
     engine/ddp.py) -- the reference is single-GPU;
   * the CLI passes arguments by keyword (the reference swaps `verbose` / `debug_dataloader` positionally);
-  * TensorBoard / debug GIFs are optional extras and skipped when their packages are missing;
+  * TensorBoard is an optional extra and skipped when its package is missing;
+  * the reference's `<model_name>_debug.gif` (input, targets and predictions of one sample of validation step 0, slice by slice)
+    is written when `tr_config.val_preview` asks for it (absent / false: off, and then nothing below differs): the panels are
+    drawn on the device (training/visualization, one HIP launch per panel), the only device-to-host copy is the finished uint8
+    frames, and the file is written through PIL (skipped when PIL is missing);
   * `tr_config.val_metrics` (absent / false: off, and then nothing below differs) adds Dice / IoU / precision / recall of the
     segmentation heads and the angular error of a normals head to the validation pass (training/metrics, HIP kernels, one host
     copy per epoch), writes them and the validation losses to TensorBoard, and with `best` keeps `<model_name>.best.pth`.
@@ -38,6 +42,7 @@ from .engine.streamed_step import StreamedOptimizerStep
 from .training.losses.losses import LOSS_FN_MAP
 from .training.metrics import ValidationMetrics, parse_config as parse_val_metrics
 from .training.optim import clip_and_step
+from .training.visualization import parse_config as parse_val_preview, sigmoid_tasks_of, write_gif
 
 _AMP = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": None}
 
@@ -161,6 +166,9 @@ class BaseTrainer:
         self.val_metrics_config = parse_val_metrics(self.mgr.tr_configs.get("val_metrics"), self.mgr.tasks)
         self.last_val_metrics = None
         self.best_val_metric = None
+        # tr_config.val_preview: checked here for the same reason
+        self.val_preview_config = parse_val_preview(self.mgr.tr_configs.get("val_preview"), self.mgr.tasks, self.mgr.model_name)
+        self.last_val_preview = None
 
     # ---- hooks ----------------------------------------------------------------------------------
     def _build_model(self):
@@ -379,6 +387,26 @@ class BaseTrainer:
         # tr_config.val_metrics: counts and sums accumulate on the device over the validation loop
         val_metrics = ValidationMetrics(self.mgr.tasks, self.val_metrics_config) if self.val_metrics_config is not None else None
         best_cfg = self.val_metrics_config["best"] if self.val_metrics_config is not None else None
+        # tr_config.val_preview: rank 0 draws validation step 0 of each epoch on the device; `armed` is set before the validation
+        # loop, the frame tensor and the pinned host buffer are kept from epoch to epoch
+        preview = self.val_preview_config if self.rank == 0 else None
+        pv = {"armed": False, "frames": None, "pinned": None, "copied": None}
+
+        def draw_preview(x, targets, out):
+            from .engine import ops
+            pv["armed"] = False
+            if preview["sample"] >= x.shape[0]:
+                raise ValueError(f"tr_config.val_preview.sample: {preview['sample']} is outside the first validation batch of {x.shape[0]}")
+            cont = lambda t: t if t.is_contiguous() else t.contiguous()
+            pv["frames"] = ops.preview_frames(cont(x), {k: cont(targets[k]) for k in preview["tasks"]},
+                                              {k: cont(out[k].detach()) for k in preview["tasks"]}, sample=preview["sample"],
+                                              every=preview["every"], sigmoid_tasks=sigmoid_tasks_of(self.mgr.tasks, preview),
+                                              out=pv["frames"])
+            if pv["pinned"] is None or pv["pinned"].shape != pv["frames"].shape:
+                pv["pinned"] = torch.empty(pv["frames"].shape, dtype=torch.uint8, pin_memory=True)
+                pv["copied"] = torch.cuda.Event()
+            pv["pinned"].copy_(pv["frames"], non_blocking=True)
+            pv["copied"].record()
 
         def forward_loss(batch, train_mode):
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
@@ -415,6 +443,8 @@ class BaseTrainer:
                     per[name] = l.detach()
             if not train_mode and val_metrics is not None:
                 val_metrics.update(out, targets)      # kernels on this stream, no host sync; read out once after the loop
+            if not train_mode and preview is not None and pv["armed"]:
+                draw_preview(x, targets, out)         # one launch per panel on this stream, then a non-blocking copy of the frames
             return total, per, x.shape[0]
 
         for epoch in range(start_epoch, self.mgr.max_epoch):
@@ -470,6 +500,8 @@ class BaseTrainer:
             model.eval()
             if val_metrics is not None:
                 val_metrics.reset()
+            if preview is not None:
+                pv["armed"] = True
             with torch.no_grad():
                 vrun, vsteps = {t: 0.0 for t in self.mgr.tasks}, 0
                 for i, batch in enumerate(val_loader):
@@ -482,6 +514,10 @@ class BaseTrainer:
                 vrun = {k: float(v) for k, v in vrun.items()}
                 for k in vrun:
                     self._log(f"Task '{k}', epoch {epoch + 1} avg val loss: {vrun[k] / max(vsteps, 1):.4f}")
+                if preview is not None and not pv["armed"]:      # (still armed: the validation loop had no step)
+                    pv["copied"].synchronize()
+                    self.last_val_preview = pv["pinned"].numpy().copy()
+                    write_gif(self.last_val_preview, preview["path"], preview["fps"])
                 if val_metrics is not None:
                     self._report_val_metrics(val_metrics.compute(), vrun, vsteps, epoch, writer, best_cfg, ckpt_dir,
                                              lambda: {"model": model.state_dict(), "optimizer": optimizer.state_dict(),
