@@ -637,6 +637,37 @@ int rx_normal_stats(const void* pred, int pred_dtype, const float* target, int n
 int rx_preview_panel(const void* src, int dtype, int c, int z, int h, int w, int z_step, int sigmoid, uint8_t* frames,
                      long frame_stride, long row_stride, int y0, int x0, float* minmax, void* stream);
 
+/* ---- mesh targets on the device: triangle meshes sliced by the z-planes of a slab into normals / label / mask volumes (host side
+ *      tasks/normals/mesh_targets.py, whose slice_normals_numpy and slice_labels_numpy are the statements).  The reference paints a
+ *      slice serially, so a pixel keeps its last writer, i.e. the largest (triangle, pair, step, sample): rx_mesh_slice_keys
+ *      scatters that tuple as an order key with an integer atomic maximum (bit-identical run to run), and the resolve calls
+ *      recompute every pixel from its winning key alone.  Geometry, shared by the three calls: slices [z0, z0 + nz) of the full
+ *      w x h image, of which only the window rows [y0, y0 + wh) and columns [x0, x0 + ww) are stored; endpoint and pixel tests
+ *      use the full image, so a slab or window result equals the full result cropped.  `vertices` and `normals`: DEVICE fp32
+ *      (n_vertices, 3); `triangles`: DEVICE int32 (n_triangles, 3).  Device data cannot be validated here: the Python wrapper
+ *      refuses non-finite vertices or normals, coordinates at or beyond 2^24 and vertex indices outside [0, n_vertices); the
+ *      kernels clamp every vertex index and bound every loop regardless.  No allocation, copy or synchronisation.
+ *
+ *      rx_mesh_slice_keys: `keys` is the ZEROED (nz, wh, ww) key buffer: uint64 `(triangle + 1) << 26 | pair << 24 | step << 4 |
+ *      sample` for normals (labels == 0; `normals` and `exp_factor` are used), uint32 `triangle + 1` for labels (labels != 0).
+ *      RX_EINVAL before anything is launched: null or misaligned pointers, n_vertices outside [1, 2^31), non-positive sizes, sides
+ *      above 2^24, slices outside (-2^24, 2^24), a window outside the image, more triangles than the key holds (2^38 - 2, labels
+ *      2^32 - 2), an exp_factor whose int(4 * 1.2 * exp_factor + 1) samples are fewer than 2 or more than 16, an image whose
+ *      diagonal allows a segment of 2^20 steps or more. */
+int rx_mesh_slice_keys(int labels, const float* vertices, long n_vertices, const int32_t* triangles, long n_triangles,
+                       const float* normals, int w, int h, int z0, int nz, int y0, int x0, int wh, int ww, double exp_factor,
+                       void* keys, void* stream);
+/* out: uint16 (nz, wh, ww, 3) channels-last codes uint16((n + 1) * 32767.5), 0 where the key is 0.  viz (optional): uint8
+ * (nz, wh, ww, 3), the reference's preview byte.  mask (optional): uint8 (nz, wh, ww), 255 where any channel is non-zero.  All
+ * three 4-byte aligned: a workgroup stages its pixels in LDS and stores whole dwords, bytes only for the last dword of an array. */
+int rx_mesh_resolve_normals(const void* keys, const float* vertices, long n_vertices, const int32_t* triangles, long n_triangles,
+                            const float* normals, int w, int h, int z0, int nz, int y0, int x0, int wh, int ww, uint16_t* out,
+                            uint8_t* viz, uint8_t* mask, void* stream);
+/* out: uint16 [npix] = tri_labels[key - 1] & 0xffff (DEVICE int32 [n_triangles]), 0 where the key is 0; mask (optional): uint8
+ * [npix], 255 where the label is non-zero.  npix = nz * wh * ww. */
+int rx_mesh_resolve_labels(const void* keys, const int32_t* tri_labels, long n_triangles, long npix, uint16_t* out, uint8_t* mask,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,9 +158,10 @@ class ChunkedWriter:
     Z is the third axis from the end ((Z, Y, X) or (C, Z, Y, X)).  `write_rows(z0, block)` takes rows [z0, z0 + n): z0 on a chunk
     boundary and n a whole number of chunk rows, or the rows up to the end of the array (the partial edge chunks are stored at full
     chunk size, as `write_array` does).  Every chunk is an independent file, so the chunk writes of one call may run on a thread
-    pool (`pool.submit`; zlib releases the GIL): the call then returns the futures.  Refuses an existing path."""
+    pool (`pool.submit`; zlib releases the GIL): the call then returns the futures.  Refuses an existing path.
+    `axis` names the Z axis where it is not the third from the end: 0 for a channels-last (Z, Y, X, C) array."""
 
-    def __init__(self, path, shape, chunks, dtype, compressor=None, fill_value=0, dimension_separator="."):
+    def __init__(self, path, shape, chunks, dtype, compressor=None, fill_value=0, dimension_separator=".", axis=None):
         self.path = str(path)
         self.shape = tuple(int(s) for s in shape)
         self.chunks = tuple(int(c) for c in chunks)
@@ -174,7 +175,9 @@ class ChunkedWriter:
         if os.path.exists(self.path):
             raise FileExistsError(f"{self.path} already exists")
         self.compressor, self.fill_value, self.sep = compressor, fill_value, dimension_separator
-        self.axis = len(self.shape) - 3
+        self.axis = len(self.shape) - 3 if axis is None else int(axis)
+        if not 0 <= self.axis < len(self.shape):
+            raise ZarrLiteError(f"ChunkedWriter: axis {axis} of a {len(self.shape)}-dimensional array")
         os.makedirs(self.path)
         _write_meta(self.path, self.shape, self.chunks, self.dtype, compressor, fill_value, dimension_separator)
 

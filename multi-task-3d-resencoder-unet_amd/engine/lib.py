@@ -178,6 +178,11 @@ _SIGNATURES = {
     "rx_normal_stats": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rx_preview_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int,
                                  c_void_p, c_void_p]),
+    "rx_mesh_slice_keys": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   c_double, c_void_p, c_void_p]),
+    "rx_mesh_resolve_normals": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rx_mesh_resolve_labels": (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
