@@ -316,6 +316,19 @@ int rx_grad_norm_clip(int count, const float* const* grad, const long* numel, fl
 int rx_adamw_flat_multi(int count, float* const* p, const float* const* grad, float* const* exp_avg,
                         float* const* exp_avg_sq, const long* numel, const float* clip, double lr, double beta1,
                         double beta2, double eps, double weight_decay, int step, void* stream);
+/* SGD with momentum / Nesterov (torch.optim.SGD arithmetic in fp32; train.py:70-77 selects SGD(momentum=0.9, nesterov=True)):
+ *   g' = g * clip;  d = wd != 0 ? g' + wd * p : g';  buf = first ? d : momentum * buf + (1 - dampening) * d;
+ *   u = nesterov ? d + momentum * buf : buf  (momentum == 0: u = d);  p -= lr * u
+ * `buf` (momentum buffers) is NULL iff momentum == 0.  `first` != 0: the buffers do not exist yet -- they are written, never
+ * read -- and it holds for the whole call.  `clip`: optional DEVICE scalar, as for AdamW.  nesterov needs momentum > 0 and
+ * dampening == 0 (RX_EINVAL otherwise).  rx_sgd_flat_multi: `count` tensors, HOST arrays of device pointers;
+ * rx_sgd_pack: one conv / convT weight (kind, A, B, taps <= 27, w_fwd, w_bwd as in rx_adamw_pack), both packed copies rewritten. */
+int rx_sgd_flat_multi(int count, float* const* p, const float* const* grad, float* const* buf, const long* numel,
+                      const float* clip, double lr, double momentum, double dampening, double weight_decay, int nesterov,
+                      int first, void* stream);
+int rx_sgd_pack(rx_dtype dt, float* p, const float* grad, float* buf, const float* clip, double lr, double momentum,
+                double dampening, double weight_decay, int nesterov, int first, int kind, int A, int B, int taps, void* w_fwd,
+                void* w_bwd, void* stream);
 
 /* ---- launch programs: the launch list of a forward / backward pass, recorded once and replayed from C ------------------
  * The reference's model call is ONE Python call (`model(x)`, train.py:204; `loss.backward()`, :224) behind which the

@@ -1,5 +1,6 @@
 // rx_pack_optim.hip -- per-step work on the parameters: the weight packers of the conv kernels, AdamW (fused with the re-pack,
-// flat, and table-driven over many tensors) and the global gradient norm with its clip coefficient.
+// flat, and table-driven over many tensors), SGD with momentum / Nesterov in the same two shapes, and the global gradient norm with
+// its clip coefficient.
 #include <math.h>
 
 #include "rx_common.h"
@@ -497,6 +498,252 @@ extern "C" int rx_adamw_flat_multi(int count, float* const* p, const float* cons
     i0 += k;
   }
   RX_CHECK_LAUNCH("rx_adamw_flat_multi");
+  return RX_OK;
+}
+
+// ---- SGD with momentum / Nesterov (torch.optim.SGD arithmetic, `_single_tensor_sgd`) -----------------------------------------
+// The reference's other optimizer (train.py:70-77: SGD(momentum=0.9, nesterov=True)).  Same two shapes as AdamW above: a table
+// kernel over the un-packed parameters and a tile-walk kernel that also rewrites both packed copies of a conv / convT weight.
+//   g' = g * clip;  d = wd != 0 ? g' + wd * p : g';  buf = first ? d : mu * buf + (1 - dampening) * d;
+//   u = nesterov ? d + mu * buf : buf  (mu == 0: u = d, no buffer);  p -= lr * u
+// 16 bytes per parameter with momentum (read p, g, buf; write p, buf; 12 on a first step, which only writes buf), 12 without.
+struct SgdArgs {
+  float lr, mu, omd, wd;          // omd = 1 - dampening, formed in double and cast once
+  int nesterov, first;            // first: no momentum buffer yet -- buf is written, never read
+};
+
+template <bool MOM>
+__device__ inline float sgd_update(float p, float g, float& buf, const SgdArgs a) {
+  const float d = a.wd != 0.f ? g + a.wd * p : g;
+  float u = d;
+  if (MOM) {
+    buf = a.first ? d : a.mu * buf + a.omd * d;
+    u = a.nesterov ? d + a.mu * buf : buf;
+  }
+  return p - a.lr * u;
+}
+
+static SgdArgs sgd_args(double lr, double momentum, double dampening, double wd, int nesterov, int first) {
+  SgdArgs a;
+  a.lr = (float)lr, a.mu = (float)momentum, a.omd = (float)(1.0 - dampening), a.wd = (float)wd;
+  a.nesterov = nesterov != 0, a.first = first != 0;
+  return a;
+}
+
+static bool sgd_hypers_bad(double momentum, double dampening, int nesterov) {
+  return nesterov && (momentum <= 0.0 || dampening != 0.0);
+}
+
+// the store half of the pack tile walk for a tile that is already in LDS as [t][32 a][RX_PACK_PB] (what adamw_pack_kernel does
+// after its barrier), for any thread count
+template <typename T, int THREADS>
+__device__ __forceinline__ void pack_tile_store(const T* __restrict__ L, int A, int B, int TT, int a0, int b0, bool full,
+                                                T* __restrict__ same, T* __restrict__ swp) {
+  if (full) {
+    for (int vv = threadIdx.x; vv < TT * 128; vv += THREADS) {
+      const int t = vv >> 7, rem = vv & 127, row = rem >> 2, c8 = (rem & 3) * 8;
+      if (same) {
+        const u32x4 x = *reinterpret_cast<const u32x4*>(L + (t * 32 + row) * RX_PACK_PB + c8);
+        *reinterpret_cast<u32x4*>(same + ((size_t)t * A + a0 + row) * B + b0 + c8) = x;
+      }
+      if (swp) {
+        T vals[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vals[j] = L[(t * 32 + c8 + j) * RX_PACK_PB + row];
+        *reinterpret_cast<u32x4*>(swp + ((size_t)t * B + b0 + row) * A + a0 + c8) = *reinterpret_cast<u32x4*>(vals);
+      }
+    }
+    return;
+  }
+  for (int i = threadIdx.x; i < TT * 32 * 32; i += THREADS) {
+    const int t = i / 1024, r = i - t * 1024;
+    {
+      const int a = r >> 5, b = r & 31;
+      if (same && a0 + a < A && b0 + b < B) same[((size_t)t * A + a0 + a) * B + b0 + b] = L[(t * 32 + a) * RX_PACK_PB + b];
+    }
+    {
+      const int b = r >> 5, a = r & 31;
+      if (swp && a0 + a < A && b0 + b < B) swp[((size_t)t * B + b0 + b) * A + a0 + a] = L[(t * 32 + a) * RX_PACK_PB + b];
+    }
+  }
+}
+
+// (the packed values are the cast of stored_f32(p'): the last multiply-subtract of sgd_update has the same f16 tie hazard as AdamW's)
+template <typename T, bool MOM>
+__global__ __launch_bounds__(256) void sgd_pack_kernel(float* __restrict__ w, const float* __restrict__ grad, float* __restrict__ buf,
+                                                       const float* __restrict__ clip, const SgdArgs aa, int A, int B, int TT,
+                                                       unsigned inv_tt, T* __restrict__ same, T* __restrict__ swp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pack_smem[];
+  T* L = reinterpret_cast<T*>(pack_smem);               // [TT][32 a][RX_PACK_PB]
+  const int a0 = blockIdx.y * 32, b0 = blockIdx.x * 32;
+  const int rowlen = 32 * TT;
+  const float cs = clip ? *clip : 1.f;
+  const bool rd = MOM && !aa.first;
+  const bool full = a0 + 32 <= A && b0 + 32 <= B && sizeof(T) == 2 && (B & 7) == 0 && (A & 7) == 0;
+  if (full && TT > 1 && (rowlen & 3) == 0 && ((size_t)B * TT & 3) == 0) {
+    const int q4 = rowlen >> 2;
+    for (int q = threadIdx.x; q < 32 * q4; q += 256) {
+      const int a = q / q4, c = q - a * q4;
+      const size_t off = ((size_t)(a0 + a) * B + b0) * TT + 4 * c;
+      f32x4 pw = *reinterpret_cast<const f32x4*>(w + off);
+      const f32x4 pg = *reinterpret_cast<const f32x4*>(grad + off);
+      f32x4 pb = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (rd) pb = *reinterpret_cast<const f32x4*>(buf + off);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float bj = pb[j];
+        pw[j] = stored_f32(sgd_update<MOM>(pw[j], pg[j] * cs, bj, aa));
+        pb[j] = bj;
+      }
+      *reinterpret_cast<f32x4*>(w + off) = pw;
+      if (MOM) *reinterpret_cast<f32x4*>(buf + off) = pb;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned r = 4 * c + j;
+        const unsigned b = __umulhi(r, inv_tt), t = r - b * TT;
+        L[((int)t * 32 + a) * RX_PACK_PB + (int)b] = Elem<T>::from_f(pw[j]);
+      }
+    }
+  } else {
+    for (int i = threadIdx.x; i < 32 * rowlen; i += 256) {
+      const int a = i / rowlen, r = i - a * rowlen;
+      const int b = r / TT, t = r - b * TT;
+      float nw = 0.f;
+      if (a0 + a < A && b0 + b < B) {
+        const size_t off = ((size_t)(a0 + a) * B + b0) * TT + r;
+        float bj = rd ? buf[off] : 0.f;
+        nw = stored_f32(sgd_update<MOM>(w[off], grad[off] * cs, bj, aa));
+        w[off] = nw;
+        if (MOM) buf[off] = bj;
+      }
+      L[(t * 32 + a) * RX_PACK_PB + b] = Elem<T>::from_f(nw);
+    }
+  }
+  __syncthreads();
+  pack_tile_store<T, 256>(L, A, B, TT, a0, b0, full, same, swp);
+}
+
+// p (A,B,T), kind, w_fwd / w_bwd as in rx_adamw_pack.  `buf` = momentum buffer (NULL iff momentum == 0); `first` != 0: the
+// buffer does not exist yet and is written with d (torch: clone of the first gradient), never read.
+extern "C" int rx_sgd_pack(rx_dtype dt, float* p, const float* grad, float* buf, const float* clip, double lr, double momentum,
+                           double dampening, double weight_decay, int nesterov, int first, int kind, int A, int B, int taps,
+                           void* w_fwd, void* w_bwd, void* stream) {
+  const bool mom = momentum != 0.0;
+  if (!p || !grad || (mom && !buf) || A < 1 || B < 1 || taps < 1 || taps > 27 || sgd_hypers_bad(momentum, dampening, nesterov))
+    RX_FAIL(RX_EINVAL, "rx_sgd_pack: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  const SgdArgs aa = sgd_args(lr, momentum, dampening, weight_decay, nesterov, first);
+  void* same = kind == 0 ? w_fwd : w_bwd;
+  void* swp = kind == 0 ? w_bwd : w_fwd;
+  RX_DISPATCH_DTYPE(dt, T, {
+    size_t lds = (size_t)taps * 32 * RX_PACK_PB * sizeof(T);
+    const unsigned inv_tt = (unsigned)(((1ull << 32) + taps - 1) / taps);
+    if (mom) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sgd_pack_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((sgd_pack_kernel<T, true>), dim3((B + 31) / 32, (A + 31) / 32), dim3(256), lds, st, p, grad, buf, clip, aa, A, B,
+                         taps, inv_tt, (T*)same, (T*)swp);
+    } else {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sgd_pack_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((sgd_pack_kernel<T, false>), dim3((B + 31) / 32, (A + 31) / 32), dim3(256), lds, st, p, grad, (float*)nullptr, clip,
+                         aa, A, B, taps, inv_tt, (T*)same, (T*)swp);
+    }
+  });
+  RX_CHECK_LAUNCH("rx_sgd_pack");
+  return RX_OK;
+}
+
+// the AdamMulti table shape for SGD: 48 tensors per launch, one workgroup per 4096 elements, four 16-byte loads per array per
+// thread, all issued before the first use; scalar path for a misaligned pointer or a tail chunk
+struct SgdMulti {
+  float* p[RX_AM_MAX];
+  const float* g[RX_AM_MAX];
+  float* buf[RX_AM_MAX];
+  long n[RX_AM_MAX];
+  int start[RX_AM_MAX + 1];       // first workgroup of tensor i; start[count] = grid size
+  int count;
+};
+
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_multi_kernel(const SgdMulti t, const float* __restrict__ clip, const SgdArgs aa) {
+  const int b = blockIdx.x;
+  int lo = 0, hi = t.count;       // start[lo] <= b < start[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (t.start[mid] <= b) lo = mid; else hi = mid;
+  }
+  const long base = (long)(b - t.start[lo]) * RX_AM_CHUNK;
+  const long n = t.n[lo];
+  float* __restrict__ w = t.p[lo];
+  const float* __restrict__ grad = t.g[lo];
+  float* __restrict__ buf = MOM ? t.buf[lo] : nullptr;
+  const float cs = clip ? *clip : 1.f;
+  const bool rd = MOM && !aa.first;
+  const bool vec = (((uintptr_t)w | (uintptr_t)grad | (uintptr_t)buf) & 15) == 0;
+  if (vec && base + RX_AM_CHUNK <= n) {
+    f32x4 pw[4], pg[4], pb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long i = base + (long)(j * 256 + threadIdx.x) * 4;
+      pw[j] = *reinterpret_cast<const f32x4*>(w + i);
+      pg[j] = *reinterpret_cast<const f32x4*>(grad + i);
+      pb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (rd) pb[j] = *reinterpret_cast<const f32x4*>(buf + i);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long i = base + (long)(j * 256 + threadIdx.x) * 4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float bj = pb[j][k];
+        pw[j][k] = sgd_update<MOM>(pw[j][k], pg[j][k] * cs, bj, aa);
+        pb[j][k] = bj;
+      }
+      *reinterpret_cast<f32x4*>(w + i) = pw[j];
+      if (MOM) *reinterpret_cast<f32x4*>(buf + i) = pb[j];
+    }
+    return;
+  }
+  const long end = base + RX_AM_CHUNK < n ? base + RX_AM_CHUNK : n;
+  for (long i = base + threadIdx.x; i < end; i += 256) {
+    float bj = rd ? buf[i] : 0.f;
+    w[i] = sgd_update<MOM>(w[i], grad[i] * cs, bj, aa);
+    if (MOM) buf[i] = bj;
+  }
+}
+
+// `count` tensors of one param group that share `first` (all have a momentum buffer, or none has one yet).  `buf` is NULL
+// iff momentum == 0.  Pointer arrays are HOST arrays.
+extern "C" int rx_sgd_flat_multi(int count, float* const* p, const float* const* grad, float* const* buf, const long* numel,
+                                 const float* clip, double lr, double momentum, double dampening, double weight_decay, int nesterov,
+                                 int first, void* stream) {
+  const bool mom = momentum != 0.0;
+  if (count < 0 || (count > 0 && (!p || !grad || !numel || (mom && !buf))) || sgd_hypers_bad(momentum, dampening, nesterov))
+    RX_FAIL(RX_EINVAL, "rx_sgd_flat_multi: bad arguments");
+  const SgdArgs aa = sgd_args(lr, momentum, dampening, weight_decay, nesterov, first);
+  for (int i = 0; i < count; ++i)
+    if (!p[i] || !grad[i] || (mom && !buf[i]) || numel[i] < 1) RX_FAIL(RX_EINVAL, "rx_sgd_flat_multi: bad tensor %d", i);
+  for (int i0 = 0; i0 < count;) {
+    SgdMulti t;
+    int k = 0;
+    long blocks = 0;
+    for (; i0 + k < count && k < RX_AM_MAX; ++k) {
+      const long nb = (numel[i0 + k] + RX_AM_CHUNK - 1) / RX_AM_CHUNK;
+      if (blocks + nb > 0x3fffffffL) break;           // keep the grid inside int range
+      t.p[k] = p[i0 + k], t.g[k] = grad[i0 + k], t.buf[k] = mom ? buf[i0 + k] : nullptr, t.n[k] = numel[i0 + k];
+      t.start[k] = (int)blocks;
+      blocks += nb;
+    }
+    if (k == 0) RX_FAIL(RX_EINVAL, "rx_sgd_flat_multi: tensor %d too large", i0);
+    for (int q = k; q <= RX_AM_MAX; ++q) t.start[q] = (int)blocks;
+    for (int q = k; q < RX_AM_MAX; ++q) t.p[q] = nullptr, t.g[q] = nullptr, t.buf[q] = nullptr, t.n[q] = 0;
+    t.count = k;
+    if (mom)
+      hipLaunchKernelGGL(sgd_multi_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t, clip, aa);
+    else
+      hipLaunchKernelGGL(sgd_multi_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t, clip, aa);
+    i0 += k;
+  }
+  RX_CHECK_LAUNCH("rx_sgd_flat_multi");
   return RX_OK;
 }
 

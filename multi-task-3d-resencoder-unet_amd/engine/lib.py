@@ -131,6 +131,10 @@ _SIGNATURES = {
                               c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rx_adamw_flat_multi": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,
                                     c_double, c_double, c_int, c_void_p]),
+    "rx_sgd_flat_multi": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double,
+                                  c_int, c_int, c_void_p]),
+    "rx_sgd_pack": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double, c_int, c_int,
+                            c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rx_prog_create": (c_void_p, []),
     "rx_prog_destroy": (None, [c_void_p]),
     "rx_prog_begin": (c_int, [c_void_p, c_void_p, c_int]),

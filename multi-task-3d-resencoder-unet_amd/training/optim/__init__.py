@@ -1,4 +1,6 @@
 from .engine_adamw import EngineAdamW  # noqa: F401
+from .engine_base import EngineOptimizerBase  # noqa: F401
+from .engine_sgd import EngineSGD  # noqa: F401
 
 
 def clip_and_step(optimizer, params, max_norm, scaler=None):
@@ -7,14 +9,21 @@ def clip_and_step(optimizer, params, max_norm, scaler=None):
     `grad_scale` input (the hook GradScaler uses; the kernel divides every gradient by it on the fly and stores the result
     back into `.grad`), so the gradients are read once by the norm and once by the update -- 1.7 GB less HBM traffic
     per cfg2 step.  Same arithmetic as the two calls (g * c vs g / (1/c): one rounding), the same total norm is returned.
-    Anything else (an enabled GradScaler, a non-fused optimizer, EngineAdamW) takes the plain two-call path."""
+    The engine's own optimizers (EngineAdamW, EngineSGD) clip inside their kernels, with or without a GradScaler.  Anything else
+    (an enabled GradScaler, a non-fused optimizer) takes the plain two-call path."""
     import torch
     params = [p for p in params if p.grad is not None]
     fused = (isinstance(optimizer, (torch.optim.AdamW, torch.optim.Adam)) and optimizer.defaults.get("fused")
              and (scaler is None or not scaler.is_enabled()) and all(p.is_cuda for p in params))
-    if isinstance(optimizer, EngineAdamW):
+    if isinstance(optimizer, (EngineAdamW, EngineSGD)):
+        # the norm is taken on the gradients as they are -- still loss-scaled under an enabled GradScaler, as on the plain path
+        # below (clip first, unscale after: the reference's order); scaler.step() hands grad_scale / found_inf to the optimizer,
+        # whose kernels apply clip * (1 / grad_scale) on the fly
         total = optimizer.clip_grad_norm(max_norm)
-        optimizer.step()
+        if scaler is not None and scaler.is_enabled():
+            scaler.step(optimizer)
+        else:
+            optimizer.step()
         return total
     if not fused or not params:
         total = torch.nn.utils.clip_grad_norm_(params, max_norm)

@@ -21,6 +21,7 @@ import torch
 
 from ...engine import lib as _l
 from ...engine.lib import check, load, stream_ptr
+from .engine_base import amp_fold
 
 
 def _p(t):
@@ -28,6 +29,9 @@ def _p(t):
 
 
 class EngineAdamW(torch.optim.Optimizer):
+    # torch.amp.GradScaler sets `grad_scale` / `found_inf` on the optimizer around step() instead of unscaling the gradients itself
+    _step_supports_amp_scaling = True
+
     def __init__(self, params, model=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
@@ -83,6 +87,11 @@ class EngineAdamW(torch.optim.Optimizer):
         lib = load()
         clip = self._clip
         self._clip = None
+        # under a GradScaler: skip the whole step on an inf / NaN gradient (one host read, no launch, no state), else fold
+        # 1 / grad_scale into the scalar the kernels multiply into the gradient (engine_base.amp_fold)
+        skip, clip = amp_fold(self, clip)
+        if skip:
+            return loss
         for group in self.param_groups:
             b1, b2 = group["betas"]
             flat = []                      # un-packed parameters of this group: one C call for all of them (rx_adamw_flat_multi)
