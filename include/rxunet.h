@@ -390,6 +390,13 @@ int rx_sw_accumulate(const float* logits, int batch, int valid, int c, int pz, i
  * wsum too (ring rows are then ready for the rows that follow). */
 int rx_sw_finalize(float* sum, float* wsum, int c, int ring, int y, int x, int z0, int rows, int blend, int cast, int reset,
                    float* blended, void* final_out, float* wsum_out, void* stream);
+/* empty-patch skipping: counts[i] = the raw voxels v of the patch at origins[i], over all cin channels, with (float)v > value (a
+ * float compare: a NaN never counts; uint8 / uint16 are exact in fp32).  `origins`: n_pos x (z, y, x) in HOST memory (any n_pos
+ * >= 0, handed to the kernels by value, 256 patches per launch); `counts`: n_pos uint64 on the device, 8-byte aligned, zeroed by
+ * the call.  Integer adds only: exact and reproducible.  RX_EINVAL before anything is launched: an origin that leaves the slab,
+ * a patch that does not fit it, rows [min z, max z + pz) that do not fit the ring, a misaligned slab or counts pointer. */
+int rx_sw_occupancy(int in_dtype, const void* slab, int cin, int ring, int y, int x, int n_pos, const int32_t* origins, int pz,
+                    int py, int px, float value, uint64_t* counts, void* stream);
 
 /* ---- training augmentation on the device (reference dataloading/dataset.py:171-205; host restatement dataloading/augment.py).
  *      The image batch is contiguous fp32 (batch, c, z, y, x).  Parameters are drawn on the host and passed as ONE table per

@@ -72,6 +72,15 @@ class ConfigManager:
         self.infer_tta = ic.get("tta", None)
         nk = ic.get("tta_normal_keys", None)
         self.infer_tta_normal_keys = None if nk is None else tuple(str(k) for k in ((nk,) if isinstance(nk, str) else nk))
+        # Y/X tiles: "auto" or [ty, tx]; empty-patch skipping: true or {value, min_fraction}.  Absent: off.
+        from ..inference import check_skip_empty, check_tile
+        try:
+            self.infer_tile = check_tile(ic.get("tile", None), self.infer_patch_size)
+            self.infer_skip_empty = check_skip_empty(ic.get("skip_empty", None))
+        except ValueError as e:
+            raise ValueError(f"inference_config.{e}") from None
+        if self.infer_tile == "auto" and self.infer_max_device_gb is None:
+            raise ValueError("inference_config.tile: \"auto\" chooses the tile from max_device_gb, which is not set")
         if verbose:
             self._print_summary()
 

@@ -12,7 +12,8 @@
 //   rx_sw_accumulate_geom  rx_sw_accumulate of the TRANSFORMED prediction: destination voxel l of slot b adds the activated logit
 //                          at i(l), a 3-vector task with the record's component permutation and signs
 // both with the gather form of rx_geom_apply, out[o] = in[i(o)], i[src_axis[d]] = flip[d] ? n_d - 1 - o_d : o_d.
-// Deterministic: no atomics.  rx_sw_accumulate runs one thread per 4 destination voxels of the batch's bounding box, each adding
+// For empty-patch skipping, rx_sw_occupancy counts per patch the raw slab voxels above a threshold (integer atomics: exact).
+// The entry points above are deterministic without atomics.  rx_sw_accumulate runs one thread per 4 destination voxels of the batch's bounding box, each adding
 // the batch's patches in patch order -- the same additions, in the same order, as one launch per patch, with every destination
 // read and written once per batch instead of once per covering patch (patches of one batch overlap by design).
 // Floating-point contraction is off in this file: every product and sum rounds like the numpy / torch statement it restates.
@@ -715,5 +716,139 @@ extern "C" int rx_sw_finalize(float* sum, float* wsum, int c, int ring, int y, i
   else
     hipLaunchKernelGGL(sw_finalize_kernel<false>, grid, dim3(RX_SW_BLOCK), 0, st, sum, wsum, blended, final_out, wsum_out, g);
   RX_CHECK_LAUNCH("rx_sw_finalize");
+  return RX_OK;
+}
+
+// ---- occupancy (empty-patch skipping) -------------------------------------------------------------------------------------------
+// counts[p] = the raw voxels v of patch p, over all channels, with float(v) > value (a float compare: a NaN never counts; uint8 and
+// uint16 are exact in fp32).  Host statement: inference.occupancy_numpy.  A patch is cin * pz * py x-runs of px voxels; a run is cut
+// at the 16-byte boundaries of its own address, so a unit of work is one aligned 16-byte window: a window that lies inside the run
+// is one vector load, the partial windows at its two ends (the scalar head and tail) are read voxel by voxel -- nothing outside
+// a run is read.  Workgroup (chunk, p) strides over the units of patch p; lane -> wave (xor shuffles) -> workgroup (LDS) -> ONE
+// 64-bit integer atomicAdd per workgroup: integer adds are order-free, so the counts are exact and reproducible.  The origins
+// travel by value, RX_OCC_MAXP patches per launch: no device table, copy, allocation or synchronisation.
+#define RX_OCC_MAXP 256
+#define RX_OCC_CHUNKS 64      // at most this many workgroups per patch
+#define RX_OCC_UNITS 8        // units per lane before a patch is cut into another chunk
+
+struct OccPatches {
+  int32_t oz[RX_OCC_MAXP], oy[RX_OCC_MAXP], ox[RX_OCC_MAXP];
+};
+struct OccGeom {
+  int cin, R, Y, X, pz, py, px;
+  int seg;          // aligned 16-byte windows a run can touch
+  long rows, units; // cin * pz * py; rows * seg
+  float value;
+};
+
+template <typename T>
+__device__ inline unsigned occ_vec(const u32x4& v, float value);
+template <>
+__device__ inline unsigned occ_vec<uint8_t>(const u32x4& v, float value) {
+  unsigned c = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c += (float)((v[j] >> (8 * k)) & 0xffu) > value ? 1u : 0u;
+  return c;
+}
+template <>
+__device__ inline unsigned occ_vec<uint16_t>(const u32x4& v, float value) {
+  unsigned c = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) c += ((float)(v[j] & 0xffffu) > value ? 1u : 0u) + ((float)(v[j] >> 16) > value ? 1u : 0u);
+  return c;
+}
+template <>
+__device__ inline unsigned occ_vec<float>(const u32x4& v, float value) {
+  unsigned c = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) c += __uint_as_float(v[j]) > value ? 1u : 0u;
+  return c;
+}
+
+template <typename T>
+__global__ __launch_bounds__(RX_SW_BLOCK) void sw_occupancy_kernel(const T* __restrict__ slab, OccGeom g, OccPatches p,
+                                                                   unsigned long long* __restrict__ counts) {
+  __shared__ unsigned long long s_cnt[RX_SW_BLOCK / RX_WAVE];
+  const int b = blockIdx.y;
+  const int oz = p.oz[b], oy = p.oy[b], ox = p.ox[b];
+  unsigned long long cnt = 0;
+  for (long u = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x; u < g.units; u += (long)gridDim.x * RX_SW_BLOCK) {
+    long r = u / g.seg;
+    const int s = (int)(u - r * g.seg);
+    const int ly = (int)(r % g.py);
+    r /= g.py;
+    const int lz = (int)(r % g.pz);
+    const int ci = (int)(r / g.pz);
+    const T* row = slab + (((long)ci * g.R + (oz + lz) % g.R) * g.Y + oy + ly) * g.X + ox;
+    const uintptr_t a0 = (uintptr_t)row, a1 = a0 + (uintptr_t)g.px * sizeof(T);
+    const uintptr_t w0 = (a0 & ~(uintptr_t)15) + (uintptr_t)16 * s, w1 = w0 + 16;
+    const uintptr_t lo = w0 > a0 ? w0 : a0, hi = w1 < a1 ? w1 : a1;
+    if (lo >= hi) continue;
+    if (hi - lo == 16) {
+      cnt += occ_vec<T>(*reinterpret_cast<const u32x4*>(lo), g.value);
+    } else {
+      for (const T* q = reinterpret_cast<const T*>(lo); q < reinterpret_cast<const T*>(hi); ++q) cnt += (float)*q > g.value ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) s_cnt[wave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < RX_SW_BLOCK / RX_WAVE; ++w) cnt += s_cnt[w];
+    if (cnt) atomicAdd(counts + b, cnt);
+  }
+}
+
+extern "C" int rx_sw_occupancy(int in_dtype, const void* slab, int cin, int ring, int y, int x, int n_pos, const int32_t* origins,
+                               int pz, int py, int px, float value, uint64_t* counts, void* stream) {
+  if (!slab || !counts || cin < 1 || ring < 1 || y < 1 || x < 1) RX_FAIL(RX_EINVAL, "rx_sw_occupancy: bad arguments");
+  if (in_dtype < RX_SW_U8 || in_dtype > RX_SW_F32) RX_FAIL(RX_EINVAL, "rx_sw_occupancy: unknown input dtype %d", in_dtype);
+  if (n_pos < 0 || (n_pos > 0 && !origins)) RX_FAIL(RX_EINVAL, "rx_sw_occupancy: n_pos must be >= 0 and the origin table non-null");
+  if (pz < 1 || py < 1 || px < 1 || pz > ring || py > y || px > x)
+    RX_FAIL(RX_EINVAL, "rx_sw_occupancy: patch (%d,%d,%d) does not fit the slab (ring %d, %d, %d)", pz, py, px, ring, y, x);
+  const int esize = in_dtype == RX_SW_U8 ? 1 : in_dtype == RX_SW_U16 ? 2 : 4;
+  if ((uintptr_t)slab & (uintptr_t)(esize - 1)) RX_FAIL(RX_EINVAL, "rx_sw_occupancy: the slab must be aligned to its %d-byte element", esize);
+  if ((uintptr_t)counts & 7) RX_FAIL(RX_EINVAL, "rx_sw_occupancy: counts must be 8-byte aligned");
+  if (n_pos == 0) return RX_OK;
+  int zmin = origins[0], zmax = origins[0];
+  for (int i = 0; i < n_pos; ++i) {
+    const int z = origins[3 * i], yy = origins[3 * i + 1], xx = origins[3 * i + 2];
+    if (z < 0 || yy < 0 || xx < 0 || yy > y - py || xx > x - px)
+      RX_FAIL(RX_EINVAL, "rx_sw_occupancy: patch %d at (%d,%d,%d) leaves the slab (%d, %d)", i, z, yy, xx, y, x);
+    zmin = z < zmin ? z : zmin, zmax = z > zmax ? z : zmax;
+  }
+  // the rows [min z, max z + pz) of the call are live together: each needs a ring row of its own
+  if ((long)zmax + pz - zmin > ring)
+    RX_FAIL(RX_EINVAL, "rx_sw_occupancy: patches span %ld rows, the ring holds %d", (long)zmax + pz - zmin, ring);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_pos * sizeof(uint64_t), st);
+  if (e != hipSuccess) RX_FAIL(RX_ELAUNCH, "rx_sw_occupancy: zeroing the counts: %s", hipGetErrorString(e));
+  OccGeom g;
+  g.cin = cin, g.R = ring, g.Y = y, g.X = x, g.pz = pz, g.py = py, g.px = px, g.value = value;
+  g.seg = (int)(((long)px * esize + 15) / 16) + 1;      // a run of n bytes at any alignment touches at most ceil(n / 16) + 1 windows
+  g.rows = (long)cin * pz * py;
+  g.units = g.rows * g.seg;
+  long chunks = (g.units + (long)RX_SW_BLOCK * RX_OCC_UNITS - 1) / ((long)RX_SW_BLOCK * RX_OCC_UNITS);
+  chunks = chunks < 1 ? 1 : chunks > RX_OCC_CHUNKS ? RX_OCC_CHUNKS : chunks;
+  for (int i0 = 0; i0 < n_pos; i0 += RX_OCC_MAXP) {
+    const int n = n_pos - i0 < RX_OCC_MAXP ? n_pos - i0 : RX_OCC_MAXP;
+    OccPatches p;
+    memset(&p, 0, sizeof(p));
+    for (int i = 0; i < n; ++i) p.oz[i] = origins[3 * (i0 + i)], p.oy[i] = origins[3 * (i0 + i) + 1], p.ox[i] = origins[3 * (i0 + i) + 2];
+    const dim3 grid((unsigned)chunks, (unsigned)n);
+    unsigned long long* out = (unsigned long long*)counts + i0;
+    if (in_dtype == RX_SW_U8)
+      hipLaunchKernelGGL(sw_occupancy_kernel<uint8_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint8_t*)slab, g, p, out);
+    else if (in_dtype == RX_SW_U16)
+      hipLaunchKernelGGL(sw_occupancy_kernel<uint16_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint16_t*)slab, g, p, out);
+    else
+      hipLaunchKernelGGL(sw_occupancy_kernel<float>, grid, dim3(RX_SW_BLOCK), 0, st, (const float*)slab, g, p, out);
+  }
+  RX_CHECK_LAUNCH("rx_sw_occupancy");
   return RX_OK;
 }

@@ -203,3 +203,34 @@ class ChunkedWriter:
             else:
                 futures.append(pool.submit(_store_chunk, *args))
         return futures
+
+    def write_block(self, z0, y0, x0, block, pool=None):
+        """`write_rows` for a box of the (Z, Y, X) axes: `block` covers [z0, z0 + n) x [y0, y0 + h) x [x0, x0 + w) and every leading
+        axis whole.  Each offset lies on a chunk boundary and each extent is a whole number of chunks or reaches the end of the
+        array (partial edge chunks are stored at full chunk size and all-fill chunks skipped, as `write_rows` does).  Blocks that
+        share no chunk may be written in any order."""
+        block = np.asarray(block)
+        if block.dtype != self.dtype:
+            raise ZarrLiteError(f"write_block: dtype {block.dtype}, array is {self.dtype}")
+        nd = len(self.shape)
+        if self.axis != nd - 3:
+            raise ZarrLiteError("write_block: needs a (..., Z, Y, X) array")
+        lead = nd - 3
+        if block.ndim != nd or block.shape[:lead] != self.shape[:lead]:
+            raise ZarrLiteError(f"write_block: block {block.shape}, expected {self.shape[:lead]} + (n, h, w)")
+        off = (0,) * lead + (int(z0), int(y0), int(x0))
+        for d in range(lead, nd):
+            o, n, c, s = off[d], block.shape[d], self.chunks[d], self.shape[d]
+            if o < 0 or o % c or n < 1 or o + n > s or (n % c and o + n != s):
+                raise ZarrLiteError(f"write_block: [{o}, {o + n}) on axis {d} is not whole chunks of {c} (extent {s})")
+        grid = [(s + c - 1) // c for s, c in zip(block.shape, self.chunks)]
+        futures = []
+        for idx in np.ndindex(*grid):
+            sl = tuple(slice(i * c, min((i + 1) * c, s)) for i, c, s in zip(idx, self.chunks, block.shape))
+            gidx = tuple(i + o // c for i, o, c in zip(idx, off, self.chunks))
+            args = (self.path, gidx, block[sl], self.chunks, self.fill_value, self.compressor, self.sep)
+            if pool is None:
+                _store_chunk(*args)
+            else:
+                futures.append(pool.submit(_store_chunk, *args))
+        return futures

@@ -158,6 +158,8 @@ _SIGNATURES = {
                                  c_int, c_int, c_int, c_void_p]),
     "rx_sw_finalize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
+    "rx_sw_occupancy": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
+                                c_void_p]),
     "rx_aug_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rx_aug_pointwise": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long,
                                  c_void_p]),
