@@ -17,18 +17,10 @@ and the oracle of the GPU tests; `ingest_rule` is the rule `__getitem__` applies
 the trainer puts behind the feeder's copies for `where: device`, before dilation, geometry and the intensity stack."""
 import numpy as np
 
-RULES = ("copy", "div255", "div65535", "normal_u16", "normal_mul2")      # index == rx_ingest_rule (include/rxunet.h)
+from ..engine.ops.core import RULES, rule_code      # noqa: F401 -- the library's codes (index == rx_ingest_rule), beside its binding
+
 DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float32))
 MAX_CHANNELS = 8
-
-
-def rule_code(rule):
-    """a rule's name (or its code) -> the code rx_ingest takes; anything else raises ValueError"""
-    if isinstance(rule, str) and rule.lower() in RULES:
-        return RULES.index(rule.lower())
-    if not isinstance(rule, (bool, str)) and isinstance(rule, (int, np.integer)) and 0 <= int(rule) < len(RULES):
-        return int(rule)
-    raise ValueError(f"ingest: unknown rule {rule!r} (one of {', '.join(RULES)})")
 
 
 def ingest_rule(key, np_dtype):

@@ -21,10 +21,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from ..engine.ops.core import BORDER, INTERP      # noqa: F401 -- the library's codes, kept beside its binding
 from .geometry_device import AXIS_OF
 
-INTERP = {"linear": 0, "nearest": 1}
-BORDER = {"constant": 0, "clamp": 1}
 MAX_EXTENT = 1 << 24      # float32 holds every voxel index below this exactly
 
 

@@ -1340,7 +1340,7 @@ class Plan:
 
     # ---- launch programs -------------------------------------------------------------------------------------
     def _programs_on(self):
-        return (self.use_programs and not self.use_graphs and self.device.type == "cuda" and ops._PROF is None
+        return (self.use_programs and not self.use_graphs and self.device.type == "cuda" and ops.profiling() is None
                 and not self._unstable_params)
 
     def _streams(self):
@@ -1408,7 +1408,7 @@ class Plan:
     def _graphs_on(self):
         # (needs_grad plans only: an inference plan re-packs nothing and has no backward list worth capturing)
         return (self.use_graphs and self.device.type == "cuda" and self.needs_grad
-                and self.grad_sync is None and ops._PROF is None and not self._drops)
+                and self.grad_sync is None and ops.profiling() is None and not self._drops)
 
     def _param_ptrs(self):
         return tuple(p.data_ptr() for p in self.params)

@@ -493,7 +493,7 @@ class MeshTargetBuilder:
     shape_zyx  (Z, h, w): Z slices of the full w x h image; volume index k is slice min_z + k
     slab       slices per device pass (the key buffer holds slab * window pixels); the default is one chunk row
     window     (y0, x0, wh, ww): store only this part of every slice (the store is then (Z, wh, ww)); None = the image
-    where      "device": csrc/rx_meshslice.hip through engine/ops.py; "host": the numpy statement
+    where      "device": csrc/rx_meshslice.hip through engine/ops/mesh.py; "host": the numpy statement
 
     `normals_volume`, `labels_volume` and `sheet_mask` each write a zarr v2 GROUP at `path` with the array `volume` (chunks
     (128, 128, 128[, 3])) and the attributes slices_to_zarr.py writes.  The sheet mask is `slices_to_zarr --binary` over the normals

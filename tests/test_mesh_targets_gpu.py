@@ -1,4 +1,4 @@
-"""GPU: csrc/rx_meshslice.hip through engine/ops.py against the numpy statement (tasks/normals/mesh_targets.py), bit for bit: every
+"""GPU: csrc/rx_meshslice.hip through engine/ops/mesh.py against the numpy statement (tasks/normals/mesh_targets.py), bit for bit: every
 golden case of tests/golden/mesh_slices.npz on every output (codes, viz bytes, mask, labels, keys), slabs that cut through a
 triangle's z-range, windows with odd offsets and widths that are no multiple of 4 (the dword stores' edges), 24 seeded random
 meshes with degenerate and duplicate triangles, and two runs of one input byte for byte.  Outputs live in 0xFF-poisoned buffers with
