@@ -634,6 +634,31 @@ size_t rx_normal_stats_workspace(int n, long v); /* bytes of partials (0 for non
 int rx_normal_stats(const void* pred, int pred_dtype, const float* target, int n, long v, int64_t* count, double* sums, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ---- surface-distance validation metrics on the device (host side training/metrics/surface.py, whose edges_numpy, edt_sq_numpy
+ *      and surface_hist_numpy are the statements).  A volume is a contiguous (z, y, x) block; `n` volumes lie back to back
+ *      (n = samples * channels).  Distances are in voxels, isotropic, squared, exact integers; no floating point beyond the one
+ *      float32 comparison against the threshold.  Each extent is 1 .. RX_EDT_MAX_EXTENT.  No allocation, copy or synchronisation.
+ *      RX_EINVAL before anything is launched, for all of them: null pointers, non-positive sizes, an extent above
+ *      RX_EDT_MAX_EXTENT, a misaligned pointer, more volumes than one call's grid covers.
+ *      rx_mask_edges: edges[v] = 1 where values[v] > threshold (IEEE float32; a NaN is off; a NaN threshold is RX_EINVAL) and v is
+ *        on the border of its volume or one of its six face neighbours is off, else 0: mask & ~erode6(mask) with everything
+ *        outside the volume off.  `values` of `dtype` (rx_dtype), aligned to its element; at most 65535 volumes.  No neighbour
+ *        outside a voxel's own volume is ever read.
+ *      rx_edt_sq: dist[v] = the squared Euclidean distance from v to the nearest voxel of its volume with feature != 0, or
+ *        RX_EDT_NONE everywhere in a volume that has none.  Three passes, x then y then z, each
+ *        g'[i] = min(RX_EDT_NONE, min_j (g[j] + (i - j)^2)) along its axis, from g = 0 on a feature and RX_EDT_NONE elsewhere; the
+ *        y and z passes run in place on `dist` (int32, 4-byte aligned; `feature` must be another buffer).
+ *      rx_surface_hist: over the `total` voxels of both arrays, for each voxel with edges != 0: count += 1, and unmatched += 1 if
+ *        dist is RX_EDT_NONE (or no distance at all: negative), else hist[min(dist, bins - 1)] += 1.  hist: int64 (bins), count
+ *        and unmatched: one int64 each, 8-byte aligned; everything is ADDED with integer atomics into buffers the caller zeroes,
+ *        so the result does not depend on arrival order. */
+#define RX_EDT_NONE (1 << 30)
+#define RX_EDT_MAX_EXTENT 1024
+int rx_mask_edges(const void* values, int dtype, float threshold, int n, int z, int y, int x, uint8_t* edges, void* stream);
+int rx_edt_sq(const uint8_t* feature, int n, int z, int y, int x, int32_t* dist, void* stream);
+int rx_surface_hist(const uint8_t* edges, const int32_t* dist, long total, long bins, int64_t* hist, int64_t* count, int64_t* unmatched,
+                    void* stream);
+
 /* ---- validation preview on the device: one panel of the debug GIF (host side training/visualization/preview.py, whose
  *      panel_numpy and minmax_numpy are the statements).  `src` is ONE sample's contiguous (c, z, h, w) block of `dtype` (rx_dtype),
  *      aligned to its element (a base that is not 16-byte aligned is fine).  c == 3 draws channels 0, 1, 2 into bytes 0, 1, 2 of

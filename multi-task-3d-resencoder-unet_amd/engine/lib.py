@@ -25,6 +25,7 @@ RX_REDUCE_MEAN, RX_REDUCE_SUM = 0, 1
 RX_INGEST_COPY, RX_INGEST_DIV255, RX_INGEST_DIV65535, RX_INGEST_NORMAL_U16, RX_INGEST_NORMAL_MUL2 = 0, 1, 2, 3, 4
 RX_AFFINE_LINEAR, RX_AFFINE_NEAREST = 0, 1
 RX_AFFINE_CONSTANT, RX_AFFINE_CLAMP = 0, 1
+RX_EDT_NONE, RX_EDT_MAX_EXTENT = 1 << 30, 1024
 
 
 class RxError(RuntimeError):
@@ -182,6 +183,9 @@ _SIGNATURES = {
     "rx_class_counts": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, c_long, c_void_p, c_void_p]),
     "rx_normal_stats_workspace": (c_size_t, [c_int, c_long]),
     "rx_normal_stats": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rx_mask_edges": (c_int, [c_void_p, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rx_edt_sq": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rx_surface_hist": (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rx_preview_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int,
                                  c_void_p, c_void_p]),
     "rx_mesh_slice_keys": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -1,5 +1,6 @@
-"""Validation on the device: the metric counts (training/metrics/metrics.py holds the numpy statements and `ValidationMetrics`) and
-the preview panels (training/visualization/preview.py holds the numpy statements, the config and the GIF writer)."""
+"""Validation on the device: the metric counts (training/metrics/metrics.py holds the numpy statements and `ValidationMetrics`), the
+surface-distance histograms (training/metrics/surface.py holds the numpy statements and the scores) and the preview panels
+(training/visualization/preview.py holds the numpy statements, the config and the GIF writer)."""
 import torch
 
 from .. import lib as _l
@@ -81,6 +82,100 @@ def normal_stats(pred, target, out=None, ws=None):
                 lambda: check(load().rx_normal_stats(_ptr(p), _code(p.dtype), _ptr(t), n, v, _ptr(count), _ptr(sums), _ptr(ws), ws.numel() * 8,
                                                      stream_ptr()), "rx_normal_stats"))
     return count, sums
+
+
+# ---- surface-distance metrics (csrc/rx_surface.hip; training/metrics/surface.py holds the numpy statements) ---------------------------
+def _surface_volumes(fn, t, what, dtypes, statement):
+    """a device (N, C, Z, Y, X) batch of `dtypes`, every extent within the library's limit -> it made contiguous"""
+    t = device_batch(fn, t, f"the host statement is training.metrics.{statement}", what=what, dtypes=dtypes, rank=5,
+                     layout="(N, C, Z, Y, X)")
+    if max(t.shape[2:]) > _l.RX_EDT_MAX_EXTENT:
+        raise _l.RxError(f"{fn}: an extent above {_l.RX_EDT_MAX_EXTENT} in {tuple(t.shape)}")
+    return t
+
+
+def _mask_edges_launch(v, threshold, out):
+    n, c, z, y, x = v.shape
+    check(load().rx_mask_edges(_ptr(v), _code(v.dtype), float(threshold), n * c, z, y, x, _ptr(out), stream_ptr()), "rx_mask_edges")
+
+
+def _edt_sq_launch(f, out):
+    n, c, z, y, x = f.shape
+    check(load().rx_edt_sq(_ptr(f), n * c, z, y, x, _ptr(out), stream_ptr()), "rx_edt_sq")
+
+
+def _surface_hist_launch(edges, dist, hist_row, count, unmatched):
+    check(load().rx_surface_hist(_ptr(edges), _ptr(dist), edges.numel(), hist_row.numel(), _ptr(hist_row), _ptr(count), _ptr(unmatched),
+                                 stream_ptr()), "rx_surface_hist")
+
+
+def mask_edges(values, threshold, out=None):
+    """the edge voxels of `values > threshold` per (sample, channel) volume of a float32 / bfloat16 / float16 (N, C, Z, Y, X) device
+    batch -> uint8 (N, C, Z, Y, X), 1 on a mask voxel that lies on its volume's border or has a face neighbour outside the mask
+    (float32 compare, a NaN is outside; training.metrics.edges_numpy is the statement).  On the current stream, no synchronisation."""
+    v = _surface_volumes("mask_edges", values, "values", FLOATS, "edges_numpy")
+    out = result_tensor("mask_edges", "out", out, v.shape, torch.uint8, v.device)
+    timed_bytes("mask_edges", v.numel() * (v.element_size() + 1), lambda: _mask_edges_launch(v, threshold, out))
+    return out
+
+
+def edt_sq(feature, out=None):
+    """the exact squared Euclidean distance transform per (sample, channel) volume of a uint8 or bool (N, C, Z, Y, X) device batch ->
+    int32 (N, C, Z, Y, X): the squared distance in voxels to the volume's nearest non-zero voxel, EDT_NONE = 1 << 30 throughout a
+    volume that has none (training.metrics.edt_sq_numpy is the statement).  Extents up to 1024.  On the current stream, no
+    synchronisation, no workspace."""
+    f = _surface_volumes("edt_sq", feature, "feature", (torch.uint8, torch.bool), "edt_sq_numpy")
+    out = result_tensor("edt_sq", "out", out, f.shape, torch.int32, f.device)
+    timed_bytes("edt_sq", f.numel() * (1 + 4), lambda: _edt_sq_launch(f, out))      # the y and z passes are extra time, not bytes
+    return out
+
+
+def surface_scratch(shape, device):
+    """the buffers `surface_hist` works in for batches of `shape` (N, C, Z, Y, X): (prediction edges uint8, target edges uint8,
+    distances int32)"""
+    shape = tuple(shape)
+    return (torch.empty(shape, dtype=torch.uint8, device=device), torch.empty(shape, dtype=torch.uint8, device=device),
+            torch.empty(shape, dtype=torch.int32, device=device))
+
+
+def surface_hist(pred, target, thr_pred, thr_target, hist=None, counts=None, scratch=None):
+    """the histograms of squared surface distances between `pred > thr_pred` and `target > thr_target`, pooled over the N * C volumes
+    of a float32 / bfloat16 / float16 (N, C, Z, Y, X) device prediction and a float32 target of the same shape
+    (training.metrics.surface_hist_numpy, summed over the volumes, is the statement): with Ep, Et the edges of the two masks,
+    hist[0] counts the voxels of Ep by their squared distance to Et and hist[1] those of Et by their squared distance to Ep;
+    counts = (|Ep|, |Et|, unmatched_pred, unmatched_target), where an edge voxel is unmatched, and goes to no bin, when the other
+    edge set of its volume is empty.  ADDED into `hist` int64 (2, bins) and `counts` int64 (4,) when given (the caller zeroes
+    them); else fresh zeroed tensors with bins = (Z-1)^2 + (Y-1)^2 + (X-1)^2 + 1, which no distance can overflow.  With a smaller
+    caller-given `bins`, a distance >= bins goes to the LAST bin.  `scratch`: what `surface_scratch(pred.shape, device)` returned,
+    kept across calls; with it the call allocates nothing.  Ten kernel launches on the current stream, no synchronisation.
+    Returns (hist, counts)."""
+    p = _surface_volumes("surface_hist", pred, "prediction", FLOATS, "surface_hist_numpy")
+    t = _metric_f32_target("surface_hist", p, target)
+    z, y, x = p.shape[2:]
+    if hist is None:
+        hist = torch.zeros((2, (z - 1) ** 2 + (y - 1) ** 2 + (x - 1) ** 2 + 1), dtype=torch.int64, device=p.device)
+    elif (not isinstance(hist, torch.Tensor) or hist.device != p.device or hist.dtype != torch.int64 or hist.dim() != 2
+          or hist.shape[0] != 2 or hist.shape[1] < 1 or not hist.is_contiguous()):
+        raise _l.RxError(f"surface_hist: `hist` must be a contiguous int64 tensor of shape (2, bins) on {p.device}")
+    counts = result_tensor("surface_hist", "counts", counts, (4,), torch.int64, p.device, torch.zeros)
+    if scratch is None:
+        scratch = surface_scratch(p.shape, p.device)
+    elif not isinstance(scratch, (tuple, list)) or len(scratch) != 3:
+        raise _l.RxError("surface_hist: `scratch` must be what surface_scratch(pred.shape, device) returned")
+    ep = result_tensor("surface_hist", "scratch[0]", scratch[0], p.shape, torch.uint8, p.device)
+    et = result_tensor("surface_hist", "scratch[1]", scratch[1], p.shape, torch.uint8, p.device)
+    dist = result_tensor("surface_hist", "scratch[2]", scratch[2], p.shape, torch.int32, p.device)
+
+    def run():
+        _mask_edges_launch(p, thr_pred, ep)
+        _mask_edges_launch(t, thr_target, et)
+        _edt_sq_launch(et, dist)
+        _surface_hist_launch(ep, dist, hist[0], counts[0:1], counts[2:3])
+        _edt_sq_launch(ep, dist)
+        _surface_hist_launch(et, dist, hist[1], counts[1:2], counts[3:4])
+    # each value once, each edge byte written once and read twice, each distance word written and read once per direction
+    timed_bytes("surface_hist", p.numel() * (p.element_size() + 4 + 2 * (1 + 1 + 1) + 2 * (4 + 4)), run)
+    return hist, counts
 
 
 # ---- validation preview ------------------------------------------------------------------------------------------------------------

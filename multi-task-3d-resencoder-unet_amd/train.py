@@ -21,7 +21,8 @@ CosineAnnealingLR stepped per epoch, final `<model_name>_final.pth`).  Differenc
     frames, and the file is written through PIL (skipped when PIL is missing);
   * `tr_config.val_metrics` (absent / false: off, and then nothing below differs) adds Dice / IoU / precision / recall of the
     segmentation heads and the angular error of a normals head to the validation pass (training/metrics, HIP kernels, one host
-    copy per epoch), writes them and the validation losses to TensorBoard, and with `best` keeps `<model_name>.best.pth`.
+    copy per epoch), writes them and the validation losses to TensorBoard, and with `best` keeps `<model_name>.best.pth`; its
+    `surface` block (off by default) adds surface Dice, ASSD and HD95 for binary tasks (training/metrics/surface.py).
 """
 import os
 import time
@@ -163,7 +164,8 @@ class BaseTrainer:
         self.local_rank = int(os.environ.get("LOCAL_RANK", 0))
         self.last_patches_per_sec = None
         # tr_config.val_metrics: checked here, so a typo stops the run before a model is built (ValueError naming the key)
-        self.val_metrics_config = parse_val_metrics(self.mgr.tr_configs.get("val_metrics"), self.mgr.tasks)
+        self.val_metrics_config = parse_val_metrics(self.mgr.tr_configs.get("val_metrics"), self.mgr.tasks,
+                                                    patch_size=self.mgr.train_patch_size)
         self.last_val_metrics = None
         self.best_val_metric = None
         # tr_config.val_preview: checked here for the same reason

@@ -5,6 +5,7 @@ Three layers:
     csrc/rx_metrics.hip (engine.ops.seg_counts / class_counts / normal_stats) compute, and the oracles of their tests;
   * `scores_from_counts`: Dice, IoU, precision and recall from (TP, FP, FN);
   * `ValidationMetrics`: the per-epoch accumulator the trainer drives (`tr_config.val_metrics`, parsed by `parse_config`).
+The opt-in surface-distance metrics (`tr_config.val_metrics.surface`) have their statements and scores in surface.py.
 
 The values compared are the ones the model hands over in eval mode: `NetworkFromConfig.forward` applies the task activation there,
 so a `sigmoid` head yields probabilities and the threshold applies as it is, while an `activation: none` head yields logits and
@@ -14,10 +15,12 @@ import math
 
 import numpy as np
 
+from .surface import default_bins, parse_surface, surface_metric_names, surface_scores
+
 KINDS = ("binary", "multiclass", "normals", "none")
 RATES = ("dice", "iou", "precision", "recall")
 MAX_CLASSES = 64
-_TOP_KEYS = ("threshold", "target_threshold", "tasks", "best")
+_TOP_KEYS = ("threshold", "target_threshold", "tasks", "best", "surface")
 _TASK_KEYS = ("kind",)
 _BEST_KEYS = ("task", "metric", "mode")
 
@@ -146,9 +149,11 @@ def pred_threshold(info, threshold):
     return float(threshold)
 
 
-def metric_names(kind):
+def metric_names(kind, surface=None):
+    """the metrics of a task of `kind`; `surface`: the parsed `surface` block when it covers the task (binary tasks only), which
+    appends surface_dice_<t> per tolerance, assd, hd95 and surface_voxels"""
     if kind == "binary":
-        return RATES + ("dice_per_patch",)
+        return RATES + ("dice_per_patch",) + (surface_metric_names(surface["tolerances"]) if surface else ())
     if kind == "multiclass":
         return RATES + tuple(f"{r}_class_mean" for r in RATES) + ("dice_per_patch",)
     if kind == "normals":
@@ -156,9 +161,15 @@ def metric_names(kind):
     return ()
 
 
-def parse_config(cfg, tasks, normal_keys=None):
+def _surface_of(surface, name):
+    """the parsed surface block if it covers task `name`, else None"""
+    return surface if surface and name in surface["tasks"] else None
+
+
+def parse_config(cfg, tasks, normal_keys=None, patch_size=None):
     """`tr_config.val_metrics` -> None (absent / false) or {"threshold", "target_threshold", "kinds": {task: kind}, "best": None |
-    {"task", "metric", "mode"}}.  A ValueError names the offending key."""
+    {"task", "metric", "mode"}, "surface": None | {"tolerances", "tasks"}}.  `patch_size`: the train patch size when known (the
+    surface block refuses 2-D patches).  A ValueError names the offending key."""
     if cfg is None or cfg is False:
         return None
     if cfg is True:
@@ -201,6 +212,7 @@ def parse_config(cfg, tasks, normal_keys=None):
         if kind == "normals" and channels != 3:
             raise ValueError(f"tr_config.val_metrics.tasks.{name}.kind: normals needs 3 channels, the task has {channels}")
     out["kinds"] = kinds
+    out["surface"] = parse_surface(cfg.get("surface"), kinds, patch_size)
     best = cfg.get("best")
     if best is not None:
         if not isinstance(best, dict):
@@ -213,7 +225,7 @@ def parse_config(cfg, tasks, normal_keys=None):
                 raise ValueError(f"tr_config.val_metrics.best.{k}: missing")
         if best["task"] not in tasks:
             raise ValueError(f"tr_config.val_metrics.best.task: unknown task '{best['task']}' (the targets are: {', '.join(tasks)})")
-        names = metric_names(kinds[best["task"]])
+        names = metric_names(kinds[best["task"]], _surface_of(out["surface"], best["task"]))
         if best["metric"] not in names:
             raise ValueError(f"tr_config.val_metrics.best.metric: unknown metric '{best['metric']}' for the {kinds[best['task']]} task "
                              f"'{best['task']}' (known: {', '.join(names) or 'none'})")
@@ -236,7 +248,11 @@ class ValidationMetrics:
     reset()                    clears the state
 
     State, one int64 buffer (float64 words are views of it): per counting task C*3 summed (TP, FP, FN), the sum of the per-patch
-    Dice values and the number of patches that had one; per normals task the masked voxels, the sum of cos and the sum of degrees."""
+    Dice values and the number of patches that had one; per normals task the masked voxels, the sum of cos and the sum of degrees.
+
+    With a `surface` block, every covered binary task also owns 4 counts and a (2, bins) histogram of squared surface distances
+    (engine.ops.surface_hist), pooled over the epoch.  `bins` follows from the first patch shape the accumulator sees, so these
+    words are appended to the state then, and a second patch shape raises ValueError."""
 
     def __init__(self, tasks, config=True, normal_keys=None):
         cfg = config if isinstance(config, dict) and "kinds" in config else parse_config(config, tasks, normal_keys)
@@ -255,6 +271,49 @@ class ValidationMetrics:
         self._words = max(n, 1)
         self._state = None
         self._scratch = {}
+        self.surface = cfg.get("surface")
+        self._surface_tasks = tuple(k for k in self.kinds if _surface_of(self.surface, k))
+        self._surface_shape = None      # the patch shape (Z, Y, X) that fixed `bins`
+        self._surface_slots = {}        # task -> offset of its 4 counts, followed by 2 * bins histogram words
+
+    def _names(self, name):
+        return metric_names(self.kinds[name], _surface_of(self.surface, name))
+
+    def _surface_views(self, name):
+        o, bins = self._surface_slots[name], default_bins(self._surface_shape)
+        return self._state[o + 4:o + 4 + 2 * bins].view(2, bins), self._state[o:o + 4]
+
+    def _surface_check(self, outputs):
+        """refuses, before anything is added, a batch the histogram cannot take"""
+        for name in self._surface_tasks:
+            if name not in outputs:
+                continue
+            shape = tuple(outputs[name].shape)
+            if len(shape) != 5:
+                raise ValueError(f"ValidationMetrics: surface metrics need (N, C, Z, Y, X) batches, task '{name}' has shape {shape}")
+            if self._surface_shape is not None and shape[2:] != self._surface_shape:
+                raise ValueError(f"ValidationMetrics: surface metrics were started on patches of shape {self._surface_shape}, task "
+                                 f"'{name}' now has {shape[2:]}: the histogram length is fixed by the first shape")
+
+    def _surface_update(self, name, pred, target):
+        import torch
+        from ...engine import ops as E
+        shape = tuple(pred.shape[2:])
+        if self._surface_shape is None:      # the state grows once, before anything was added to the new words
+            self._surface_shape = shape
+            n = self._words
+            for k in self._surface_tasks:
+                self._surface_slots[k] = n
+                n += 4 + 2 * default_bins(shape)
+            grown = torch.zeros(n, dtype=torch.int64, device=self._state.device)
+            grown[:self._words].copy_(self._state)
+            self._state, self._words = grown, n
+        key = ("surface", name, tuple(pred.shape), pred.device)
+        scratch = self._scratch.get(key)
+        if scratch is None:
+            scratch = self._scratch[key] = E.surface_scratch(pred.shape, pred.device)
+        hist, counts = self._surface_views(name)
+        E.surface_hist(pred, target, self.thr_pred[name], self.target_threshold, hist=hist, counts=counts, scratch=scratch)
 
     def _views(self, name):
         o, w = self._slots[name]
@@ -285,6 +344,7 @@ class ValidationMetrics:
         import torch
         from ...engine import ops as E
         self._f64 = torch.float64
+        self._surface_check(outputs)
         for name, kind in self.kinds.items():
             if name not in outputs or name not in targets:
                 continue
@@ -314,13 +374,15 @@ class ValidationMetrics:
             den.masked_fill_(~valid, 1.0)
             num.div_(den).masked_fill_(~valid, 0.0)
             dsum.add_(num.sum()), dcnt.add_(valid.sum())
+            if name in self._surface_tasks:      # last: it may move the state, and the views above are of the old one
+                self._surface_update(name, pred, target)
 
     def reset(self):
         if self._state is not None:
             self._state.zero_()
 
     def compute(self):
-        out = {name: {m: float("nan") for m in metric_names(kind)} for name, kind in self.kinds.items()}
+        out = {name: {m: float("nan") for m in self._names(name)} for name in self.kinds}
         if self._state is None:
             return out
         host = self._state.cpu().numpy()      # the one copy (and the one synchronisation) of the epoch
@@ -341,6 +403,11 @@ class ValidationMetrics:
                     ok = ~np.isnan(per_class[r])
                     res[f"{r}_class_mean"] = float(per_class[r][ok].mean()) if ok.any() else float("nan")
             res["dice_per_patch"] = dsum / dcnt if dcnt else float("nan")
+            if name in self._surface_slots:
+                so, bins = self._surface_slots[name], default_bins(self._surface_shape)
+                res.update(surface_scores(host[so + 4:so + 4 + 2 * bins].reshape(2, bins), host[so:so + 4], self.surface["tolerances"]))
+            elif name in self._surface_tasks:      # covered, but no batch seen yet
+                res.update({m: float("nan") for m in surface_metric_names(self.surface["tolerances"])})
             out[name] = res
         return out
 
