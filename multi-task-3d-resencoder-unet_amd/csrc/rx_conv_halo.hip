@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "rx_common.h"
+#include "rx_conv_halo_plan.h"
 #include "rx_internal.h"
 
 struct ConvHaloGeom {
@@ -1098,307 +1099,99 @@ __global__ __launch_bounds__(512, 1) void conv_halo64ws_kernel(const T* __restri
   }
 }
 
+// ---- host side: rx_ch_choose (rx_conv_halo_plan.h) decides, ch_launch starts the instantiation it names -------------------------
+static_assert(RX_CH_PLAN_MAX_HV == RX_CH_MAX_HV && RX_CH_LDS_HALO32 == CH32P_HALO_BYTES + 9 * 32 * 64 &&
+                  RX_CH_LDS_HALO32P == CH32P_W_BYTES + 2 * CH32P_HALO_BYTES && RX_CH_LDS_HALO32WS == 2 * (9 * 32 * 64 + CH64_X_BYTES) &&
+                  RX_CH_LDS_HALO64WS == 2 * (CH64_W_BYTES + CH64_X_BYTES),
+              "rx_conv_halo_plan.h sizes the LDS of the kernels above");
+
+// One row per instantiation in the object: (family, FLIP, XDMA, STATS, ACC, BS) of the choice -> the kernel, which gets its
+// dynamic-LDS limit and its launch in the same place.  The persistent families take their tiles per workgroup as a last argument.
+// false: no such instantiation (the selector and this table disagree).
 template <typename T>
-static void ch64ws_launch(hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
-  const size_t lds = (size_t)2 * (CH64_W_BYTES + CH64_X_BYTES);
-  const int cob = g.Co / 64;
-  int wgs = 256 / cob;                                   // one persistent workgroup per CU in total
-  if (wgs < 1) wgs = 1;
-  if (wgs > g.NT) wgs = g.NT;
-  // a workgroup's tile range never straddles samples (the fused InstanceNorm statistics are per (n, c))
-  const int NTs = g.NT / g.N;
-  int wgs_s = wgs / g.N > 0 ? wgs / g.N : 1;
-  const int per = (NTs + wgs_s - 1) / wgs_s;
-  wgs_s = (NTs + per - 1) / per;
-  wgs = wgs_s * g.N;
-  const_cast<ConvHaloGeom&>(g).wgs_s = wgs_s;
-  dim3 grid(wgs, cob);
-#define RX_64WS(...)                                                                                                                   \
-  do {                                                                                                                                 \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, __VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((conv_halo64ws_kernel<T, __VA_ARGS__>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per); \
-  } while (0)
-  // the weight planes always go by LDS-DMA; the halo too unless the input is past the buffer-descriptor range (out-of-range
-  // offsets must stay out of range of the descriptor)
-  const bool dma_ok = (long)g.N * g.in_ss * 2 < 0x7fffff00L;
-  if (dma_ok && g.stat_part && !g.flip && !g.bs_y) {
-    RX_64WS(false, true, true);
-    return;
+static bool ch_launch(const RxChChoice& c, hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
+  const dim3 grid(c.grid_x, c.grid_y), block(c.block);
+#define RX_CH_ROW(FAM, F, X, S, A, B, KERNEL, ...)                                                                                      \
+  if (c.family == FAM && c.FLIP == F && c.XDMA == X && c.STATS == S && c.ACC == A && c.BS == B) {                                       \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds);           \
+    hipLaunchKernelGGL(KERNEL, grid, block, c.lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, ##__VA_ARGS__);                      \
+    return true;                                                                                                                       \
   }
-  if (dma_ok && g.bs_y && g.stat_part && g.flip && !((uintptr_t)out & 15) && g.ldo % 8 == 0 && g.out_cs % 8 == 0 && !((uintptr_t)g.bs_y & 15) &&
-      g.bs_ldy % 8 == 0) {     // backward sums on the producer waves (whole-row 16-byte stores / loads)
-    if (g.accumulate) RX_64WS(true, true, false, true, true);
-    else RX_64WS(true, true, false, false, true);
-    return;
+  if constexpr (!std::is_same<T, float>::value) {
+    RX_CH_ROW(RX_CH_HALO64WS, 0, 1, 1, 0, 0, (conv_halo64ws_kernel<T, false, true, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO64WS, 1, 1, 0, 1, 1, (conv_halo64ws_kernel<T, true, true, false, true, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO64WS, 1, 1, 0, 0, 1, (conv_halo64ws_kernel<T, true, true, false, false, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO64WS, 1, 1, 0, 1, 0, (conv_halo64ws_kernel<T, true, true, false, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO64WS, 1, 1, 0, 0, 0, (conv_halo64ws_kernel<T, true, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO64WS, 0, 1, 0, 0, 0, (conv_halo64ws_kernel<T, false, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO64WS, 1, 0, 0, 0, 0, (conv_halo64ws_kernel<T, true, false>), c.per)
+    RX_CH_ROW(RX_CH_HALO64WS, 0, 0, 0, 0, 0, (conv_halo64ws_kernel<T, false, false>), c.per)
+    RX_CH_ROW(RX_CH_HALO32WS, 0, 1, 0, 0, 0, (conv_halo64ws_kernel<T, false, true, false, false, false, 1>), c.per)
+    RX_CH_ROW(RX_CH_HALO32WS, 0, 1, 1, 0, 0, (conv_halo64ws_kernel<T, false, true, true, false, false, 1>), c.per)
+    RX_CH_ROW(RX_CH_HALO32WS, 1, 1, 0, 0, 0, (conv_halo64ws_kernel<T, true, true, false, false, false, 1>), c.per)
+    RX_CH_ROW(RX_CH_HALO32WS, 1, 1, 0, 1, 0, (conv_halo64ws_kernel<T, true, true, false, true, false, 1>), c.per)
+    RX_CH_ROW(RX_CH_HALO32P, 0, 0, 0, 0, 0, (conv_halo32p_kernel<T, false, false, false>), c.per)
+    RX_CH_ROW(RX_CH_HALO32P, 0, 0, 1, 0, 0, (conv_halo32p_kernel<T, true, false, false>), c.per)
+    RX_CH_ROW(RX_CH_HALO32P, 1, 0, 0, 0, 0, (conv_halo32p_kernel<T, false, false, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO32P, 1, 0, 0, 1, 0, (conv_halo32p_kernel<T, false, true, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO32P, 0, 0, 0, 1, 0, (conv_halo32p_kernel<T, false, true, false>), c.per)
+    RX_CH_ROW(RX_CH_HALO32P, 1, 0, 0, 0, 1, (conv_halo32p_kernel<T, false, false, true, true>), c.per)
+    RX_CH_ROW(RX_CH_HALO32P, 1, 0, 0, 1, 1, (conv_halo32p_kernel<T, false, true, true, true>), c.per)
   }
-  const_cast<ConvHaloGeom&>(g).bs_y = nullptr;                   // (not taken: the caller runs the separate reduce pass)
-  const_cast<ConvHaloGeom&>(g).stat_part = nullptr;              // only the instantiations above accumulate statistics
-  if (dma_ok && g.accumulate && g.flip) RX_64WS(true, true, false, true);     // dx +=: old values prefetched
-  else if (dma_ok && g.flip) RX_64WS(true, true);
-  else if (dma_ok) RX_64WS(false, true);
-  else if (g.flip) RX_64WS(true, false);
-  else RX_64WS(false, false);
-#undef RX_64WS
-}
-
-// the 32-channel-block instantiations (NA = 1) of conv_halo64ws: LDS-DMA only.  Returns false (nothing launched) when the DMA
-// preconditions do not hold -- the caller then takes conv_halo32_kernel as before.
-template <typename T>
-static bool ch32ws_launch(hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
-  const size_t lds = (size_t)2 * (9 * 32 * 64 + CH64_X_BYTES);
-  if (!(((long)g.N * g.in_ss + (g.in_cs == 32 ? 0L : (long)(g.Ci / 32 - 1) * g.in_cs)) * 2 < 0x7fffff00L)) return false;   // (planar concat input: the planes lie in_cs apart)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, false, true, true, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo64ws_kernel<T, true, true, false, true, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int cob = g.Co / 32;
-  int wgs = 256 / cob;                                   // one persistent workgroup per CU in total
-  if (wgs < 1) wgs = 1;
-  if (wgs > g.NT) wgs = g.NT;
-  const int NTs = g.NT / g.N;                            // a workgroup's tile range never straddles samples
-  int wgs_s = wgs / g.N > 0 ? wgs / g.N : 1;
-  const int per = (NTs + wgs_s - 1) / wgs_s;
-  wgs_s = (NTs + per - 1) / per;
-  wgs = wgs_s * g.N;
-  const_cast<ConvHaloGeom&>(g).wgs_s = wgs_s;
-  dim3 grid(wgs, cob);
-#define RX_32WS(F, S, A) hipLaunchKernelGGL((conv_halo64ws_kernel<T, F, true, S, A, false, 1>), grid, dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per)
-  if (g.stat_part && !g.flip && !g.accumulate) {
-    RX_32WS(false, true, false);
-    return true;
-  }
-  const_cast<ConvHaloGeom&>(g).stat_part = nullptr;
-  if (g.flip && g.accumulate) RX_32WS(true, false, true);
-  else if (g.flip) RX_32WS(true, false, false);
-  else RX_32WS(false, false, false);
-#undef RX_32WS
-  return true;
-}
-
-template <typename T>
-static void ch32p_launch(hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
-  const size_t lds = (size_t)CH32P_W_BYTES + 2 * (size_t)CH32P_HALO_BYTES;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32p_kernel<T, false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  int wgs = g.NT < 256 ? g.NT : 256;                    // one persistent workgroup per CU
-  const int NTs = g.NT / g.N;                           // a workgroup's tile range never straddles samples
-  int wgs_s = wgs / g.N > 0 ? wgs / g.N : 1;
-  const int per = (NTs + wgs_s - 1) / wgs_s;
-  wgs_s = (NTs + per - 1) / per;
-  wgs = wgs_s * g.N;
-  const_cast<ConvHaloGeom&>(g).wgs_s = wgs_s;
-#define RX_32P(S, A, F) hipLaunchKernelGGL((conv_halo32p_kernel<T, S, A, F>), dim3(wgs), dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per)
-#define RX_32PB(A) hipLaunchKernelGGL((conv_halo32p_kernel<T, false, A, true, true>), dim3(wgs), dim3(512), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g, per)
-  if (g.bs_y && g.flip && g.accumulate) RX_32PB(true);
-  else if (g.bs_y && g.flip) RX_32PB(false);
-  else
-#undef RX_32PB
-  if (g.stat_part && !g.accumulate && !g.flip) RX_32P(true, false, false);
-  else if (g.flip && g.accumulate) RX_32P(false, true, true);
-  else if (g.flip) RX_32P(false, false, true);
-  else if (g.accumulate) RX_32P(false, true, false);
-  else RX_32P(false, false, false);
-#undef RX_32P
-}
-
-template <typename T>
-static void ch32_launch(dim3 grid, hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
-  const size_t lds = (size_t)648 * 80 + (size_t)9 * 32 * 64;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (g.stat_part && !g.flip && !g.accumulate) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo32_kernel<T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((conv_halo32_kernel<T, false, true>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
-  } else if (g.flip)
-    hipLaunchKernelGGL((conv_halo32_kernel<T, true>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
-  else
-    hipLaunchKernelGGL((conv_halo32_kernel<T, false>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
-}
-
-static int ch_p2ceil(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-static int ch_ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
-}
-
-template <typename T>
-static void ch_dispatch(int BN, dim3 grid, hipStream_t st, const void* in, const void* w, const float* bias, void* out, const ConvHaloGeom& g) {
-  if (BN == 64) {
-    const size_t lds = (size_t)(RX_CH_MAX_HV * 4 + 9 * 64 * 4) * 16;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<T, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((conv_halo_kernel<T, 64>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
-  } else {
-    const size_t lds = (size_t)(RX_CH_MAX_HV * 4 + 9 * 32 * 4) * 16;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<T, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((conv_halo_kernel<T, 32>), grid, dim3(256), lds, st, (const T*)in, (const T*)w, bias, (T*)out, g);
-  }
+  RX_CH_ROW(RX_CH_HALO32, 0, 0, 0, 0, 0, (conv_halo32_kernel<T, false>))
+  RX_CH_ROW(RX_CH_HALO32, 1, 0, 0, 0, 0, (conv_halo32_kernel<T, true>))
+  RX_CH_ROW(RX_CH_HALO32, 0, 0, 1, 0, 0, (conv_halo32_kernel<T, false, true>))
+  RX_CH_ROW(RX_CH_GENERIC64, 0, 0, 0, 0, 0, (conv_halo_kernel<T, 64>))
+  RX_CH_ROW(RX_CH_GENERIC32, 0, 0, 0, 0, 0, (conv_halo_kernel<T, 32>))
+#undef RX_CH_ROW
+  return false;
 }
 
 // returns 1 if handled, 0 to fall through to the generic kernel, negative on error.
 // in/out: same spatial dims (stride 1, kernel 3x3x3, padding 1).  flip = 1 for backward-data.
-// stat_part / stat_chunks (forward only, optional): when the launch goes to a persistent kernel, per-wave partial sums of
-// y and y^2 are left in stat_part ([n][*stat_chunks][2][Co] floats) and *stat_chunks > 0; otherwise *stat_chunks = 0.
+// stat_part / stat_chunks (optional): when the launch goes to a kernel that sums in its epilogue, per-wave partial sums are left in
+// stat_part ([n][*stat_chunks][2][Co] floats) and *stat_chunks > 0; otherwise *stat_chunks = 0.  Forward: sums of y and y^2.
+// Backward-data with `bs`: the two InstanceNorm backward sums of the layer `bs` describes.
 int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip, int accumulate,
                      hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks, const RxBwdStat* bs) {
   if (stat_chunks) *stat_chunks = 0;
-  const int per16 = dt == RX_F32 ? 4 : 8;
-  const int KB = 4 * per16;
-  if (in->c % KB || out->c % 32 || in->ld % per16 || out->ld % 4) return 0;
-  if (((uintptr_t)in->ptr & 15) || ((uintptr_t)out->ptr & 7) || ((uintptr_t)w & 15)) return 0;
-  if (rx_act_voxels(in) * (long)in->ld >= (1L << 31)) return 0;  // 32-bit halo offsets
+  RxChQuery q = {};
+  q.dt = dt;
+  q.N = in->n, q.Z = in->z, q.Y = in->y, q.X = in->x;
+  q.Ci = in->c, q.Co = out->c, q.ldi = in->ld, q.ldo = out->ld;
+  q.in_cs = in->cs, q.out_cs = out->cs;
+  q.in_lo = (unsigned)((uintptr_t)in->ptr & 15), q.out_lo = (unsigned)((uintptr_t)out->ptr & 15), q.w_lo = (unsigned)((uintptr_t)w & 15);
+  q.flip = flip, q.accumulate = accumulate;
+  q.stat_offered = stat_part && stat_chunks, q.stat_bytes = stat_bytes;
+  q.want_bs = bs != nullptr;
+  if (bs) q.bsy_lo = (unsigned)((uintptr_t)bs->y->ptr & 15), q.bs_ldy = bs->y->ld;
+  const RxChChoice c = rx_ch_choose(q);
+  if (c.kind == RX_CH_FALLTHROUGH) return 0;
+  if (c.kind == RX_CH_REFUSE) RX_FAIL(RX_EUNSUPPORTED, "%s", c.message);
   ConvHaloGeom g;
   memset(&g, 0, sizeof(g));
-  g.N = in->n, g.Z = in->z, g.Y = in->y, g.X = in->x;
-  g.Ci = in->c, g.Co = out->c, g.ldi = in->ld, g.ldo = out->ld;
-  g.in_ss = rx_act_voxels(in) * (long)in->ld;
-  g.out_ss = rx_act_voxels(out) * (long)out->ld;
-  g.in_cs = in->cs ? in->cs : KB, g.out_cs = out->cs ? out->cs : 32;
-  if ((in->cs || out->cs) && dt == RX_F32) return 0;
-  int TX = ch_p2ceil(g.X);
-  TX = TX < 4 ? 4 : (TX > 16 ? 16 : TX);
-  int rem = 256 / TX;
-  int TY = ch_p2ceil(g.Y);
-  int capy = TX == 16 ? 4 : 8;
-  if (TY > capy) TY = capy;
-  if (TY > rem) TY = rem;
-  int TZ = ch_p2ceil(g.Z);
-  if (TZ > rem / TY) TZ = rem / TY;
-  if (TZ * TY * TX != 256) return 0;  // the kernel is written for full 256-voxel tiles
-  g.TZ = TZ, g.TY = TY, g.TX = TX, g.lTX = ch_ilog2(TX), g.lTY = ch_ilog2(TY);
-  g.VT = 256;
-  g.HY = TY + 2, g.HX = TX + 2, g.HV = (TZ + 2) * g.HY * g.HX;
-  if (g.HV > RX_CH_MAX_HV) return 0;
-  g.tz_n = (g.Z + TZ - 1) / TZ, g.ty_n = (g.Y + TY - 1) / TY, g.tx_n = (g.X + TX - 1) / TX;
-  g.NT = g.N * g.tz_n * g.ty_n * g.tx_n;
+  g.N = q.N, g.Z = q.Z, g.Y = q.Y, g.X = q.X;
+  g.Ci = q.Ci, g.Co = q.Co, g.ldi = q.ldi, g.ldo = q.ldo;
+  g.in_ss = c.in_ss, g.out_ss = c.out_ss, g.in_cs = c.in_cs, g.out_cs = c.out_cs;
+  g.TZ = c.TZ, g.TY = c.TY, g.TX = c.TX, g.lTX = c.lTX, g.lTY = c.lTY;
+  g.HY = c.HY, g.HX = c.HX, g.HV = c.HV, g.VT = 256;
+  g.tz_n = c.tz_n, g.ty_n = c.ty_n, g.tx_n = c.tx_n, g.NT = c.NT;
+  g.order = c.order, g.wgs_s = c.wgs_s;
+  g.stat_part = c.take_stats ? stat_part : nullptr;
+  if (c.take_bs) {
+    g.bs_y = bs->y->ptr, g.bs_ldy = bs->y->ld, g.bs_yss = rx_act_voxels(bs->y) * (long)bs->y->ld;
+    g.bs_stats = bs->stats, g.bs_slope = bs->slope;
+  }
   g.accumulate = accumulate, g.flip = flip;
-  g.order = 1;               // persistent kernels: z-fastest columns; one-tile grids: 4x4x4 bricks where the tile grid allows
   static const int dbg = rx_env_mask("RX_DBG");
   g.dbg = dbg;
-  int BN = (g.Co % 64 == 0) ? 64 : 32;
-  if (BN == 64 && (long)g.NT * (g.Co / 64) < 256) BN = 32;  // under-filled grid: twice the workgroups, half the work each
-  if ((in->cs || out->cs) && (long)g.NT * (g.Co / BN) < 192) RX_FAIL(RX_EUNSUPPORTED, "conv_halo: planar-concat operand on a layer too small for the halo kernels");
-  // Too few (tile, channel block) pairs to fill 256 CUs (128 pairs -- the 1024-channel data gradient of the first decoder conv
-  // at 8^3 -- measured 93 us here, ~60 us on igemm_fat): the split-K gather kernel takes them.  A split-K variant of this kernel
-  // (input channels over blockIdx.z, fp32 slabs + a fixed-order reduce) measured no gain against it, 35.7 + 5.5 us against 36 +
-  // 5 us inside the cfg2 step: with 3-6 phases per workgroup it is a chain of cold weight-slice fetches, not an L2-bandwidth
-  // problem.
-  if ((long)g.NT * (g.Co / BN) < 192) return 0;
-  dim3 grid(g.NT, g.Co / BN);
-  if (BN == 32 && TZ == 4 && TY == 4 && TX == 16 && dt != RX_F32 && g.Ci == 32 && g.Co == 32 && g.NT >= 512) {
-    rx_note_kernel("conv_halo32p_kernel");               // 32 -> 32 channels: persistent, weights stationary in LDS
-    if (in->cs || out->cs) RX_FAIL(RX_EUNSUPPORTED, "conv_halo32p: planar-concat operand");
-    const bool room = stat_part && stat_chunks && (size_t)g.N * 1024 * 2 * g.Co * sizeof(float) <= stat_bytes;
-    const bool fuse32 = room && ((!flip && !accumulate && !bs) || (flip && bs));
-    g.stat_part = fuse32 ? stat_part : nullptr;
-    if (fuse32 && bs) {
-      g.bs_y = bs->y->ptr, g.bs_ldy = bs->y->ld, g.bs_yss = rx_act_voxels(bs->y) * (long)bs->y->ld;
-      g.bs_stats = bs->stats, g.bs_slope = bs->slope;
-    }
-    if (dt == RX_BF16)
-      ch32p_launch<bf16_t>(st, in->ptr, w, bias, out->ptr, g);
-    else
-      ch32p_launch<f16_t>(st, in->ptr, w, bias, out->ptr, g);
-    hipError_t e4 = hipGetLastError();
-    if (e4 != hipSuccess) {
-      rx_set_error("conv_halo32p: %s", hipGetErrorString(e4));
-      return RX_ELAUNCH;
-    }
-    if (fuse32) *stat_chunks = g.wgs_s * 4;
-    g.stat_part = nullptr, g.bs_y = nullptr;
-    return 1;
-  }
-  ConvHaloGeom g1 = g;                                // one tile per workgroup: bricks of tiles where the tile grid allows
-  if (g.tx_n % 4 == 0 && g.ty_n % 4 == 0 && g.tz_n % 4 == 0) g1.order = 2;
-  if (BN == 32 && TZ == 4 && TY == 4 && TX == 16 && dt != RX_F32 && !out->cs && g.Ci >= 64 && (long)g.NT * (g.Co / 32) >= 256 &&
-      !(accumulate && !flip)) {
-    // 32-channel blocks on the wave-specialised DMA pipeline (the 256-channel layers at 16^3: 32 tiles x 8 blocks = one workgroup
-    // per CU; alone 43 -> ~30 us against conv_halo32_kernel's one tile per workgroup)
-    const bool fuse = stat_part && stat_chunks && !flip && !accumulate && (size_t)g.N * 1024 * 2 * g.Co * sizeof(float) <= stat_bytes;
-    ConvHaloGeom g2 = g;
-    g2.stat_part = fuse ? stat_part : nullptr;
-    g2.bs_y = nullptr;
-    const bool launched = dt == RX_BF16 ? ch32ws_launch<bf16_t>(st, in->ptr, w, bias, out->ptr, g2) : ch32ws_launch<f16_t>(st, in->ptr, w, bias, out->ptr, g2);
-    if (launched) {
-      rx_note_kernel("conv_halo32ws_kernel");
-      hipError_t e7 = hipGetLastError();
-      if (e7 != hipSuccess) {
-        rx_set_error("conv_halo32ws: %s", hipGetErrorString(e7));
-        return RX_ELAUNCH;
-      }
-      if (fuse && g2.stat_part) *stat_chunks = g2.wgs_s * 4;
-      return 1;
-    }
-  }
-  if (BN == 32 && TZ == 4 && TY == 4 && TX == 16) {  // full-resolution layers: compile-time tile, padded rows
-    if (out->cs) RX_FAIL(RX_EUNSUPPORTED, "conv_halo32: planar-concat output");
-    rx_note_kernel("conv_halo32_kernel");
-    // statistics in the epilogue only for DEEP layers (>= 4 input-channel chunks: >= 432 MFMAs per wave behind the one wavefront
-    // reduction) with few tiles per sample (the finalize reads 4 partial rows per tile): the 16^3 layers
-    const int NTs32 = g.NT / g.N;
-    const bool fuse32n = stat_part && stat_chunks && !flip && !accumulate && dt != RX_F32 && g.Ci / KB >= 4 && NTs32 * 4 <= 1024 &&
-                         (size_t)g.N * NTs32 * 4 * 2 * g.Co * sizeof(float) <= stat_bytes;
-    g1.stat_part = fuse32n ? stat_part : nullptr;
-    switch (dt) {
-      case RX_F32: ch32_launch<float>(grid, st, in->ptr, w, bias, out->ptr, g1); break;
-      case RX_BF16: ch32_launch<bf16_t>(grid, st, in->ptr, w, bias, out->ptr, g1); break;
-      case RX_F16: ch32_launch<f16_t>(grid, st, in->ptr, w, bias, out->ptr, g1); break;
-      default: return 0;
-    }
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) {
-      rx_set_error("conv_halo32: %s", hipGetErrorString(e2));
-      return RX_ELAUNCH;
-    }
-    if (fuse32n) *stat_chunks = NTs32 * 4;
-    return 1;
-  }
-  if (g.Co % 64 == 0 && TZ == 4 && TY == 4 && TX == 16 && dt != RX_F32 && (long)g.NT * (g.Co / 64) >= 256) {
-    if (in->cs) RX_FAIL(RX_EUNSUPPORTED, "conv_halo64ws: planar-concat input");
-    rx_note_kernel("conv_halo64ws_kernel");
-    const bool room64 = stat_part && stat_chunks && (size_t)g.N * 1024 * 2 * g.Co * sizeof(float) <= stat_bytes;
-    const bool fuse64 = room64 && !flip && !accumulate && !bs;
-    const bool fuse64b = room64 && flip && bs;
-    g.stat_part = (fuse64 || fuse64b) ? stat_part : nullptr;
-    if (fuse64b) {
-      g.bs_y = bs->y->ptr, g.bs_ldy = bs->y->ld, g.bs_yss = rx_act_voxels(bs->y) * (long)bs->y->ld;
-      g.bs_stats = bs->stats, g.bs_slope = bs->slope;
-    }
-    if (dt == RX_BF16)
-      ch64ws_launch<bf16_t>(st, in->ptr, w, bias, out->ptr, g);
-    else
-      ch64ws_launch<f16_t>(st, in->ptr, w, bias, out->ptr, g);
-    hipError_t e5 = hipGetLastError();
-    if (e5 != hipSuccess) {
-      rx_set_error("conv_halo64ws: %s", hipGetErrorString(e5));
-      return RX_ELAUNCH;
-    }
-    if (fuse64 && g.stat_part) *stat_chunks = g.wgs_s * 4;      // (the launcher clears stat_part when it took a variant without them)
-    if (fuse64b && g.bs_y && g.stat_part) *stat_chunks = g.wgs_s * 4;
-    g.stat_part = nullptr, g.bs_y = nullptr;
-    return 1;
-  }
-  if (in->cs || out->cs) RX_FAIL(RX_EUNSUPPORTED, "conv_halo: planar-concat operand on the generic halo kernel");
-  rx_note_kernel(BN == 64 ? "conv_halo_kernel<64>" : "conv_halo_kernel<32>");
-  switch (dt) {
-    case RX_F32: ch_dispatch<float>(BN, grid, st, in->ptr, w, bias, out->ptr, g1); break;
-    case RX_BF16: ch_dispatch<bf16_t>(BN, grid, st, in->ptr, w, bias, out->ptr, g1); break;
-    case RX_F16: ch_dispatch<f16_t>(BN, grid, st, in->ptr, w, bias, out->ptr, g1); break;
-    default: return 0;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    rx_set_error("conv_halo: %s", hipGetErrorString(e));
-    return RX_ELAUNCH;
-  }
+  rx_note_kernel(c.name);
+  const bool found = dt == RX_F32    ? ch_launch<float>(c, st, in->ptr, w, bias, out->ptr, g)
+                     : dt == RX_BF16 ? ch_launch<bf16_t>(c, st, in->ptr, w, bias, out->ptr, g)
+                                     : ch_launch<f16_t>(c, st, in->ptr, w, bias, out->ptr, g);
+  if (!found) RX_FAIL(RX_ELAUNCH, "%s: the selector chose a variant that is not instantiated", c.name);
+  RX_CHECK_LAUNCH(c.name);
+  if (stat_chunks) *stat_chunks = c.stat_chunks;
   return 1;
 }
+

@@ -614,8 +614,7 @@ extern "C" int rx_conv3d_bwd_data_instats(rx_dtype dt, const rx_act* dy, const v
     if (rc == 1) {
       if (chunks > 0) {
         rx_inbwd_fused_finalize_launch((const float*)ws, dx->n, chunks, dx->c, (double)rx_act_voxels(dx), in_stats, m12, (hipStream_t)stream);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) RX_FAIL(RX_ELAUNCH, "rx_conv3d_bwd_data_instats(finalize): %s", hipGetErrorString(e));
+        RX_CHECK_LAUNCH("rx_conv3d_bwd_data_instats(finalize)");
         *fused = 1;
       }
       return RX_OK;
@@ -639,8 +638,7 @@ extern "C" int rx_conv3d_fwd_stats(rx_dtype dt, const rx_act* x, const void* w_f
     if (rc < 0) return rc;
     if (rc == 1 && chunks > 0) {
       rx_stats_finalize_launch((const float*)ws, y->n, chunks, y->c, (double)rx_act_voxels(y), eps, stats, (hipStream_t)stream);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) RX_FAIL(RX_ELAUNCH, "rx_conv3d_fwd_stats(finalize): %s", hipGetErrorString(e));
+      RX_CHECK_LAUNCH("rx_conv3d_fwd_stats(finalize)");
       return RX_OK;
     }
     if (rc == 1) return rx_instnorm_stats(dt, y, eps, stats, ws, wsb, stream);

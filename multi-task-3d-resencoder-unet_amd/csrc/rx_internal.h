@@ -8,6 +8,10 @@ int rx_note_seq(void);   // how many times rx_note_kernel ran on this thread
 
 // ---- rx_conv_halo.hip, rx_pointwise.hip, rx_dgrad_s2.hip: fast paths of the conv entry points in rx_igemm.hip.
 // Return 1 if they handled the launch, 0 to fall through to the generic kernel, negative on error.
+// rx_conv_halo_try, stat_part / stat_bytes / stat_chunks (optional): a launch that sums in its epilogue leaves per-wave partial
+// rows in stat_part and their number per sample in *stat_chunks (else 0: the caller reduces in a pass of its own) -- forward the
+// sums of y and y^2, backward-data with `bs` the two InstanceNorm backward sums of the layer `bs` describes.  Which kernel and
+// which of these a call gets is decided by rx_ch_choose (rx_conv_halo_plan.h).
 int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip, int accumulate,
                      hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks, const RxBwdStat* bs);
 int rx_pointwise_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, const int32_t stride[3],
