@@ -659,6 +659,25 @@ int rx_edt_sq(const uint8_t* feature, int n, int z, int y, int x, int32_t* dist,
 int rx_surface_hist(const uint8_t* edges, const int32_t* dist, long total, long bins, int64_t* hist, int64_t* count, int64_t* unmatched,
                     void* stream);
 
+/* ---- connected components of a thresholded uint8 volume (host side postprocess/components.py, whose label_numpy,
+ *      component_sizes_numpy and filter_numpy are the statements).  A volume is a contiguous (z, y, x) block; `nvol` volumes lie back
+ *      to back, at most 65535 of them, each of at most RX_CC_MAX_VOXELS = 2^31 - 2 voxels.  Integers only; no allocation, copy or
+ *      synchronisation.  RX_EINVAL before anything is launched: null pointers, an extent of 0, more voxels or volumes than that, a
+ *      connectivity other than 6, 18 or 26, a level outside 0 .. 254, a misaligned pointer.
+ *      rx_cc_label: labels[v] = 0 where values[v] <= level, else 1 + the smallest linear index z*Y*X + y*X + x over the voxels of
+ *        v's component of the mask values > level under `connectivity` (6 faces, 18 + edges, 26 + corners), within v's own volume.
+ *        The label is a property of the mask alone: it does not depend on the order anything ran in.  `labels`: int32, 4-byte
+ *        aligned, another buffer than `values`.  Up to five launches: tiles, the tile faces of each axis, roots.
+ *      rx_cc_sizes: sizes (int32, nvol * voxels words) is zeroed, then sizes[volume * voxels + label - 1] += 1 for every voxel with a
+ *        label in 1 .. voxels: at a component's root its voxel count, 0 everywhere else.  Integer atomics.
+ *      rx_cc_filter: out[v] = values[v] where labels[v] is in 1 .. voxels and sizes[volume * voxels + labels[v] - 1] >= min_voxels,
+ *        else 0.  It compares whatever `sizes` holds.  `out` may be `values`. */
+#define RX_CC_MAX_VOXELS 2147483646L
+int rx_cc_label(const uint8_t* values, int level, int nvol, int z, int y, int x, int connectivity, int32_t* labels, void* stream);
+int rx_cc_sizes(const int32_t* labels, int nvol, long voxels, int32_t* sizes, void* stream);
+int rx_cc_filter(const uint8_t* values, const int32_t* labels, const int32_t* sizes, int min_voxels, int nvol, long voxels, uint8_t* out,
+                 void* stream);
+
 /* ---- validation preview on the device: one panel of the debug GIF (host side training/visualization/preview.py, whose
  *      panel_numpy and minmax_numpy are the statements).  `src` is ONE sample's contiguous (c, z, h, w) block of `dtype` (rx_dtype),
  *      aligned to its element (a base that is not 16-byte aligned is fine).  c == 3 draws channels 0, 1, 2 into bytes 0, 1, 2 of

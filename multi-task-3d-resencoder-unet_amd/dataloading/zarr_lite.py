@@ -44,6 +44,7 @@ class Array:
         fv = m.get("fill_value")
         self.fill_value = 0 if fv is None else fv
         self._sep = m.get("dimension_separator", ".")
+        self.compressor, self.dimension_separator = self._codec, self._sep      # what a writer of a sibling array needs to match
         self.ndim = len(self.shape)
         self.store = self           # `arr.store.close()` of the reference's loop is a no-op here
 

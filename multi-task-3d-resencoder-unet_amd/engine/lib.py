@@ -26,6 +26,7 @@ RX_INGEST_COPY, RX_INGEST_DIV255, RX_INGEST_DIV65535, RX_INGEST_NORMAL_U16, RX_I
 RX_AFFINE_LINEAR, RX_AFFINE_NEAREST = 0, 1
 RX_AFFINE_CONSTANT, RX_AFFINE_CLAMP = 0, 1
 RX_EDT_NONE, RX_EDT_MAX_EXTENT = 1 << 30, 1024
+RX_CC_MAX_VOXELS = 2**31 - 2
 
 
 class RxError(RuntimeError):
@@ -186,6 +187,9 @@ _SIGNATURES = {
     "rx_mask_edges": (c_int, [c_void_p, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rx_edt_sq": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rx_surface_hist": (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rx_cc_label": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rx_cc_sizes": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
+    "rx_cc_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p, c_void_p]),
     "rx_preview_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int,
                                  c_void_p, c_void_p]),
     "rx_mesh_slice_keys": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -1,6 +1,6 @@
 """Thin Python wrappers over the C ABI (one function per entry point of include/rxunet.h), split by subject: core (Act, workspace,
 events and programs, the profiler and its accounting, the argument checks, codes), network, losses, pipeline, infer, validation,
-mesh.  Nothing here computes on the host or with torch ops: every function enqueues HIP kernels on torch's current stream.
+mesh, postprocess.  Nothing here computes on the host or with torch ops: every function enqueues HIP kernels on torch's current stream.
 
 Every wrapper is reached as `ops.NAME`, looked up at call time, so a replaced `ops.NAME` (a test's spy, a tracer) is what callers
 get.  A subject module imports from core only.  The profiler is read with `ops.profiling()`, never as a variable."""
@@ -11,7 +11,7 @@ import torch      # noqa: F401
 
 from .. import lib as _l      # noqa: F401
 from ..lib import I3, RxAct, check, load, stream_ptr      # noqa: F401
-from . import core, infer, losses, mesh, network, pipeline, validation      # noqa: F401
+from . import core, infer, losses, mesh, network, pipeline, postprocess, validation      # noqa: F401
 from .core import (_U16, Act, LaunchProfiler, Program, event_free, event_new, event_record, profiling,      # noqa: F401
                    set_profiler, stream_wait, timed_bytes, workspace)
 from .infer import (SW_ACT, SW_BLEND, SW_CAST, SW_NORM, sw_accumulate, sw_finalize, sw_gather,      # noqa: F401
@@ -28,5 +28,6 @@ from .network import (avgpool_bwd, avgpool_fwd, channel_sum, conv3d_bwd_data, co
                       stem_conv_bwd_weight, stem_conv_fwd, stem_conv_fwd_stats)
 from .pipeline import (affine_apply, affine_table, aug_filter_zy, aug_philox_u32, aug_pointwise, augment_batch,      # noqa: F401
                        box_stats, elastic_apply, elastic_nodes, elastic_tables, geom_apply, geom_table, ingest, label_dilate)
+from .postprocess import cc_filter, cc_label, cc_sizes      # noqa: F401
 from .validation import (class_counts, edt_sq, mask_edges, normal_stats, preview_frames, preview_panel, seg_counts,      # noqa: F401
                          surface_hist, surface_scratch)

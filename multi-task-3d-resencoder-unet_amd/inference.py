@@ -778,6 +778,13 @@ def main(argv=None):
                               normal_keys=mgr.infer_tta_normal_keys, tile=mgr.infer_tile, skip_empty=mgr.infer_skip_empty)
     store = runner.run(src, a.output_path or mgr.infer_output_path, compressor=None if a.compressor == "none" else "zlib")
     print(store, flush=True)
+    pp = (mgr.infer_postprocess or {}).get("components")
+    if pp:
+        from .postprocess import ComponentFilter
+        gb = pp["max_device_gb"]
+        for task in pp["tasks"]:
+            print(task, ComponentFilter(pp["level"], pp["connectivity"], pp["min_voxels"], pp["write_labels"],
+                                        None if gb is None else int(gb * 2**30)).run(store, task), flush=True)
     return store
 
 
