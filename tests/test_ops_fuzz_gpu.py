@@ -1,7 +1,10 @@
 """GPU (-m gpu): randomized shapes through the conv / transposed-conv / InstanceNorm entry points against torch CPU fp64 --
 channel counts, extents (ragged against every tile size: 4x4x16 halo tiles, 128 / 256-row GEMM tiles, 16-voxel K steps), per-axis
-kernels and strides, batch, bias, accumulation, strided input views.  The fixed cases of tests/test_ops_gpu.py pin the kernels the
-comments name; these draws walk the dispatch table between them (RX_FUZZ_SEED picks other draws)."""
+kernels and strides, batch, bias, accumulation, strided input views.  These draws are EXTRA: nothing states or asserts which
+dispatch branch a draw lands on, and another seed (RX_FUZZ_SEED) or a moved threshold moves them.  What guarantees that every
+branch of the conv family is reached and checked per element is the ledger, tests/conv_dispatch_cases.py: each of its rows names
+the kernel, the shape and the test (test_conv_dispatch_gpu.py or a pinned case of test_ops_gpu.py) that holds the branch, and
+test_conv_dispatch_cpu.py keeps the ledger complete against the sources."""
 import os
 import random
 

@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_dispatch_cases
 from exact_ops import (U32, Guarded, assert_bits, assert_exact_precondition, assert_within, exact_tensor, gamma, half_ulp,
                        poisoned)
 from norm_bounds import _mr, _ncdhw, check_norm_bwd, check_norm_fwd, check_stats, lrelu_mask, norm_bwd_ref  # noqa: F401
@@ -214,18 +215,9 @@ CONV_CASES = [
 
 # which kernel instantiation the library must dispatch (16-bit modes) for the cases whose comment names one: a dispatch change
 # that silently moved them back onto the generic gather kernels would otherwise keep this file green.
-# (fwd, bwd-data, bwd-weight) as reported by rx_last_conv_kernel(); None = not pinned.
-EXPECT_KERNELS = {
-    (256, 256, (4, 4, 4), (3, 3, 3), (1, 1, 1)): ("igemm_fat_kernel", "igemm_fat_kernel", "wgrad_halo_kernel"),
-    (512, 512, (4, 4, 4), (3, 3, 3), (1, 1, 1)): ("igemm_fat_kernel", "igemm_fat_kernel", "wgrad_halo_kernel"),
-    (512, 512, (3, 8, 8), (3, 3, 3), (1, 1, 1)): ("igemm_fat_kernel", "igemm_fat_kernel", "wgrad_halo_kernel"),
-    (32, 32, (30, 36, 64), (3, 3, 3), (1, 1, 1)): ("conv_halo32p_kernel", "conv_halo32p_kernel", "wgrad_halo16ws_kernel"),
-    (64, 64, (14, 32, 64), (3, 3, 3), (1, 1, 1)): ("conv_halo64ws_kernel", "conv_halo64ws_kernel", "wgrad_halo16ws_kernel"),
-    (64, 96, (14, 32, 32), (3, 3, 3), (1, 1, 1)): ("conv_halo32ws_kernel", "conv_halo32ws_kernel", None),
-    (128, 64, (32, 32, 64), (3, 3, 3), (2, 2, 2)): (None, "dgrad_s2p_kernel", None),
-    (128, 64, (24, 40, 72), (3, 3, 3), (2, 2, 2)): (None, "dgrad_s2p_kernel", None),
-    (64, 128, (12, 20, 18), (1, 1, 1), (1, 1, 1)): ("pointwise_kernel", "pointwise_kernel", None),
-}
+# (fwd, bwd-data, bwd-weight) as reported by rx_last_conv_kernel(); None = not pinned.  The pins are the rows of the dispatch ledger
+# (tests/conv_dispatch_cases.py) that point at this test; test_conv_dispatch_cpu.py keeps them from shrinking.
+EXPECT_KERNELS = conv_dispatch_cases.expect_kernels()
 
 
 def last_kernel(ops):
@@ -277,6 +269,8 @@ def test_conv3d_fwd_bwd(ops, dtype, case):
     if dtype != torch.float32 and case in EXPECT_KERNELS:
         for which, want in zip(("fwd", "dgrad", "wgrad"), EXPECT_KERNELS[case]):
             assert want is None or seen[which] == want, (case, which, seen)
+        want = conv_dispatch_cases.covered_kernel("test_conv3d_fwd_bwd", case, conv_dispatch_cases.DXA)      # dx +=: its own ledger row
+        assert want is None or seen_exact["dgrad+"] == want, (case, seen_exact)
     assert {w: seen_exact[w] for w in seen} == seen, (case, seen, seen_exact)      # both passes run the same kernels
 
 
@@ -667,6 +661,8 @@ def test_conv3d_fwd_stats(ops, dtype, case):
     ops.conv3d_fwd(x, wf, b, y1, k, s)
     ops.instnorm_stats(y1, s1)
     ops.conv3d_fwd_stats(x, wf, b, y2, k, s, s2)
+    want = conv_dispatch_cases.covered_kernel("test_conv3d_fwd_stats", case, conv_dispatch_cases.STATS)       # the ledger rows that point here
+    assert dtype == torch.float32 or want is None or last_kernel(ops) == want, (case, last_kernel(ops), want)
     torch.cuda.synchronize()
     assert torch.equal(y1.t, y2.t)
     assert torch.allclose(s1, s2, rtol=2e-5, atol=2e-6), (s1 - s2).abs().max()
@@ -765,6 +761,9 @@ def test_conv3d_bwd_data_instats(ops, dtype, slope, accumulate, c, dims):
     k, s = (3, 3, 3), (1, 1, 1)
     ops.conv3d_bwd_data(dyv, wb, dx1, k, s, accumulate)
     fused = ops.conv3d_bwd_data_instats(dyv, wb, dx2, k, s, accumulate, yv, stats, slope, m12)
+    want = conv_dispatch_cases.covered_kernel("test_conv3d_bwd_data_instats", (c, dims),
+                                              conv_dispatch_cases.BSA if accumulate else conv_dispatch_cases.BS)
+    assert want is None or last_kernel(ops) == want, ((c, dims), last_kernel(ops), want)
     torch.cuda.synchronize()
     assert fused, "these layers must take a persistent kernel that delivers the sums"
     assert torch.equal(dx1.t, dx2.t)
