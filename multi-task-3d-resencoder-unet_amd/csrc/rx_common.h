@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "../../include/rxunet.h"
+#include "rx_wgrad_plan.h"   // the HIP-free planners of the conv family, with the structs its kernels take by value
 
 // Host-side per-launch overhead: the dispatch code (re)sets the dynamic-LDS limit of the kernel it is about to launch on EVERY
 // call (~700 launches per train step).  That is answered from a per-thread cache keyed by (device, kernel) after the first time
@@ -160,7 +161,6 @@ __device__ inline double wave_sum_d(double v) {
 static inline size_t rx_dtype_size(int dt) { return dt == RX_F32 ? 4 : 2; }
 static inline size_t rx_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static inline long rx_act_voxels(const rx_act* a) { return (long)a->z * a->y * a->x; }
 static inline bool rx_act_ok(const rx_act* a) {
   return a && a->ptr && a->n > 0 && a->z > 0 && a->y > 0 && a->x > 0 && a->c > 0 && a->ld >= a->c && a->cs == 0;
 }
@@ -184,18 +184,7 @@ static inline bool rx_act_ok_planar(const rx_act* a) {
     else body(std::integral_constant<bool, true>{}, std::integral_constant<bool, true>{});                            \
   } while (0)
 
-// ---- tap tables and MFMA wrappers shared by the implicit-GEMM and weight-gradient kernels ------
-// kernel sizes 1..7 and strides 1..4 per axis (the reference passes any `kernel_sizes` / `strides` of a manual model_config
-// straight to Conv(k, stride, pad = (k-1)//2), build_network_from_config.py:85-148): up to 7^3 = 343 taps per launch, so the
-// weight index needs 9 bits and the tables live in the kernel arguments (RX_MAX_TAPS x 8 bytes, within the 4 KB kernarg limit)
-#define RX_MAX_TAPS 344
-#define RX_MAX_KERNEL 7
-#define RX_MAX_STRIDE 4
-struct RxTap {
-  int8_t dz, dy, dx, pad_;
-  uint16_t w, pad2_;
-};
-
+// ---- MFMA wrappers shared by the implicit-GEMM and weight-gradient kernels (their tap tables and launch geometry: the planners) ------
 // one 32x32 accumulator update from two 16-byte operand fragments (lane = row/col (lane&31),
 // k-half (lane>>5)): 16 k-values for 16-bit types, 8 for fp32 (4 exact-fp32 MFMAs).
 template <typename T>

@@ -1147,31 +1147,16 @@ static bool ch_launch(const RxChChoice& c, hipStream_t st, const void* in, const
   return false;
 }
 
-// returns 1 if handled, 0 to fall through to the generic kernel, negative on error.
+// launches the choice `c` of rx_ch_choose for the query rx_ch_query builds of the same operands.
 // in/out: same spatial dims (stride 1, kernel 3x3x3, padding 1).  flip = 1 for backward-data.
-// stat_part / stat_chunks (optional): when the launch goes to a kernel that sums in its epilogue, per-wave partial sums are left in
-// stat_part ([n][*stat_chunks][2][Co] floats) and *stat_chunks > 0; otherwise *stat_chunks = 0.  Forward: sums of y and y^2.
-// Backward-data with `bs`: the two InstanceNorm backward sums of the layer `bs` describes.
-int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip, int accumulate,
-                     hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks, const RxBwdStat* bs) {
-  if (stat_chunks) *stat_chunks = 0;
-  RxChQuery q = {};
-  q.dt = dt;
-  q.N = in->n, q.Z = in->z, q.Y = in->y, q.X = in->x;
-  q.Ci = in->c, q.Co = out->c, q.ldi = in->ld, q.ldo = out->ld;
-  q.in_cs = in->cs, q.out_cs = out->cs;
-  q.in_lo = (unsigned)((uintptr_t)in->ptr & 15), q.out_lo = (unsigned)((uintptr_t)out->ptr & 15), q.w_lo = (unsigned)((uintptr_t)w & 15);
-  q.flip = flip, q.accumulate = accumulate;
-  q.stat_offered = stat_part && stat_chunks, q.stat_bytes = stat_bytes;
-  q.want_bs = bs != nullptr;
-  if (bs) q.bsy_lo = (unsigned)((uintptr_t)bs->y->ptr & 15), q.bs_ldy = bs->y->ld;
-  const RxChChoice c = rx_ch_choose(q);
-  if (c.kind == RX_CH_FALLTHROUGH) return 0;
-  if (c.kind == RX_CH_REFUSE) RX_FAIL(RX_EUNSUPPORTED, "%s", c.message);
+// stat_part: when the choice sums in its epilogue (c.take_stats), per-wave partial sums are left there ([n][c.stat_chunks][2][Co]
+// floats).  Forward: sums of y and y^2.  Backward-data with c.take_bs: the two InstanceNorm backward sums of the layer `bs` describes.
+int rx_conv_halo_launch(const RxChChoice& c, rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip,
+                        int accumulate, hipStream_t st, float* stat_part, const RxBwdStat* bs) {
   ConvHaloGeom g;
   memset(&g, 0, sizeof(g));
-  g.N = q.N, g.Z = q.Z, g.Y = q.Y, g.X = q.X;
-  g.Ci = q.Ci, g.Co = q.Co, g.ldi = q.ldi, g.ldo = q.ldo;
+  g.N = in->n, g.Z = in->z, g.Y = in->y, g.X = in->x;
+  g.Ci = in->c, g.Co = out->c, g.ldi = in->ld, g.ldo = out->ld;
   g.in_ss = c.in_ss, g.out_ss = c.out_ss, g.in_cs = c.in_cs, g.out_cs = c.out_cs;
   g.TZ = c.TZ, g.TY = c.TY, g.TX = c.TX, g.lTX = c.lTX, g.lTY = c.lTY;
   g.HY = c.HY, g.HX = c.HX, g.HV = c.HV, g.VT = 256;
@@ -1191,7 +1176,6 @@ int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* 
                                      : ch_launch<f16_t>(c, st, in->ptr, w, bias, out->ptr, g);
   if (!found) RX_FAIL(RX_ELAUNCH, "%s: the selector chose a variant that is not instantiated", c.name);
   RX_CHECK_LAUNCH(c.name);
-  if (stat_chunks) *stat_chunks = c.stat_chunks;
-  return 1;
+  return RX_OK;
 }
 

@@ -21,7 +21,7 @@ struct RxChQuery {
   bool want_bs;                          // the caller asks for the InstanceNorm backward sums (RxBwdStat)
 };
 
-enum RxChKind { RX_CH_FALLTHROUGH = 0, RX_CH_REFUSE, RX_CH_LAUNCH };   // rx_conv_halo_try returns 0 / RX_EUNSUPPORTED / 1
+enum RxChKind { RX_CH_FALLTHROUGH = 0, RX_CH_REFUSE, RX_CH_LAUNCH };   // the route goes on to the gather kernels / fails with RX_EUNSUPPORTED / launches
 enum RxChFamily { RX_CH_GENERIC32, RX_CH_GENERIC64, RX_CH_HALO32, RX_CH_HALO32P, RX_CH_HALO32WS, RX_CH_HALO64WS };
 
 struct RxChChoice {
@@ -78,6 +78,23 @@ inline RxChChoice rx_ch_refuse(RxChChoice c, const char* message) {
 inline RxChChoice rx_ch_launch(RxChChoice c, RxChFamily family, const char* name, size_t lds) {
   c.kind = RX_CH_LAUNCH, c.family = family, c.name = name, c.lds = lds;
   return c;
+}
+
+inline unsigned rx_lo4(const void* p) { return (unsigned)((uintptr_t)p & 15); }
+// the query of a call: in / out of the launch (backward-data: dy / dx), bs_y: the y of the backward sums the caller asks for, or null
+inline RxChQuery rx_ch_query(rx_dtype dt, const rx_act* in, unsigned w_lo, const rx_act* out, int flip, int accumulate, bool stat_offered,
+                             size_t stat_bytes, const rx_act* bs_y) {
+  RxChQuery q = {};
+  q.dt = dt;
+  q.N = in->n, q.Z = in->z, q.Y = in->y, q.X = in->x;
+  q.Ci = in->c, q.Co = out->c, q.ldi = in->ld, q.ldo = out->ld;
+  q.in_cs = in->cs, q.out_cs = out->cs;
+  q.in_lo = rx_lo4(in->ptr), q.out_lo = rx_lo4(out->ptr), q.w_lo = w_lo;
+  q.flip = flip, q.accumulate = accumulate;
+  q.stat_offered = stat_offered, q.stat_bytes = stat_bytes;
+  q.want_bs = bs_y != nullptr;
+  if (bs_y) q.bsy_lo = rx_lo4(bs_y->ptr), q.bs_ldy = bs_y->ld;
+  return q;
 }
 
 inline RxChChoice rx_ch_choose(const RxChQuery& q) {

@@ -24,20 +24,7 @@
 #include "rx_common.h"
 #include "rx_internal.h"
 
-#define DS2_HZ 5
-#define DS2_HY 5
-#define DS2_HX 17
-#define DS2_HV (DS2_HZ * DS2_HY * DS2_HX)   // 425 rows per chunk
-
-struct DgradS2Geom {
-  int N, Zo, Yo, Xo;       // dY grid
-  int Z, Y, X;             // dX grid (= 2 * dY grid)
-  int Ci, Co;              // dX channels (conv input), dY channels (conv output, == 64)
-  int ldy, ldx;
-  long dy_ss, dx_ss;
-  int tz_n, ty_n, tx_n, NT;
-  int accumulate, dbg;
-};
+// DS2_H*, DS2P_*_BYTES, DgradS2Geom and which calls take this kernel (rx_ds2_choose): rx_gather_plan.h
 
 __device__ inline int ds2_lane_voxel(int l) { return l < 4 ? l : l < 12 ? l + 12 : l < 16 ? l - 8 : l < 20 ? l + 8 : l < 28 ? l - 12 : l; }
 
@@ -45,8 +32,6 @@ __device__ constexpr int DS2_SLOT_K[26] = {12, 14, 10, 16, 9, 11, 15, 17, 4, 22,
 __device__ constexpr int DS2_SLOT_OFF[26] = {1, 0, 17, 0, 18, 17, 1, 0, 85, 0, 86, 85, 1, 0, 102, 85, 17, 0, 103, 102, 86, 85, 18, 17, 1, 0};
 __device__ constexpr int DS2_CLS_BASE[8] = {0, 0, 2, 4, 8, 10, 14, 18};
 __device__ constexpr int DS2_CLS_NT[8] = {1, 2, 2, 4, 2, 4, 4, 8};
-#define DS2P_W_BYTES (26 * 2 * 32 * 64)       // 106,496
-#define DS2P_X_BYTES (2 * DS2_HV * 64)        // 54,400
 #define DS2P_HP ((2 * DS2_HV * 4 + 511) / 512)  // halo pieces per thread: 7
 
 template <typename T, bool ACC>
@@ -193,48 +178,18 @@ __global__ __launch_bounds__(512, 1) void dgrad_s2p_kernel(const T* __restrict__
   }
 }
 
-// returns 1 if handled, 0 to fall through to the generic kernel, negative on error
-int rx_dgrad_s2_halo_try(rx_dtype dt, const rx_act* dy, const void* w_bwd, const rx_act* dx, int accumulate, hipStream_t st) {
-  if (dt == RX_F32 || dy->c != 64 || dx->c % 32 || dy->ld % 8 || dx->ld % 4 || ((uintptr_t)dy->ptr & 15) || ((uintptr_t)dx->ptr & 7) ||
-      ((uintptr_t)w_bwd & 15))
-    return 0;
-  if (dx->z != 2 * dy->z || dx->y != 2 * dy->y || dx->x != 2 * dy->x) return 0;     // even input extents only
-  if (rx_act_voxels(dx) * (long)dx->ld >= (1L << 31) || rx_act_voxels(dy) * (long)dy->ld >= (1L << 31)) return 0;
-  DgradS2Geom g;
-  memset(&g, 0, sizeof(g));
-  g.N = dy->n, g.Zo = dy->z, g.Yo = dy->y, g.Xo = dy->x;
-  g.Z = dx->z, g.Y = dx->y, g.X = dx->x;
-  g.Ci = dx->c, g.Co = dy->c, g.ldy = dy->ld, g.ldx = dx->ld;
-  g.dy_ss = rx_act_voxels(dy) * (long)dy->ld, g.dx_ss = rx_act_voxels(dx) * (long)dx->ld;
-  g.tz_n = (g.Zo + 3) / 4, g.ty_n = (g.Yo + 3) / 4, g.tx_n = (g.Xo + 15) / 16;
-  g.NT = g.N * g.tz_n * g.ty_n * g.tx_n;
-  g.accumulate = accumulate;
+int rx_dgrad_s2_launch(const RxDs2Choice& c, rx_dtype dt, const void* dy, const void* w_bwd, void* dx, hipStream_t st) {
+  DgradS2Geom g = c.g;
   static const int dbg = rx_env_mask("RX_DBG");
   g.dbg = dbg;
-  if ((long)g.NT * (g.Ci / 32) < 256) return 0;                 // small layers: the gather kernel's split-K fills the chip better
-  const size_t ldsp = (size_t)DS2P_W_BYTES + DS2P_X_BYTES;      // 160,896 B
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_s2p_kernel<bf16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_s2p_kernel<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_s2p_kernel<f16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_s2p_kernel<f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-  int wgs = 256 / (g.Ci / 32);
-  if (wgs < 1) wgs = 1;
-  if (wgs > g.NT) wgs = g.NT;
-  const int per = (g.NT + wgs - 1) / wgs;
-  wgs = (g.NT + per - 1) / per;
   rx_note_kernel("dgrad_s2p_kernel");
-  dim3 gridp(wgs, g.Ci / 32);
-#define RX_DS2P(TT, A) hipLaunchKernelGGL((dgrad_s2p_kernel<TT, A>), gridp, dim3(512), ldsp, st, (const TT*)dy->ptr, (const TT*)w_bwd, (TT*)dx->ptr, g, per)
-  if (dt == RX_BF16) {
-    if (accumulate) RX_DS2P(bf16_t, true); else RX_DS2P(bf16_t, false);
-  } else {
-    if (accumulate) RX_DS2P(f16_t, true); else RX_DS2P(f16_t, false);
+#define RX_DS2P_ROW(TT, A)                                                                                                             \
+  if ((dt == RX_BF16) == std::is_same<TT, bf16_t>::value && (g.accumulate != 0) == A) {                                                 \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_s2p_kernel<TT, A>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds); \
+    hipLaunchKernelGGL((dgrad_s2p_kernel<TT, A>), dim3(c.grid[0], c.grid[1]), dim3(512), c.lds, st, (const TT*)dy, (const TT*)w_bwd, (TT*)dx, g, c.per); \
   }
-#undef RX_DS2P
-  hipError_t ep = hipGetLastError();
-  if (ep != hipSuccess) {
-    rx_set_error("dgrad_s2p: %s", hipGetErrorString(ep));
-    return RX_ELAUNCH;
-  }
-  return 1;
+  RX_DS2P_ROW(bf16_t, false) RX_DS2P_ROW(bf16_t, true) RX_DS2P_ROW(f16_t, false) RX_DS2P_ROW(f16_t, true)
+#undef RX_DS2P_ROW
+  RX_CHECK_LAUNCH("dgrad_s2p");
+  return RX_OK;
 }

@@ -23,28 +23,7 @@
 #include "rx_internal.h"
 
 
-// One launch covers up to 8 PHASES that share input / output / weights but differ in iteration grid, output
-// phase offset and tap list: the 8 output parity classes of a stride-2 backward-data, or the 8 kernel positions
-// of a k=s=2 transposed convolution (previously 8 launches of ~10 us each).
-struct IgemmPhase {
-  int Qz, Qy, Qx, Vq;
-  int opz, opy, opx;
-  int tap0, ntaps;
-  int mtile0, mtiles;
-  long slab_off;  // element offset of this phase's split-K slabs
-};
-
-struct IgemmGeom {
-  int Zi, Yi, Xi, Ci, ldi;
-  long in_ss;
-  int isz, isy, isx;
-  int Zo, Yo, Xo, Co, ldo;
-  long out_ss;
-  int osz, osy, osx;
-  int accumulate, ksplit, nph, total_mtiles;
-  IgemmPhase ph[8];
-  RxTap taps[RX_MAX_TAPS];
-};
+// IgemmPhase / IgemmGeom, the geometry builders and the choice of kernel and split: rx_gather_plan.h
 
 __device__ inline int swz(int row, int chunk) { return row * 4 + (chunk ^ ((row >> 2) & 3)); }
 
@@ -398,195 +377,72 @@ __global__ __launch_bounds__(256, 2) void igemm_fat_kernel(const T* __restrict__
 // host side
 // ---------------------------------------------------------------------------------------------
 
+// launches what rx_gather_choose chose for `g`: one table row per instantiation
 template <typename T>
-static void igemm_dispatch_tile(int BM, int BN, dim3 grid, hipStream_t st, const void* in, const void* w, const float* bias, void* out,
-                                void* ws, const IgemmGeom& g, int N, int ks) {
-  rx_note_kernel(BM == 256 ? (BN == 64 ? "igemm_kernel<256,64>" : "igemm_kernel<256,32>")
-                            : (BN == 64 ? "igemm_kernel<128,64>" : "igemm_kernel<128,32>"));
-  if (BM == 256 && BN == 64)
-    hipLaunchKernelGGL((igemm_kernel<T, 256, 64>), grid, dim3(256), 0, st, (const T*)in, (const T*)w, bias, (T*)out, (float*)ws, g);
-  else if (BM == 256 && BN == 32)
-    hipLaunchKernelGGL((igemm_kernel<T, 256, 32>), grid, dim3(256), 0, st, (const T*)in, (const T*)w, bias, (T*)out, (float*)ws, g);
-  else if (BM == 128 && BN == 64)
-    hipLaunchKernelGGL((igemm_kernel<T, 128, 64>), grid, dim3(256), 0, st, (const T*)in, (const T*)w, bias, (T*)out, (float*)ws, g);
-  else
-    hipLaunchKernelGGL((igemm_kernel<T, 128, 32>), grid, dim3(256), 0, st, (const T*)in, (const T*)w, bias, (T*)out, (float*)ws, g);
-  if (ks > 1) {
-    int vmax = 0;
-    for (int i = 0; i < g.nph; ++i) vmax = g.ph[i].Vq > vmax ? g.ph[i].Vq : vmax;
-    long total = (long)N * vmax * (g.Co / 4);
-    int G = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-    hipLaunchKernelGGL((igemm_splitk_reduce<T>), dim3(G, g.nph), dim3(256), 0, st, (const float*)ws, bias, (T*)out, g, N);
+static void igemm_launch_as(const RxGatherChoice& c, hipStream_t st, const void* in, const void* w, const float* bias, void* out, void* ws,
+                            const IgemmGeom& g, int N) {
+  const dim3 grid(c.grid[0], c.grid[1], c.grid[2]), rgrid(c.rgrid[0], c.rgrid[1]);
+#define RX_IG_ROW(BM_, BN_) \
+  if (c.kind == RX_GA_TILE && c.BM == BM_ && c.BN == BN_) \
+    hipLaunchKernelGGL((igemm_kernel<T, BM_, BN_>), grid, dim3(256), 0, st, (const T*)in, (const T*)w, bias, (T*)out, (float*)ws, g);
+  RX_IG_ROW(256, 64) RX_IG_ROW(256, 32) RX_IG_ROW(128, 64) RX_IG_ROW(128, 32)
+#undef RX_IG_ROW
+  if constexpr (!std::is_same<T, float>::value) {
+#define RX_FAT_ROW(KERNEL)                                                                                                          \
+  {                                                                                                                                 \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds);      \
+    hipLaunchKernelGGL(KERNEL, grid, dim3(256), c.lds, st, (const T*)in, (const T*)w, (float*)ws, g, c.NV, c.nsteps);               \
   }
+    if (c.kind == RX_GA_FAT) {
+#if RX_ABLATION
+      static const int abl = rx_env_mask("RX_FAT_ABL");
+#define RX_FAT_ABL(A) case A: RX_FAT_ROW((igemm_fat_kernel<T, A>)) break;
+      if constexpr (std::is_same<T, bf16_t>::value) {
+        switch (abl) {
+          RX_FAT_ABL(1) RX_FAT_ABL(2) RX_FAT_ABL(3) RX_FAT_ABL(4) RX_FAT_ABL(5) RX_FAT_ABL(6) RX_FAT_ABL(7)
+          default: RX_FAT_ROW((igemm_fat_kernel<T>))
+        }
+      } else
+#undef RX_FAT_ABL
+#endif
+        RX_FAT_ROW((igemm_fat_kernel<T>))
+    }
+#undef RX_FAT_ROW
+  }
+  if (c.rgrid[0]) hipLaunchKernelGGL((igemm_splitk_reduce<T>), rgrid, dim3(256), 0, st, (const float*)ws, bias, (T*)out, g, N);
 }
 
 static int igemm_launch(rx_dtype dt, const void* in, const void* w, const float* bias, void* out, IgemmGeom& g, int N, void* ws,
                         size_t ws_bytes, hipStream_t st) {
-  const int per16 = dt == RX_F32 ? 4 : 8;
-  const int KB = 4 * per16;
-  if (g.Ci % KB) RX_FAIL(RX_EUNSUPPORTED, "igemm: input channels must be a multiple of %d (got %d)", KB, g.Ci);
-  if (g.Co % 32) RX_FAIL(RX_EUNSUPPORTED, "igemm: output channels must be a multiple of 32 (got %d)", g.Co);
-  if (g.ldi % per16 || g.ldo % 4 || ((uintptr_t)in & 15) || ((uintptr_t)out & 7) || ((uintptr_t)w & 15))
-    RX_FAIL(RX_EUNSUPPORTED, "igemm: misaligned operand (ldi=%d ldo=%d)", g.ldi, g.ldo);
-  int vmax = 0, nkt_max = 0;
-  for (int i = 0; i < g.nph; ++i) {
-    vmax = g.ph[i].Vq > vmax ? g.ph[i].Vq : vmax;
-    nkt_max = g.ph[i].ntaps > nkt_max ? g.ph[i].ntaps : nkt_max;
-  }
-  nkt_max *= g.Ci / KB;
-  if (vmax <= 0 || g.nph <= 0) return RX_OK;
-  // low-resolution layers: fat K steps, batch folded into M (see igemm_fat_kernel)
-  {
-    const int KE = 16 * per16;
-    const long NV = (long)N * g.ph[0].Vq;
-    if (dt != RX_F32 && g.nph == 1 && g.Ci % KE == 0 && g.Co % 64 == 0 && NV <= 2048 && ws &&
-        g.ph[0].ntaps * (g.Ci / KE) >= 8 && g.ph[0].opz == 0 && g.ph[0].opy == 0 && g.ph[0].opx == 0 && g.osz == 1 && g.osy == 1 &&
-        g.osx == 1) {
-      const int mtiles = (int)((NV + 127) / 128);
-      const int nsteps = g.ph[0].ntaps * (g.Ci / KE);
-      const long base_wgs = (long)mtiles * (g.Co / 64);
-      int ks = (int)((512 + base_wgs - 1) / base_wgs);      // aim at 512 workgroups
-      if (ks > nsteps / 4) ks = nsteps / 4;   // >= 4 K steps per workgroup; also bounds the serial sum of the reduce
-      if (ks < 1) ks = 1;
-      while (ks > 1 && (size_t)ks * NV * g.Co * sizeof(float) > ws_bytes) --ks;
-      if ((size_t)ks * NV * g.Co * sizeof(float) <= ws_bytes) {
-        g.ksplit = ks;
-        g.total_mtiles = mtiles;
-        g.ph[0].mtile0 = 0, g.ph[0].mtiles = mtiles, g.ph[0].slab_off = 0;
-        const size_t lds = (size_t)(128 + 64) * 256;
-        rx_note_kernel("igemm_fat_kernel");
-        dim3 grid(mtiles * ks, g.Co / 64);
-        if (dt == RX_BF16) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fat_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#if RX_ABLATION
-          {
-            static const int abl = rx_env_mask("RX_FAT_ABL");
-#define RX_FAT_L(A)                                                                                                                     \
-  case A:                                                                                                                               \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fat_kernel<bf16_t, A>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((igemm_fat_kernel<bf16_t, A>), grid, dim3(256), lds, st, (const bf16_t*)in, (const bf16_t*)w, (float*)ws, g, (int)NV, nsteps); \
-    break;
-            switch (abl) {
-              RX_FAT_L(1) RX_FAT_L(2) RX_FAT_L(3) RX_FAT_L(4) RX_FAT_L(5) RX_FAT_L(6) RX_FAT_L(7)
-              default:
-                hipLaunchKernelGGL((igemm_fat_kernel<bf16_t>), grid, dim3(256), lds, st, (const bf16_t*)in, (const bf16_t*)w, (float*)ws, g, (int)NV, nsteps);
-            }
-#undef RX_FAT_L
-          }
-#else
-          hipLaunchKernelGGL((igemm_fat_kernel<bf16_t>), grid, dim3(256), lds, st, (const bf16_t*)in, (const bf16_t*)w, (float*)ws, g, (int)NV, nsteps);
-#endif
-        } else {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_fat_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          hipLaunchKernelGGL((igemm_fat_kernel<f16_t>), grid, dim3(256), lds, st, (const f16_t*)in, (const f16_t*)w, (float*)ws, g, (int)NV, nsteps);
-        }
-        // the reduce always runs here (even for ks == 1 the kernel only writes fp32 slabs): force its split path
-        const long total = NV * (g.Co / 4);
-        const int G = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-        RX_DISPATCH_DTYPE(dt, T, hipLaunchKernelGGL((igemm_splitk_reduce<T>), dim3(G, 1), dim3(256), 0, st, (const float*)ws, bias, (T*)out, g, N));
-        RX_CHECK_LAUNCH("igemm_fat");
-        return RX_OK;
-      }
-    }
-  }
-  const int BN = (g.Co % 64 == 0) ? 64 : 32;
-  const int BM = (vmax <= 128) ? 128 : 256;
-  g.total_mtiles = 0;
-  long vsum = 0;
-  for (int i = 0; i < g.nph; ++i) {
-    g.ph[i].mtile0 = g.total_mtiles;
-    g.ph[i].mtiles = (g.ph[i].Vq + BM - 1) / BM;
-    g.total_mtiles += g.ph[i].mtiles;
-    vsum += g.ph[i].Vq;
-  }
-  // split-K when the natural grid cannot fill the chip and K is deep
-  const long wgs = (long)g.total_mtiles * (g.Co / BN) * N;
-  int ks = 1;
-  if (wgs < 192 && nkt_max >= 16 && ws) {
-    ks = (int)((512 + wgs - 1) / wgs);
-    if (ks > nkt_max / 4) ks = nkt_max / 4;
-    if (ks > 32) ks = 32;
-    size_t need = (size_t)ks * N * vsum * g.Co * sizeof(float);
-    while (ks > 1 && need > ws_bytes) {
-      --ks;
-      need = (size_t)ks * N * vsum * g.Co * sizeof(float);
-    }
-    if (ks < 1) ks = 1;
-  }
-  long off = 0;
-  for (int i = 0; i < g.nph; ++i) {
-    g.ph[i].slab_off = off;
-    off += (long)ks * N * g.ph[i].Vq * g.Co;
-  }
-  g.ksplit = ks;
-  dim3 grid(g.total_mtiles * ks, g.Co / BN, N);
-  RX_DISPATCH_DTYPE(dt, T, igemm_dispatch_tile<T>(BM, BN, grid, st, in, w, bias, out, ws, g, N, ks));
-  RX_CHECK_LAUNCH("igemm");
+  const RxGatherChoice c = rx_gather_choose(dt, g, N, ws != nullptr, ws_bytes, rx_lo4(in), rx_lo4(out), rx_lo4(w));
+  if (c.kind == RX_GA_REFUSE) RX_FAIL(RX_EUNSUPPORTED, "%s", c.message);
+  if (c.kind == RX_GA_NOTHING) return RX_OK;
+  rx_note_kernel(c.name);
+  RX_DISPATCH_DTYPE(dt, T, igemm_launch_as<T>(c, st, in, w, bias, out, ws, g, N));
+  RX_CHECK_LAUNCH(c.kind == RX_GA_FAT ? "igemm_fat" : "igemm");
   return RX_OK;
 }
 
-static bool is_333_s1(const int32_t k[3], const int32_t s[3]) {
-  return k[0] == 3 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1;
-}
-
-static int check13(const int32_t k[3], const int32_t s[3], const char* who) {
-  for (int i = 0; i < 3; ++i) {
-    if (k[i] < 1 || k[i] > RX_MAX_KERNEL) RX_FAIL(RX_EUNSUPPORTED, "%s: kernel sizes must be 1..%d per axis (got %d)", who, RX_MAX_KERNEL, k[i]);
-    if (s[i] < 1 || s[i] > RX_MAX_STRIDE) RX_FAIL(RX_EUNSUPPORTED, "%s: strides must be 1..%d per axis (got %d)", who, RX_MAX_STRIDE, s[i]);
+// the legs of a route that other files launch; RX_RT_GATHER stays with the caller
+static int route_launch(const RxConvRoute& r, rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip,
+                        int accumulate, hipStream_t st, float* stat_part, const RxBwdStat* bs, const char* who) {
+  switch (r.kind) {
+    case RX_RT_REFUSE: RX_FAIL(r.code, "%s", r.message);
+    case RX_RT_HALO: return rx_conv_halo_launch(r.halo, dt, in, w, bias, out, flip, accumulate, st, stat_part, bs);
+    case RX_RT_POINTWISE: return rx_pointwise_launch(r.pw, dt, in->ptr, w, bias, out->ptr, st, who);
+    case RX_RT_DS2: return rx_dgrad_s2_launch(r.ds2, dt, in->ptr, w, out->ptr, st);
+    default: return RX_OK;
   }
-  return RX_OK;
-}
-static int conv_out_dim(int in, int k, int s) { return (in + 2 * ((k - 1) / 2) - k) / s + 1; }
-
-static void geom_in(IgemmGeom& g, const rx_act* a) {
-  g.Zi = a->z, g.Yi = a->y, g.Xi = a->x, g.Ci = a->c, g.ldi = a->ld;
-  g.in_ss = rx_act_voxels(a) * (long)a->ld;
-}
-static void geom_out(IgemmGeom& g, const rx_act* a) {
-  g.Zo = a->z, g.Yo = a->y, g.Xo = a->x, g.Co = a->c, g.ldo = a->ld;
-  g.out_ss = rx_act_voxels(a) * (long)a->ld;
 }
 
 extern "C" int rx_conv3d_fwd(rx_dtype dt, const rx_act* x, const void* w_fwd, const float* bias, const rx_act* y,
                              const int32_t kernel[3], const int32_t stride[3], void* ws, size_t wsb, void* stream) {
   RX_RECORD(stream, [=, x_ = RxActV(x), y_ = RxActV(y), kernel_ = RxI3V(kernel), stride_ = RxI3V(stride)](void* s) { return rx_conv3d_fwd(dt, x_.p(), w_fwd, bias, y_.p(), kernel_.v, stride_.v, ws, wsb, s); });
   if (!rx_act_ok_planar(x) || !rx_act_ok(y) || !w_fwd) RX_FAIL(RX_EINVAL, "rx_conv3d_fwd: bad arguments");
-  int rc = check13(kernel, stride, "rx_conv3d_fwd");
-  if (rc) return rc;
-  if (y->n != x->n || y->z != conv_out_dim(x->z, kernel[0], stride[0]) || y->y != conv_out_dim(x->y, kernel[1], stride[1]) ||
-      y->x != conv_out_dim(x->x, kernel[2], stride[2]))
-    RX_FAIL(RX_EINVAL, "rx_conv3d_fwd: output geometry mismatch");
-  if (is_333_s1(kernel, stride)) {
-    rc = rx_conv_halo_try(dt, x, w_fwd, bias, y, 0, 0, (hipStream_t)stream, nullptr, 0, nullptr, nullptr);  // LDS-halo kernel
-    if (rc < 0) return rc;
-    if (rc == 1) return RX_OK;
-  }
-  if (x->cs) RX_FAIL(RX_EUNSUPPORTED, "rx_conv3d_fwd: a planar-concat input needs the 3x3x3 stride-1 halo kernel (Co = 32, X >= 16)");
-  if (kernel[0] == 1 && kernel[1] == 1 && kernel[2] == 1 && stride[0] == 1 && stride[1] == 1 && stride[2] == 1) {
-    const int32_t one[3] = {1, 1, 1};
-    if (rx_pointwise_try(dt, x, w_fwd, bias, y, one, 0, (hipStream_t)stream) == 1) {      // streaming kernel, no spatial footprint
-      RX_CHECK_LAUNCH("rx_conv3d_fwd(pointwise)");
-      return RX_OK;
-    }
-  }
+  const RxConvRoute r = rx_route_conv(dt, x, rx_lo4(w_fwd), y, kernel, stride, 0, 0);
+  if (r.kind != RX_RT_GATHER) return route_launch(r, dt, x, w_fwd, bias, y, 0, 0, (hipStream_t)stream, nullptr, nullptr, "rx_conv3d_fwd(pointwise)");
   IgemmGeom g;
-  memset(&g, 0, sizeof(g));
-  geom_in(g, x);
-  geom_out(g, y);
-  g.nph = 1;
-  IgemmPhase& P = g.ph[0];
-  P.Qz = y->z, P.Qy = y->y, P.Qx = y->x, P.Vq = (int)rx_act_voxels(y);
-  g.isz = stride[0], g.isy = stride[1], g.isx = stride[2];
-  g.osz = g.osy = g.osx = 1;
-  const int pz = (kernel[0] - 1) / 2, py = (kernel[1] - 1) / 2, px = (kernel[2] - 1) / 2;
-  for (int a = 0; a < kernel[0]; ++a)
-    for (int b = 0; b < kernel[1]; ++b)
-      for (int c = 0; c < kernel[2]; ++c) {
-        RxTap& t = g.taps[P.ntaps];
-        t.dz = (int8_t)(a - pz), t.dy = (int8_t)(b - py), t.dx = (int8_t)(c - px);
-        t.w = (uint16_t)P.ntaps;
-        ++P.ntaps;
-      }
+  rx_gather_fwd(g, x, y, kernel, stride);
   return igemm_launch(dt, x->ptr, w_fwd, bias, y->ptr, g, x->n, ws, wsb, (hipStream_t)stream);
 }
 
@@ -602,25 +458,15 @@ extern "C" int rx_conv3d_bwd_data_instats(rx_dtype dt, const rx_act* dy, const v
   if (!fused || !m12 || !in_stats || !rx_act_ok(in_y) || !ws) RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_data_instats: bad arguments");
   *fused = 0;
   if (!rx_act_ok(dy) || !rx_act_ok(dx) || !w_bwd) RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_data_instats: bad arguments");
-  int rc = check13(kernel, stride, "rx_conv3d_bwd_data_instats");
-  if (rc) return rc;
-  const bool same = in_y->n == dx->n && in_y->z == dx->z && in_y->y == dx->y && in_y->x == dx->x && in_y->c == dx->c;
-  if (same && is_333_s1(kernel, stride) && dx->z == dy->z && dx->y == dy->y && dx->x == dy->x && in_y->ld % 4 == 0 &&
-      !((uintptr_t)in_y->ptr & 7)) {
-    RxBwdStat bs{in_y, in_stats, slope};
-    int chunks = 0;
-    rc = rx_conv_halo_try(dt, dy, w_bwd, nullptr, dx, 1, accumulate, (hipStream_t)stream, (float*)ws, wsb, &chunks, &bs);
-    if (rc < 0) return rc;
-    if (rc == 1) {
-      if (chunks > 0) {
-        rx_inbwd_fused_finalize_launch((const float*)ws, dx->n, chunks, dx->c, (double)rx_act_voxels(dx), in_stats, m12, (hipStream_t)stream);
-        RX_CHECK_LAUNCH("rx_conv3d_bwd_data_instats(finalize)");
-        *fused = 1;
-      }
-      return RX_OK;
-    }
-  }
-  return rx_conv3d_bwd_data(dt, dy, w_bwd, dx, kernel, stride, accumulate, ws, wsb, stream);
+  const RxConvRoute r = rx_route_conv_stats(dt, dy, rx_lo4(w_bwd), dx, kernel, stride, accumulate, in_y, wsb);
+  if (r.kind == RX_RT_PLAIN) return rx_conv3d_bwd_data(dt, dy, w_bwd, dx, kernel, stride, accumulate, ws, wsb, stream);
+  const RxBwdStat bs{in_y, in_stats, slope};
+  const int rc = route_launch(r, dt, dy, w_bwd, nullptr, dx, 1, accumulate, (hipStream_t)stream, (float*)ws, &bs, "");
+  if (rc || r.halo.stat_chunks <= 0) return rc;
+  rx_inbwd_fused_finalize_launch((const float*)ws, dx->n, r.halo.stat_chunks, dx->c, (double)rx_act_voxels(dx), in_stats, m12, (hipStream_t)stream);
+  RX_CHECK_LAUNCH("rx_conv3d_bwd_data_instats(finalize)");
+  *fused = 1;
+  return RX_OK;
 }
 
 // conv + InstanceNorm statistics of its output in one call.  When the layer runs on a persistent halo kernel the sums of y and
@@ -630,117 +476,28 @@ extern "C" int rx_conv3d_fwd_stats(rx_dtype dt, const rx_act* x, const void* w_f
                                    void* stream) {
   RX_RECORD(stream, [=, x_ = RxActV(x), y_ = RxActV(y), kernel_ = RxI3V(kernel), stride_ = RxI3V(stride)](void* s) { return rx_conv3d_fwd_stats(dt, x_.p(), w_fwd, bias, y_.p(), kernel_.v, stride_.v, eps, stats, ws, wsb, s); });
   if (!rx_act_ok_planar(x) || !rx_act_ok(y) || !w_fwd || !stats || !ws) RX_FAIL(RX_EINVAL, "rx_conv3d_fwd_stats: bad arguments");
-  int rc = check13(kernel, stride, "rx_conv3d_fwd_stats");
+  const RxConvRoute r = rx_route_conv_stats(dt, x, rx_lo4(w_fwd), y, kernel, stride, 0, nullptr, wsb);
+  const int rc = r.kind == RX_RT_PLAIN ? rx_conv3d_fwd(dt, x, w_fwd, bias, y, kernel, stride, ws, wsb, stream)
+                                       : route_launch(r, dt, x, w_fwd, bias, y, 0, 0, (hipStream_t)stream, (float*)ws, nullptr, "");
   if (rc) return rc;
-  if (is_333_s1(kernel, stride) && y->n == x->n && y->z == x->z && y->y == x->y && y->x == x->x) {
-    int chunks = 0;
-    rc = rx_conv_halo_try(dt, x, w_fwd, bias, y, 0, 0, (hipStream_t)stream, (float*)ws, wsb, &chunks, nullptr);
-    if (rc < 0) return rc;
-    if (rc == 1 && chunks > 0) {
-      rx_stats_finalize_launch((const float*)ws, y->n, chunks, y->c, (double)rx_act_voxels(y), eps, stats, (hipStream_t)stream);
-      RX_CHECK_LAUNCH("rx_conv3d_fwd_stats(finalize)");
-      return RX_OK;
-    }
-    if (rc == 1) return rx_instnorm_stats(dt, y, eps, stats, ws, wsb, stream);
-  }
-  rc = rx_conv3d_fwd(dt, x, w_fwd, bias, y, kernel, stride, ws, wsb, stream);
-  if (rc) return rc;
-  return rx_instnorm_stats(dt, y, eps, stats, ws, wsb, stream);
+  if (r.kind == RX_RT_PLAIN || r.halo.stat_chunks <= 0) return rx_instnorm_stats(dt, y, eps, stats, ws, wsb, stream);
+  rx_stats_finalize_launch((const float*)ws, y->n, r.halo.stat_chunks, y->c, (double)rx_act_voxels(y), eps, stats, (hipStream_t)stream);
+  RX_CHECK_LAUNCH("rx_conv3d_fwd_stats(finalize)");
+  return RX_OK;
 }
 
 extern "C" int rx_conv3d_bwd_data(rx_dtype dt, const rx_act* dy, const void* w_bwd, const rx_act* dx, const int32_t kernel[3],
                                   const int32_t stride[3], int accumulate, void* ws, size_t wsb, void* stream) {
   RX_RECORD(stream, [=, dy_ = RxActV(dy), dx_ = RxActV(dx), kernel_ = RxI3V(kernel), stride_ = RxI3V(stride)](void* s) { return rx_conv3d_bwd_data(dt, dy_.p(), w_bwd, dx_.p(), kernel_.v, stride_.v, accumulate, ws, wsb, s); });
   if (!rx_act_ok(dy) || !rx_act_ok_planar(dx) || !w_bwd) RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_data: bad arguments");
-  int rc = check13(kernel, stride, "rx_conv3d_bwd_data");
-  if (rc) return rc;
-  if (dy->n != dx->n || dy->z != conv_out_dim(dx->z, kernel[0], stride[0]) || dy->y != conv_out_dim(dx->y, kernel[1], stride[1]) ||
-      dy->x != conv_out_dim(dx->x, kernel[2], stride[2]))
-    RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_data: geometry mismatch");
-  if (is_333_s1(kernel, stride)) {
-    rc = rx_conv_halo_try(dt, dy, w_bwd, nullptr, dx, 1, accumulate, (hipStream_t)stream, nullptr, 0, nullptr, nullptr);
-    if (rc < 0) return rc;
-    if (rc == 1) return RX_OK;
-  }
-  if (dx->cs) RX_FAIL(RX_EUNSUPPORTED, "rx_conv3d_bwd_data: a planar-concat dx needs the wave-specialised 64-channel halo kernel");
-  if (kernel[0] == 1 && kernel[1] == 1 && kernel[2] == 1 && stride[0] == 1 && stride[1] == 1 && stride[2] == 1) {
-    const int32_t one[3] = {1, 1, 1};
-    if (rx_pointwise_try(dt, dy, w_bwd, nullptr, dx, one, accumulate, (hipStream_t)stream) == 1) {
-      RX_CHECK_LAUNCH("rx_conv3d_bwd_data(pointwise)");
-      return RX_OK;
-    }
-  }
-  if (kernel[0] == 3 && kernel[1] == 3 && kernel[2] == 3 && stride[0] == 2 && stride[1] == 2 && stride[2] == 2) {
-    rc = rx_dgrad_s2_halo_try(dt, dy, w_bwd, dx, accumulate, (hipStream_t)stream);   // LDS-halo kernel, all 8 parity classes
-    if (rc < 0) return rc;
-    if (rc == 1) return RX_OK;
-  }
-  const int k[3] = {kernel[0], kernel[1], kernel[2]}, s[3] = {stride[0], stride[1], stride[2]};
-  const int p[3] = {(k[0] - 1) / 2, (k[1] - 1) / 2, (k[2] - 1) / 2};
-  const int din[3] = {dx->z, dx->y, dx->x};
-  // dx[s*q + r] = sum_{t : (r+p-t) % s == 0} dy[q + (r+p-t)/s] * W[t]^T      per axis; one PHASE per parity class r.
-  // Up to 8 phases and RX_MAX_TAPS taps per launch: stride 2 is one launch (8 classes, 27 taps), strides 3 / 4 or 5..7-wide
-  // kernels take a few (the classes write disjoint voxels, so the launches are independent).
+  const RxConvRoute r = rx_route_conv(dt, dy, rx_lo4(w_bwd), dx, kernel, stride, 1, accumulate);
+  if (r.kind != RX_RT_GATHER)
+    return route_launch(r, dt, dy, w_bwd, nullptr, dx, 1, accumulate, (hipStream_t)stream, nullptr, nullptr, "rx_conv3d_bwd_data(pointwise)");
   IgemmGeom g;
-  auto reset = [&]() {
-    memset(&g, 0, sizeof(g));
-    geom_in(g, dy);
-    geom_out(g, dx);
-    g.isz = g.isy = g.isx = 1;
-    g.osz = s[0], g.osy = s[1], g.osx = s[2];
-    g.accumulate = accumulate;
-  };
-  reset();
-  int ntap_total = 0;
-  for (int r0 = 0; r0 < s[0]; ++r0)
-    for (int r1 = 0; r1 < s[1]; ++r1)
-      for (int r2 = 0; r2 < s[2]; ++r2) {
-        const int r[3] = {r0, r1, r2};
-        int Q[3];
-        for (int a = 0; a < 3; ++a) Q[a] = (din[a] - r[a] + s[a] - 1) / s[a];
-        if (Q[0] * Q[1] * Q[2] <= 0) continue;
-        int cnt = 0;
-        for (int a = 0; a < k[0]; ++a)
-          if ((r0 + p[0] - a) % s[0] == 0)
-            for (int b = 0; b < k[1]; ++b)
-              if ((r1 + p[1] - b) % s[1] == 0)
-                for (int c = 0; c < k[2]; ++c)
-                  if ((r2 + p[2] - c) % s[2] == 0) ++cnt;
-        if (g.nph == 8 || ntap_total + cnt > RX_MAX_TAPS) {
-          rc = igemm_launch(dt, dy->ptr, w_bwd, nullptr, dx->ptr, g, dx->n, ws, wsb, (hipStream_t)stream);
-          if (rc) return rc;
-          reset();
-          ntap_total = 0;
-        }
-        IgemmPhase& P = g.ph[g.nph++];
-        P.Qz = Q[0], P.Qy = Q[1], P.Qx = Q[2], P.Vq = Q[0] * Q[1] * Q[2];
-        P.opz = r0, P.opy = r1, P.opx = r2;
-        P.tap0 = ntap_total;
-        // a class without any tap (kernel narrower than the stride) still has to WRITE its voxels: zeros (or keep dx when accumulating)
-        for (int a = 0; a < k[0]; ++a) {
-          if ((r0 + p[0] - a) % s[0]) continue;
-          for (int b = 0; b < k[1]; ++b) {
-            if ((r1 + p[1] - b) % s[1]) continue;
-            for (int c = 0; c < k[2]; ++c) {
-              if ((r2 + p[2] - c) % s[2]) continue;
-              RxTap& t = g.taps[ntap_total++];
-              t.dz = (int8_t)((r0 + p[0] - a) / s[0]);
-              t.dy = (int8_t)((r1 + p[1] - b) / s[1]);
-              t.dx = (int8_t)((r2 + p[2] - c) / s[2]);
-              t.w = (uint16_t)((a * k[1] + b) * k[2] + c);
-              ++P.ntaps;
-            }
-          }
-        }
-      }
-  return igemm_launch(dt, dy->ptr, w_bwd, nullptr, dx->ptr, g, dx->n, ws, wsb, (hipStream_t)stream);
-}
-
-static int checkT(const int32_t s[3], const rx_act* small, const rx_act* big, const char* who) {
-  for (int i = 0; i < 3; ++i)
-    if (s[i] < 1 || s[i] > RX_MAX_STRIDE) RX_FAIL(RX_EUNSUPPORTED, "%s: strides must be 1..%d per axis", who, RX_MAX_STRIDE);
-  if (small->n != big->n || big->z != small->z * s[0] || big->y != small->y * s[1] || big->x != small->x * s[2])
-    RX_FAIL(RX_EINVAL, "%s: geometry mismatch", who);
+  for (int cls = 0; rx_gather_bwd_data_next(g, dy, dx, kernel, stride, accumulate, &cls);) {
+    const int rc = igemm_launch(dt, dy->ptr, w_bwd, nullptr, dx->ptr, g, dx->n, ws, wsb, (hipStream_t)stream);
+    if (rc) return rc;
+  }
   return RX_OK;
 }
 
@@ -748,67 +505,24 @@ extern "C" int rx_convT3d_fwd(rx_dtype dt, const rx_act* x, const void* w_fwd, c
                               const int32_t stride[3], void* ws, size_t wsb, void* stream) {
   RX_RECORD(stream, [=, x_ = RxActV(x), y_ = RxActV(y), stride_ = RxI3V(stride)](void* s) { return rx_convT3d_fwd(dt, x_.p(), w_fwd, bias, y_.p(), stride_.v, ws, wsb, s); });
   if (!rx_act_ok(x) || !rx_act_ok(y) || !w_fwd) RX_FAIL(RX_EINVAL, "rx_convT3d_fwd: bad arguments");
-  int rc = checkT(stride, x, y, "rx_convT3d_fwd");
-  if (rc) return rc;
-  if (rx_pointwise_try(dt, x, w_fwd, bias, y, stride, 0, (hipStream_t)stream) == 1) {       // x once, y once (rx_pointwise.hip)
-    RX_CHECK_LAUNCH("rx_convT3d_fwd(pointwise)");
-    return RX_OK;
-  }
-  // y[i*s + t] = sum_ci x[i] W[ci][co][t] + b : one single-tap PHASE per kernel position t, up to 8 per launch
+  const RxConvRoute r = rx_route_convT(dt, x, rx_lo4(w_fwd), y, stride, true);
+  if (r.kind != RX_RT_GATHER) return route_launch(r, dt, x, w_fwd, bias, y, 0, 0, (hipStream_t)stream, nullptr, nullptr, "rx_convT3d_fwd(pointwise)");
   IgemmGeom g;
-  auto reset = [&]() {
-    memset(&g, 0, sizeof(g));
-    geom_in(g, x);
-    geom_out(g, y);
-    g.isz = g.isy = g.isx = 1;
-    g.osz = stride[0], g.osy = stride[1], g.osx = stride[2];
-  };
-  reset();
-  for (int a = 0; a < stride[0]; ++a)
-    for (int b = 0; b < stride[1]; ++b)
-      for (int c = 0; c < stride[2]; ++c) {
-        if (g.nph == 8) {
-          rc = igemm_launch(dt, x->ptr, w_fwd, bias, y->ptr, g, x->n, ws, wsb, (hipStream_t)stream);
-          if (rc) return rc;
-          reset();
-        }
-        IgemmPhase& P = g.ph[g.nph];
-        P.Qz = x->z, P.Qy = x->y, P.Qx = x->x, P.Vq = (int)rx_act_voxels(x);
-        P.opz = a, P.opy = b, P.opx = c;
-        P.tap0 = g.nph, P.ntaps = 1;
-        RxTap& t = g.taps[g.nph];
-        t.dz = t.dy = t.dx = 0;
-        t.w = (uint16_t)((a * stride[1] + b) * stride[2] + c);
-        ++g.nph;
-      }
-  return igemm_launch(dt, x->ptr, w_fwd, bias, y->ptr, g, x->n, ws, wsb, (hipStream_t)stream);
+  for (int pos = 0; rx_gather_convT_fwd_next(g, x, y, stride, &pos);) {
+    const int rc = igemm_launch(dt, x->ptr, w_fwd, bias, y->ptr, g, x->n, ws, wsb, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return RX_OK;
 }
 
 extern "C" int rx_convT3d_bwd_data(rx_dtype dt, const rx_act* dy, const void* w_bwd, const rx_act* dx, const int32_t stride[3],
                                    int accumulate, void* ws, size_t wsb, void* stream) {
   RX_RECORD(stream, [=, dy_ = RxActV(dy), dx_ = RxActV(dx), stride_ = RxI3V(stride)](void* s) { return rx_convT3d_bwd_data(dt, dy_.p(), w_bwd, dx_.p(), stride_.v, accumulate, ws, wsb, s); });
   if (!rx_act_ok(dy) || !rx_act_ok(dx) || !w_bwd) RX_FAIL(RX_EINVAL, "rx_convT3d_bwd_data: bad arguments");
-  int rc = checkT(stride, dx, dy, "rx_convT3d_bwd_data");
-  if (rc) return rc;
-  // dx[i] = sum_t dy[i*s + t] W[t]^T
+  const RxConvRoute r = rx_route_convT(dt, dx, rx_lo4(w_bwd), dy, stride, false);
+  if (r.kind != RX_RT_GATHER) return route_launch(r, dt, dy, w_bwd, nullptr, dx, 1, accumulate, (hipStream_t)stream, nullptr, nullptr, "");
   IgemmGeom g;
-  memset(&g, 0, sizeof(g));
-  geom_in(g, dy);
-  geom_out(g, dx);
-  g.nph = 1;
-  IgemmPhase& P = g.ph[0];
-  P.Qz = dx->z, P.Qy = dx->y, P.Qx = dx->x, P.Vq = (int)rx_act_voxels(dx);
-  g.isz = stride[0], g.isy = stride[1], g.isx = stride[2];
-  g.osz = g.osy = g.osx = 1;
-  g.accumulate = accumulate;
-  for (int a = 0; a < stride[0]; ++a)
-    for (int b = 0; b < stride[1]; ++b)
-      for (int c = 0; c < stride[2]; ++c) {
-        RxTap& t = g.taps[P.ntaps];
-        t.dz = (int8_t)a, t.dy = (int8_t)b, t.dx = (int8_t)c;
-        t.w = (uint16_t)P.ntaps;
-        ++P.ntaps;
-      }
+  rx_gather_convT_bwd_data(g, dy, dx, stride, accumulate);
   return igemm_launch(dt, dy->ptr, w_bwd, nullptr, dx->ptr, g, dx->n, ws, wsb, (hipStream_t)stream);
 }
 

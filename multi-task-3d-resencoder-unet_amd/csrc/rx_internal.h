@@ -6,22 +6,19 @@
 // ---- rx_runtime.hip
 int rx_note_seq(void);   // how many times rx_note_kernel ran on this thread
 
-// ---- rx_conv_halo.hip, rx_pointwise.hip, rx_dgrad_s2.hip: fast paths of the conv entry points in rx_igemm.hip.
-// Return 1 if they handled the launch, 0 to fall through to the generic kernel, negative on error.
-// rx_conv_halo_try, stat_part / stat_bytes / stat_chunks (optional): a launch that sums in its epilogue leaves per-wave partial
-// rows in stat_part and their number per sample in *stat_chunks (else 0: the caller reduces in a pass of its own) -- forward the
-// sums of y and y^2, backward-data with `bs` the two InstanceNorm backward sums of the layer `bs` describes.  Which kernel and
-// which of these a call gets is decided by rx_ch_choose (rx_conv_halo_plan.h).
-int rx_conv_halo_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip, int accumulate,
-                     hipStream_t st, float* stat_part, size_t stat_bytes, int* stat_chunks, const RxBwdStat* bs);
-int rx_pointwise_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, const int32_t stride[3],
-                     int accumulate, hipStream_t st);
-int rx_dgrad_s2_halo_try(rx_dtype dt, const rx_act* dy, const void* w_bwd, const rx_act* dx, int accumulate, hipStream_t st);
+// ---- rx_conv_halo.hip, rx_pointwise.hip, rx_dgrad_s2.hip: the fast paths of the conv entry points in rx_igemm.hip.  Which of them
+// a call takes is decided by the routes of rx_gather_plan.h (the halo kernels: rx_ch_choose, rx_conv_halo_plan.h); these launch
+// the choice they are handed and return RX_OK or an error.
+// rx_conv_halo_launch, stat_part / bs: a choice with take_stats leaves per-wave partial rows in stat_part, c.stat_chunks per sample
+// -- forward the sums of y and y^2, backward-data with take_bs the two InstanceNorm backward sums of the layer `bs` describes.
+int rx_conv_halo_launch(const RxChChoice& c, rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, int flip,
+                        int accumulate, hipStream_t st, float* stat_part, const RxBwdStat* bs);
+int rx_pointwise_launch(const RxPwChoice& c, rx_dtype dt, const void* in, const void* w, const float* bias, void* out, hipStream_t st,
+                        const char* who);
+int rx_dgrad_s2_launch(const RxDs2Choice& c, rx_dtype dt, const void* dy, const void* w_bwd, void* dx, hipStream_t st);
 
-// ---- rx_wgrad_halo.hip: fast path of rx_conv3d_bwd_weight (rx_wgrad.hip), same return convention
-size_t rx_wgrad_halo_ws_bytes(const rx_act* x, const rx_act* dy);
-int rx_wgrad_halo_try(rx_dtype dt, const rx_act* x, const rx_act* dy, const int32_t stride[3], float* dw, void* ws, size_t ws_bytes,
-                      hipStream_t st);
+// ---- rx_wgrad_halo.hip: fast path of rx_conv3d_bwd_weight (rx_wgrad.hip), chosen by rx_wgh_choose (rx_wgrad_plan.h)
+int rx_wgrad_halo_launch(const RxWghChoice& c, rx_dtype dt, const void* x, const void* dy, float* dw, void* ws, hipStream_t st);
 // ---- rx_wgrad.hip: the split reduce both weight-gradient files end with
 void rx_wgrad_reduce_launch(const float* slab, int S, int T_, int R, int C, float* dw, hipStream_t st);
 

@@ -11,17 +11,7 @@
 #include "rx_common.h"
 #include "rx_internal.h"
 
-struct PwGeom {
-  int N, Zi, Yi, Xi, Ci, ldi;
-  long in_ss;
-  int Yo, Xo, Co, ldo;
-  long out_ss;
-  int sz, sy, sx;      // output voxel = s * input voxel + tap (1 or 2 per axis); taps = sz * sy * sx
-  int accumulate;
-  int ntiles;          // tiles of 128 rows (n, z, y, x flattened)
-};
-
-#define RX_PW_MAXKS 16   // Ci <= 256: 16 B-fragment registers of 16 bytes per lane
+// PwGeom, RX_PW_MAXKS and which calls take this kernel (rx_pw_choose): rx_gather_plan.h
 
 template <typename T>
 __global__ __launch_bounds__(256) void pointwise_kernel(const T* __restrict__ in, const T* __restrict__ w, const float* __restrict__ bias,
@@ -96,44 +86,16 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const T* __restrict__ in
   }
 }
 
-// 1 = handled.  in: the tensor on the small grid (Zi, Yi, Xi); out voxel = s * in voxel + tap; w = [taps][Co][Ci] packed weights.
-int rx_pointwise_try(rx_dtype dt, const rx_act* in, const void* w, const float* bias, const rx_act* out, const int32_t stride[3],
-                     int accumulate, hipStream_t st) {
-  if (dt == RX_F32 || in->cs || out->cs) return 0;
-  const int taps = stride[0] * stride[1] * stride[2];
-  const int Ci = in->c, Co = out->c;
-  if (Ci % 16 || Ci > 16 * RX_PW_MAXKS || Co % 32 || in->ld % 8 || out->ld % 8 || ((uintptr_t)in->ptr & 15) || ((uintptr_t)out->ptr & 15) ||
-      ((uintptr_t)w & 15))
-    return 0;
-  const size_t lds = (size_t)taps * 32 * (Ci * 2 + 16);
-  if (lds > 150 * 1024) return 0;
-  if (taps > 1 && lds > 80 * 1024) return 0;          // one workgroup per CU: the 256 -> 128 transposed conv measured 20.7 vs 19.1 us on the gather kernel
-  const long NV = (long)in->n * rx_act_voxels(in);
-  if (NV < 4096) return 0;                            // the low-resolution layers stay on the split-K kernels
-  PwGeom g;
-  g.N = in->n, g.Zi = in->z, g.Yi = in->y, g.Xi = in->x, g.Ci = Ci, g.ldi = in->ld;
-  g.in_ss = rx_act_voxels(in) * (long)in->ld;
-  g.Yo = out->y, g.Xo = out->x, g.Co = Co, g.ldo = out->ld;
-  g.out_ss = rx_act_voxels(out) * (long)out->ld;
-  g.sz = stride[0], g.sy = stride[1], g.sx = stride[2];
-  g.accumulate = accumulate;
-  g.ntiles = (int)((NV + 127) / 128);
-  // persistent: as many workgroups as stay resident (LDS-limited), each walking tiles with stride gridDim.x
-  int per_cu = (int)((160 * 1024) / (lds + 1024));
-  if (per_cu > 8) per_cu = 8;
-  if (per_cu < 1) per_cu = 1;
-  int gx = 256 * per_cu / (Co / 32);
-  if (gx < 1) gx = 1;
-  if (gx > g.ntiles) gx = g.ntiles;
-  dim3 grid(gx, Co / 32);
+int rx_pointwise_launch(const RxPwChoice& c, rx_dtype dt, const void* in, const void* w, const float* bias, void* out, hipStream_t st,
+                        const char* who) {
   rx_note_kernel("pointwise_kernel");
-  if (dt == RX_BF16) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pointwise_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((pointwise_kernel<bf16_t>), grid, dim3(256), lds, st, (const bf16_t*)in->ptr, (const bf16_t*)w, bias, (bf16_t*)out->ptr, g);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pointwise_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((pointwise_kernel<f16_t>), grid, dim3(256), lds, st, (const f16_t*)in->ptr, (const f16_t*)w, bias, (f16_t*)out->ptr, g);
+#define RX_PW_ROW(TT)                                                                                                                  \
+  {                                                                                                                                    \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pointwise_kernel<TT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+    hipLaunchKernelGGL((pointwise_kernel<TT>), dim3(c.grid[0], c.grid[1]), dim3(256), c.lds, st, (const TT*)in, (const TT*)w, bias, (TT*)out, c.g); \
   }
-  return 1;
+  if (dt == RX_BF16) RX_PW_ROW(bf16_t) else RX_PW_ROW(f16_t)
+#undef RX_PW_ROW
+  RX_CHECK_LAUNCH(who);
+  return RX_OK;
 }
-

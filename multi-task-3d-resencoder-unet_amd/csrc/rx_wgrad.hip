@@ -22,17 +22,7 @@
 #include "rx_internal.h"
 
 
-struct WgradGeom {
-  int Qz, Qy, Qx, Vq, NQ;
-  int R, ldg;
-  long g_ss;
-  int Zx, Yx, Xx, Cc, ldx;
-  long x_ss;
-  int isz, isy, isx;
-  int ntaps, ksplit, q_per_split, tiles_c;
-  RxTap taps[RX_MAX_TAPS];
-};
-
+// WgradGeom / ConvTWgGeom, the splits, the workspace sizes and the routes of the two entry points: rx_wgrad_plan.h
 
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
@@ -226,126 +216,65 @@ __global__ __launch_bounds__(256) void wgrad_reduce_manysplits(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------
-static int plan_split(const WgradGeom& g, int BR, int BC, size_t ws_bytes, int* ksplit, int* qps) {
-  const long tiles = (long)(g.R / BR) * (g.Cc / BC) * g.ntaps;
-  const long ktiles = ((long)g.NQ + 63) / 64;
-  long S = (1024 + tiles - 1) / tiles;
-  if (S > ktiles / 4) S = ktiles / 4;
-  if (S < 1) S = 1;
-  const size_t slab1 = (size_t)g.ntaps * g.R * g.Cc * sizeof(float);
-  while (S > 1 && S * slab1 > ws_bytes) --S;
-  if (slab1 > ws_bytes) return RX_EWORKSPACE;
-  long per = (ktiles + S - 1) / S;
-  S = (ktiles + per - 1) / per;
-  *ksplit = (int)S;
-  *qps = (int)(per * 64);
-  return RX_OK;
-}
-
-static size_t wgrad_ws_bytes(int R, int C, int taps, long NQ) {
-  const size_t slab1 = (size_t)taps * R * C * sizeof(float);
-  const long tiles = (long)((R + 63) / 64) * ((C + 63) / 64) * taps;
-  long S = (1024 + tiles - 1) / tiles;
-  long ktiles = (NQ + 63) / 64;
-  if (S > ktiles / 4) S = ktiles / 4;
-  if (S < 1) S = 1;
-  // BR/BC may fall back to 32 (4x the tiles) -> S only shrinks; this bound is safe
-  if (R % 64 || C % 64) {
-    const long t32 = (long)(R / 32) * (C / 32) * taps;
-    long S2 = (1024 + t32 - 1) / t32;
-    if (S2 > S) S = S2;
-  }
-  return S * slab1 + 256;
-}
-
-template <typename T>
-static void wgrad_dispatch(int BR, int BC, dim3 grid, hipStream_t st, const void* gt, const void* xt, float* slab, const WgradGeom& g) {
-  const size_t lds = 65536;
-#define RX_WG(BR_, BC_)                                                                                                            \
-  do {                                                                                                                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BR_, BC_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds);                                                                                           \
-    hipLaunchKernelGGL((wgrad_kernel<T, BR_, BC_>), grid, dim3(256), lds, st, (const T*)gt, (const T*)xt, slab, g);                \
-  } while (0)
-  if (BR == 64 && BC == 64)
-    RX_WG(64, 64);
-  else if (BR == 64 && BC == 32)
-    RX_WG(64, 32);
-  else if (BR == 32 && BC == 64)
-    RX_WG(32, 64);
-  else
-    RX_WG(32, 32);
-#undef RX_WG
-}
-
-static int wgrad_launch(rx_dtype dt, const void* gt, const void* xt, float* dw, WgradGeom& g, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int per16 = dt == RX_F32 ? 4 : 8;
-  if (g.R % 32 || g.Cc % 32) RX_FAIL(RX_EUNSUPPORTED, "wgrad: channel counts must be multiples of 32 (R=%d C=%d)", g.R, g.Cc);
-  if (g.ldg % per16 || g.ldx % per16 || ((uintptr_t)gt & 15) || ((uintptr_t)xt & 15)) RX_FAIL(RX_EUNSUPPORTED, "wgrad: misaligned operand");
-  if (!ws || !dw) RX_FAIL(RX_EINVAL, "wgrad: null workspace / output");
-  const int BR = g.R % 64 == 0 ? 64 : 32, BC = g.Cc % 64 == 0 ? 64 : 32;
-  g.tiles_c = g.Cc / BC;
-  int rc = plan_split(g, BR, BC, ws_bytes, &g.ksplit, &g.q_per_split);
-  if (rc) RX_FAIL(rc, "wgrad: workspace too small (%zu bytes)", ws_bytes);
-  dim3 grid((g.R / BR) * (g.Cc / BC), g.ntaps, g.ksplit);
-  rx_note_kernel(BR == 64 ? (BC == 64 ? "wgrad_kernel<64,64>" : "wgrad_kernel<64,32>") : (BC == 64 ? "wgrad_kernel<32,64>" : "wgrad_kernel<32,32>"));
-  RX_DISPATCH_DTYPE(dt, T, wgrad_dispatch<T>(BR, BC, grid, st, gt, xt, (float*)ws, g));
-  rx_wgrad_reduce_launch((const float*)ws, g.ksplit, g.ntaps, g.R, g.Cc, dw, st);
-  RX_CHECK_LAUNCH("wgrad");
-  return RX_OK;
-}
-
-static int conv_out_dim(int in, int k, int s) { return (in + 2 * ((k - 1) / 2) - k) / s + 1; }
-
 // shared with rx_wgrad_halo.hip
 void rx_wgrad_reduce_launch(const float* slab, int S, int T_, int R, int C, float* dw, hipStream_t st) {
   long RC = (long)R * C;
-  if (S >= 8 || T_ > 27)       // (wgrad_reduce transposes a [256][T <= 27] tile through LDS)
+  if (rx_wgrad_reduce_manysplits(S, T_))
     hipLaunchKernelGGL(wgrad_reduce_manysplits, dim3((unsigned)((RC + 255) / 256), T_), dim3(256), 0, st, slab, S, T_, R, C, dw);
   else
     hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((RC + 255) / 256)), dim3(256), 0, st, slab, S, T_, R, C, dw);
 }
 
+template <typename T>
+static void wgrad_launch_as(const RxWgradChoice& c, hipStream_t st, const void* gt, const void* xt, float* slab, const WgradGeom& g) {
+#define RX_WG_ROW(BR_, BC_)                                                                                                          \
+  if (c.BR == BR_ && c.BC == BC_) {                                                                                                  \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BR_, BC_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                              (int)c.lds);                                                                                           \
+    hipLaunchKernelGGL((wgrad_kernel<T, BR_, BC_>), dim3(c.grid[0], c.grid[1], c.grid[2]), dim3(256), c.lds, st, (const T*)gt,        \
+                       (const T*)xt, slab, g);                                                                                       \
+  }
+  RX_WG_ROW(64, 64) RX_WG_ROW(64, 32) RX_WG_ROW(32, 64) RX_WG_ROW(32, 32)
+#undef RX_WG_ROW
+}
+
+// wgrad_kernel on the geometry `g` (rows from gt, columns from xt), then the reduce
+static int wgrad_launch(rx_dtype dt, const void* gt, const void* xt, float* dw, WgradGeom& g, void* ws, size_t ws_bytes, hipStream_t st) {
+  const RxWgradChoice c = rx_wgrad_choose(dt, g, rx_lo4(gt), rx_lo4(xt), ws != nullptr, dw != nullptr, ws_bytes);
+  if (c.code) RX_FAIL(c.code, "%s", c.message);
+  rx_note_kernel(c.name);
+  RX_DISPATCH_DTYPE(dt, T, wgrad_launch_as<T>(c, st, gt, xt, (float*)ws, g));
+  rx_wgrad_reduce_launch((const float*)ws, g.ksplit, g.ntaps, g.R, g.Cc, dw, st);
+  RX_CHECK_LAUNCH("wgrad");
+  return RX_OK;
+}
+
 extern "C" size_t rx_conv3d_bwd_weight_workspace(const rx_act* x, const rx_act* dy, const int32_t kernel[3]) {
-  if (!rx_act_ok_planar(x) || !rx_act_ok(dy)) return 0;
-  size_t a = wgrad_ws_bytes(dy->c, x->c, kernel[0] * kernel[1] * kernel[2], (long)dy->n * rx_act_voxels(dy));
-  size_t b = (kernel[0] == 3 && kernel[1] == 3 && kernel[2] == 3) ? rx_wgrad_halo_ws_bytes(x, dy) : 0;
-  return a > b ? a : b;
+  return rx_act_ok_planar(x) && rx_act_ok(dy) ? rx_conv_bwd_weight_ws_bytes(x, dy, kernel) : 0;
+}
+
+static int convT_wgrad_launch(const RxCtwChoice& c, rx_dtype dt, const void* x, const void* dy, float* dw, void* ws, hipStream_t st);
+
+// both entry points after their argument checks (kernel null: the transposed conv, dW[ci][co][t] = sum_i x[i][ci] * dy[i*s + t][co])
+static int bwd_weight(rx_dtype dt, const rx_act* x, const rx_act* dy, float* dw, const int32_t* kernel, const int32_t stride[3], void* ws,
+                      size_t ws_bytes, hipStream_t st) {
+  const RxWgradRoute r = rx_route_bwd_weight(dt, x, dy, kernel, stride, ws != nullptr, dw != nullptr, ws_bytes);
+  switch (r.kind) {
+    case RX_WR_REFUSE: RX_FAIL(r.code, "%s", r.message);
+    case RX_WR_HALO: return rx_wgrad_halo_launch(r.halo, dt, x->ptr, dy->ptr, dw, ws, st);
+    case RX_WR_CONVT: return convT_wgrad_launch(r.ctw, dt, x->ptr, dy->ptr, dw, ws, st);
+    default: break;
+  }
+  WgradGeom g;
+  rx_wgrad_geom(g, kernel ? dy : x, kernel ? x : dy, kernel, stride);
+  return wgrad_launch(dt, kernel ? dy->ptr : x->ptr, kernel ? x->ptr : dy->ptr, dw, g, ws, ws_bytes, st);
 }
 
 extern "C" int rx_conv3d_bwd_weight(rx_dtype dt, const rx_act* x, const rx_act* dy, float* dw, const int32_t kernel[3],
                                     const int32_t stride[3], void* ws, size_t ws_bytes, void* stream) {
   RX_RECORD(stream, [=, x_ = RxActV(x), dy_ = RxActV(dy), kernel_ = RxI3V(kernel), stride_ = RxI3V(stride)](void* s) { return rx_conv3d_bwd_weight(dt, x_.p(), dy_.p(), dw, kernel_.v, stride_.v, ws, ws_bytes, s); });
   if (!rx_act_ok_planar(x) || !rx_act_ok(dy)) RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_weight: bad arguments");
-  for (int i = 0; i < 3; ++i) {
-    if (kernel[i] < 1 || kernel[i] > RX_MAX_KERNEL) RX_FAIL(RX_EUNSUPPORTED, "rx_conv3d_bwd_weight: kernel sizes must be 1..%d per axis", RX_MAX_KERNEL);
-    if (stride[i] < 1 || stride[i] > RX_MAX_STRIDE) RX_FAIL(RX_EUNSUPPORTED, "rx_conv3d_bwd_weight: strides must be 1..%d per axis", RX_MAX_STRIDE);
-  }
-  if (dy->n != x->n || dy->z != conv_out_dim(x->z, kernel[0], stride[0]) || dy->y != conv_out_dim(x->y, kernel[1], stride[1]) ||
-      dy->x != conv_out_dim(x->x, kernel[2], stride[2]))
-    RX_FAIL(RX_EINVAL, "rx_conv3d_bwd_weight: geometry mismatch");
-  if (kernel[0] == 3 && kernel[1] == 3 && kernel[2] == 3 && ws && dw) {
-    int rc = rx_wgrad_halo_try(dt, x, dy, stride, dw, ws, ws_bytes, (hipStream_t)stream);  // LDS-halo kernel (16-bit types), stride 1 or 2
-    if (rc < 0) return rc;
-    if (rc == 1) return RX_OK;
-  }
-  if (x->cs) RX_FAIL(RX_EUNSUPPORTED, "rx_conv3d_bwd_weight: a planar-concat x needs the LDS-halo weight-gradient kernels");
-  WgradGeom g;
-  memset(&g, 0, sizeof(g));
-  g.Qz = dy->z, g.Qy = dy->y, g.Qx = dy->x, g.Vq = (int)rx_act_voxels(dy), g.NQ = dy->n * g.Vq;
-  g.R = dy->c, g.ldg = dy->ld, g.g_ss = (long)g.Vq * dy->ld;
-  g.Zx = x->z, g.Yx = x->y, g.Xx = x->x, g.Cc = x->c, g.ldx = x->ld, g.x_ss = rx_act_voxels(x) * (long)x->ld;
-  g.isz = stride[0], g.isy = stride[1], g.isx = stride[2];
-  const int pz = (kernel[0] - 1) / 2, py = (kernel[1] - 1) / 2, px = (kernel[2] - 1) / 2;
-  for (int a = 0; a < kernel[0]; ++a)
-    for (int b = 0; b < kernel[1]; ++b)
-      for (int c = 0; c < kernel[2]; ++c) {
-        RxTap& t = g.taps[g.ntaps];
-        t.dz = (int8_t)(a - pz), t.dy = (int8_t)(b - py), t.dx = (int8_t)(c - px);
-        t.w = (uint16_t)g.ntaps;
-        ++g.ntaps;
-      }
-  return wgrad_launch(dt, dy->ptr, x->ptr, dw, g, ws, ws_bytes, (hipStream_t)stream);
+  return bwd_weight(dt, x, dy, dw, kernel, stride, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -356,16 +285,6 @@ extern "C" int rx_conv3d_bwd_weight(rx_dtype dt, const rx_act* x, const rx_act* 
 // LDS panels read with ds_read_b64_tr_b16 as in wgrad_kernel) and wave w accumulates tap w: every operand byte is read from
 // HBM once.  Slabs [split][tap][Ci][Co] + the fixed-order reduce.  16-bit types, taps <= 8, (Ci/32)*(Co/32) <= 8.
 // ---------------------------------------------------------------------------------------------------------------------
-struct ConvTWgGeom {
-  int Vq, NQ, Qy, Qx;         // coarse voxels per sample / in total, coarse Y, X
-  int R, ldr;                 // coarse channels (rows of dW)
-  long r_ss;
-  int Yf, Xf, Cc, ldc;        // fine tensor
-  long c_ss;
-  int sz, sy, sx, ntaps;
-  int q_per_split;
-};
-
 template <typename T, int NR, int NC>
 __global__ __launch_bounds__(512) void convT_wgrad_kernel(const T* __restrict__ xt, const T* __restrict__ yt, float* __restrict__ slab,
                                                           const ConvTWgGeom g) {
@@ -479,101 +398,30 @@ __global__ __launch_bounds__(512) void convT_wgrad_kernel(const T* __restrict__ 
   }
 }
 
-static int convT_wgrad_splits(long NQ, size_t slab1) {
-  long ktiles = (NQ + 63) / 64;
-  long S = ktiles / 8;                    // >= 8 tiles per workgroup
-  if (S > 256) S = 256;
-  while (S > 32 && (size_t)S * slab1 > ((size_t)32 << 20)) S /= 2;      // slabs stay within ~32 MB (MALL-resident round trip)
-  if (S < 1) S = 1;
-  return (int)S;
-}
-
-// 1 = handled, 0 = not applicable (fall through to wgrad_kernel), < 0 error
-static int convT_wgrad_try(rx_dtype dt, const rx_act* x, const rx_act* dy, const int32_t stride[3], float* dw, void* ws, size_t ws_bytes,
-                           hipStream_t st) {
-  const int taps = stride[0] * stride[1] * stride[2];
-  const int R = x->c, C = dy->c;
-  if (dt == RX_F32 || taps > 8 || R % 32 || C % 32 || x->ld % 8 || dy->ld % 8 || ((uintptr_t)x->ptr & 15) || ((uintptr_t)dy->ptr & 15)) return 0;
-  const int NR = R / 32, NC = C / 32;
-  if (!((NR == 2 && NC == 1) || (NR == 4 && NC == 2) || (NR == 1 && NC == 1) || (NR == 2 && NC == 2))) return 0;
-  const long NQ = (long)x->n * rx_act_voxels(x);
-  if (NQ < 32768) return 0;               // the low-resolution layers: too few tiles to split, the generic kernel is fine there
-  const size_t slab1 = (size_t)taps * R * C * sizeof(float);
-  const int S = convT_wgrad_splits(NQ, slab1);
-  if ((size_t)S * slab1 > ws_bytes) return 0;
-  ConvTWgGeom g;
-  g.Vq = (int)rx_act_voxels(x), g.NQ = (int)NQ, g.Qy = x->y, g.Qx = x->x;
-  g.R = R, g.ldr = x->ld, g.r_ss = (long)g.Vq * x->ld;
-  g.Yf = dy->y, g.Xf = dy->x, g.Cc = C, g.ldc = dy->ld, g.c_ss = rx_act_voxels(dy) * (long)dy->ld;
-  g.sz = stride[0], g.sy = stride[1], g.sx = stride[2], g.ntaps = taps;
-  const long ktiles = (NQ + 63) / 64;
-  g.q_per_split = (int)(((ktiles + S - 1) / S) * 64);
-  const int S2 = (int)((NQ + g.q_per_split - 1) / g.q_per_split);
-  const size_t lds = (size_t)64 * (R + taps * C) * 2;
+// launches what rx_ctw_choose chose, then the reduce
+static int convT_wgrad_launch(const RxCtwChoice& c, rx_dtype dt, const void* x, const void* dy, float* dw, void* ws, hipStream_t st) {
   rx_note_kernel("convT_wgrad_kernel");
-#define RX_CTW(NR_, NC_)                                                                                                              \
-  do {                                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convT_wgrad_kernel<T, NR_, NC_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((convT_wgrad_kernel<T, NR_, NC_>), dim3(S2), dim3(512), lds, st, (const T*)x->ptr, (const T*)dy->ptr, (float*)ws, g);            \
-  } while (0)
-#define RX_CTW_ALL()                       \
-  if (NR == 2 && NC == 1) RX_CTW(2, 1);    \
-  else if (NR == 4 && NC == 2) RX_CTW(4, 2); \
-  else if (NR == 1 && NC == 1) RX_CTW(1, 1); \
-  else RX_CTW(2, 2)
-  if (dt == RX_BF16) {
-    using T = bf16_t;
-    RX_CTW_ALL();
-  } else {
-    using T = f16_t;
-    RX_CTW_ALL();
+#define RX_CTW_ROW(TT, NR_, NC_)                                                                                                        \
+  if ((dt == RX_BF16) == std::is_same<TT, bf16_t>::value && c.NR == NR_ && c.NC == NC_) {                                                \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convT_wgrad_kernel<TT, NR_, NC_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+    hipLaunchKernelGGL((convT_wgrad_kernel<TT, NR_, NC_>), dim3(c.S2), dim3(512), c.lds, st, (const TT*)x, (const TT*)dy, (float*)ws, c.g); \
   }
-#undef RX_CTW_ALL
-#undef RX_CTW
-  rx_wgrad_reduce_launch((const float*)ws, S2, taps, R, C, dw, st);
-  return 1;
+#define RX_CTW_ROWS(TT) RX_CTW_ROW(TT, 2, 1) RX_CTW_ROW(TT, 4, 2) RX_CTW_ROW(TT, 1, 1) RX_CTW_ROW(TT, 2, 2)
+  RX_CTW_ROWS(bf16_t) RX_CTW_ROWS(f16_t)
+#undef RX_CTW_ROWS
+#undef RX_CTW_ROW
+  rx_wgrad_reduce_launch((const float*)ws, c.S2, c.g.ntaps, c.g.R, c.g.Cc, dw, st);
+  RX_CHECK_LAUNCH("rx_convT3d_bwd_weight(convT_wgrad)");
+  return RX_OK;
 }
 
 extern "C" size_t rx_convT3d_bwd_weight_workspace(const rx_act* x, const rx_act* dy, const int32_t stride[3]) {
-  if (!rx_act_ok(x) || !rx_act_ok(dy)) return 0;
-  const int taps = stride[0] * stride[1] * stride[2];
-  const long NQ = (long)x->n * rx_act_voxels(x);
-  const size_t slab1 = (size_t)taps * x->c * dy->c * sizeof(float);
-  const size_t a = wgrad_ws_bytes(x->c, dy->c, taps, NQ);
-  const size_t b = (size_t)convT_wgrad_splits(NQ, slab1) * slab1 + 256;
-  return a > b ? a : b;
+  return rx_act_ok(x) && rx_act_ok(dy) ? rx_convT_bwd_weight_ws_bytes(x, dy, stride) : 0;
 }
 
 extern "C" int rx_convT3d_bwd_weight(rx_dtype dt, const rx_act* x, const rx_act* dy, float* dw, const int32_t stride[3], void* ws,
                                      size_t ws_bytes, void* stream) {
   RX_RECORD(stream, [=, x_ = RxActV(x), dy_ = RxActV(dy), stride_ = RxI3V(stride)](void* s) { return rx_convT3d_bwd_weight(dt, x_.p(), dy_.p(), dw, stride_.v, ws, ws_bytes, s); });
   if (!rx_act_ok(x) || !rx_act_ok(dy)) RX_FAIL(RX_EINVAL, "rx_convT3d_bwd_weight: bad arguments");
-  for (int i = 0; i < 3; ++i)
-    if (stride[i] < 1 || stride[i] > RX_MAX_STRIDE) RX_FAIL(RX_EUNSUPPORTED, "rx_convT3d_bwd_weight: strides must be 1..%d per axis", RX_MAX_STRIDE);
-  if (dy->n != x->n || dy->z != x->z * stride[0] || dy->y != x->y * stride[1] || dy->x != x->x * stride[2])
-    RX_FAIL(RX_EINVAL, "rx_convT3d_bwd_weight: geometry mismatch");
-  if (ws && dw) {
-    const int rc = convT_wgrad_try(dt, x, dy, stride, dw, ws, ws_bytes, (hipStream_t)stream);    // every operand byte once
-    if (rc < 0) return rc;
-    if (rc == 1) {
-      RX_CHECK_LAUNCH("rx_convT3d_bwd_weight(convT_wgrad)");
-      return RX_OK;
-    }
-  }
-  // dW[ci][co][t] = sum_i x[i][ci] * dy[i*s + t][co]
-  WgradGeom g;
-  memset(&g, 0, sizeof(g));
-  g.Qz = x->z, g.Qy = x->y, g.Qx = x->x, g.Vq = (int)rx_act_voxels(x), g.NQ = x->n * g.Vq;
-  g.R = x->c, g.ldg = x->ld, g.g_ss = (long)g.Vq * x->ld;
-  g.Zx = dy->z, g.Yx = dy->y, g.Xx = dy->x, g.Cc = dy->c, g.ldx = dy->ld, g.x_ss = rx_act_voxels(dy) * (long)dy->ld;
-  g.isz = stride[0], g.isy = stride[1], g.isx = stride[2];
-  for (int a = 0; a < stride[0]; ++a)
-    for (int b = 0; b < stride[1]; ++b)
-      for (int c = 0; c < stride[2]; ++c) {
-        RxTap& t = g.taps[g.ntaps];
-        t.dz = (int8_t)a, t.dy = (int8_t)b, t.dx = (int8_t)c;
-        t.w = (uint16_t)g.ntaps;
-        ++g.ntaps;
-      }
-  return wgrad_launch(dt, x->ptr, dy->ptr, dw, g, ws, ws_bytes, (hipStream_t)stream);
+  return bwd_weight(dt, x, dy, dw, nullptr, stride, ws, ws_bytes, (hipStream_t)stream);
 }

@@ -21,25 +21,10 @@
 #include "rx_common.h"
 #include "rx_internal.h"
 
-struct WgHaloGeom {
-  int N, Z, Y, X;
-  int R, Cc, ldg, ldx;
-  long g_ss, x_ss;
-  long x_cs;             // planar concat x (rx_act.cs): element offset of 32-channel group j = j * x_cs; 0 = contiguous channels
-  int TZ, TY, TX, lTX, lTY;
-  int HY, HX, HV, VT;
-  int tz_n, ty_n, tx_n, NT;
-  int S, tiles_per_split, panels_c;
-  int sz, sy, sx;        // conv stride per axis (1 or 2); the X halo of a TZ x TY x TX tile of dY is (s*(T-1)+3) per axis
-  int Zi, Yi, Xi;        // extent of X (the conv INPUT); Z, Y, X above are the extent of dY
-  int order; // tile walk order (rx_tile_coords)
-  int dbg;   // ablation mask (RX_DBG env): 1 stage only the first tile, 2 no MFMA loop
-};
+// WgHaloGeom, RX_WGH_MAX_*, the tiling, the split and the choice between the two kernels (rx_wgh_choose): rx_wgrad_plan.h
 
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4_h;
 
-#define RX_WGH_MAX_HV 768
-#define RX_WGH_MAX_VT 256
 #define RX_WGH_XPIECES ((RX_WGH_MAX_HV * 4 + 255) / 256)  // 16-byte pieces of the halo panel per thread
 #define RX_WGH_GPIECES (RX_WGH_MAX_VT * 4 / 256)
 
@@ -245,7 +230,6 @@ __device__ inline u32x4 tr_frag_at(const lds_byte* p, int off0, int off1) {
 
 #define WGH16_HY 6
 #define WGH16_HX 18
-#define WGH16_HV 648
 #define WGH16_XPIECES 11   // ceil(648 * 4 / 256)
 
 // gb: lane base into sG (row 8h+q4 of k-step 0), xb: lane base into sX (halo row (0,0,8h+q4) i.e. tap (-1,-1,-1) of
@@ -286,7 +270,6 @@ __device__ __forceinline__ void wgh16_tile_mma(const lds_byte* gb, const lds_byt
   }
 }
 
-#define WGH16_BUF_BYTES ((256 + WGH16_HV) * 64)   // one (dY tile, X halo tile) pair: 57,856 bytes
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The 4x4x16 kernel is wave-specialised: 512 threads = 4 CONSUMER waves (the MFMA loop above, 7 taps each, no staging
@@ -487,122 +470,22 @@ __global__ __launch_bounds__(512, 1) void wgrad_halo16ws_kernel(const T* __restr
   }
 }
 
-static int p2ceil(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-static int ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
-}
-
-// returns 1 and fills `g` when the halo kernel applies
-static int wgh_plan(const rx_act* x, const rx_act* dy, const int32_t stride[3], WgHaloGeom* g, size_t ws_bytes) {
-  memset(g, 0, sizeof(*g));
-  g->N = dy->n, g->Z = dy->z, g->Y = dy->y, g->X = dy->x;
-  g->Zi = x->z, g->Yi = x->y, g->Xi = x->x;
-  g->sz = stride[0], g->sy = stride[1], g->sx = stride[2];
-  g->R = dy->c, g->Cc = x->c, g->ldg = dy->ld, g->ldx = x->ld;
-  g->g_ss = rx_act_voxels(dy) * (long)dy->ld;
-  g->x_ss = rx_act_voxels(x) * (long)x->ld;
-  g->x_cs = x->cs;
-  const bool strided = stride[0] > 1 || stride[1] > 1 || stride[2] > 1;
-  int TX = p2ceil(g->X);
-  TX = TX < 4 ? 4 : (TX > 16 ? 16 : TX);
-  if (strided && TX > 8) TX = 8;               // the X halo grows with the stride: 64-voxel tiles (2 x 4 x 8) keep it in LDS
-  int budget = strided ? 64 : 256;
-  int rem = budget / TX;
-  int TY = p2ceil(g->Y);
-  int capy = TX == 16 ? 4 : (strided ? 4 : 8);
-  if (TY > capy) TY = capy;
-  if (TY > rem) TY = rem;
-  int TZ = p2ceil(g->Z);
-  if (TZ > rem / TY) TZ = rem / TY;
-  g->TZ = TZ, g->TY = TY, g->TX = TX, g->lTX = ilog2(TX), g->lTY = ilog2(TY);
-  g->VT = TZ * TY * TX;
-  const int HZ = g->sz * (TZ - 1) + 3;
-  g->HY = g->sy * (TY - 1) + 3, g->HX = g->sx * (TX - 1) + 3, g->HV = HZ * g->HY * g->HX;
-  if (g->VT < 16 || g->VT > RX_WGH_MAX_VT || g->HV > RX_WGH_MAX_HV || HZ > 255 || g->HY > 255 || g->HX > 255) return 0;
-  g->tz_n = (g->Z + TZ - 1) / TZ, g->ty_n = (g->Y + TY - 1) / TY, g->tx_n = (g->X + TX - 1) / TX;
-  g->NT = g->N * g->tz_n * g->ty_n * g->tx_n;
-  g->panels_c = g->Cc / 32;
-  const long PP = (long)(g->R / 32) * g->panels_c;
-  // the wave-specialised 4x4x16 kernel runs ONE workgroup per CU: 256 workgroups are one full wave of the chip (half the
-  // slab traffic and reduce work of 512); the generic kernel runs two per CU
-  long target = (!strided && TZ == 4 && TY == 4 && TX == 16) ? 256 : 512;
-  if (target == 256 && g->NT * PP < 16 * 256) target = 512;   // few tiles (16^3 layers): shorter per-workgroup chains win
-  long S = (target + PP - 1) / PP;
-  if (PP >= 256) S = 1;  // the panel pairs alone fill the chip: accumulate every tile in registers, write dw directly
-  if (S > g->NT) S = g->NT;
-  if (S < 1) S = 1;
-  const size_t slab1 = (size_t)27 * g->R * g->Cc * sizeof(float);
-  while (S > 1 && S * slab1 > ws_bytes) --S;
-  if (S > 1 && slab1 > ws_bytes) return 0;
-  g->tiles_per_split = (int)((g->NT + S - 1) / S);
-  g->S = (g->NT + g->tiles_per_split - 1) / g->tiles_per_split;
-  return 1;
-}
-
-size_t rx_wgrad_halo_ws_bytes(const rx_act* x, const rx_act* dy) {
-  const long PP = (long)(dy->c / 32) * (x->c / 32);
-  long S = PP > 0 ? (512 + PP - 1) / PP : 1;
-  return (size_t)S * 27 * dy->c * x->c * sizeof(float) + 256;
-}
-
-// called by rx_conv3d_bwd_weight; returns 1 if it handled the launch, 0 to fall through to the generic kernel,
-// negative on error
-int rx_wgrad_halo_try(rx_dtype dt, const rx_act* x, const rx_act* dy, const int32_t stride[3], float* dw, void* ws, size_t ws_bytes,
-                      hipStream_t st) {
-  if (dt == RX_F32) return 0;
-  if (x->c % 32 || dy->c % 32 || x->ld % 8 || dy->ld % 8 || ((uintptr_t)x->ptr & 15) || ((uintptr_t)dy->ptr & 15)) return 0;
-  WgHaloGeom g;
-  if (!wgh_plan(x, dy, stride, &g, ws_bytes)) return 0;
-  const size_t lds = (size_t)(RX_WGH_MAX_VT + RX_WGH_MAX_HV) * 64;
-  dim3 grid((g.R / 32) * g.panels_c, g.S);
+// launches what rx_wgh_choose chose: one table row per instantiation; S == 1 writes dw directly, S > 1 slabs and the reduce
+int rx_wgrad_halo_launch(const RxWghChoice& c, rx_dtype dt, const void* x, const void* dy, float* dw, void* ws, hipStream_t st) {
+  WgHaloGeom g = c.g;
   static const int dbg = rx_env_mask("RX_DBG");
   g.dbg = dbg;
-  g.order = 1;   // z-fastest walk of each split's tile range (rx_tile_coords)
-  if (g.TZ == 4 && g.TY == 4 && g.TX == 16 && g.sz == 1 && g.sy == 1 && g.sx == 1) {   // compile-time tile
-    const size_t lds16 = (size_t)WGH16_BUF_BYTES;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<bf16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<f16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo16ws_kernel<f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16));
-    rx_note_kernel("wgrad_halo16ws_kernel");
-    // the DMA producers address both tensors through 32-bit buffer offsets; larger tensors take the register-staged producers
-    const bool dma_ok = (long)g.N * g.g_ss * 2 < 0x7fffff00L &&
-                        ((long)g.N * g.x_ss + (g.x_cs ? (long)(g.Cc / 32 - 1) * g.x_cs : 0)) * 2 < 0x7fffff00L;
-    if (dma_ok && dt == RX_BF16)
-      hipLaunchKernelGGL((wgrad_halo16ws_kernel<bf16_t, true>), grid, dim3(512), 2 * lds16, st, (const bf16_t*)dy->ptr, (const bf16_t*)x->ptr, (float*)ws, dw, g);
-    else if (dma_ok)
-      hipLaunchKernelGGL((wgrad_halo16ws_kernel<f16_t, true>), grid, dim3(512), 2 * lds16, st, (const f16_t*)dy->ptr, (const f16_t*)x->ptr, (float*)ws, dw, g);
-    else if (dt == RX_BF16)
-      hipLaunchKernelGGL((wgrad_halo16ws_kernel<bf16_t, false>), grid, dim3(512), 2 * lds16, st, (const bf16_t*)dy->ptr, (const bf16_t*)x->ptr, (float*)ws, dw, g);
-    else
-      hipLaunchKernelGGL((wgrad_halo16ws_kernel<f16_t, false>), grid, dim3(512), 2 * lds16, st, (const f16_t*)dy->ptr, (const f16_t*)x->ptr, (float*)ws, dw, g);
-    if (g.S > 1) rx_wgrad_reduce_launch((const float*)ws, g.S, 27, g.R, g.Cc, dw, st);
-    hipError_t e16 = hipGetLastError();
-    if (e16 != hipSuccess) {
-      rx_set_error("wgrad_halo16: %s", hipGetErrorString(e16));
-      return RX_ELAUNCH;
-    }
-    return 1;
+  rx_note_kernel(c.name);
+#define RX_WGH_ROW(TT, WS16, DMA_, KERNEL)                                                                                             \
+  if ((dt == RX_BF16) == std::is_same<TT, bf16_t>::value && c.ws16 == WS16 && c.DMA == DMA_) {                                          \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds);           \
+    hipLaunchKernelGGL(KERNEL, dim3(c.grid[0], c.grid[1]), dim3(c.block), c.lds, st, (const TT*)dy, (const TT*)x, (float*)ws, dw, g);   \
   }
-  rx_note_kernel("wgrad_halo_kernel");
-  if (dt == RX_BF16) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((wgrad_halo_kernel<bf16_t>), grid, dim3(256), lds, st, (const bf16_t*)dy->ptr, (const bf16_t*)x->ptr, (float*)ws, dw, g);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_halo_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((wgrad_halo_kernel<f16_t>), grid, dim3(256), lds, st, (const f16_t*)dy->ptr, (const f16_t*)x->ptr, (float*)ws, dw, g);
-  }
+  RX_WGH_ROW(bf16_t, true, true, (wgrad_halo16ws_kernel<bf16_t, true>)) RX_WGH_ROW(f16_t, true, true, (wgrad_halo16ws_kernel<f16_t, true>))
+  RX_WGH_ROW(bf16_t, true, false, (wgrad_halo16ws_kernel<bf16_t, false>)) RX_WGH_ROW(f16_t, true, false, (wgrad_halo16ws_kernel<f16_t, false>))
+  RX_WGH_ROW(bf16_t, false, false, (wgrad_halo_kernel<bf16_t>)) RX_WGH_ROW(f16_t, false, false, (wgrad_halo_kernel<f16_t>))
+#undef RX_WGH_ROW
   if (g.S > 1) rx_wgrad_reduce_launch((const float*)ws, g.S, 27, g.R, g.Cc, dw, st);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    rx_set_error("wgrad_halo: %s", hipGetErrorString(e));
-    return RX_ELAUNCH;
-  }
-  return 1;
+  RX_CHECK_LAUNCH(c.ws16 ? "wgrad_halo16" : "wgrad_halo");
+  return RX_OK;
 }

@@ -1,4 +1,4 @@
-// conv_halo_plan_check.cpp -- runs rx_ch_choose (../rx_conv_halo_plan.h, the function rx_conv_halo_try launches by) on the CPU.
+// conv_halo_plan_check.cpp -- runs rx_ch_choose (../rx_conv_halo_plan.h, the function rx_conv_halo_launch launches by) on the CPU.
 // Built by tests/test_conv_halo_plan_cpu.py with -fsanitize=address,undefined.
 //
 //   stdin:  one query per line, 21 integers: dt N Z Y X Ci Co ldi ldo in_cs out_cs in_lo out_lo w_lo bsy_lo bs_ldy flip accumulate

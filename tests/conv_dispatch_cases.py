@@ -9,7 +9,8 @@ dispatch condition in csrc/.  It is the single place that says which test covers
   * every other row names a key of SHAPES, and test_conv_dispatch_gpu.py runs that shape in each of the row's dtypes: kernel name,
     bit-exact integer pass, per-element fp64 bound.
 
-test_conv_dispatch_cpu.py holds the ledger against the code: rx_ch_choose swept on the CPU, the kernel names read from the sources.
+test_conv_dispatch_cpu.py holds the ledger against the code on the CPU: rx_ch_choose swept, every row put to the route of its entry
+point (csrc/rx_gather_plan.h, csrc/rx_wgrad_plan.h), the kernel names read from the sources.
 
 Entry points: conv3d_fwd, conv3d_fwd_stats, conv3d_bwd_data (accumulate 0), conv3d_bwd_data+ (accumulate 1), conv3d_bwd_data_instats
 (and +), conv3d_bwd_weight, convT3d_fwd, convT3d_bwd_data (and +), convT3d_bwd_weight.
@@ -128,7 +129,7 @@ ROWS = [
     Row(DXA, "conv_halo_kernel<64>", ALL, "E4", "the same with accumulate", sub="g.flip=1 g.accumulate=1", flags=(0, 0, 0, 0)),
     Row(FWD, "conv_halo_kernel<64>", F32, "B2", "fp32 has no wave-specialised kernel: 4x4x16 tiles on the generic one, 512 pairs",
         sub="tile 4x4x16", flags=(0, 0, 0, 0)),
-    # ---- igemm_kernel<BM,BN>: BM = 128 iff voxels per phase <= 128, BN = 64 iff Co % 64 == 0.  ks: see igemm_ks()
+    # ---- igemm_kernel<BM,BN>: BM = 128 iff voxels per phase <= 128, BN = 64 iff Co % 64 == 0.  ks: rx_gather_choose (csrc/rx_gather_plan.h)
     Row(FWD, "igemm_kernel<128,32>", ALL, "I1", "128 voxels, Co = 32; 1 workgroup, nkt = 9*64/32 = 18 >= 16: ks = min(512, 18/4) = 4 "
         "(fp32: nkt 36, ks 9)", sub={"ks": {"half": 4, "float32": 9}}),
     Row(DX, "igemm_kernel<128,64>", ALL, "I1", "dx has 64 channels; 16 bit: nkt = 9*32/32 = 9 < 16: ks = 1 (fp32: nkt 18, ks 4)",
@@ -180,7 +181,7 @@ ROWS = [
     Row(DX, "pointwise_kernel", HALF, P_PW, "the same backwards", covered_by=PIN),
     Row(TFWD, "pointwise_kernel", HALF, (64, 32, (12, 18, 20), S2), "8 taps * 32 * (128 + 16) B = 36 KB of weights, 8640 voxels",
         covered_by=OPS + "test_convT3d_fwd_bwd"),
-    # ---- wgrad_kernel<BR,BC>: BR = 64 iff Co % 64 == 0, BC = 64 iff Ci % 64 == 0; S: see wgrad_splits()
+    # ---- wgrad_kernel<BR,BC>: BR = 64 iff Co % 64 == 0, BC = 64 iff Ci % 64 == 0; S: rx_wgrad_split (csrc/rx_wgrad_plan.h)
     Row(DW, "wgrad_kernel<32,64>", ALL, "I1", "1x3x3 is not for the halo kernels; Co = 32, Ci = 64; 2 K tiles: S = 1", sub={"S": 1}),
     Row(DW, "wgrad_kernel<64,32>", ALL, "I4", "Co = 64, Ci = 32; 3 K tiles: S = 1", sub={"S": 1}),
     Row(DW, "wgrad_kernel<32,32>", ALL, "I7", "Co = Ci = 32; 3 K tiles: S = 1", sub={"S": 1}),
@@ -219,7 +220,7 @@ ROWS = [
 ]
 
 # Instantiations no test of a few seconds can reach: each needs an operand past the 32-bit buffer range (or an alignment torch never
-# hands out).  test_conv_halo_plan_cpu.py executes the selector's side of these on the CPU.
+# hands out).  test_conv_halo_plan_cpu.py and test_conv_dispatch_cpu.py execute the planners' side of these on the CPU.
 UNREACHABLE = {
     "conv_halo64ws_kernel<XDMA=false>": "input of n * voxels * ld * 2 bytes >= 0x7fffff00 (2 GiB): the register-staged producers",
     "wgrad_halo16ws_kernel<DMA=false>": "dy or x of >= 2 GiB: the register-staged producers",

@@ -6,14 +6,15 @@
   * every kernel name the conv sources can hand to rx_note_kernel needs a row, in every dtype in which it is reachable;
   * no row is spare: each one is the only cover of something, and a test deletes every row in turn and requires a failure that
     names its kernel;
-  * the split counts rows claim are recomputed by a pure-Python restatement of igemm_launch, plan_split and wgh_plan (source lines
-    cited).  That restatement DOCUMENTS the rows; it does not follow later changes to the C++ -- the kernel names asserted on the
-    GPU, and the exact values, are what follows those."""
+  * every row, in every dtype, is put to the route functions of csrc/rx_gather_plan.h and csrc/rx_wgrad_plan.h -- the code the entry
+    points launch by, run by csrc/tools/conv_plan_check.cpp under ASan / UBSan: the kernel, and the split counts the row claims;
+  * the planners are swept over small layers for what the kernels assume of every launch."""
 import collections
 import itertools
 import math
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -124,16 +125,18 @@ def test_every_halo_row_reaches_what_it_claims(choose):  # noqa: F811
 # ---- kernel names, read from the sources -------------------------------------------------------------------------------------------
 # the 16-bit-only kernels: (source, the guard that keeps fp32 off them, quoted).  Every other name is reachable in all three dtypes.
 F32_GUARD = {
-    "igemm_fat_kernel": ("rx_igemm.hip", "if (dt != RX_F32 && g.nph == 1 && g.Ci % KE == 0"),
-    "dgrad_s2p_kernel": ("rx_dgrad_s2.hip", "if (dt == RX_F32 || dy->c != 64"),
-    "pointwise_kernel": ("rx_pointwise.hip", "if (dt == RX_F32 || in->cs || out->cs) return 0;"),
-    "wgrad_halo_kernel": ("rx_wgrad_halo.hip", "if (dt == RX_F32) return 0;"),
-    "wgrad_halo16ws_kernel": ("rx_wgrad_halo.hip", "if (dt == RX_F32) return 0;"),
-    "convT_wgrad_kernel": ("rx_wgrad.hip", "if (dt == RX_F32 || taps > 8"),
+    "igemm_fat_kernel": ("rx_gather_plan.h", "if (dt != RX_F32 && g.nph == 1 && g.Ci % KE == 0"),
+    "dgrad_s2p_kernel": ("rx_gather_plan.h", "if (dt == RX_F32 || dy->c != 64"),
+    "pointwise_kernel": ("rx_gather_plan.h", "if (dt == RX_F32 || in->cs || out->cs) return c;"),
+    "wgrad_halo_kernel": ("rx_wgrad_plan.h", "if (dt == RX_F32) return c;"),
+    "wgrad_halo16ws_kernel": ("rx_wgrad_plan.h", "if (dt == RX_F32) return c;"),
+    "convT_wgrad_kernel": ("rx_wgrad_plan.h", "if (dt == RX_F32 || taps > 8"),
     "conv_halo32p_kernel": ("rx_conv_halo_plan.h", "if (BN == 32 && tile4416 && dt != RX_F32 && Ci == 32 && Co == 32 && c.NT >= 512) {"),
     "conv_halo32ws_kernel": ("rx_conv_halo_plan.h", "if (BN == 32 && tile4416 && dt != RX_F32 && !q.out_cs && Ci >= 64"),
     "conv_halo64ws_kernel": ("rx_conv_halo_plan.h", "if (Co % 64 == 0 && tile4416 && dt != RX_F32 && (long)c.NT * (Co / 64) >= 256) {"),
 }
+CONV_SOURCES = ("rx_igemm.hip", "rx_wgrad.hip", "rx_wgrad_halo.hip", "rx_dgrad_s2.hip", "rx_pointwise.hip")
+PLAN_HEADERS = ("rx_gather_plan.h", "rx_wgrad_plan.h")
 
 
 def reach(name):
@@ -146,10 +149,14 @@ def source(f):
 
 
 def source_names():
+    """every name handed to rx_note_kernel: literally in the launch functions, or as the `name` of a planner's choice"""
     names = set()
-    for f in ("rx_igemm.hip", "rx_wgrad.hip", "rx_wgrad_halo.hip", "rx_dgrad_s2.hip", "rx_pointwise.hip"):
+    for f in CONV_SOURCES:
         for call in re.finditer(r"rx_note_kernel\(([^;]*)\);", source(f)):
             names.update(re.findall(r'"([^"]+)"', call.group(1)))
+    for f in PLAN_HEADERS:
+        for value in re.findall(r"\bname = ([^;]*);", source(f)):
+            names.update(re.findall(r'"([^"]+)"', value))
     names.update(re.findall(r'rx_ch_launch\(c, \w+, "([^"]+)"', source("rx_conv_halo_plan.h")))
     return names
 
@@ -162,7 +169,7 @@ def test_the_fp32_guards_are_where_they_are_quoted_from():
     # element sizes (per16 / KB / KE), the selector's planar-concat refusal or its statistics flag
     known = [g for _, g in F32_GUARD.values()] + ["dt == RX_F32 ? 4 : 8", "dt == RX_F32 ? ", "if (planar && dt == RX_F32) return c;",
                                                   "dt != RX_F32 && Ci / KB >= 4", "if (dt != RX_F32 && dt != RX_BF16 && dt != RX_F16) return c;"]
-    for f in ("rx_igemm.hip", "rx_wgrad.hip", "rx_wgrad_halo.hip", "rx_dgrad_s2.hip", "rx_pointwise.hip", "rx_conv_halo_plan.h"):
+    for f in CONV_SOURCES + PLAN_HEADERS + ("rx_conv_halo_plan.h",):
         for line in source(f).splitlines():
             if "RX_F32" in line and "RX_DISPATCH" not in line and not line.lstrip().startswith("//"):
                 assert any(k in line for k in known), f"{f}: an fp32 condition the ledger's dtype column does not know: {line.strip()}"
@@ -301,146 +308,196 @@ def test_deleting_any_one_row_is_noticed_and_names_it(sweep):
         assert any(r.kernel in p for p in problems), f"row {i} ({r.entry}, {r.kernel}, {r.shape}) can be deleted unnoticed: {problems}"
 
 
-def test_unreachable_instantiations_are_past_the_buffer_range(choose):  # noqa: F811
+# ---- the routes and planners the entry points launch by, on the CPU --------------------------------------------------------------
+ENTRY_CODE = {L.FWD: 0, L.STATS: 1, L.DX: 2, L.DXA: 2, L.BS: 3, L.BSA: 3, L.TFWD: 4, L.TDX: 5, L.TDXA: 5, L.DW: 6, L.TDW: 7}
+LIMIT = 0x7fffff00
+NUMERIC = re.compile(r"-?\d+$")
+
+
+def act(n, dims, c, ld=None, cs=0, lo=0):
+    return [n, *dims, c, c if ld is None else ld, cs, lo]
+
+
+def pq(entry, dt, a, b, k=(0, 0, 0), s=(1, 1, 1), acc=0, ws=1, ws_bytes=WS, dw=1, w_lo=0):
+    """one query of csrc/tools/conv_plan_check.cpp: a / b are the entry point's two activations in its own argument order"""
+    return [entry, C.DT_CODE[dt], *a, *b, w_lo, *k, *s, acc, ws, ws_bytes, dw]
+
+
+@pytest.fixture(scope="module")
+def plan(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("plan") / "conv_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(CSRC, "tools", "conv_plan_check.cpp"), "-o", exe])
+
+    def run(queries):
+        text = "".join(" ".join(str(int(v)) for v in q) + "\n" for q in queries)
+        r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and not r.stderr, r.stderr[-3000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == len(queries)
+        out = []
+        for q, line in zip(queries, lines):
+            head, _, message = line.partition(" message=")
+            ch = {k: (int(v) if NUMERIC.match(v) else v) for k, v in (kv.split("=", 1) for kv in head.split(" "))}
+            if message:
+                ch["message"] = message
+            check_plan_invariants(q, ch)
+            out.append(ch)
+        return out
+    return run
+
+
+def check_plan_invariants(q, ch):
+    """what the kernels assume of every launch"""
+    if ch["path"] == "refuse":
+        return
+    ws_bytes = q[27]
+    assert ch["lds"] <= 160 * 1024 and ch["grid_ok"] == 1, (q, ch)
+    if ch["path"] == "gather":
+        assert ch["slab_bytes"] <= ws_bytes and 1 <= ch["phases"] <= 8 and ch["taps"] <= 344 and ch["ks"] >= 1, (q, ch)
+        assert ch["once"] == 1, (q, ch)                    # the phases of all launches write every output voxel exactly once
+    if ch["path"] in ("generic", "convT") or (ch["path"] == "halo" and "S" in ch):
+        assert ch["S"] >= 1 and ch["S"] * ch["per"] >= ch["NT"] and ch["slab_bytes"] <= ws_bytes, (q, ch)
+
+
+def shape_of(row):
+    """(kind, n, ci, co, dims, k, s) of a row: a key of SHAPES, or the case tuple of the test the row points at"""
+    sh = row.shape
+    if isinstance(sh, str):
+        s = L.SHAPES[sh]
+        return s.kind, s.n, s.ci, s.co, s.dims, s.k, s.s
+    if len(sh) == 5:                                  # CONV_CASES: n = 2
+        return ("conv", 2, *sh)
+    if len(sh) == 4:                                  # CONVT_CASES: n = 2
+        return "convT", 2, sh[0], sh[1], sh[2], None, sh[3]
+    if len(sh) == 3:                                  # test_conv3d_fwd_stats: n = 3 for the 30-deep case
+        return "conv", (3 if sh[2][0] == 30 else 2), sh[0], sh[1], sh[2], L.K3, L.S1
+    return "conv", 3, sh[0], sh[0], sh[1], L.K3, L.S1     # test_conv3d_bwd_data_instats: n = 3
+
+
+def row_plan_query(row, dt):
+    """the call behind a row as test_conv_dispatch_gpu.py makes it: the input a channel slice of a wider buffer (ld = c + 32), dy of the
+    transposed conv the second half of a concat (ld = 2 co); both offsets are multiples of 16 bytes"""
+    kind, n, ci, co, dims, k, s = shape_of(row)
+    acc = int(row.entry.endswith("+"))
+    code = ENTRY_CODE[row.entry]
+    if kind == "convT":
+        od = tuple(d * ss for d, ss in zip(dims, s))
+        x, y = act(n, dims, ci, ci + 32), act(n, od, co, 2 * co)
+        return pq(code, dt, *{4: (x, y), 5: (y, act(n, dims, ci)), 7: (x, y)}[code], s=s, acc=acc)
+    od = tuple((d + 2 * ((kk - 1) // 2) - kk) // ss + 1 for d, kk, ss in zip(dims, k, s))
+    x, y = act(n, dims, ci, ci + 32), act(n, od, co)
+    return pq(code, dt, *{0: (x, y), 1: (x, y), 2: (y, act(n, dims, ci)), 3: (y, act(n, dims, ci)), 6: (x, y)}[code], k=k, s=s, acc=acc)
+
+
+def test_every_row_is_what_the_route_of_its_entry_point_returns(plan):
+    """all rows -- gather, fat, pointwise, stride-2, weight gradients, the halo ones once more through the route -- in every dtype"""
+    rows = [(r, dt) for r in L.ROWS for dt in r.dtypes]
+    assert {r.kernel for r, _ in rows} >= {"dgrad_s2p_kernel", "pointwise_kernel", "convT_wgrad_kernel"}
+    for (r, dt), ch in zip(rows, plan([row_plan_query(r, dt) for r, dt in rows])):
+        assert ch["path"] != "refuse" and ch["name"] == r.kernel, (r.entry, r.shape, dt, ch)
+        if r.kernel in HALO and r.entry != L.DW:
+            assert ch["path"] == "halo" and (ch["FLIP"], ch["STATS"], ch["ACC"], ch["BS"]) == r.flags, (r.entry, r.shape, dt, ch)
+
+
+def test_unreachable_instantiations_are_past_the_buffer_range(choose, plan):  # noqa: F811
     """each entry of UNREACHABLE, held against the code: the instantiation appears exactly where an operand passes 0x7fffff00 bytes
     (64 channels at 128^3 are 2^28 bytes a sample: 7 samples fit, 8 do not), and nothing the ledger runs comes near"""
     big = (128, 128, 128)
     ch = choose([C.query("bfloat16", n, big, 64, 64) for n in (7, 8)] + [C.query("float16", n, big, 64, 96) for n in (7, 8)])
+    V = 128 ** 3
+
+    def wg(n, ldg=64, ldx=64, c=64, cs=0):
+        return pq(6, "bfloat16", act(n, big, c, ldx, cs), act(n, big, 64, ldg), k=L.K3)
+    # bytes of an operand = n * 2^21 voxels * ld * 2.  ld = 64: n = 7 is 7 * 2^28 < LIMIT, n = 8 is 2^31 > LIMIT.  n = 7: ld = 72 gives
+    # 2,113,929,216 < LIMIT = 2,147,483,392, ld = 80 gives 2,348,810,240 > LIMIT.  Planar x (two dense 32-channel planes, ld = 32):
+    # (7 * 2^21 * 32 + cs) * 2 bytes: cs = 603,900,000 gives 2,147,324,096 < LIMIT, cs = 604,000,000 gives 2,147,524,096 > LIMIT
+    for n, ld in ((7, 64), (8, 64), (7, 72), (7, 80)):
+        assert (n * V * ld * 2 < LIMIT) == ((n, ld) in ((7, 64), (7, 72)))
+    for cs in (603900000, 604000000):
+        assert cs % 8 == 0 and ((7 * V * 32 + cs) * 2 < LIMIT) == (cs == 603900000)
+    w = plan([wg(7), wg(8), wg(7, ldg=72), wg(7, ldg=80), wg(7, ldx=72), wg(7, ldx=80), wg(7, ldx=32, c=64, cs=603900000),
+              wg(7, ldx=32, c=64, cs=604000000)])
     checks = {
         "conv_halo64ws_kernel<XDMA=false>": [c["name"] == "conv_halo64ws_kernel" for c in ch[:2]] + [ch[0]["XDMA"] == 1, ch[1]["XDMA"] == 0],
         "conv_halo32_kernel in place of conv_halo32ws_kernel": [ch[2]["name"] == "conv_halo32ws_kernel", ch[3]["name"] == "conv_halo32_kernel"],
-        "wgrad_halo16ws_kernel<DMA=false>": ["const bool dma_ok = (long)g.N * g.g_ss * 2 < 0x7fffff00L &&" in source("rx_wgrad_halo.hip"),
-                                             "if (dma_ok && dt == RX_BF16)" in source("rx_wgrad_halo.hip")],
+        # both operands on either side; dy on either side with x below; x on either side with dy below; a planar x pushed over by cs
+        "wgrad_halo16ws_kernel<DMA=false>": [c["name"] == "wgrad_halo16ws_kernel" for c in w] + [[c["DMA"] for c in w] == [1, 0, 1, 0, 1, 0, 1, 0]],
     }
     assert set(checks) == set(L.UNREACHABLE)
     for what, oks in checks.items():
         assert all(oks), (what, oks)
         assert re.search(r"GiB|0x7fffff00", L.UNREACHABLE[what]), what
     for key, s in L.SHAPES.items():                    # (the sweep asserts XDMA for every query it makes)
-        assert s.n * math.prod(s.dims) * (max(s.ci, s.co) + 32) * 4 < 0x7fffff00 // 8, key
+        assert s.n * math.prod(s.dims) * (max(s.ci, s.co) + 32) * 4 < LIMIT // 8, key
 
 
-# ---- split counts: a restatement of the host code, to document the rows --------------------------------------------------------------
-def cdiv(a, b):
-    return -(-a // b)
-
-
-def p2ceil(v):
-    p = 1
-    while p < v:
-        p <<= 1
-    return p
-
-
-def out_dim(i, k, s):
-    return (i + 2 * ((k - 1) // 2) - k) // s + 1
-
-
-def igemm_ks(dt, n, ci, co, phases, out_stride1=True):
-    """rx_igemm.hip igemm_launch (lines 423-526): (kernel, ks).  phases = [(voxels, taps)]; ci / co as the launch sees them"""
-    f32 = dt == "float32"
-    KB = 16 if f32 else 32
-    vmax = max(v for v, _ in phases)
-    nkt_max = max(t for _, t in phases) * (ci // KB)
-    NV = n * phases[0][0]
-    if not f32 and len(phases) == 1 and ci % 128 == 0 and co % 64 == 0 and NV <= 2048 and phases[0][1] * (ci // 128) >= 8 and out_stride1:
-        nsteps = phases[0][1] * (ci // 128)                                  # lines 442-450
-        base = cdiv(NV, 128) * (co // 64)
-        ks = max(1, min(cdiv(512, base), nsteps // 4))
-        assert ks * NV * co * 4 <= WS
-        return "igemm_fat_kernel", ks
-    BN = 64 if co % 64 == 0 else 32                                          # lines 492-515
-    BM = 128 if vmax <= 128 else 256
-    wgs = sum(cdiv(v, BM) for v, _ in phases) * (co // BN) * n
-    ks = 1
-    if wgs < 192 and nkt_max >= 16:
-        ks = max(1, min(cdiv(512, wgs), nkt_max // 4, 32))
-        assert ks * n * sum(v for v, _ in phases) * co * 4 <= WS
-    return f"igemm_kernel<{BM},{BN}>", ks
-
-
-def dgrad_phases(dims, k, s):
-    """rx_igemm.hip rx_conv3d_bwd_data (lines 695-735): one phase per parity class"""
-    ph = []
-    for r in itertools.product(*[range(ss) for ss in s]):
-        q = [cdiv(dims[a] - r[a], s[a]) for a in range(3)]
-        cnt = math.prod(sum(1 for t in range(k[a]) if (r[a] + (k[a] - 1) // 2 - t) % s[a] == 0) for a in range(3))
-        if math.prod(q) > 0:
-            ph.append((math.prod(q), cnt))
-    assert len(ph) <= 8
-    return ph
-
-
-def wgrad_splits(R, Cc, taps, NQ):
-    """rx_wgrad.hip plan_split (lines 229-243) and wgrad_launch (286)"""
-    BR, BC = (64 if R % 64 == 0 else 32), (64 if Cc % 64 == 0 else 32)
-    ktiles = cdiv(NQ, 64)
-    S = max(1, min(cdiv(1024, (R // BR) * (Cc // BC) * taps), ktiles // 4))
-    return f"wgrad_kernel<{BR},{BC}>", cdiv(ktiles, cdiv(ktiles, S))
-
-
-def wgh_splits(n, ci, co, odims, s):
-    """rx_wgrad_halo.hip wgh_plan (lines 502-546) and rx_wgrad_halo_try (567): (kernel, S), None when the plan refuses"""
-    strided = max(s) > 1
-    TX = min(16, max(4, p2ceil(odims[2])))
-    if strided:
-        TX = min(TX, 8)
-    rem = (64 if strided else 256) // TX
-    TY = min(p2ceil(odims[1]), 4 if (TX == 16 or strided) else 8, rem)
-    TZ = min(p2ceil(odims[0]), rem // TY)
-    HV = (s[0] * (TZ - 1) + 3) * (s[1] * (TY - 1) + 3) * (s[2] * (TX - 1) + 3)
-    if not 16 <= TZ * TY * TX <= 256 or HV > 768:
-        return None
-    NT = n * cdiv(odims[0], TZ) * cdiv(odims[1], TY) * cdiv(odims[2], TX)
-    PP = (co // 32) * (ci // 32)
-    t16 = not strided and (TZ, TY, TX) == (4, 4, 16)
-    target = 256 if (t16 and NT * PP >= 16 * 256) else 512
-    S = 1 if PP >= 256 else cdiv(target, PP)
-    S = max(1, min(S, NT))
-    assert S * 27 * co * ci * 4 <= WS
-    return ("wgrad_halo16ws_kernel" if t16 else "wgrad_halo_kernel"), cdiv(NT, cdiv(NT, S))
-
-
-def reduce_form(S, taps):
-    """rx_wgrad.hip rx_wgrad_reduce_launch (lines 301-307); the halo kernels skip it when S == 1"""
-    return "wgrad_reduce_manysplits" if (S >= 8 or taps > 27) else "wgrad_reduce"
-
-
-def shape_of(row):
-    if isinstance(row.shape, str):
-        s = L.SHAPES[row.shape]
-        return s.kind, s.n, s.ci, s.co, s.dims, s.k, s.s
-    ci, co, dims, k, s = row.shape
-    return "conv", 2, ci, co, dims, k, s
-
-
-def test_the_split_counts_rows_claim():
+def test_the_split_counts_rows_claim(plan):
+    """ks per dtype class, S and the reduce form of every row that claims one: the expected values are the ledger's hand-derived
+    ones, `got` is what the planners the entry points launch by return"""
+    rows = [(r, dt) for r in L.ROWS if isinstance(r.sub, dict) and set(r.sub) & {"ks", "S"} for dt in r.dtypes]
     checked = 0
-    for r in L.ROWS:
-        if not isinstance(r.sub, dict) or not (set(r.sub) & {"ks", "S"}):
-            continue
-        kind, n, ci, co, dims, k, s = shape_of(r)
-        for dt in r.dtypes:
-            if kind == "convT":
-                v, taps = math.prod(dims), math.prod(s)
-                got = {L.TFWD: lambda: igemm_ks(dt, n, ci, co, [(v, 1)] * taps, False), L.TDX: lambda: igemm_ks(dt, n, co, ci, [(v, taps)]),
-                       L.TDXA: lambda: igemm_ks(dt, n, co, ci, [(v, taps)]), L.TDW: lambda: wgrad_splits(ci, co, taps, n * v)}[r.entry]()
-            else:
-                od = tuple(out_dim(d, kk, ss) for d, kk, ss in zip(dims, k, s))
-                taps = math.prod(k)
-                if r.entry == L.FWD:
-                    got = igemm_ks(dt, n, ci, co, [(math.prod(od), taps)])
-                elif r.entry in (L.DX, L.DXA):
-                    got = igemm_ks(dt, n, co, ci, dgrad_phases(dims, k, s), s == (1, 1, 1))
-                else:
-                    halo = wgh_splits(n, ci, co, od, s) if (k == (3, 3, 3) and dt != "float32") else None
-                    got = halo or wgrad_splits(co, ci, taps, n * math.prod(od))
-            assert got[0] == r.kernel, (r.entry, r.shape, dt, got)
-            want = r.sub["ks"][cls(dt)] if "ks" in r.sub else r.sub["S"]
-            assert got[1] == want, (r.entry, r.shape, dt, got, want)
-            if "S" in r.sub:
-                assert r.sub.get("reduce") == (None if (got[1] == 1) else reduce_form(got[1], taps)), (r.entry, r.shape, dt, got)
-            if "stride" in r.sub:
-                assert s == (r.sub["stride"] if isinstance(r.sub["stride"], tuple) else (r.sub["stride"],) * 3), r
-            checked += 1
+    for (r, dt), ch in zip(rows, plan([row_plan_query(r, dt) for r, dt in rows])):
+        s = shape_of(r)[6]
+        got = (ch["name"], ch["ks"] if "ks" in r.sub else ch["S"])
+        assert got[0] == r.kernel, (r.entry, r.shape, dt, got)
+        want = r.sub["ks"][cls(dt)] if "ks" in r.sub else r.sub["S"]
+        assert got[1] == want, (r.entry, r.shape, dt, got, want)
+        if "S" in r.sub:
+            form = "wgrad_reduce_manysplits" if ch["manysplits"] else "wgrad_reduce"
+            assert r.sub.get("reduce") == (None if (got[1] == 1) else form), (r.entry, r.shape, dt, got)
+        if "stride" in r.sub:
+            assert s == (r.sub["stride"] if isinstance(r.sub["stride"], tuple) else (r.sub["stride"],) * 3), r
+        checked += 1
     assert checked >= 100
+
+
+# ---- a sweep of the planners over small layers --------------------------------------------------------------------------------------
+SWEEP_DIMS = ((4, 4, 4), (3, 8, 8), (8, 8, 16), (5, 12, 13), (16, 16, 32), (6, 10, 64))
+SWEEP_C = (32, 64, 96, 128, 256, 512)
+SWEEP_K = ((1, 1, 1), L.K3, L.K133, (5, 5, 5))
+SWEEP_S = (L.S1, L.S2, L.S122, (3, 3, 3))
+
+
+def test_planner_sweep_keeps_what_the_kernels_assume(plan):
+    """N in {1, 2}, channels 32 .. 512, extents up to 64, kernels 1 / 3 / (1,3,3) / 5, strides 1 / 2 / (1,2,2) / 3, every entry point:
+    check_plan_invariants on every outcome (ks * need <= workspace, <= 8 phases and <= RX_MAX_TAPS taps a launch, every output voxel
+    of a launch sequence written once, S * tiles_per_split >= NT, LDS <= 160 KiB, no empty grid), nothing refused, and what
+    rx_wgrad_ws_bytes only says in a comment: with exactly the bytes the workspace function returns, the split is the unlimited one"""
+    qs = []
+    for dt, n, dims, ci, co in itertools.product(L.ALL, (1, 2), SWEEP_DIMS, SWEEP_C, SWEEP_C):
+        for k, s in itertools.product(SWEEP_K, SWEEP_S):
+            od = tuple((d + 2 * ((kk - 1) // 2) - kk) // ss + 1 for d, kk, ss in zip(dims, k, s))
+            x, y = act(n, dims, ci, ci + 32), act(n, od, co)
+            qs += [pq(0, dt, x, y, k, s), pq(2, dt, y, act(n, dims, ci), k, s), pq(6, dt, x, y, k, s)]
+        if math.prod(dims) <= 1024:                       # (the fine tensor has up to 27 times the voxels)
+            for s in SWEEP_S[1:]:
+                x, y = act(n, dims, ci, ci + 32), act(n, tuple(d * ss for d, ss in zip(dims, s)), co, 2 * co)
+                qs += [pq(4, dt, x, y, s=s), pq(5, dt, y, act(n, dims, ci), s=s), pq(7, dt, x, y, s=s)]
+    seen, broken = collections.Counter(), []
+    for i in range(0, len(qs), 20000):
+        for q, ch in zip(qs[i:i + 20000], plan(qs[i:i + 20000])):
+            assert ch["path"] != "refuse", (q, ch)
+            seen[ch["name"]] += 1
+            if "S_fn" in ch and ch["S_fn"] != ch["S_unl"]:
+                broken.append((q, ch["name"], ch["S_fn"], ch["S_unl"]))
+    assert not broken, broken[:5]
+    assert len(seen) >= 14, seen
+
+
+def test_refusal_texts_of_the_gather_path(plan):
+    """asserted literally, with the code: what RX_FAIL hands to rx_last_error"""
+    x, k = act(1, (4, 4, 8), 64), L.K133
+    got = plan([pq(0, "bfloat16", act(1, (4, 4, 8), 48), act(1, (4, 4, 8), 32), k), pq(0, "float32", act(1, (4, 4, 8), 24, 32), act(1, (4, 4, 8), 32), k),
+                pq(0, "bfloat16", x, act(1, (4, 4, 8), 48), k), pq(0, "bfloat16", act(1, (4, 4, 8), 64, lo=8), act(1, (4, 4, 8), 32), k),
+                pq(0, "bfloat16", x, act(1, (4, 4, 8), 32, 34), k), pq(6, "bfloat16", x, act(1, (4, 4, 8), 48), k),
+                pq(6, "bfloat16", x, act(1, (4, 4, 8), 32), k, ws_bytes=1000), pq(6, "bfloat16", x, act(1, (4, 4, 8), 32), k, ws=0)])
+    assert [(c["path"], c["code"], c["message"]) for c in got] == [
+        ("refuse", -2, "igemm: input channels must be a multiple of 32 (got 48)"),
+        ("refuse", -2, "igemm: input channels must be a multiple of 16 (got 24)"),
+        ("refuse", -2, "igemm: output channels must be a multiple of 32 (got 48)"),
+        ("refuse", -2, "igemm: misaligned operand (ldi=64 ldo=32)"),
+        ("refuse", -2, "igemm: misaligned operand (ldi=64 ldo=34)"),
+        ("refuse", -2, "wgrad: channel counts must be multiples of 32 (R=48 C=64)"),
+        ("refuse", -4, "wgrad: workspace too small (1000 bytes)"),
+        ("refuse", -1, "wgrad: null workspace / output")]

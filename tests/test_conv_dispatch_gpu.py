@@ -9,6 +9,9 @@ its dtypes.  One case is one ledger shape in one dtype, run through every entry 
     term each; then one rounding into the storage type.  dw is an fp32 output of K = batch * voxels terms.
   * the rows of the statistics entry points keep what test_conv3d_fwd_stats / test_conv3d_bwd_data_instats assert.
 
+  * every output of the random pass is hashed and compared with tests/data/conv_dispatch.json, recorded before the dispatch moved
+    into the planners of csrc/rx_gather_plan.h and csrc/rx_wgrad_plan.h (conv_dispatch_record.py): the same launches, no new work.
+
 The input is read through a channel slice of a wider buffer (ld = c + 32, c0 = 32) in every case, and dy of the transposed conv through
 the second half of a concat (ld = 2 co, c0 = co), so an addressing error cannot hide behind a dense tensor.  The two 16-bit types share one
 reference: their data is representable in both (8 significant bits within the fp16 range)."""
@@ -19,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_dispatch_cases as L
+import conv_dispatch_record as REC
 from exact_ops import U32, assert_within, gamma, half_ulp, poisoned
 from norm_bounds import check_stats
 from test_ops_gpu import _EXACT, exact_conv_pass, exact_conv_ref, exact_convT_pass, last_kernel, nan_act, to_act
@@ -43,6 +47,14 @@ def rnd(shape, half, seed, scale=1.0):
     return (t.to(torch.bfloat16).to(torch.float16) if half else t).double()
 
 
+def operands(s, half):
+    """x, w and the bias of a shape"""
+    T = s.kind == "convT"
+    x = rnd((s.n, s.ci, *s.dims), half, 1)
+    w = rnd((s.ci, s.co, *s.s) if T else (s.co, s.ci, *s.k), half, 2, (s.ci * (1 if T else math.prod(s.k))) ** -0.5)
+    return x, w, rnd((s.co,), False, 3).float().double()
+
+
 _REF = {}
 
 
@@ -55,9 +67,7 @@ def reference(key, half):
     s = L.SHAPES[key]
     T = s.kind == "convT"
     taps = math.prod(s.s if T else s.k)
-    x = rnd((s.n, s.ci, *s.dims), half, 1)
-    w = rnd((s.ci, s.co, *s.s) if T else (s.co, s.ci, *s.k), half, 2, (s.ci * (1 if T else taps)) ** -0.5)
-    b = rnd((s.co,), False, 3).float().double()
+    x, w, b = operands(s, half)
     if T:
         conv = lambda a, c: F.conv_transpose3d(a, c, stride=s.s)                                          # noqa: E731
     else:
@@ -92,15 +102,16 @@ def expected(key, dtn):
     return {r.entry: r for r in rows}
 
 
-@pytest.mark.parametrize("key,dtn", CASES, ids=[f"{k}-{d}" for k, d in CASES])
-def test_ledger_row(ops, key, dtn):
-    s = L.SHAPES[key]
-    dtype = getattr(torch, dtn)
-    rows = expected(key, dtn)
-    r = reference(key, dtype != torch.float32)
-    Kf, Kd, Kw = r["K"]
+def run_entries(ops, s, dtype, r, case):
+    """every entry point of the family of `s` on the operands r (x, w, b, gy, base, odims): the kernel each call names, the handles
+    of what it read and wrote; each name and output goes through REC.note as `case`"""
+    seen, h = {}, {}
     bias = r["b"].float().cuda()
-    seen = {}
+
+    def ran(entry, out):
+        seen[entry] = last_kernel(ops)
+        REC.note(case, entry, seen[entry], out)
+
     if s.kind == "convT":
         co = s.co
         xa = to_act(ops, r["x"], dtype, ld=s.ci + 32, c0=32)        # x through a channel slice, dy through the SECOND half of a concat
@@ -108,49 +119,67 @@ def test_ledger_row(ops, key, dtn):
         cat = ops.Act(torch.full((s.n, *r["odims"], 2 * co), 3.0, dtype=dtype, device="cuda"))
         cat.t[..., :co] = float("nan")
         ops.convT3d_fwd(xa, w_fwd, bias, cat.slice(0, co), s.s)
-        seen[L.TFWD] = last_kernel(ops)
-        check(cat.slice(0, co).to_ncdhw(), r["y"], r["a_y"], Kf, dtype, f"up ({seen[L.TFWD]})")
-        assert torch.all(cat.slice(co, co).tensor() == 3.0)
+        ran(L.TFWD, cat.t)
         gya = to_act(ops, r["gy"], dtype, ld=2 * co, c0=co)
         dx = nan_act(s.n, s.dims, s.ci, dtype)
         ops.convT3d_bwd_data(gya, w_bwd, dx, s.s)
-        seen[L.TDX] = last_kernel(ops)
-        check(dx.to_ncdhw(), r["dx"], r["a_dx"], Kd, dtype, f"dx ({seen[L.TDX]})")
+        ran(L.TDX, dx.t)
         dxa = to_act(ops, r["base"], dtype)
         ops.convT3d_bwd_data(gya, w_bwd, dxa, s.s, True)
-        seen[L.TDXA] = last_kernel(ops)
-        check(dxa.to_ncdhw(), r["base"] + r["dx"], r["a_dx"] + r["base"].abs(), Kd + 1, dtype, f"dx += ({seen[L.TDXA]})")
+        ran(L.TDXA, dxa.t)
         dw = poisoned(r["w"].shape)
         ops.convT3d_bwd_weight(xa, gya, dw, s.s)
-        seen[L.TDW] = last_kernel(ops)
-        check(dw, r["dw"], r["a_dw"], Kw, dtype, f"dw ({seen[L.TDW]})", names=("ci", "co", "kz", "ky", "kx"))
-        ex = exact_convT_pass(ops, dtype, exact_conv_ref(("dispatch", key), s.ci, s.co, s.dims, None, s.s, s.n, transposed=True), s.s)
-        assert ex["fwd"] == seen[L.TFWD] and ex["wgrad"] == seen[L.TDW], (seen, ex)
+        ran(L.TDW, dw)
+        h.update(cat=cat)
     else:
         xa = to_act(ops, r["x"], dtype, ld=s.ci + 32, c0=32)
         w_fwd, w_bwd = ops.pack_conv_weight(r["w"].float().cuda(), dtype)
         y = nan_act(s.n, r["odims"], s.co, dtype)
         ops.conv3d_fwd(xa, w_fwd, bias, y, s.k, s.s)
-        seen[L.FWD] = last_kernel(ops)
-        check(y.to_ncdhw(), r["y"], r["a_y"], Kf, dtype, f"y ({seen[L.FWD]})")
+        ran(L.FWD, y.t)
         gya = to_act(ops, r["gy"], dtype)
         dx = nan_act(s.n, s.dims, s.ci, dtype)
         ops.conv3d_bwd_data(gya, w_bwd, dx, s.k, s.s, accumulate=False)
-        seen[L.DX] = last_kernel(ops)
-        check(dx.to_ncdhw(), r["dx"], r["a_dx"], Kd, dtype, f"dx ({seen[L.DX]})")
+        ran(L.DX, dx.t)
         dxa = to_act(ops, r["base"], dtype)
         ops.conv3d_bwd_data(gya, w_bwd, dxa, s.k, s.s, accumulate=True)
-        seen[L.DXA] = last_kernel(ops)
-        check(dxa.to_ncdhw(), r["base"] + r["dx"], r["a_dx"] + r["base"].abs(), Kd + 1, dtype, f"dx += ({seen[L.DXA]})")
+        ran(L.DXA, dxa.t)
         dw = poisoned(r["w"].shape)
         ops.conv3d_bwd_weight(xa, gya, dw, s.k, s.s)
-        seen[L.DW] = last_kernel(ops)
-        check(dw, r["dw"], r["a_dw"], Kw, dtype, f"dw ({seen[L.DW]})", names=DW5)
+        ran(L.DW, dw)
+        h.update(y=y, w_fwd=w_fwd)
+    h.update(xa=xa, gya=gya, w_bwd=w_bwd, dx=dx, dxa=dxa, dw=dw, bias=bias)
+    return seen, h
+
+
+@pytest.mark.parametrize("key,dtn", CASES, ids=[f"{k}-{d}" for k, d in CASES])
+def test_ledger_row(ops, key, dtn):
+    s = L.SHAPES[key]
+    dtype = getattr(torch, dtn)
+    rows = expected(key, dtn)
+    r = reference(key, dtype != torch.float32)
+    Kf, Kd, Kw = r["K"]
+    seen, h = run_entries(ops, s, dtype, r, f"{key}-{dtn}")
+    dx, dxa = h["dx"], h["dxa"]
+    if s.kind == "convT":
+        co = s.co
+        check(h["cat"].slice(0, co).to_ncdhw(), r["y"], r["a_y"], Kf, dtype, f"up ({seen[L.TFWD]})")
+        assert torch.all(h["cat"].slice(co, co).tensor() == 3.0)
+        check(dx.to_ncdhw(), r["dx"], r["a_dx"], Kd, dtype, f"dx ({seen[L.TDX]})")
+        check(dxa.to_ncdhw(), r["base"] + r["dx"], r["a_dx"] + r["base"].abs(), Kd + 1, dtype, f"dx += ({seen[L.TDXA]})")
+        check(h["dw"], r["dw"], r["a_dw"], Kw, dtype, f"dw ({seen[L.TDW]})", names=("ci", "co", "kz", "ky", "kx"))
+        ex = exact_convT_pass(ops, dtype, exact_conv_ref(("dispatch", key), s.ci, s.co, s.dims, None, s.s, s.n, transposed=True), s.s)
+        assert ex["fwd"] == seen[L.TFWD] and ex["wgrad"] == seen[L.TDW], (seen, ex)
+    else:
+        check(h["y"].to_ncdhw(), r["y"], r["a_y"], Kf, dtype, f"y ({seen[L.FWD]})")
+        check(dx.to_ncdhw(), r["dx"], r["a_dx"], Kd, dtype, f"dx ({seen[L.DX]})")
+        check(dxa.to_ncdhw(), r["base"] + r["dx"], r["a_dx"] + r["base"].abs(), Kd + 1, dtype, f"dx += ({seen[L.DXA]})")
+        check(h["dw"], r["dw"], r["a_dw"], Kw, dtype, f"dw ({seen[L.DW]})", names=DW5)
         if L.STATS in rows:
-            stats_rows(ops, s, dtype, rows, xa, w_fwd, bias, y)
+            stats_rows(ops, s, dtype, rows, h["xa"], h["w_fwd"], h["bias"], h["y"])
         for e, acc, plain in ((L.BS, False, dx), (L.BSA, True, dxa)):
             if e in rows:
-                instats_rows(ops, s, dtype, rows[e], r, gya, w_bwd, acc, plain)
+                instats_rows(ops, s, dtype, rows[e], r, h["gya"], h["w_bwd"], acc, plain)
         ex = exact_conv_pass(ops, dtype, exact_conv_ref(("dispatch", key), s.ci, s.co, s.dims, s.k, s.s, s.n), s.k, s.s, 32)
         assert {L.FWD: ex["fwd"], L.DX: ex["dgrad"], L.DXA: ex["dgrad+"], L.DW: ex["wgrad"]} == seen, (seen, ex)     # same kernels
     for e, row in rows.items():
