@@ -101,3 +101,44 @@ def lrelu_mask(out, y, stats, slope):
     y = _ncdhw(y)
     mean, rstd = _mr(stats, *y.shape[:2])
     return (y - mean) * rstd > 0
+
+
+def check_dres(got, g, mask, slope, dtype, what="d_residual", old=None):
+    """the residual gradient of rx_instnorm_act_bwd: g' = g * lrelu'(out) -- fl(slope) and the product, 2u -- then one rounding
+    into the storage type; accumulating (old: the destination before the call, fp64 NCDHW) adds one fp32 rounding of the sum.
+    Returns g'."""
+    g = _ncdhw(g)
+    gp = g if mask is None else torch.where(mask, g, g * slope)       # g' = g * lrelu'(out): fl(slope) and the product
+    if old is None:
+        e = 2 * U32 * gp.abs()
+        assert_within(_ncdhw(got), gp, e + half_ulp(gp.abs() + e, dtype), what)
+    else:
+        want = old + gp
+        e = U32 * (want.abs() + 2 * gp.abs())
+        assert_within(_ncdhw(got), want, e + half_ulp(want.abs() + e, dtype), what)
+    return gp
+
+
+def check_norm_bwd_res(d_res, dy, g, pool_dy, pool, out, y, stats, slope, dtype, what="bwd_res"):
+    """rx_instnorm_act_bwd_res per element: g' = (g + pool term) * lrelu'(out) in fp32 -- the pool scale and product, the add and the
+    slope product, 4u of |g| + |pool term| -- then one rounding into d_residual.  dy: the norm-backward bound of g', plus the error
+    of g' itself carried through rstd (g' - mean g' - xhat mean(g' xhat)), counting half an ulp more in case the sums read g' as
+    stored.  g, out, y, pool_dy: as the launch read them; pool: the stride of the deferred AvgPool or None."""
+    g, outd, yd = _ncdhw(g), _ncdhw(out), _ncdhw(y)
+    n, c = yd.shape[:2]
+    up = 0
+    if pool:
+        up = _ncdhw(pool_dy)
+        for ax, s in enumerate(pool):
+            up = up.repeat_interleave(s, dim=2 + ax)
+        up = up / (pool[0] * pool[1] * pool[2])
+    gd_c = g + up
+    gd_c = torch.where(outd > 0, gd_c, gd_c * slope)
+    e_c = 4 * U32 * (g.abs() + (up.abs() if pool else 0))
+    assert_within(_ncdhw(d_res), gd_c, e_c + half_ulp(gd_c.abs() + e_c, dtype), f"{what}: d_residual")
+    ref_c, e32, _ = norm_bwd_ref(gd_c, yd, stats, None, 1.0)
+    mean, rstd_c = _mr(stats, n, c)
+    xh_c = (yd - mean) * rstd_c
+    d_g = e_c + half_ulp(gd_c.abs() + e_c, dtype)
+    e_dy = e32 + rstd_c * (d_g + d_g.mean((2, 3, 4), keepdim=True) + xh_c.abs() * (d_g * xh_c.abs()).mean((2, 3, 4), keepdim=True))
+    assert_within(_ncdhw(dy), ref_c, e_dy + half_ulp(ref_c.abs() + e_dy, dtype), f"{what}: dy")

@@ -23,8 +23,9 @@ import torch.nn.functional as F
 
 import conv_dispatch_cases as L
 import conv_dispatch_record as REC
-from exact_ops import U32, assert_within, gamma, half_ulp, poisoned
+from exact_ops import poisoned
 from norm_bounds import check_stats
+from op_bounds import check, check_m12
 from test_ops_gpu import _EXACT, exact_conv_pass, exact_conv_ref, exact_convT_pass, last_kernel, nan_act, to_act
 
 pytestmark = pytest.mark.gpu
@@ -87,13 +88,6 @@ def reference(key, half):
              K=(s.ci * (1 if T else taps) + 1, s.co * taps, s.n * math.prod(s.dims if T else odims)))
     _REF[(key, half)] = r
     return r
-
-
-def check(got, ref, a, terms, dtype, what, names=("n", "c", "z", "y", "x")):
-    """|got - ref| <= gamma(terms - 1 [+ 1 in fp32 mode]) * sum|a b|, then half an ulp of the storage type"""
-    e = gamma(terms - 1 + (dtype == torch.float32)) * a
-    out16 = got.dtype != torch.float32
-    assert_within(got, ref, e + (half_ulp(ref.abs() + e, dtype) if out16 else 0), what, names=names)
 
 
 def expected(key, dtn):
@@ -221,14 +215,7 @@ def instats_rows(ops, s, dtype, row, r, gya, w_bwd, acc, plain):
     if not fused:
         assert (m12 == -3.0).all(), "m12 written by a call that returned fused = 0"
         return
-    g = dx2.to_ncdhw().double().cpu()
     mean = stats[..., 0].double().cpu().view(n, c, 1, 1, 1)
     rstd = stats[..., 1].double().cpu().view(n, c, 1, 1, 1)
     xh = (yv.to_ncdhw().double().cpu() - mean) * rstd
-    g = torch.where(xh > 0, g, g * slope)
-    want = torch.stack([g.mean((2, 3, 4)), (g * xh).mean((2, 3, 4))], -1)
-    V = dims[0] * dims[1] * dims[2]
-    hu = half_ulp(g.abs(), dtype)
-    bnd = torch.stack([g.abs().mean((2, 3, 4)), (g * xh).abs().mean((2, 3, 4))], -1) * (gamma(V) + 6 * U32) + \
-        torch.stack([hu.mean((2, 3, 4)), (hu * xh.abs()).mean((2, 3, 4))], -1)
-    assert_within(m12, want, bnd, f"m12 ({name})", names=("n", "c", "m"))
+    check_m12(m12, dx2.to_ncdhw().double().cpu(), xh, slope, dtype, f"m12 ({name})")

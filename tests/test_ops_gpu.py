@@ -16,7 +16,9 @@ import torch.nn.functional as F
 import conv_dispatch_cases
 from exact_ops import (U32, Guarded, assert_bits, assert_exact_precondition, assert_within, exact_tensor, gamma, half_ulp,
                        poisoned)
-from norm_bounds import _mr, _ncdhw, check_norm_bwd, check_norm_fwd, check_stats, lrelu_mask, norm_bwd_ref  # noqa: F401
+from norm_bounds import (_mr, _ncdhw, check_dres, check_norm_bwd, check_norm_bwd_res, check_norm_fwd, check_stats,  # noqa: F401
+                         lrelu_mask, norm_bwd_ref)
+from op_bounds import pool_bwd_bound, pool_fwd_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -389,16 +391,12 @@ def test_instnorm_lrelu_residual(ops, dtype, c, dims):
         if with_res:
             assert rel(dra.to_ncdhw(), rr.grad) < TOL[dtype]
             drg.check("d_residual")
-            gp = g if mask is None else torch.where(mask, g, g * slope)       # g' = g * lrelu'(out): fl(slope) and the product
-            e = 2 * U32 * gp.abs()
-            assert_within(dra.to_ncdhw(), gp, e + half_ulp(gp.abs() + e, dtype), "d_residual")
+            gp = check_dres(dra, g, mask, slope, dtype, "d_residual")
             old = dra.to_ncdhw().double().cpu()
             ops.instnorm_act_bwd(ga, ya, stats, out_ref_act, dya, slope, dra, True)   # accumulate
             assert rel(dra.to_ncdhw(), 2 * rr.grad) < 2 * TOL[dtype]
             drg.check("d_residual +=")
-            want = old + gp
-            e = U32 * (want.abs() + 2 * gp.abs())
-            assert_within(dra.to_ncdhw(), want, e + half_ulp(want.abs() + e, dtype), "d_residual +=")
+            check_dres(dra, g, mask, slope, dtype, "d_residual +=", old=old)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -451,7 +449,7 @@ def test_avgpool(ops, dtype, s):
     ops.avgpool_fwd(xa, ya, s)
     assert rel(ya.to_ncdhw(), ref.detach()) < TOL[dtype]
     K = s[0] * s[1] * s[2]
-    e = (gamma(K) + 2 * U32) * F.avg_pool3d(x.abs(), s, s)          # an fp32 sum of K terms, the scale 1/K and its product
+    e = pool_fwd_bound(x, s)                                        # an fp32 sum of K terms, the scale 1/K and its product
     assert_within(ya.to_ncdhw(), ref, e + half_ulp(ref.abs() + e, dtype), "pool")
     dxa = nan_act(n, dims, c, dtype)
     ops.avgpool_bwd(to_act(ops, g, dtype), dxa, s)
@@ -474,7 +472,7 @@ def test_avgpool(ops, dtype, s):
         if pool2:
             assert_bits(got, want, dtype, what)
         else:
-            e = 2.0001 * U32 * want.abs()
+            e = pool_bwd_bound(want)
             assert_within(got, want, e + half_ulp(want.abs() + e, dtype), what)
     yg = Guarded(n, odims, c, dtype)
     ops.avgpool_fwd(to_act(ops, xe, dtype), yg.act(ops), s)
@@ -490,7 +488,7 @@ def test_avgpool(ops, dtype, s):
     if pool2:
         assert_bits(dga.ncdhw(), base + de, dtype, "pool dx+ (exact data)")        # old + g / K: one rounding
     else:
-        e = 2.0001 * U32 * de.abs() + U32 * (base + de).abs()
+        e = pool_bwd_bound(de, base)
         assert_within(dga.ncdhw(), base + de, e + half_ulp((base + de).abs() + e, dtype), "pool dx+ (exact data)")
 
 
@@ -1009,16 +1007,7 @@ def test_instnorm_act_bwd_res_masked_gradient_written_once(ops, dtype, pool):
     # per element: g' = (g + pool term) * lrelu'(out) in fp32 -- the pool scale and product, the add and the slope product, 4u of
     # |g| + |pool term| -- then one rounding into d_residual.  dy: the norm-backward bound of g', plus the error of g' itself carried
     # through rstd (g' - mean g' - xhat mean(g' xhat)), counting half an ulp more in case the sums read g' as stored
-    g_abs = to_act(ops, g0, dtype).t.double().abs() + ((up / (pool[0] * pool[1] * pool[2])).abs() if pool else 0)
-    e_g = 4 * U32 * g_abs
-    gd_c, e_c = gd.permute(0, 4, 1, 2, 3).cpu(), e_g.permute(0, 4, 1, 2, 3).cpu()
-    assert_within(dr2.to_ncdhw(), gd_c, e_c + half_ulp(gd_c.abs() + e_c, dtype), "d_residual")
-    ref_c, e32, _ = norm_bwd_ref(gd_c, y, stats, None, 1.0)
-    rstd_c = stats[..., 1].double().cpu().view(n, c, 1, 1, 1)
-    xh_c = xh.permute(0, 4, 1, 2, 3).cpu()
-    d_g = e_c + half_ulp(gd_c.abs() + e_c, dtype)
-    e_dy = e32 + rstd_c * (d_g + d_g.mean((2, 3, 4), keepdim=True) + xh_c.abs() * (d_g * xh_c.abs()).mean((2, 3, 4), keepdim=True))
-    assert_within(dy2.to_ncdhw(), ref_c, e_dy + half_ulp(ref_c.abs() + e_dy, dtype), "dy")
+    check_norm_bwd_res(dr2, dy2, to_act(ops, g0, dtype), pg, pool, out, y, stats, slope, dtype)
     # in place (d_residual == g) is allowed: same results
     g3 = to_act(ops, g0, dtype)
     dy3 = nan_act(n, dims, c, dtype)

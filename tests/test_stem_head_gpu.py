@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from exact_ops import (NAMES5, Guarded, assert_bits, assert_exact_precondition, assert_within, exact_tensor, gamma, half_ulp,
                        poisoned)
 from norm_bounds import check_norm_bwd, check_norm_fwd, check_stats, lrelu_mask
+from op_bounds import head_dx_ref, head_grads_ref, head_logits_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -414,9 +415,7 @@ def test_fused_head_pair(ops, dtype, c, k, slope):
     assert torch.equal(l2, l3), f"{what}: logits depend on whether the output is stored"
     check_norm_fwd(o1, y, stats, None, slope, dtype, f"{what} out")
     a = ncdhw(o1).double().cpu()                                      # the activated output as stored
-    bb = b64.view(1, k, 1, 1, 1)
-    want = torch.einsum("nczyx,kc->nkzyx", a, w64) + bb
-    e = gamma(c + 1) * (torch.einsum("nczyx,kc->nkzyx", a.abs(), w64.abs()) + bb.abs())
+    want, e = head_logits_ref(a, w64, b64)
     for lg, nm in ((l1, "head_fwd"), (l2, "fused")):
         assert_within(lg, want, e, f"{what} logits ({nm})")
     # backward
@@ -432,15 +431,12 @@ def test_fused_head_pair(ops, dtype, c, k, slope):
     ops.instnorm_act_bwd_head(dout, w, y, stats, dy3, slope, dw=dw3, db=db3)
     assert torch.equal(dy1.t, dy2.t) and torch.equal(dy3.t, dy2.t), f"{what}: dy differs from the two calls"
     assert torch.equal(dw1, dw2) and torch.equal(db1, db2), f"{what}: head_bwd's dw / db depend on dx"
-    dw_ref, db_ref = torch.einsum("nkzyx,nczyx->kc", d64, a), d64.sum((0, 2, 3, 4))
-    e_dw, e_db = gamma(n * V) * torch.einsum("nkzyx,nczyx->kc", d64.abs(), a.abs()), gamma(n * V) * d64.abs().sum((0, 2, 3, 4))
+    dw_ref, db_ref, e_dw, e_db = head_grads_ref(d64, a)
     for dw, db, nm in ((dw1, db1, "head_bwd"), (dw3, db3, "fused")):
         assert_within(dw, dw_ref, e_dw, f"{what} dw ({nm})", names=("k", "c"))
         assert_within(db, db_ref, e_db, f"{what} db ({nm})", names=("k",))
     # dy: g = dout x w is an fp32 sum of k products (gamma_k of the magnitudes), rounded into the storage type (half an ulp)
-    g_un = torch.einsum("nkzyx,kc->nczyx", d64, w64)
-    e_g = gamma(k) * torch.einsum("nkzyx,kc->nczyx", d64.abs(), w64.abs())
-    d_g = e_g + half_ulp(g_un.abs() + e_g, dtype)
+    g_un, d_g = head_dx_ref(d64, w64, dtype)
     assert_within(ncdhw(g), g_un, d_g, f"{what} g")
     mask = lrelu_mask(None, y, stats, slope)
     check_norm_bwd((dy1, dy2, dy3), g_un, y, stats, mask, slope, dtype, f"{what} dy", d_g=d_g)
