@@ -15,9 +15,12 @@ Layout decisions:
     initialises the buffer the other decoders and the encoder accumulate into), then the encoder
     in reverse.
   * per-parameter packed copies ([tap][Co][Ci] and [tap][Ci][Co], compute dtype) are refreshed only
-    when the parameter's version counter moved.
+    when the parameter went stale: `plan.packs`, a `WeightPacks` of typed `Pack` entries (engine/packs.py), which also holds
+    the only definition of staleness and the padded parameters' `Shadow` records.
+
+The run side (`# ---- run` down) replays the two static lists: eagerly, as a recorded launch program or as a captured HIP graph.
+Both replay backends climb the same ladder (engine/replay.py::ladder: two eager passes, record once, replay ever after).
 """
-import contextlib
 import os
 from dataclasses import dataclass
 from typing import Callable, ClassVar, Dict, List, NamedTuple, Optional
@@ -28,6 +31,8 @@ from torch import nn
 from . import lib as _l
 from . import ops
 from .ops import Act
+from .packs import Pack, Shadow, WeightPacks
+from .replay import as_f32, fresh_views, ladder, unalias_grads
 
 
 class UnsupportedConfig(NotImplementedError):
@@ -114,10 +119,6 @@ class Drop:
     eps_now: float             # eps * (1-p)^2 in training, eps in eval (_forward_pre)
     active: bool = False       # follows net.training (_forward_pre)
 
-    def __getitem__(self, name):
-        """d["keep"]: replacements of `Plan._draw_dropout` written when these entries of `plan._drops` were dicts keep working"""
-        return getattr(self, name)
-
 
 # ---- the tape: one record per layer.  Fields without a default are the layer itself (set by the emitters in _build);
 # ---- fields with a default are FUSION LINKS, set by the passes named in their comment and read by the step builders.
@@ -147,7 +148,7 @@ class ConvRec:
     kind: ClassVar[str] = "conv"
     x: AT
     y: AT
-    pk: dict
+    pk: Pack
     b: Optional[torch.Tensor]
     widx: int
     bidx: Optional[int]
@@ -162,7 +163,7 @@ class ConvTRec:
     kind: ClassVar[str] = "convT"
     x: AT
     y: AT
-    pk: dict
+    pk: Pack
     b: Optional[torch.Tensor]
     widx: int
     bidx: Optional[int]
@@ -276,7 +277,7 @@ class Plan:
 
         self.params: List[nn.Parameter] = []
         self._pidx: Dict[int, int] = {}
-        self.packs: List[dict] = []          # {param, kind, w_fwd, w_bwd, version}
+        self.packs = WeightPacks(self, dtype, self.two_d)     # packed conv / convT weights, in first-use order
         self.enc_tape: list = []             # records (StemRec ... HeadRec) of the encoder, forward order
         self.dec_tapes: List[list] = []      # ... and of each task decoder
         self.fwd: List[Callable] = []
@@ -304,19 +305,11 @@ class Plan:
         self._dy_ev: Dict[int, int] = {}          # id(dy tensor) -> event slot
         self._ev_fork = None                      # main -> side
         self._ev_join = None                      # side -> main
-        self._pack_groups = None                  # [(entries, event slot)] in first-use order (static per plan)
         self._gates: List[Gate] = []              # SqueezeExcite / DropPath state of every gated block, forward order
         self._drops: List[Drop] = []              # channel-dropout layers (dropout_op_kwargs p > 0), forward order
-        # Channel counts that are not a multiple of the kernels' K tile (features_per_stage is free in the reference,
-        # build_network_from_config.py:85-148): every activation buffer is PADDED to the next multiple, and each parameter that
-        # touches a padded extent gets a zero-padded fp32 SHADOW that the kernels read instead (refreshed from the real
-        # parameter in _forward_pre; zero weights / bias keep the padding channels exactly 0 through conv, InstanceNorm,
-        # LeakyReLU, pool, transposed conv and head); its gradient is produced padded and sliced back in _backward_finish.
-        # No kernel knows about it.  (Cost: the padded FLOPs and ~3 small torch copies per padded parameter and step.)
-        self._shadows: List[dict] = []
-        self._shadow_of: Dict[int, dict] = {}
-        self._pad_idx: Dict[int, dict] = {}       # parameter index -> shadow entry
-        self._pad_done: List[int] = []
+        self._shadows: List[Shadow] = []          # padded parameters (engine/packs.py::Shadow), in creation order
+        self._pad_idx: Dict[int, Shadow] = {}     # parameter index -> its shadow
+        self._pad_done: List[int] = []            # padded parameters whose gradient this backward produced (_backward_finish)
         # Launch programs (default on; RX_PROGRAMS=0 = one ctypes call per launch): the forward / backward lists are static, so
         # after two eager passes each is RECORDED once by the library while it executes (rx_prog_begin/end) and every later
         # step replays it with one C call -- the same launches on the same two streams, without ~700 host-language calls
@@ -330,8 +323,7 @@ class Plan:
         self._on_side = False
         self._use_gstore = False
         self._gflat_range = (0, 0)
-        self._pack_slots: List[int] = []
-        self._unstable_params = False
+        self._unstable_params = False         # a pack had to copy its parameter (not fp32 / contiguous): no recorded programs
         self._ws_refs: List[object] = []
         self._raw_seen = None                 # last `net._raw_param_event` (engine/streamed_step.py) this plan waited for
         # HIP graphs (opt-in: RX_GRAPHS=1 or plan.use_graphs = True): the forward / backward launch lists are static
@@ -349,7 +341,6 @@ class Plan:
         self._cat_written: Dict[int, bool] = {}   # backward build: concat gradient buffers a full-buffer write has initialised
         self._skip = frozenset()                  # RX_SKIP timing ablations (_gen_backward)
         self._pack_delay_at = None                # forward-list index behind the full-resolution encoder stage (deferred weight packs)
-        self._pack_deferred = None
         self._build()
 
     def release(self):
@@ -358,14 +349,12 @@ class Plan:
         by `__del__` and by the model when it discards its plans."""
         try:
             self._pstate.clear()                  # programs first: they mention the slots
-            slots = set(self._dy_ev.values()) | set(self._pack_slots)
+            slots = set(self._dy_ev.values()) | set(self.packs.release())
             for s in (self._ev_fork, self._ev_join):
                 if s is not None:
                     slots.add(s)
-            self._dy_ev, self._pack_slots, self._ev_fork, self._ev_join = {}, [], None, None
+            self._dy_ev, self._ev_fork, self._ev_join = {}, None, None
             self._dy_free = {}
-            for ent in self.packs:
-                ent["event"] = None
             for s in slots:
                 ops.event_free(s)
         except Exception:       # interpreter shutdown: the library may be gone
@@ -424,11 +413,10 @@ class Plan:
         a, b = p.shape[0], p.shape[1]
         taps = p[0, 0].numel()
         co, ci = (a, b) if kind == "conv" else (b, a)
-        ent = dict(param=p, kind=kind, version=-1,
-                   w_fwd=torch.empty((taps, co, ci), dtype=self.dtype, device=self.device),
+        ent = Pack(param=p, kind=kind, w_fwd=torch.empty((taps, co, ci), dtype=self.dtype, device=self.device),
                    w_bwd=torch.empty((taps, ci, co), dtype=self.dtype, device=self.device) if self.needs_grad else None)
-        self.bytes_alloc += 2 * ent["w_fwd"].numel() * ent["w_fwd"].element_size()
-        self.packs.append(ent)
+        self.bytes_alloc += 2 * ent.w_fwd.numel() * ent.w_fwd.element_size()
+        self.packs.entries.append(ent)
         return ent
 
     def _cp(self, c):
@@ -440,28 +428,16 @@ class Plan:
         whose index ranges `pairs` = [(dst index, src index)] mirror p (see self._shadows)"""
         if p is None or tuple(shape) == tuple(p.shape):
             return p
-        ent = self._shadow_of.get(id(p))
+        ent = self._pad_idx.get(self._pidx.get(id(p)))
         if ent is None:
             sh = torch.zeros(tuple(shape), dtype=p.dtype, device=self.device)
             self.bytes_alloc += sh.numel() * sh.element_size()
-            ent = dict(param=p, sh=sh, pairs=list(pairs), seen=None, gpad=None)
+            ent = Shadow(param=p, sh=sh, pairs=list(pairs))
             self._shadows.append(ent)
-            self._shadow_of[id(p)] = ent
             self._pad_idx[self._param(p)] = ent
-        elif tuple(ent["sh"].shape) != tuple(shape):
+        elif tuple(ent.sh.shape) != tuple(shape):
             raise UnsupportedConfig("one parameter read with two different padded shapes")
-        return ent["sh"]
-
-    def _refresh_shadows(self):
-        epoch = getattr(self.net, "_weights_epoch", 0)
-        for e in self._shadows:
-            q = e["param"]
-            tag = (q._version, q.data_ptr(), epoch)
-            if e["seen"] != tag:
-                src = q.detach()
-                for dst, sidx in e["pairs"]:
-                    e["sh"][dst].copy_(src[sidx])
-                e["seen"] = tag
+        return ent.sh
 
     @staticmethod
     def _out_dims(dims, kernel, stride):
@@ -832,19 +808,19 @@ class Plan:
 
     def _fwd_conv(self, r: ConvRec):
         def step():
-            self._await_pack(r.pk)
+            self.packs.wait(r.pk)
             st = r.stats_to
             if st is not None:
-                ops.conv3d_fwd_stats(r.x.act, r.pk["w_fwd"], r.b, r.y.act, r.kernel, r.stride, st.stats, self._eps_now(st))
+                ops.conv3d_fwd_stats(r.x.act, r.pk.w_fwd, r.b, r.y.act, r.kernel, r.stride, st.stats, self._eps_now(st))
                 self._mask_dropped(st)
             else:
-                ops.conv3d_fwd(r.x.act, r.pk["w_fwd"], r.b, r.y.act, r.kernel, r.stride)
+                ops.conv3d_fwd(r.x.act, r.pk.w_fwd, r.b, r.y.act, r.kernel, r.stride)
         return [step]
 
     def _fwd_convT(self, r: ConvTRec):
         def step():
-            self._await_pack(r.pk)
-            ops.convT3d_fwd(r.x.act, r.pk["w_fwd"], r.b, r.y.act, r.stride)
+            self.packs.wait(r.pk)
+            ops.convT3d_fwd(r.x.act, r.pk.w_fwd, r.b, r.y.act, r.stride)
         return [step]
 
     def _fwd_inact(self, r: InactRec):
@@ -942,10 +918,10 @@ class Plan:
         hand out views of its flat buckets instead (engine/ddp.py)"""
         ent = self._pad_idx.get(idx)
         if ent is not None:                 # padded parameter: the kernels write the padded gradient, _backward_finish slices it
-            if ent["gpad"] is None:
-                ent["gpad"] = torch.empty(tuple(ent["sh"].shape), dtype=torch.float32, device=self.device)
+            if ent.gpad is None:
+                ent.gpad = torch.empty(tuple(ent.sh.shape), dtype=torch.float32, device=self.device)
             self._pad_done.append(idx)
-            return ent["gpad"]
+            return ent.gpad
         if self.grad_sync is not None:
             g = self.grad_sync.alloc(idx)
         elif self._use_gstore:             # program mode: the same storage every backward (see _grad_store)
@@ -1160,9 +1136,9 @@ class Plan:
                     return
                 ia = r.instats_for
                 if ia is None:
-                    ops.conv3d_bwd_data(dy, r.pk["w_bwd"], gx, r.kernel, r.stride, acc)
+                    ops.conv3d_bwd_data(dy, r.pk.w_bwd, gx, r.kernel, r.stride, acc)
                 else:
-                    ia.m12_valid = ops.conv3d_bwd_data_instats(dy, r.pk["w_bwd"], gx, r.kernel, r.stride, acc, ia.y.act, ia.stats,
+                    ia.m12_valid = ops.conv3d_bwd_data_instats(dy, r.pk.w_bwd, gx, r.kernel, r.stride, acc, ia.y.act, ia.stats,
                                                                ia.slope, ia.m12)
             steps.append(dstep)
         return steps
@@ -1177,7 +1153,7 @@ class Plan:
 
         def step():
             wstep()
-            ops.convT3d_bwd_data(gy, r.pk["w_bwd"], gx, r.stride, acc)
+            ops.convT3d_bwd_data(gy, r.pk.w_bwd, gx, r.stride, acc)
         return [step]
 
     def _bwd_pool(self, r: PoolRec, tape, i):
@@ -1234,109 +1210,28 @@ class Plan:
         if self._ev_fork is None and self.device.type == "cuda":
             self._ev_fork, self._ev_join = ops.event_new(), ops.event_new()
 
-    def _await_pack(self, ent):
-        if ent.get("deferred") and self._pack_deferred is not None:
-            self._issue_deferred_packs()
-        slot = ent.get("event")
-        if slot is not None:
-            ops.stream_wait(slot)
-            for e in ent["group"]:          # one event per pack group: the first consumer's wait covers them all (stream order)
-                e["event"] = None
-
-    def _packs_stale(self, force=False):
-        """Staleness: tensor version / address AND the model's weight epoch.  torch's FUSED optimizers (fused=True
-        Adam/AdamW/SGD: `_fused_adamw_` ...) update parameters WITHOUT bumping `Tensor._version`, so a version check alone
-        would keep the initial packed weights for a whole training run.  Every backward pass through the engine
-        therefore starts a new weight epoch (an optimizer step is what normally follows it) and all plans of the model
-        re-pack on their next forward; pure inference (no backward) keeps its packs."""
-        epoch = getattr(self.net, "_weights_epoch", 0)
-        return [e for e in self.packs
-                if force or e.get("epoch") != epoch
-                or not (e["version"] == e["param"]._version and e.get("ptr") == e["param"].data_ptr())]
-
-    def refresh_packs(self, force=False):
-        """re-pack every parameter whose version moved (all of them with `force`: inside a captured graph).  The packs are pure HBM
-        traffic (1.7 GB at cfg2) while the first stages of the forward pass are MFMA/LDS bound: they run on the side stream in
-        first-use order, in a few table launches, and each consumer conv waits for its group's event."""
-        stale = self._packs_stale(force)
-        if not stale:
-            return
-        side = None
+    def _pack_stream(self):
+        """the stream weight packs run on: the side stream (made on first use), or None = the current one"""
         if self.device.type == "cuda" and self.overlap_wgrad:
             self._ensure_side()
-            side = self._side
-            ops.event_record(self._ev_fork)                    # the optimizer's writes are on the main stream
-            ops.stream_wait(self._ev_fork, side)
-        self._pack_entries(stale, side, defer=True)
+            return self._side
+        return None
 
-    def _issue_deferred_packs(self):
-        """(from inside the forward list) the pack groups that refresh_packs held back: ordered after the optimizer's writes by the
-        fork event recorded there (the side stream executes in order), and before their first consumer by position in the list"""
-        d, self._pack_deferred = self._pack_deferred, None
-        if d is not None:
-            groups, side = d
-            ops.event_record(self._ev_fork)                    # main stream: everything up to here
-            ops.stream_wait(self._ev_fork, side)
-            self._pack_groups_now(groups, side, 1)
+    # ---- weight packs (engine/packs.py): the plan supplies the model's weight epoch and whether its forward list defers -------
+    def _epoch(self):
+        return getattr(self.net, "_weights_epoch", 0)
 
-    def _pack_entries(self, entries, side, defer=False):
-        """re-pack `entries` (in first-use order) on `side` (or the current stream).  Table launches (rx_pack_multi, 40 tensors
-        each) in GROUPS of ~96 MB of parameters with one numbered event per group: the first convs of the forward
-        wait for the first (small) group only, the 512-channel stages' packing runs under the stages before them.  Was: one
-        launch + one event per tensor, 66 launches of 17 us on average per cfg2 step."""
-        limit = 96 << 20
-        groups, cur, cur_bytes = [], [], 0
-        for ent in entries:
-            nb = ent["param"].numel() * 4
-            if cur and cur_bytes + nb > limit and len(groups) < 3:     # at most 4 groups: [first ~96 MB] [next] [next] [rest]
-                groups.append(cur)
-                cur, cur_bytes = [], 0
-            cur.append(ent)
-            cur_bytes += nb
-        if cur:
-            groups.append(cur)
-        # Only the first group is packed now; the others (the 512-channel stages: 80 % of the bytes) are
-        # issued from inside the forward list, behind the full-resolution stage (see _forward_body) -- the packing then competes
-        # with the 64^3 / 32^3 convolutions instead of the HBM-bound full-resolution InstanceNorm passes
-        self._pack_deferred = None
-        if defer and side is not None and len(groups) > 1 and self._pack_delay_at is not None:
-            self._pack_deferred = (groups[1:], side)
-            for grp in groups[1:]:
-                for ent in grp:
-                    ent["deferred"] = True        # a consumer that comes earlier than expected issues them itself (_await_pack)
-            groups = groups[:1]
-        self._pack_groups_now(groups, side, 0)
+    def _packs_stale(self, force=False):
+        return self.packs.stale(self._epoch(), force)
 
-    def _pack_groups_now(self, groups, side, gi0):
-        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-            for gi, grp in enumerate(groups, gi0):
-                items = []
-                for ent in grp:
-                    w = ent["param"].detach()
-                    if w.dtype != torch.float32 or not w.is_contiguous():
-                        w = w.float().contiguous()
-                        self._unstable_params = True        # a temporary: its address is not replayable
-                    if self.two_d:
-                        w = w.unsqueeze(2)
-                    items.append((w, 0 if ent["kind"] == "conv" else 1, ent["w_fwd"], ent["w_bwd"]))
-                ops.pack_weights_multi(items, self.dtype)
-                slot = None
-                if side is not None:
-                    while len(self._pack_slots) <= gi:
-                        self._pack_slots.append(ops.event_new())
-                    slot = self._pack_slots[gi]
-                    ops.event_record(slot)
-                for ent in grp:
-                    p = ent["param"]
-                    ent["deferred"] = False
-                    ent["event"], ent["group"] = slot, grp
-                    ent["version"], ent["ptr"] = p._version, p.data_ptr()
-                    ent["epoch"] = getattr(self.net, "_weights_epoch", 0)
+    def _mark_packs_fresh(self):
+        self.packs.mark_fresh(self._epoch())
+
+    def refresh_packs(self, force=False):
+        self.packs.refresh(self._epoch(), force, defer=self._pack_delay_at is not None)
 
     def repack(self, entries):
-        """re-pack `entries` on the side stream NOW (called from inside a `torch.cuda.stream(side)` block by the streamed
-        optimizer step, right after the update of those parameters) and mark them fresh"""
-        self._pack_entries(entries, self._side)
+        self.packs.repack(entries, self._epoch())
 
     # ---- launch programs -------------------------------------------------------------------------------------
     def _programs_on(self):
@@ -1348,38 +1243,30 @@ class Plan:
         return [main] + ([self._side] if self._side is not None else [])
 
     def _programmed(self, key, body, segments=None):
-        """run `body` eagerly twice (lazy allocations, workspace growth, first-use attributes), then once more under the
-        library's recorder, and replay the recorded program ever after.  `segments(prog, streams)` (optional) replays it
-        piecewise (the gradient synchroniser's bucket launches sit between segments).  Returns (state, replayed?)."""
-        st = self._pstate.setdefault(key, {"calls": 0})
-        ptrs = self._param_ptrs()
-        if st.get("prog") is not None and st["ptrs"] != ptrs:       # parameters were re-allocated: start over
-            st.clear()
-            st["calls"] = 0
-        if st.get("prog") is not None:
-            streams = self._streams()
+        """`body` on the replay ladder (engine/replay.py) of launch programs: recorded by the library while it executes, replayed
+        with one C call.  `segments(st, streams)` (optional) replays it piecewise (the gradient synchroniser's bucket launches sit
+        between segments).  Returns (state, "eager" | "record" | "replay")."""
+        def record(st, body):
+            prog = ops.Program()
+            self._ws_refs += [ops.workspace(), self._ws2]     # the recorded scratch pointers stay alive with the plan
+            self._marks = []
+            self._recording = prog
+            self._on_side = False
+            prog.begin(self._streams())
+            try:
+                st["result"] = body()
+            finally:
+                self._recording = None
+                prog.end()
+            st["marks"] = list(self._marks)
+            return prog
+
+        def replay(st):
             if segments is not None:
-                segments(st, streams)
+                segments(st, self._streams())
             else:
-                st["prog"].run(streams)
-            return st, True
-        if st["calls"] < 2:
-            st["calls"] += 1
-            st["result"] = body()
-            return st, False
-        prog = ops.Program()
-        self._ws_refs += [ops.workspace(), self._ws2]     # the recorded scratch pointers stay alive with the plan
-        self._marks = []
-        self._recording = prog
-        self._on_side = False
-        prog.begin(self._streams())
-        try:
-            st["result"] = body()
-        finally:
-            self._recording = None
-            prog.end()
-        st["prog"], st["ptrs"], st["marks"] = prog, ptrs, list(self._marks)
-        return st, False
+                st["prog"].run(self._streams())
+        return ladder(self._pstate, "prog", key, self._param_ptrs(), body, record, replay)
 
     def _grad_store(self):
         """one flat fp32 buffer for every parameter gradient, in readiness order: a recorded backward writes the SAME addresses
@@ -1399,10 +1286,7 @@ class Plan:
                 p = self.params[idx]
                 self._gviews[idx] = self._gflat[o:o + p.numel()].view(p.shape)
         lo, hi = self._gflat_range
-        for p in self.params:                      # gradient accumulation: a kept .grad must not alias what we overwrite now
-            gr = p.grad
-            if gr is not None and lo <= gr.data_ptr() < hi:
-                p.grad = gr.clone()
+        unalias_grads(self.params, lambda ptr: lo <= ptr < hi)
 
     # ---- HIP graph plumbing ---------------------------------------------------------------------------------
     def _graphs_on(self):
@@ -1414,28 +1298,16 @@ class Plan:
         return tuple(p.data_ptr() for p in self.params)
 
     def _graphed(self, key, body):
-        """run `body` eagerly twice, then capture it once and replay it ever after.  Returns the state dict."""
-        st = self._gstate.setdefault(key, {"calls": 0})
-        ptrs = self._param_ptrs()
-        if st.get("graph") is not None and st["ptrs"] != ptrs:      # parameters were re-allocated: start over
-            st.clear()
-            st["calls"] = 0
-        if st.get("graph") is not None:
-            st["graph"].replay()
-        elif st["calls"] < 2:
-            st["calls"] += 1
-            st["result"] = body()
-            st["eager"] = True
-            return st
-        else:
+        """`body` on the replay ladder of HIP graphs: a capture launches nothing, so the new graph is replayed right away.
+        Returns (state, "eager" | "record" | "replay")."""
+        def record(st, body):
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 st["result"] = body()
-            st["graph"], st["ptrs"] = g, ptrs
             g.replay()
-        st["eager"] = False
-        return st
+            return g
+        return ladder(self._gstate, "graph", key, self._param_ptrs(), body, record, lambda st: st["graph"].replay())
 
     def _forward_pre(self):
         """host-side work of a forward that is not a library call (never part of a recorded program)"""
@@ -1445,8 +1317,9 @@ class Plan:
             self._raw_seen = ev
         for g in self._gates:                               # DropPath: this step's per-sample factors (torch RNG)
             g.scale_now = self._draw_path_scale(g)
-        if self._shadows:                                   # padded channel extents: zero-padded copies of the parameters
-            self._refresh_shadows()
+        epoch = self._epoch()
+        for sh in self._shadows:                            # padded channel extents: zero-padded copies of the parameters
+            sh.refresh(epoch)
         training = bool(self.net.training)
         for d in self._drops:                               # channel dropout: this step's kept planes, in forward order
             d.active = training
@@ -1458,31 +1331,15 @@ class Plan:
         self.refresh_packs(force=force_packs)
         for i, step in enumerate(self.fwd):
             if i == self._pack_delay_at:
-                self._issue_deferred_packs()
+                self.packs.issue_deferred()
             step()
-        self._finish_packs()
-
-    def _finish_packs(self):
-        """issue the pack groups still held back, then wait for every pack (parameters of unused branches included: never leave
-        a pack in flight)"""
-        self._issue_deferred_packs()
-        for ent in self.packs:
-            self._await_pack(ent)
-
-    def _mark_packs_fresh(self):
-        epoch = getattr(self.net, "_weights_epoch", 0)
-        for ent in self.packs:
-            ent["version"], ent["ptr"], ent["event"] = ent["param"]._version, ent["param"].data_ptr(), None
-            ent["epoch"] = epoch
+        self.packs.finish()
 
     def _as_input(self, x):
         """the caller's image as the first-layer kernels read it: detached, fp32, contiguous, of the shape the plan was built for"""
         if tuple(x.shape) != self.in_shape:
             raise ValueError(f"plan built for input {self.in_shape}, got {tuple(x.shape)}")
-        x = x.detach()
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
-        return x
+        return as_f32(x)[0]
 
     def _set_input(self, x, static=False):
         """make x this step's image; `static`: through a persistent copy (a graph / program reads a fixed address)"""
@@ -1503,9 +1360,8 @@ class Plan:
             self._set_input(x, static=True)
             st = self._gstate.get(("f", apply_act))
             capturing = st is not None and st.get("graph") is None and st["calls"] >= 2
-            self._graphed(("f", apply_act), lambda: self._forward_body(force_packs=capturing))
-            st = self._gstate[("f", apply_act)]
-            if not st["eager"]:                       # the graph re-packed every parameter
+            _, how = self._graphed(("f", apply_act), lambda: self._forward_body(force_packs=capturing))
+            if how != "eager":                        # the graph re-packed every parameter
                 self._mark_packs_fresh()
         elif self._programs_on():
             self._ensure_side()
@@ -1514,8 +1370,8 @@ class Plan:
             dropping = any(g.scale_now is not None for g in self._gates) or any(d.active for d in self._drops)
             # one program per launch-list VARIANT: with / without the weight re-pack, with / without DropPath factors
             key = ("f", apply_act, stale, dropping, self.overlap_wgrad)
-            _, replayed = self._programmed(key, lambda: self._forward_body(force_packs=stale))
-            if replayed and stale:
+            _, how = self._programmed(key, lambda: self._forward_body(force_packs=stale))
+            if how == "replay" and stale:
                 self._mark_packs_fresh()
         else:
             self._set_input(x)
@@ -1537,7 +1393,7 @@ class Plan:
         n = self.n_fwd_enc if self.n_fwd_enc is not None else len(self.fwd)
         for step in self.fwd[:n]:
             step()
-        self._finish_packs()
+        self.packs.finish()
         outs = []
         for at, c in self.enc_skips:
             t = at.act.to_ncdhw()[:, :c].float()
@@ -1554,7 +1410,7 @@ class Plan:
         self._apply_act = False
         self._forward_pre()
         self.refresh_packs(force=False)
-        self._finish_packs()
+        self.packs.finish()
         for (at, c), t in zip(self.enc_skips, skips):
             t = t.detach()
             if self.two_d:
@@ -1589,15 +1445,14 @@ class Plan:
             sync = self.grad_sync
             for idx in sorted(set(self._pad_done)):
                 ent = self._pad_idx[idx]
-                q = ent["param"]
                 if sync is not None:
                     real = sync.alloc(idx)
                 elif self._use_gstore:
                     real = self._gviews[idx]
                 else:
-                    real = torch.empty_like(q, memory_format=torch.contiguous_format)
-                for dst, sidx in ent["pairs"]:
-                    real[sidx].copy_(ent["gpad"][dst])
+                    real = torch.empty_like(ent.param, memory_format=torch.contiguous_format)
+                for dst, sidx in ent.pairs:
+                    real[sidx].copy_(ent.gpad[dst])
                 grads[idx] = real
                 if sync is not None:
                     sync.ready(idx)
@@ -1633,9 +1488,7 @@ class Plan:
         for k, g in dlogits.items():
             if g is None:
                 continue
-            g = g.detach()
-            if g.dtype != torch.float32 or not g.is_contiguous():
-                g = g.float().contiguous()
+            g = as_f32(g)[0]
             if graphs or programs:
                 buf = self._dl_static.get(k)
                 if buf is None or buf.shape != g.shape:
@@ -1656,16 +1509,14 @@ class Plan:
                 sync.persistent = True          # bucket storage is reused step after step (recorded pointers)
                 sync.begin(self)
             key = ("b", tuple(sorted(self._dlogits)), id(sync) if sync is not None else 0, self.overlap_wgrad)
-            st, replayed = self._programmed(key, self._backward_body,
-                                            segments=self._replay_backward_segments if sync is not None else None)
-            if replayed:
+            _, how = self._programmed(key, self._backward_body,
+                                      segments=self._replay_backward_segments if sync is not None else None)
+            if how == "replay":
                 self._pad_done = [idx for idx in set(self.grad_order) if idx in self._pad_idx]
-            if replayed and sync is None:
-                for idx in set(self.grad_order):
-                    self._grads[idx] = self._gviews[idx]
-            grads = self._backward_finish()
-            # fresh tensor objects over the persistent storage (autograd adopts a gradient only if nobody else holds it)
-            return [t.detach() if t is not None else None for t in grads]
+                if sync is None:
+                    for idx in set(self.grad_order):
+                        self._grads[idx] = self._gviews[idx]
+            return fresh_views(self._backward_finish())
         self._use_gstore = False
         if self.grad_sync is not None:
             self.grad_sync.persistent = False
@@ -1676,22 +1527,15 @@ class Plan:
         key = ("b", tuple(sorted(self._dlogits)))
         st = self._gstate.get(key)
         if st is not None and st.get("graph") is not None:
-            # the graph rewrites the SAME gradient storage every replay.  autograd normally steals the tensors we
-            # return as .grad; if the caller kept such a .grad (gradient accumulation) move it out of the way first.
-            owned = st["owned"]
-            for p in self.params:
-                gr = p.grad
-                if gr is not None and gr.data_ptr() in owned:
-                    p.grad = gr.clone()
+            unalias_grads(self.params, st["owned"].__contains__)     # the graph rewrites the SAME gradient storage every replay
 
         def body():
             self._backward_body()
             return self._backward_finish()
-        st = self._graphed(key, body)
+        st, how = self._graphed(key, body)
         grads = st["result"]
-        if st["eager"]:
+        if how == "eager":
             return grads
         if "owned" not in st:
             st["owned"] = {t.data_ptr() for t in grads if t is not None}
-        # fresh tensor objects over the graph-owned storage (autograd steals a gradient only if nobody else holds it)
-        return [t.detach() if t is not None else None for t in grads]
+        return fresh_views(grads)

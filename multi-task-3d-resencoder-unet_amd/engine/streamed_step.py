@@ -3,7 +3,7 @@
 `optimizer.step()` of the train loop (train.py:229) is 2.2 ms of pure HBM traffic at cfg2 (213 M parameters x 7 fp32
 accesses) at the very end of a step, with nothing to overlap it.  The engine never reads a convolution weight directly:
 every conv consumes a packed compute-dtype copy that is refreshed on the side HIP stream and awaited through a
-per-parameter event (engine/plan.py::refresh_packs).  So the update itself can move to that stream:
+per-group event (engine/packs.py::WeightPacks.refresh).  So the update itself can move to that stream:
 
     StreamedOptimizerStep(optimizer, model).step()
 
@@ -85,9 +85,9 @@ class StreamedOptimizerStep:
         if not engine and any(p not in self.opt.state or "exp_avg" not in self.opt.state[p] for p in with_grad):
             self.opt.step()                               # a parameter got its first gradient: let torch create its state
             return
-        packed = {id(e["param"]): e for e in plan.packs}
+        packed = plan.packs.by_param(wait_side=False)     # (the side stream does this step's work: it waits for main, below)
         raw = [p for p in with_grad if id(p) not in packed]
-        ordered = [e["param"] for e in plan.packs if e["param"].grad is not None]     # plan.packs is in first-use order
+        ordered = [e.param for e in plan.packs if e.param.grad is not None]     # plan.packs is in first-use order
         chunks: List[List[torch.Tensor]] = []
         cur, size = [], 0
         for p in ordered:

@@ -81,9 +81,7 @@ class EngineAdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         plan = self._plan()
-        packed = {id(e["param"]): e for e in plan.packs} if plan is not None else {}
-        if plan is not None and plan._side is not None:
-            torch.cuda.current_stream().wait_stream(plan._side)     # nobody may still read the packs / gradients
+        packed = plan.packs.by_param() if plan is not None else {}      # (waits for the side stream)
         lib = load()
         clip = self._clip
         self._clip = None
@@ -111,14 +109,13 @@ class EngineAdamW(torch.optim.Optimizer):
                 # (rx_adamw_pack holds a [taps][32][40] tile in LDS: up to 27 taps.  A 5- / 7-wide kernel or a stride-3 / -4
                 # transposed conv takes the flat update; its pack entry stays stale and the next forward re-packs it)
                 if ent is not None and p[0, 0].numel() <= 27:
-                    kind = 0 if ent["kind"] == "conv" else 1
+                    kind = 0 if ent.kind == "conv" else 1
                     A, B = p.shape[0], p.shape[1]
                     taps = p[0, 0].numel()
                     check(lib.rx_adamw_pack(_l.DTYPE_CODE[plan.dtype], _p(p), _p(g), _p(st["exp_avg"]), _p(st["exp_avg_sq"]), _p(clip),
                                             group["lr"], b1, b2, group["eps"], group["weight_decay"], st["step"], kind, A, B, taps,
-                                            _p(ent["w_fwd"]), _p(ent["w_bwd"]), stream_ptr()), "rx_adamw_pack")
-                    ent["version"], ent["ptr"], ent["event"] = p._version, p.data_ptr(), None
-                    ent["epoch"] = getattr(plan.net, "_weights_epoch", 0)
+                                            _p(ent.w_fwd), _p(ent.w_bwd), stream_ptr()), "rx_adamw_pack")
+                    ent.mark_fresh(plan._epoch())
                 else:
                     flat.append((p, g, st))
             self._flat_update(group, flat, clip)

@@ -67,9 +67,7 @@ class EngineSGD(EngineOptimizerBase):
         if skip:                           # the GradScaler found an inf / NaN: no launch, no state
             return loss
         plan = self._plan()
-        packed = {id(e["param"]): e for e in plan.packs} if plan is not None else {}
-        if plan is not None and plan._side is not None:
-            torch.cuda.current_stream().wait_stream(plan._side)     # nobody may still read the packs / gradients
+        packed = plan.packs.by_param() if plan is not None else {}      # (waits for the side stream)
         lib = load()
         for group in self.param_groups:
             flat = []                      # un-packed parameters of this group: one C call per `first` set (rx_sgd_flat_multi)
@@ -81,13 +79,12 @@ class EngineSGD(EngineOptimizerBase):
                 # (rx_sgd_pack holds a [taps][32][40] tile in LDS: up to 27 taps; wider kernels take the flat update, their pack
                 # entry stays stale and the next forward re-packs it)
                 if ent is not None and p[0, 0].numel() <= 27:
-                    kind = 0 if ent["kind"] == "conv" else 1
+                    kind = 0 if ent.kind == "conv" else 1
                     check(lib.rx_sgd_pack(_l.DTYPE_CODE[plan.dtype], _p(p), _p(g), _p(buf), _p(clip), group["lr"], group["momentum"],
                                           group["dampening"], group["weight_decay"], int(group["nesterov"]), int(first), kind,
-                                          p.shape[0], p.shape[1], p[0, 0].numel(), _p(ent["w_fwd"]), _p(ent["w_bwd"]), stream_ptr()),
+                                          p.shape[0], p.shape[1], p[0, 0].numel(), _p(ent.w_fwd), _p(ent.w_bwd), stream_ptr()),
                           "rx_sgd_pack")
-                    ent["version"], ent["ptr"], ent["event"] = p._version, p.data_ptr(), None
-                    ent["epoch"] = getattr(plan.net, "_weights_epoch", 0)
+                    ent.mark_fresh(plan._epoch())
                 else:
                     flat.append((p, g, buf, first))
             self._flat_update(group, flat, clip)

@@ -43,14 +43,14 @@ print(f"cfg2: {len(params)} parameters with gradients, {n_par / 1e6:.1f} M eleme
 
 def repack():
     """every packed weight of the plan from its fp32 parameter (rx_pack_multi: 40 tensors per launch), on the current stream"""
-    ents = [e for e in plan.packs if e["param"][0, 0].numel() <= 27]
+    ents = [e for e in plan.packs if e.param[0, 0].numel() <= 27]
     n = len(ents)
     VP, IP = ctypes.c_void_p * n, ctypes.c_int * n
-    lib.check(lib.load().rx_pack_multi(lib.DTYPE_CODE[plan.dtype], n, VP(*[e["param"].data_ptr() for e in ents]),
-                                       IP(*[0 if e["kind"] == "conv" else 1 for e in ents]), IP(*[e["param"].shape[0] for e in ents]),
-                                       IP(*[e["param"].shape[1] for e in ents]), IP(*[e["param"][0, 0].numel() for e in ents]),
-                                       VP(*[e["w_fwd"].data_ptr() if e["w_fwd"] is not None else 0 for e in ents]),
-                                       VP(*[e["w_bwd"].data_ptr() if e["w_bwd"] is not None else 0 for e in ents]), lib.stream_ptr()),
+    lib.check(lib.load().rx_pack_multi(lib.DTYPE_CODE[plan.dtype], n, VP(*[e.param.data_ptr() for e in ents]),
+                                       IP(*[0 if e.kind == "conv" else 1 for e in ents]), IP(*[e.param.shape[0] for e in ents]),
+                                       IP(*[e.param.shape[1] for e in ents]), IP(*[e.param[0, 0].numel() for e in ents]),
+                                       VP(*[e.w_fwd.data_ptr() if e.w_fwd is not None else 0 for e in ents]),
+                                       VP(*[e.w_bwd.data_ptr() if e.w_bwd is not None else 0 for e in ents]), lib.stream_ptr()),
               "rx_pack_multi")
 
 

@@ -7,7 +7,15 @@ A refactor of engine/plan.py must leave the output byte-identical: run this same
     python scripts/trace_launch_lists.py --root <checkout of the parent> > a.txt
     python scripts/trace_launch_lists.py > b.txt
 (`--digest`: one sha256 per configuration instead of the full trace).  It uses only names a plan keeps:
-fwd / bwd / outputs / params / packs / grad_order / _drops / _gates / _x / _apply_act / _dlogits / _grads."""
+fwd / bwd / outputs / params / packs / grad_order / _drops / _gates / _x / _apply_act / _dlogits / _grads.
+
+`--run` traces the RUN side instead: `run_forward` / `run_backward` are driven for whole steps, weight packing included
+(`pack_weights_multi` is logged with its items).  On the meta device (default; single stream) over every configuration:
+a training plan's step 1, step 2 behind a fused optimizer step (every pack marked fresh: nothing is packed), step 3 behind a
+plain backward (new weight epoch: everything is packed), step 4 with one parameter's version bumped (that entry alone), and
+an inference plan's two forwards, encoder and decoders.  `--run --device cuda` (needs the GPU) runs `--steps` SGD training
+steps of the golden case `--only` (default auto16_2head) on the real `ops`, each wrapped by the logger: the host-call order
+on two streams, event slots numbered by first appearance.  `--pack-limit BYTES` lowers `plan.packs.limit` there."""
 import argparse
 import hashlib
 import os
@@ -18,6 +26,10 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--digest", action="store_true")
 ap.add_argument("--only", default=None, help="substring of the configuration names to run")
+ap.add_argument("--run", action="store_true", help="trace run_forward / run_backward instead of the launch lists")
+ap.add_argument("--device", default="meta", choices=("meta", "cuda"), help="--run only: cuda = the real ops, logged")
+ap.add_argument("--steps", type=int, default=3, help="--run --device cuda: training steps")
+ap.add_argument("--pack-limit", type=int, default=None, help="--run --device cuda: plan.packs.limit")
 args = ap.parse_args()
 ROOT = os.path.abspath(args.root)
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
@@ -54,24 +66,43 @@ def canon(v):
         return "{" + ", ".join(f"{k}: {canon(v[k])}" for k in sorted(v)) + "}"
     if isinstance(v, (list, tuple)):
         return "[" + ", ".join(canon(e) for e in v) + "]"
+    if REAL and isinstance(v, torch.cuda.Stream):
+        return "main" if v == torch.cuda.default_stream() else "side"
+    if callable(v):
+        return "<fn>"
     return repr(v)
 
 
 RETURNS = {"workspace": lambda: torch.empty(1, dtype=torch.uint8, device="meta"), "event_new": lambda: 7,
            "conv3d_bwd_data_instats": lambda: True}
+REAL = args.run and args.device == "cuda"       # the real ops run; the logger only listens
+EVENT_OPS = ("event_record", "stream_wait", "event_free")
+_slots = {}
 
 
-def _logger(name):
+def _slot(s):
+    """numbered events of the library, renumbered by first appearance"""
+    return f"ev{_slots.setdefault(s, len(_slots))}"
+
+
+def _logger(name, real=None):
     def call(*a, **k):
         if name != "workspace":
-            LOG.append(name + "(" + ", ".join([canon(e) for e in a] + [f"{n}={canon(k[n])}" for n in sorted(k)]) + ")")
+            shown = [_slot(a[0])] + [canon(e) for e in a[1:]] if REAL and name in EVENT_OPS else [canon(e) for e in a]
+            on = f" @{canon(torch.cuda.current_stream())}" if REAL else ""
+            LOG.append(name + "(" + ", ".join(shown + [f"{n}={canon(k[n])}" for n in sorted(k)]) + ")" + on)
+        if real is not None:
+            out = real(*a, **k)
+            if name == "event_new":
+                LOG[-1] += f" -> {_slot(out)}"
+            return out
         return RETURNS[name]() if name in RETURNS else None
     return call
 
 
 for _n, _f in list(vars(ops).items()):
     if isinstance(_f, types.FunctionType) and not _n.startswith("_"):
-        setattr(ops, _n, _logger(_n))
+        setattr(ops, _n, _logger(_n, _f if REAL else None))
 
 
 def _get(o, k):
@@ -142,7 +173,90 @@ def trace(name, mgr, shape):
             plan.release()
 
 
+def trace_run(name, mgr, shape):
+    """whole steps through run_forward / run_backward on the meta device (see the module docstring)"""
+    for dtype in (torch.float32, torch.bfloat16):
+        title = f"{name} {str(dtype)[6:]} run"
+        net = NetworkFromConfig(mgr).to("meta")
+        try:
+            plan = Plan(net, shape, dtype, "meta", needs_grad=True)
+            infer = Plan(net, shape, dtype, "meta", needs_grad=False)
+        except UnsupportedConfig as e:
+            emit(title, [f"UnsupportedConfig: {e}"])
+            continue
+        _ids.clear()
+        _alive.clear()
+        x = torch.empty(shape, dtype=torch.float32, device="meta")
+
+        def step(label):
+            del LOG[:]
+            outs = plan.run_forward(x, apply_act=False)
+            emit(f"{title} {label} forward", LOG + [f"outputs={canon(outs)}"])
+            del LOG[:]
+            grads = plan.run_backward({k: torch.empty(tuple(v.shape), dtype=torch.float32, device="meta") for k, v in outs.items()})
+            emit(f"{title} {label} backward", LOG + [f"grads={canon(grads)}", f"stale={len(plan._packs_stale())}"])
+
+        net.train()
+        step("step 1")
+        plan._mark_packs_fresh()            # what a fused engine optimizer step leaves behind
+        step("step 2 (packs fresh)")
+        step("step 3 (new weight epoch)")
+        plan._mark_packs_fresh()
+        packs = list(plan.packs)
+        with torch.no_grad():
+            _get(packs[len(packs) // 2], "param").zero_()
+        step("step 4 (one version bumped)")
+        net.eval()
+        for label in ("forward 1", "forward 2"):
+            del LOG[:]
+            outs = infer.run_forward(x, apply_act=True)
+            emit(f"{title} inference {label}", LOG + [f"outputs={canon(outs)}"])
+        del LOG[:]
+        skips = infer.run_encoder(x)
+        emit(f"{title} inference encoder", LOG + [f"skips={canon(skips)}"])
+        for d, task in enumerate(infer.outputs):
+            del LOG[:]
+            out = infer.run_decoder(d, task, skips)
+            emit(f"{title} inference decoder {task}", LOG + [f"out={canon(out)}"])
+        plan.release()
+        infer.release()
+
+
+def trace_cuda():
+    """the host-call order of `--steps` SGD training steps on the GPU, two streams (see the module docstring)"""
+    case = args.only or "auto16_2head"
+    c = CASES[case]
+    mgr = oracle.make_mgr(c["patch"], c["tasks"], c["in_channels"], c["batch"], c["autoconfigure"], c["model_config"])
+    torch.manual_seed(c["seed"])
+    net = NetworkFromConfig(mgr).cuda()
+    net.compute_dtype = torch.bfloat16
+    net.train()
+    opt = torch.optim.SGD(list(net.parameters()), lr=0.05)
+    shape = (c["batch"], c["in_channels"], *c["patch"])
+    plan = net.plan_for(shape, torch.bfloat16, torch.device("cuda", torch.cuda.current_device()), True)
+    if args.pack_limit is not None:
+        plan.packs.limit = args.pack_limit
+    print(f"== {case} bf16 programs={int(plan.use_programs)} pack_limit={args.pack_limit}")
+    for step in range(args.steps):
+        x, targets = oracle.synthetic_batch(c["batch"], c["in_channels"], c["patch"], c["tasks"], 100 + step)
+        x, targets = x.cuda(), {k: v.cuda() for k, v in targets.items()}
+        del LOG[:]
+        out = net(x)
+        emit(f"step {step + 1} forward", list(LOG))
+        loss = oracle.train_loss(out, targets, c["tasks"])
+        del LOG[:]
+        loss.backward()
+        emit(f"step {step + 1} backward", LOG + [f"loss={loss.item()!r}"])
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+    assert list(net._plans.values()) == [plan]
+    torch.cuda.synchronize()
+
+
 def main():
+    if REAL:
+        trace_cuda()
+        return
     jobs = []
     for kind, gen in (("small", fz.configs), ("medium", fz.medium_configs), ("large", fz.large_configs)):
         for i, c in enumerate(gen()):
@@ -156,7 +270,7 @@ def main():
     n = 0
     for name, mgr, shape in jobs:
         if args.only is None or args.only in name:
-            trace(name, mgr, shape)
+            (trace_run if args.run else trace)(name, mgr, shape)
             n += 1
     print(f"{n} configurations traced", file=sys.stderr)
 

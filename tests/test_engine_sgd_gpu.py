@@ -169,7 +169,7 @@ def test_engine_sgd_rewrites_the_plans_packs(opt_mod):
     _train(net, c, x, targets, opt, 1, clip)
     torch.cuda.synchronize()
     plan = [p for p in net._plans.values() if p.needs_grad][0]
-    assert opt._plan() is plan and not plan._packs_stale() and all(e.get("event") is None for e in plan.packs)
+    assert opt._plan() is plan and not plan._packs_stale() and all(e.event is None for e in plan.packs)
     assert clips[0] < 1.0
     args = sgd_ref.sgd_args(*HYPER, True)
     for (name, p), before, g in zip(net.named_parameters(), clip.before, clip.grads):

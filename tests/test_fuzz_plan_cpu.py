@@ -50,7 +50,7 @@ def test_every_fuzz_draw_plans_on_the_meta_device(dtype):
         for n, p in net.named_parameters():
             assert (id(p) in used) or ".seg_layers." in n, (kind, i, n)
         for e in plan._shadows:              # a shadow is at least as large as its parameter in every dimension
-            assert all(a >= b for a, b in zip(e["sh"].shape, e["param"].shape)), (kind, i)
+            assert all(a >= b for a, b in zip(e.sh.shape, e.param.shape)), (kind, i)
         assert len(ev.bwd) == 0
     assert built >= 55, built
 

@@ -536,6 +536,70 @@ def test_launch_program_replay_is_bit_identical_to_eager(NetworkFromConfig, monk
         assert torch.equal(p_e[n], p_p[n]), n
 
 
+def test_deferred_weight_packs_are_bit_identical(NetworkFromConfig, monkeypatch):
+    """Weight packs in more than one group (engine/packs.py): at the default `plan.packs.limit` every test-sized net packs in ONE
+    group, so the groups held back by `refresh` never ran below benchmark scale.  The 16^3 two-head case (the smallest net with
+    a stage below full resolution) trains 4 SGD steps (plain torch SGD: every step re-packs) with the limit lowered to
+      * the bytes of the full-resolution stage's packs: the other groups are issued from inside the forward list,
+      * 1 byte: the second full-resolution conv finds its pack held back and issues the deferred groups itself,
+    eagerly and with launch programs (two eager passes, the recording, one replay).  Losses and parameters must equal the
+    default run's bit for bit; which of the two places issued the deferred groups is observed on every pass that runs in
+    Python."""
+    import sys
+    c = CASES["auto16_2head"]
+    shape = (c["batch"], c["in_channels"], *c["patch"])
+
+    def run(limit, programs):
+        monkeypatch.setenv("RX_PROGRAMS", "1" if programs else "0")
+        net, _, _ = build(NetworkFromConfig, "auto16_2head")
+        net.compute_dtype = torch.bfloat16
+        net.train()
+        plan = net.plan_for(shape, torch.bfloat16, torch.device("cuda", torch.cuda.current_device()), True)
+        wp = plan.packs
+        if limit == "full_res_stage":
+            full_res, n_full = plan.spatial[0] * plan.spatial[1] * plan.spatial[2], 0
+            for r in plan.enc_tape:
+                if r.kind in ("conv", "pool") and r.y.act.voxels < full_res:
+                    break
+                n_full += r.kind == "conv"
+            assert 0 < n_full < len(wp)
+            wp.limit = sum(e.param.numel() * 4 for e in list(wp)[:n_full])
+        elif limit is not None:
+            wp.limit = limit
+        issued, inner = [], wp.issue_deferred
+
+        def spy():
+            if wp.deferred is not None:
+                issued.append(sys._getframe(1).f_code.co_name)
+            inner()
+        wp.issue_deferred = spy
+        opt = torch.optim.SGD(list(net.parameters()), lr=0.05)
+        losses = []
+        for step in range(4):
+            x, targets = oracle.synthetic_batch(c["batch"], c["in_channels"], c["patch"], c["tasks"], 100 + step)
+            out = net(x.cuda())
+            loss = oracle.train_loss(out, {k: v.cuda() for k, v in targets.items()}, c["tasks"])
+            loss.backward()
+            losses.append(loss.item())
+            opt.step()
+            opt.zero_grad(set_to_none=True)
+        assert list(net._plans.values()) == [plan]
+        recorded = sum(st.get("prog") is not None for st in plan._pstate.values())
+        assert recorded == (2 if programs else 0)         # the forward and the backward list
+        return losses, {n: p.detach().clone() for n, p in net.named_parameters()}, len(wp.slots), issued
+
+    l0, p0, groups0, issued0 = run(None, True)
+    assert groups0 == 1 and not issued0
+    for limit, where in (("full_res_stage", "_forward_body"), (1, "wait")):
+        for programs in (False, True):
+            l1, p1, groups, issued = run(limit, programs)
+            assert groups > 1, (limit, programs)
+            assert issued == [where] * (3 if programs else 4), (limit, programs, issued)
+            assert l1 == l0, (limit, programs)
+            for n in p0:
+                assert torch.equal(p0[n], p1[n]), (limit, programs, n)
+
+
 def test_channel_dropout_on_the_fused_paths(NetworkFromConfig):
     """dropout_op_kwargs p > 0 at a size where the statistics come out of conv epilogues, the head is fused into the layer below
     it and the InstanceNorm backward sums ride in data-gradient epilogues (bf16, 64^3): with FORCED masks the planes the masks

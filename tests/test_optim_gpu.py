@@ -68,7 +68,7 @@ def test_engine_adamw_tracks_torch_adamw():
     for k in o1:
         assert torch.equal(o1[k], o2[k]), k
     plan = [p for p in net_b._plans.values() if p.needs_grad][0]
-    assert all(e.get("event") is None for e in plan.packs)
+    assert all(e.event is None for e in plan.packs)
 
 
 # Both golden cases with more than 27 taps (big_kernels, stride4_mixed) widen their 5-wide stem weight into a zero-padded shadow, and a
@@ -105,11 +105,11 @@ def test_engine_adamw_steps_a_plan_with_more_than_27_taps(case):
     plan = plans[0]
     fused = case == "wide_taps_no_shadow"
     assert bool(plan._shadows) == (not fused) and (oa._plan() is plan) == fused
-    taps = {id(e["param"]): e["param"][0, 0].numel() for e in plan.packs}
+    taps = {id(e.param): e.param[0, 0].numel() for e in plan.packs}
     big = {i for i, t in taps.items() if t > 27}
     assert big and len(big) < len(taps), sorted(taps.values())
     if fused:                                                     # a transposed conv among them (kind 1 of rx_adamw_pack's refusal)
-        assert any(e["kind"] == "convT" and e["param"][0, 0].numel() > 27 for e in plan.packs)
+        assert any(e.kind == "convT" and e.param[0, 0].numel() > 27 for e in plan.packs)
     before = []
     for a, b in zip(pa, pb):
         assert torch.equal(a, b)
@@ -132,7 +132,7 @@ def test_engine_adamw_steps_a_plan_with_more_than_27_taps(case):
             assert st["step"] == 1
             check_step((p.detach().flatten(), st["exp_avg"].flatten(), st["exp_avg_sq"].flatten()), (p0, zero, zero), a.grad.flatten().cpu(),
                        clip, args, f"engine_adamw plan: {case} {name} ({'fused' if opt is oa else 'flat'})")
-    stale = {id(e["param"]) for e in plan._packs_stale()}
+    stale = {id(e.param) for e in plan._packs_stale()}
     assert stale == (big if fused else set(taps)), "exactly the weights that took the flat update wait for a re-pack"
     fresh = N(mgr).cuda()
     fresh.load_state_dict(net_a.state_dict())

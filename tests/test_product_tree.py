@@ -55,7 +55,7 @@ def test_plan_structure_on_meta_device(case, dtype):
         spatial = c["patch"] if len(c["patch"]) == 3 else (1, *c["patch"])      # a 2-D net runs with a unit Z axis inside
         assert tuple(plan.outputs[name].shape) == (c["batch"], info["channels"], *spatial)
     ev = Plan(net, shape, dtype, "meta", needs_grad=False)
-    assert len(ev.bwd) == 0 and all(e["w_bwd"] is None for e in ev.packs)
+    assert len(ev.bwd) == 0 and all(e.w_bwd is None for e in ev.packs)
 
 
 def test_planner_matches_oracle():
