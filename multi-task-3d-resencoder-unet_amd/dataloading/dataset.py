@@ -9,32 +9,16 @@ by default with ONE warning saying so (`dataset_config.augment: "restated"` ackn
 feeds raw patches and leaves the stack to the HIP kernels behind `augment_device.DeviceAugmenter`); remote
 (http) stores are refused (no network).
 
-`dataset_config.geometric` (absent: off) adds axis flips and 90-degree rotations that move the image and every target together
-and keep a normals target consistent (`geometry_device.py`): `where: device` leaves the items alone (the trainer applies
-`DeviceGeometry` to the staged batch), `where: host` runs the host classes inside `__getitem__`, before the intensity stack.
-
-`tr_setup.dilate_label` dilates every target that is not `normals` with a ball; `dataset_config.dilate` (absent: `{where: host,
-radius: 5}`, the reference's behaviour) says where: `host` is scipy's `binary_dilation` inside `__getitem__`, `device` hands out
-the scaled raw label and leaves the dilation to `dilate_device.DeviceDilate` (the trainer reads `device_dilate`).
-
-`dataset_config.spatial` (absent: off) adds small-angle rotation and mild isotropic scaling about the patch centre, image and
-targets together, a normals target turned with them (`spatial_device.py`): `where: device` leaves the items alone and exposes
-`device_spatial` (the trainer applies `DeviceSpatial` to the staged batch, after geometry), `where: host` draws one op per item
-and runs `affine_numpy` inside `__getitem__`, after the host geometric classes and before the intensity stack.
-
-`dataset_config.elastic` (absent: off) adds a smooth B-spline deformation, image and targets together, a normals target carried
-as a covector (`elastic_device.py`): `where: device` leaves the items alone and exposes `device_elastic` (the trainer applies
-`DeviceElastic` to the staged batch, after spatial), `where: host` draws one field per item and runs `elastic_numpy` inside
-`__getitem__`, after the host spatial stage and before the intensity stack.
-
-`dataset_config.patch_search` (absent: `{where: host}`, `find_valid_patches` below) says where the valid-patch search of the
-constructor runs: `device` hands each volume's reference label to `patch_search_device.find_valid_patches_device` (HIP box
-statistics, the same list and the same cache file; no device is an error, not a fallback).
-
-`dataset_config.ingest` (absent: `{where: host}`, every item as described above) says where the float32 conversion, the dtype
-scaling and the channels-last transpose of `__getitem__` run: `device` hands out `torch.from_numpy` of the raw slices -- uint8,
-uint16 or float32, (Z, Y, X) or (Z, Y, X, C), no channel axis added -- and leaves the rest to `ingest_device.DeviceIngest` (the
-trainer reads `device_ingest`, {key: rule}); it needs every host stage that works on scaled floats off or on the device."""
+The stage blocks of `dataset_config` -- `geometric` (flips and 90-degree rotations, `geometry_device.py`), `spatial` (small-angle
+rotation and scale, `spatial_device.py`), `elastic` (a B-spline deformation, `elastic_device.py`), each absent: off and moving the
+image and every target together, a normals target kept consistent; `dilate` under `tr_setup.dilate_label` (absent: `{where: host,
+radius: 5}`, the reference's ball, `dilate_device.py`); `ingest` (absent: `{where: host}`: where the float32 conversion, the dtype
+scaling and the channels-last transpose run, `ingest_device.py`) and `patch_search` (absent: `{where: host}`: where the
+constructor's valid-patch search runs, `patch_search_device.py`; no device is an error, not a fallback) -- are parsed and checked
+against each other by ONE call, `stages.parse_stages`; both datasets expose what it returns as `geometric`, `spatial`, ... and
+`device_spatial`, ... (the block if it says `where: device`, else None).  `where: host` stages run inside `__getitem__`; `where:
+device` ones leave the items alone (`ingest`: hands out `torch.from_numpy` of the raw slices, and `device_ingest` is {key: rule})
+and are the trainer's business.  The ORDER of the stages, on either side, is stated once: `stages.DevicePipeline`'s docstring."""
 import json
 import os
 import warnings
@@ -63,20 +47,13 @@ class SyntheticPatchDataset(Dataset):
         self.seed = seed
         self.pool = int(mgr.dataset_config.get("synthetic_pool", 16))
         self._cache = {}
-        from .geometry_device import parse_geometric
-        self.geometric = parse_geometric(mgr.dataset_config, self.patch, self.tasks)
+        from .stages import parse_stages
+        vars(self).update(parse_stages(mgr.dataset_config, self.patch, self.tasks).attributes())
         if self.geometric is not None and self.geometric["where"] != "device":
             raise ValueError("dataset_config.geometric.where: \"host\" is served by the zarr dataset; synthetic patches take \"device\"")
-        # dataset_config.spatial: "device" is the trainer's business (`device_spatial`); "host" resamples every item handed out,
-        # one draw per item from `spatial_rng` (None: the `random` module, which a DataLoader seeds per worker)
-        from .spatial_device import parse_spatial
-        self.spatial = parse_spatial(mgr.dataset_config, self.patch, self.tasks)
-        self.device_spatial = self.spatial if self.spatial is not None and self.spatial["where"] == "device" else None
+        # `where: host` resamples every item handed out, one draw per item from `spatial_rng` / `elastic_rng` (None: the `random`
+        # module, which a DataLoader seeds per worker)
         self.spatial_rng, self.last_spatial_op = None, None
-        # dataset_config.elastic: the same two places ("host": one field per item from `elastic_rng`, after the spatial stage)
-        from .elastic_device import parse_elastic
-        self.elastic = parse_elastic(mgr.dataset_config, self.patch, self.tasks)
-        self.device_elastic = self.elastic if self.elastic is not None and self.elastic["where"] == "device" else None
         self.elastic_rng, self.last_elastic_field = None, None
 
     def __len__(self):
@@ -214,36 +191,15 @@ class ZarrSegmentationDataset3D(Dataset):
                           "(dataloading/augment.py: same structure and probabilities, the members' default parameters as "
                           "documented; not compared with albumentations).  Set dataset_config.augment: \"restated\" to "
                           "acknowledge, or false to feed raw patches.", RuntimeWarning, stacklevel=2)
-        # dataset_config.geometric: parsed and checked here; "device" is the trainer's business (`geometric` is what it reads)
-        from .geometry_device import host_transforms, parse_geometric
-        self.geometric = parse_geometric(getattr(mgr, "dataset_config", {}), self.patch_size, self.tasks)
-        self._host_geometry = (host_transforms(self.geometric)
-                               if self.geometric is not None and self.geometric["where"] == "host" else [])
-        # dataset_config.dilate under tr_setup.dilate_label: "host" dilates in __getitem__, "device" is the trainer's business
-        from .dilate_device import parse_dilate
-        self.dilate = parse_dilate(getattr(mgr, "dataset_config", {}), self.dilate_label, self.tasks)
-        self.device_dilate = self.dilate if self.dilate is not None and self.dilate["where"] == "device" else None
-        # dataset_config.patch_search: where the valid-patch search below runs (the list and the cache file are the same)
-        from .patch_search_device import find_valid_patches_device, parse_patch_search
-        self.patch_search = parse_patch_search(getattr(mgr, "dataset_config", {}))
-        # dataset_config.ingest: "device" hands out what the store holds; the scaling is the trainer's business (`device_ingest`)
-        from .ingest_device import check_host_stages, parse_ingest
-        self.ingest = parse_ingest(getattr(mgr, "dataset_config", {}))
-        self.device_ingest = None
-        if self.ingest["where"] == "device":
-            check_host_stages(self.augment, self.geometric, self.dilate)
-        # dataset_config.spatial: "device" is the trainer's business (`device_spatial`); "host" resamples in __getitem__ and needs
-        # scaled float items with their labels already dilated
-        from .spatial_device import check_host_spatial, parse_spatial
-        self.spatial = parse_spatial(getattr(mgr, "dataset_config", {}), self.patch_size, self.tasks)
-        check_host_spatial(self.spatial, self.ingest, self.dilate)
-        self.device_spatial = self.spatial if self.spatial is not None and self.spatial["where"] == "device" else None
+        # the stage blocks, parsed and checked against each other; "device" stages are the trainer's business
+        from .geometry_device import host_transforms
+        from .patch_search_device import find_valid_patches_device
+        from .stages import parse_stages
+        vars(self).update(parse_stages(getattr(mgr, "dataset_config", {}), self.patch_size, self.tasks, self.dilate_label,
+                                       self.augment).attributes())
+        self._host_geometry = host_transforms(self.geometric) if self.geometric is not None and self.geometric["where"] == "host" else []
+        self.device_ingest = None          # {key: rule} once the stores are known (`_ingest_rules`)
         self.spatial_rng, self.last_spatial_op = None, None
-        # dataset_config.elastic: as spatial ("host" needs scaled float items with their labels already dilated)
-        from .elastic_device import check_host_elastic, parse_elastic
-        self.elastic = parse_elastic(getattr(mgr, "dataset_config", {}), self.patch_size, self.tasks)
-        check_host_elastic(self.elastic, self.ingest, self.dilate)
-        self.device_elastic = self.elastic if self.elastic is not None and self.elastic["where"] == "device" else None
         self.elastic_rng, self.last_elastic_field = None, None
         self.volumes = []
         for vol_idx, info in enumerate(self.volume_paths):

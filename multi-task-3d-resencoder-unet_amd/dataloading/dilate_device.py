@@ -17,6 +17,8 @@ from math import isqrt
 
 import numpy as np
 
+from . import stages
+
 MAX_RADIUS = 8
 
 
@@ -86,19 +88,9 @@ def parse_dilate(dataset_config, dilate_label, tasks):
     that is neither host nor device and a radius that is not an integer in 1..8 raise with the key named."""
     if not dilate_label:
         return None
-    d = (dataset_config or {}).get("dilate", None)
-    if d is None:
-        d = {}
-    if not isinstance(d, dict):
-        raise ValueError(f"dataset_config.dilate: expected a mapping (where, radius), got {d!r}")
-    unknown = set(d) - {"where", "radius"}
-    if unknown:
-        raise ValueError(f"dataset_config.dilate: unknown key(s) {sorted(str(k) for k in unknown)} (known: where, radius)")
-    where = d.get("where", "host")
-    if not isinstance(where, str) or where.lower() not in ("host", "device"):
-        raise ValueError(f"dataset_config.dilate.where: {where!r} (\"host\" or \"device\")")
+    d = stages.block(dataset_config, "dilate", ("where", "radius"), "host", {})
     radius = _check_radius("dataset_config.dilate.radius", d.get("radius", 5))
-    return {"radius": radius, "where": where.lower(), "keys": dilate_keys(tasks)}
+    return {"radius": radius, "where": d["where"], "keys": dilate_keys(tasks)}
 
 
 class DeviceDilate:
@@ -117,9 +109,6 @@ class DeviceDilate:
             if k not in batch:
                 raise RxError(f"DeviceDilate: the batch has no {k!r} (it has {sorted(batch)})")
             t = batch[k]
-            if not hasattr(t, "is_cuda") or not t.is_cuda:
-                raise RxError(f"DeviceDilate: {k!r} must be a device tensor (dataset_config.dilate.where: host dilates in the dataset)")
-            if t.dim() not in (4, 5):
-                raise RxError(f"DeviceDilate: {k!r} {tuple(t.shape)}: expected (B, C, Z, Y, X) or (B, Z, Y, X)")
+            stages.check_tensor("DeviceDilate", k, t, "dataset_config.dilate.where: host dilates in the dataset")
             E.label_dilate(t if t.dim() == 5 else t.unsqueeze(1), self.radius)
         return batch

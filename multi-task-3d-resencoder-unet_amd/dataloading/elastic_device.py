@@ -16,11 +16,10 @@ normal stays exactly zero.  For a field that equals a linear map this is `spatia
 
 `DeviceElastic` draws one field per sample of a batch and applies it to the image (trilinear) and to every target (nearest) on
 the current stream (csrc/rx_elastic.hip: rx_elastic_apply)."""
-import random as _random
-
 import numpy as np
 
-from .spatial_device import BORDER, INTERP, MAX_EXTENT, sample_numpy
+from . import stages
+from .spatial_device import BORDER, INTERP, sample_numpy      # noqa: F401
 
 MIN_SPACING = 8          # the kernel's LDS lines are sized for it: 64 voxels touch at most 12 node columns
 
@@ -162,19 +161,8 @@ def elastic_numpy(field, arr, interp, border, fill=0.0, is_normal=False):
 
     Nodes of any finite size are served: a coordinate beyond the int range counts as outside; a NaN coordinate yields an unspecified
     value and never an access outside the array."""
-    if interp not in INTERP:
-        raise ValueError(f"elastic_numpy: interp {interp!r} (linear or nearest)")
-    if border not in BORDER:
-        raise ValueError(f"elastic_numpy: border {border!r} (constant or clamp)")
-    arr = np.asarray(arr)
-    a = arr[None] if arr.ndim == 3 else arr
-    if a.ndim != 4 or a.dtype != np.float32:
-        raise ValueError(f"elastic_numpy: expected float32 (Z, Y, X) or (C, Z, Y, X), got {arr.dtype} {arr.shape}")
-    if is_normal and a.shape[0] != 3:
-        raise ValueError(f"elastic_numpy: a normals array has 3 components, got {a.shape[0]}")
+    arr, a = stages.check_resample_args("elastic_numpy", arr, interp, border, is_normal)
     n = a.shape[1:]
-    if max(n) > MAX_EXTENT:
-        raise ValueError(f"elastic_numpy: an extent of {n} is beyond {MAX_EXTENT} (float32 coordinates)")
     f32 = np.float32
     D, E = displacement_numpy(field, n)
     shp = [(-1, 1, 1), (1, -1, 1), (1, 1, -1)]
@@ -183,28 +171,12 @@ def elastic_numpy(field, arr, interp, border, fill=0.0, is_normal=False):
         s = sample_numpy(a, p, interp, border, fill)
         if is_normal:
             s = vector_rule_numpy(s, E)
-    out = np.ascontiguousarray(s, dtype=f32)
-    if np.shares_memory(out, arr):
-        out = out.copy()
-    return out[0] if arr.ndim == 3 else out
+    return stages.finish_resample(s, arr)
 
 
 def apply_item_numpy(field, item, normal_keys=("normals",), image_border="constant", image_fill=0.0):
-    """the host path: `field` on every array of a dataset item -- `image` linear with the image border rule, every target nearest /
-    constant / fill 0, the arrays named in `normal_keys` with the vector rule.  Torch tensors come back as torch tensors."""
-    out = {}
-    for k, v in item.items():
-        is_t = hasattr(v, "numpy")
-        x = np.ascontiguousarray(v.numpy() if is_t else v, dtype=np.float32)
-        if k == "image":
-            y = elastic_numpy(field, x, "linear", image_border, image_fill)
-        else:
-            y = elastic_numpy(field, x, "nearest", "constant", 0.0, k in normal_keys)
-        if is_t:
-            import torch
-            y = torch.from_numpy(y)
-        out[k] = y
-    return out
+    """the host path: `field` on every array of a dataset item, under the rules of `stages.apply_item`"""
+    return stages.apply_item(item, normal_keys, image_border, image_fill, lambda *a: elastic_numpy(field, *a))
 
 
 def draw_elastic(rng, shape, spacing, magnitude=(0.0, 4.0), p=0.3):
@@ -233,18 +205,14 @@ class DeviceElastic:
 
     def __init__(self, spacing=32, magnitude=(0.0, 4.0), p=0.3, normal_keys=("normals",), image_border="constant", image_fill=0.0,
                  seed=None, rank=0):
-        import torch
         self.spacing = _spacing("DeviceElastic", spacing)
         self.magnitude = check_magnitude("DeviceElastic", magnitude, self.spacing)
-        self.p = float(p)
-        if not 0.0 <= self.p <= 1.0:
-            raise ValueError(f"DeviceElastic.p: {p!r} is not a probability")
+        self.p = stages.probability("DeviceElastic", "p", p)
         if image_border not in BORDER:
             raise ValueError(f"DeviceElastic.image_border: {image_border!r} (constant or clamp)")
         self.normal_keys = set(normal_keys)
         self.image_border, self.image_fill = image_border, float(image_fill)
-        seed = torch.initial_seed() if seed is None else int(seed)
-        self.rng = _random.Random((seed % (1 << 63)) * 4096 + int(rank) % 4096)
+        self.rng = stages.stage_rng(seed, rank)
         self.last_fields = None
 
     def draw(self, shape):
@@ -253,40 +221,18 @@ class DeviceElastic:
     def __call__(self, batch, fields=None):
         from ..engine import ops as E
         from ..engine.lib import RxError
-        first = next(iter(batch.values()))
-        B = int(first.shape[0])
-        shape = None
+        B, shape = stages.check_batch("DeviceElastic", batch, self.normal_keys, "the host path is elastic_device.elastic_numpy")
         for k, t in batch.items():
-            if not hasattr(t, "is_cuda") or not t.is_cuda:
-                raise RxError(f"DeviceElastic: {k!r} must be a device tensor (the host path is elastic_device.elastic_numpy)")
-            if t.dim() not in (4, 5) or int(t.shape[0]) != B:
-                raise RxError(f"DeviceElastic: {k!r} {tuple(t.shape)}: expected (B, C, Z, Y, X) or (B, Z, Y, X) with B = {B}")
-            if k in self.normal_keys and (t.dim() != 5 or int(t.shape[1]) != 3):
-                raise RxError(f"DeviceElastic: {k!r} {tuple(t.shape)} is in normal_keys and must be (B, 3, Z, Y, X)")
-            if shape is None:
-                shape = tuple(int(v) for v in t.shape[-3:])
-            elif tuple(int(v) for v in t.shape[-3:]) != shape:
+            if tuple(int(v) for v in t.shape[-3:]) != shape:
                 raise RxError(f"DeviceElastic: {k!r} {tuple(t.shape)}: every tensor of a batch has the extents {shape}")
-        if fields is None:
-            fields = [self.draw(shape) for _ in range(B)]
-        fields = list(fields)
-        if len(fields) != B:
-            raise ValueError(f"DeviceElastic: {len(fields)} fields for a batch of {B}")
-        self.last_fields = fields
+        self.last_fields = fields = stages.batch_draws("DeviceElastic", "fields", fields, B, lambda: self.draw(shape))
         if all(f.is_identity() for f in fields):
             return batch
         spacing = fields[0].spacing
         nodes = E.elastic_nodes(fields)
-        tables = E.elastic_tables(shape, spacing, first.device)
-        out = {}
-        for k, t in batch.items():
-            five = t if t.dim() == 5 else t.unsqueeze(1)
-            if k == "image":
-                r = E.elastic_apply(five, nodes, tables, spacing, "linear", self.image_border, self.image_fill)
-            else:
-                r = E.elastic_apply(five, nodes, tables, spacing, "nearest", "constant", 0.0, vector=k in self.normal_keys)
-            out[k] = r if t.dim() == 5 else r.squeeze(1)
-        return out
+        tables = E.elastic_tables(shape, spacing, next(iter(batch.values())).device)
+        return stages.resample_batch(batch, self.normal_keys, self.image_border, self.image_fill,
+                                     lambda five, *mode, **kw: E.elastic_apply(five, nodes, tables, spacing, *mode, **kw))
 
 
 # ---- dataset_config.elastic ---------------------------------------------------------------------------------------------------------
@@ -311,53 +257,12 @@ def parse_elastic(dataset_config, patch_size, tasks):
     """`dataset_config.elastic` -> None (absent / false) or {"spacing": (sz, sy, sx), "magnitude": (lo, hi), "p": float,
     "normal_keys": tuple, "image_border": "constant" | "clamp", "where": "device" | "host"}.  Everything that would otherwise fail
     at some later step fails here, with the key named."""
-    g = (dataset_config or {}).get("elastic", None)
-    if g is None or g is False:
+    g = stages.block(dataset_config, "elastic", ("spacing", "magnitude", "p", "normal_keys", "image_border", "where"), "device", None)
+    if g is None:
         return None
-    if g is True:
-        g = {}
-    if not isinstance(g, dict):
-        raise ValueError(f"dataset_config.elastic: expected a mapping (spacing, magnitude, p, normal_keys, image_border, where), got {g!r}")
-    known = ("spacing", "magnitude", "p", "normal_keys", "image_border", "where")
-    unknown = set(g) - set(known)
-    if unknown:
-        raise ValueError(f"dataset_config.elastic: unknown key(s) {sorted(unknown)} (known: {', '.join(known)})")
-    where = str(g.get("where", "device")).lower()
-    if where not in ("device", "host"):
-        raise ValueError(f"dataset_config.elastic.where: {g.get('where')!r} (\"device\" or \"host\")")
-    patch = tuple(int(v) for v in patch_size)
-    if len(patch) != 3:
-        raise ValueError(f"dataset_config.elastic: needs a 3-D patch, patch_size is {list(patch)}")
-    border = str(g.get("image_border", "constant")).lower()
-    if border not in BORDER:
-        raise ValueError(f"dataset_config.elastic.image_border: {g.get('image_border')!r} (\"constant\" or \"clamp\")")
+    stages.patch3d("dataset_config.elastic", patch_size)
     spacing = _spacing("dataset_config.elastic", g.get("spacing", 32))
-    magnitude = check_magnitude("dataset_config.elastic", g.get("magnitude", (0.0, 4.0)), spacing)
-    try:
-        p = float(g.get("p", 0.3))
-    except (TypeError, ValueError):
-        p = -1.0
-    if not 0.0 <= p <= 1.0:
-        raise ValueError(f"dataset_config.elastic.p: {g.get('p')!r} is not a probability")
-    out = {"spacing": spacing, "magnitude": magnitude, "p": p, "image_border": border, "where": where}
-    nk = g.get("normal_keys", ("normals",))
-    if isinstance(nk, str):
-        nk = (nk,)
-    out["normal_keys"] = tuple(str(k) for k in nk)
-    for k in out["normal_keys"]:
-        if k in (tasks or {}) and int(tasks[k].get("channels", 0)) != 3:
-            raise ValueError(f"dataset_config.elastic.normal_keys: task {k!r} has channels = {tasks[k].get('channels')}, "
-                             "a normals target has 3")
-    return out
-
-
-def check_host_elastic(cfg, ingest, dilate):
-    """`where: host` resamples scaled float items inside `__getitem__`: refused where an earlier stage runs on the device"""
-    if cfg is None or cfg["where"] != "host":
-        return
-    if ingest is not None and ingest.get("where") == "device":
-        raise ValueError("dataset_config.elastic.where: \"host\" cannot follow dataset_config.ingest.where: \"device\" (the items are "
-                         "the store's integers); take elastic.where: \"device\"")
-    if dilate is not None and dilate.get("where") == "device":
-        raise ValueError("dataset_config.elastic.where: \"host\" cannot precede dataset_config.dilate.where: \"device\" (the ball is "
-                         "not deformation-invariant: dilation comes first); take elastic.where: \"device\" or dilate.where: \"host\"")
+    return {"spacing": spacing, "magnitude": check_magnitude("dataset_config.elastic", g.get("magnitude", (0.0, 4.0)), spacing),
+            "p": stages.probability("dataset_config.elastic", "p", g.get("p", 0.3)),
+            "image_border": stages.image_border("dataset_config.elastic", g), "where": g["where"],
+            "normal_keys": stages.normal_keys("dataset_config.elastic", g, tasks)}

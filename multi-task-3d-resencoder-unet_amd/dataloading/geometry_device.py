@@ -14,10 +14,11 @@ Negation is IEEE negation: an exact zero becomes -0.0, as the reference's `*= -1
 
 `DeviceGeometry` draws one composed op per sample of a batch (flip, then rot90) and applies it to the image and to every target
 on the current stream."""
-import random as _random
 from dataclasses import dataclass
 
 import numpy as np
+
+from . import stages
 
 AXIS_OF = {"z": 0, "y": 1, "x": 2}
 # rotation about an axis turns the plane of the other two: np.rot90(arr, k, axes=PLANE[axis]) on a (Z, Y, X) volume
@@ -159,12 +160,10 @@ class DeviceGeometry:
     `DeviceAugmenter`'s is: ranks differ, a seeded run repeats.  `last_ops` keeps the draws of the last call."""
 
     def __init__(self, flip=None, rot90=None, normal_keys=("normals",), seed=None, rank=0):
-        import torch
         self.flip = check_transform_kwargs("DeviceGeometry", "flip", flip)
         self.rot90 = check_transform_kwargs("DeviceGeometry", "rot90", rot90)
         self.normal_keys = set(normal_keys)
-        seed = torch.initial_seed() if seed is None else int(seed)
-        self.rng = _random.Random((seed % (1 << 63)) * 4096 + int(rank) % 4096)
+        self.rng = stages.stage_rng(seed, rank)
         self.last_ops = None
 
     def draw(self):
@@ -177,21 +176,8 @@ class DeviceGeometry:
 
     def __call__(self, batch, ops=None):
         from ..engine import ops as E
-        from ..engine.lib import RxError
-        first = next(iter(batch.values()))
-        B = int(first.shape[0])
-        for k, t in batch.items():
-            if not hasattr(t, "is_cuda") or not t.is_cuda:
-                raise RxError(f"DeviceGeometry: {k!r} must be a device tensor (the host classes are training/transforms/geometric)")
-            if t.dim() not in (4, 5) or int(t.shape[0]) != B:
-                raise RxError(f"DeviceGeometry: {k!r} {tuple(t.shape)}: expected (B, C, Z, Y, X) or (B, Z, Y, X) with B = {B}")
-            if k in self.normal_keys and (t.dim() != 5 or int(t.shape[1]) != 3):
-                raise RxError(f"DeviceGeometry: {k!r} {tuple(t.shape)} is in normal_keys and must be (B, 3, Z, Y, X)")
-        if ops is None:
-            ops = [self.draw() for _ in range(B)]
-        ops = list(ops)
-        if len(ops) != B:
-            raise ValueError(f"DeviceGeometry: {len(ops)} ops for a batch of {B}")
+        B, _ = stages.check_batch("DeviceGeometry", batch, self.normal_keys, "the host classes are training/transforms/geometric")
+        ops = stages.batch_draws("DeviceGeometry", "ops", ops, B, self.draw)
         for k, t in batch.items():
             for i, op in enumerate(ops):
                 if not op.preserves(t.shape):
@@ -201,12 +187,7 @@ class DeviceGeometry:
         if all(op.is_identity() for op in ops):
             return batch
         table = E.geom_table(ops)
-        out = {}
-        for k, t in batch.items():
-            five = t if t.dim() == 5 else t.unsqueeze(1)
-            r = E.geom_apply(five, table, k in self.normal_keys)
-            out[k] = r if t.dim() == 5 else r.squeeze(1)
-        return out
+        return stages.per_tensor(batch, lambda k, five: E.geom_apply(five, table, k in self.normal_keys))
 
 
 # ---- dataset_config.geometric -------------------------------------------------------------------------------------------------------
@@ -230,34 +211,19 @@ def check_transform_kwargs(owner, name, kw):
                 raise ValueError(f"{owner}.{name}.axes: {list(axes)} (a non-empty choice of x, y, z)")
             out[k] = axes
         else:
-            if not 0.0 <= float(v) <= 1.0:
-                raise ValueError(f"{owner}.{name}.{k}: {v!r} is not a probability")
-            out[k] = float(v)
+            out[k] = stages.probability(f"{owner}.{name}", k, v)
     return out
 
 
 def parse_geometric(dataset_config, patch_size, tasks):
     """`dataset_config.geometric` -> None (absent / false) or {"flip": kwargs | None, "rot90": kwargs | None, "normal_keys": tuple,
     "where": "device" | "host"}.  Everything that would otherwise fail at some later step fails here, with the key named."""
-    g = (dataset_config or {}).get("geometric", None)
-    if g is None or g is False:
+    g = stages.block(dataset_config, "geometric", ("flip", "rot90", "normal_keys", "where"), "device", None)
+    if g is None:
         return None
-    if g is True:
-        g = {}
-    if not isinstance(g, dict):
-        raise ValueError(f"dataset_config.geometric: expected a mapping (flip, rot90, normal_keys, where), got {g!r}")
-    unknown = set(g) - {"flip", "rot90", "normal_keys", "where"}
-    if unknown:
-        raise ValueError(f"dataset_config.geometric: unknown key(s) {sorted(unknown)} (known: flip, rot90, normal_keys, where)")
-    where = str(g.get("where", "device")).lower()
-    if where not in ("device", "host"):
-        raise ValueError(f"dataset_config.geometric.where: {g.get('where')!r} (\"device\" or \"host\")")
-    patch = tuple(int(v) for v in patch_size)
-    if len(patch) != 3:
-        raise ValueError(f"dataset_config.geometric: needs a 3-D patch, patch_size is {list(patch)}")
-    out = {"flip": None, "rot90": None, "where": where}
-    for name in ("flip", "rot90"):
-        out[name] = check_transform_kwargs("dataset_config.geometric", name, g.get(name, None))
+    patch = stages.patch3d("dataset_config.geometric", patch_size)
+    out = {name: check_transform_kwargs("dataset_config.geometric", name, g.get(name, None)) for name in ("flip", "rot90")}
+    out["where"] = g["where"]
     if out["rot90"] is not None:
         allowed = allowed_rot90_axes(patch)
         axes = out["rot90"].get("axes", ("x", "y", "z"))
@@ -266,14 +232,7 @@ def parse_geometric(dataset_config, patch_size, tasks):
             raise ValueError(f"dataset_config.geometric.rot90.axes: a rotation about {wrong} turns a plane of unequal extents of "
                              f"the patch {list(patch)} and would change its shape; axes this patch allows: {list(allowed)}")
         out["rot90"]["axes"] = axes
-    nk = g.get("normal_keys", ("normals",))
-    if isinstance(nk, str):
-        nk = (nk,)
-    out["normal_keys"] = tuple(str(k) for k in nk)
-    for k in out["normal_keys"]:
-        if k in (tasks or {}) and int(tasks[k].get("channels", 0)) != 3:
-            raise ValueError(f"dataset_config.geometric.normal_keys: task {k!r} has channels = {tasks[k].get('channels')}, "
-                             "a normals target has 3")
+    out["normal_keys"] = stages.normal_keys("dataset_config.geometric", g, tasks)
     return out
 
 

@@ -18,6 +18,7 @@ the trainer puts behind the feeder's copies for `where: device`, before dilation
 import numpy as np
 
 from ..engine.ops.core import RULES, rule_code      # noqa: F401 -- the library's codes (index == rx_ingest_rule), beside its binding
+from . import stages
 
 DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float32))
 MAX_CHANNELS = 8
@@ -58,33 +59,7 @@ def ingest_numpy(arr, rule):
 def parse_ingest(dataset_config):
     """`dataset_config.ingest` -> {"where": "host" | "device"}.  Absent: {where: host}.  Unknown keys and a `where` that is
     neither host nor device raise with the key named."""
-    d = (dataset_config or {}).get("ingest", None)
-    if d is None:
-        d = {}
-    if not isinstance(d, dict):
-        raise ValueError(f"dataset_config.ingest: expected a mapping (where), got {d!r}")
-    unknown = set(d) - {"where"}
-    if unknown:
-        raise ValueError(f"dataset_config.ingest: unknown key(s) {sorted(str(k) for k in unknown)} (known: where)")
-    where = d.get("where", "host")
-    if not isinstance(where, str) or where.lower() not in ("host", "device"):
-        raise ValueError(f"dataset_config.ingest.where: {where!r} (\"host\" or \"device\")")
-    return {"where": where.lower()}
-
-
-def check_host_stages(host_augment, geometric, dilate):
-    """device ingest hands out integers, so every host stage that works on scaled floats must be off or on the device as well:
-    `host_augment` (the dataset applies the restated stack), `geometric` and `dilate` as `parse_geometric` / `parse_dilate`
-    return them.  Raises ValueError naming the offending key."""
-    if host_augment:
-        raise ValueError("dataset_config.augment: the restated stack runs on the host, on scaled floats; "
-                         "dataset_config.ingest.where: device needs augment: \"device\" or false")
-    if geometric is not None and geometric["where"] != "device":
-        raise ValueError("dataset_config.geometric.where: the host transforms work on scaled floats; "
-                         "dataset_config.ingest.where: device needs geometric absent or where: device")
-    if dilate is not None and dilate["where"] != "device":
-        raise ValueError("dataset_config.dilate.where: the host dilation (the default under tr_setup.dilate_label) works on scaled "
-                         "floats; dataset_config.ingest.where: device needs dilate.where: device or dilate_label off")
+    return {"where": stages.block(dataset_config, "ingest", ("where",), "host", {})["where"]}
 
 
 class DeviceIngest:
@@ -108,10 +83,8 @@ class DeviceIngest:
                     raise RxError(f"DeviceIngest: {k!r} is {getattr(t, 'dtype', type(t))} and has no rule (rules: {sorted(self.rules)})")
                 out[k] = t
                 continue
-            if not hasattr(t, "is_cuda") or not t.is_cuda:
-                raise RxError(f"DeviceIngest: {k!r} must be a device tensor (dataset_config.ingest.where: host scales in the dataset)")
-            if t.dim() not in (4, 5):
-                raise RxError(f"DeviceIngest: {k!r} {tuple(t.shape)}: expected (B, Z, Y, X) or (B, Z, Y, X, C)")
+            stages.check_tensor("DeviceIngest", k, t, "dataset_config.ingest.where: host scales in the dataset",
+                                "(B, Z, Y, X) or (B, Z, Y, X, C)")
             r = E.ingest(t, rule)
             out[k] = r[:, 0] if t.dim() == 4 and k.lower() == "normals" else r
         for k in self.rules:

@@ -17,6 +17,8 @@ import time
 
 import numpy as np
 
+from . import stages
+
 BUDGET_FRACTION = 0.5      # max_device_bytes=None: this share of the device's free bytes
 MAX_BOXES_PER_CALL = 1 << 20
 DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float32))
@@ -70,23 +72,13 @@ def parse_patch_search(dataset_config):
     """`dataset_config.patch_search` -> {"where": "host" | "device", "max_device_bytes": None | int}.  An absent block is
     {where: host}.  Unknown keys, a `where` that is neither host nor device and a `max_device_gb` that is not a positive number
     raise with the key named."""
-    d = (dataset_config or {}).get("patch_search", None)
-    if d is None:
-        d = {}
-    if not isinstance(d, dict):
-        raise ValueError(f"dataset_config.patch_search: expected a mapping (where, max_device_gb), got {d!r}")
-    unknown = set(d) - {"where", "max_device_gb"}
-    if unknown:
-        raise ValueError(f"dataset_config.patch_search: unknown key(s) {sorted(str(k) for k in unknown)} (known: where, max_device_gb)")
-    where = d.get("where", "host")
-    if not isinstance(where, str) or where.lower() not in ("host", "device"):
-        raise ValueError(f"dataset_config.patch_search.where: {where!r} (\"host\" or \"device\")")
+    d = stages.block(dataset_config, "patch_search", ("where", "max_device_gb"), "host", {})
     gb = d.get("max_device_gb", None)
     if gb is not None:
         if isinstance(gb, bool) or not isinstance(gb, (int, float, np.integer, np.floating)) or not float(gb) > 0 or not np.isfinite(gb):
             raise ValueError(f"dataset_config.patch_search.max_device_gb: {gb!r} (a positive number of GiB)")
         gb = int(float(gb) * (1 << 30))
-    return {"where": where.lower(), "max_device_bytes": gb}
+    return {"where": d["where"], "max_device_bytes": gb}
 
 
 def _pieces(arr, z0, z1, y0, y1):

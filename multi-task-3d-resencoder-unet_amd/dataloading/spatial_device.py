@@ -16,15 +16,14 @@ float32 operation at a time; it is the oracle of the GPU tests and it IS the hos
 `DeviceSpatial` draws one op per sample of a batch (rotation, then scale) and applies it to the image (trilinear) and to every
 target (nearest: a dilated label stays binary, a normals target stays exactly zero off the sheet) on the current stream."""
 import math
-import random as _random
 from dataclasses import dataclass
 
 import numpy as np
 
 from ..engine.ops.core import BORDER, INTERP      # noqa: F401 -- the library's codes, kept beside its binding
+from . import stages
 from .geometry_device import AXIS_OF
-
-MAX_EXTENT = 1 << 24      # float32 holds every voxel index below this exactly
+from .stages import MAX_EXTENT      # noqa: F401
 
 
 def _matrix(owner, name, value):
@@ -208,19 +207,8 @@ def affine_numpy(op, arr, interp, border, fill=0.0, is_normal=False):
 
     A coordinate beyond the int range (a huge matrix entry) counts as outside; one that overflowed to NaN yields an unspecified
     value and never an access outside the array."""
-    if interp not in INTERP:
-        raise ValueError(f"affine_numpy: interp {interp!r} (linear or nearest)")
-    if border not in BORDER:
-        raise ValueError(f"affine_numpy: border {border!r} (constant or clamp)")
-    arr = np.asarray(arr)
-    a = arr[None] if arr.ndim == 3 else arr
-    if a.ndim != 4 or a.dtype != np.float32:
-        raise ValueError(f"affine_numpy: expected float32 (Z, Y, X) or (C, Z, Y, X), got {arr.dtype} {arr.shape}")
-    if is_normal and a.shape[0] != 3:
-        raise ValueError(f"affine_numpy: a normals array has 3 components, got {a.shape[0]}")
+    arr, a = stages.check_resample_args("affine_numpy", arr, interp, border, is_normal)
     n = a.shape[1:]
-    if max(n) > MAX_EXTENT:
-        raise ValueError(f"affine_numpy: an extent of {n} is beyond {MAX_EXTENT} (float32 coordinates)")
     f32 = np.float32
     m = op.point
     c = [f32(n[d] - 1) * f32(0.5) for d in range(3)]
@@ -232,28 +220,12 @@ def affine_numpy(op, arr, interp, border, fill=0.0, is_normal=False):
         if is_normal:
             v = op.vector
             s = np.stack([(v[k, 0] * s[0] + v[k, 1] * s[1]) + v[k, 2] * s[2] for k in range(3)])
-    out = np.ascontiguousarray(s, dtype=f32)
-    if np.shares_memory(out, arr):
-        out = out.copy()
-    return out[0] if arr.ndim == 3 else out
+    return stages.finish_resample(s, arr)
 
 
 def apply_item_numpy(op, item, normal_keys=("normals",), image_border="constant", image_fill=0.0):
-    """the host path: `op` on every array of a dataset item -- `image` linear with the image border rule, every target nearest /
-    constant / fill 0, the arrays named in `normal_keys` with the vector rule.  Torch tensors come back as torch tensors."""
-    out = {}
-    for k, v in item.items():
-        is_t = hasattr(v, "numpy")
-        x = np.ascontiguousarray(v.numpy() if is_t else v, dtype=np.float32)
-        if k == "image":
-            y = affine_numpy(op, x, "linear", image_border, image_fill)
-        else:
-            y = affine_numpy(op, x, "nearest", "constant", 0.0, k in normal_keys)
-        if is_t:
-            import torch
-            y = torch.from_numpy(y)
-        out[k] = y
-    return out
+    """the host path: `op` on every array of a dataset item, under the rules of `stages.apply_item`"""
+    return stages.apply_item(item, normal_keys, image_border, image_fill, lambda *a: affine_numpy(op, *a))
 
 
 class DeviceSpatial:
@@ -266,15 +238,13 @@ class DeviceSpatial:
     all the identity is handed back untouched."""
 
     def __init__(self, rotation=None, scale=None, normal_keys=("normals",), image_border="constant", image_fill=0.0, seed=None, rank=0):
-        import torch
         self.rotation = check_rotation("DeviceSpatial", rotation)
         self.scale = check_scale("DeviceSpatial", scale)
         if image_border not in BORDER:
             raise ValueError(f"DeviceSpatial.image_border: {image_border!r} (constant or clamp)")
         self.normal_keys = set(normal_keys)
         self.image_border, self.image_fill = image_border, float(image_fill)
-        seed = torch.initial_seed() if seed is None else int(seed)
-        self.rng = _random.Random((seed % (1 << 63)) * 4096 + int(rank) % 4096)
+        self.rng = stages.stage_rng(seed, rank)
         self.last_ops = None
 
     def draw(self):
@@ -282,34 +252,13 @@ class DeviceSpatial:
 
     def __call__(self, batch, ops=None):
         from ..engine import ops as E
-        from ..engine.lib import RxError
-        first = next(iter(batch.values()))
-        B = int(first.shape[0])
-        for k, t in batch.items():
-            if not hasattr(t, "is_cuda") or not t.is_cuda:
-                raise RxError(f"DeviceSpatial: {k!r} must be a device tensor (the host path is spatial_device.affine_numpy)")
-            if t.dim() not in (4, 5) or int(t.shape[0]) != B:
-                raise RxError(f"DeviceSpatial: {k!r} {tuple(t.shape)}: expected (B, C, Z, Y, X) or (B, Z, Y, X) with B = {B}")
-            if k in self.normal_keys and (t.dim() != 5 or int(t.shape[1]) != 3):
-                raise RxError(f"DeviceSpatial: {k!r} {tuple(t.shape)} is in normal_keys and must be (B, 3, Z, Y, X)")
-        if ops is None:
-            ops = [self.draw() for _ in range(B)]
-        ops = list(ops)
-        if len(ops) != B:
-            raise ValueError(f"DeviceSpatial: {len(ops)} ops for a batch of {B}")
-        self.last_ops = ops
+        B, _ = stages.check_batch("DeviceSpatial", batch, self.normal_keys, "the host path is spatial_device.affine_numpy")
+        self.last_ops = ops = stages.batch_draws("DeviceSpatial", "ops", ops, B, self.draw)
         if all(op.is_identity() for op in ops):
             return batch
         table = E.affine_table(ops)
-        out = {}
-        for k, t in batch.items():
-            five = t if t.dim() == 5 else t.unsqueeze(1)
-            if k == "image":
-                r = E.affine_apply(five, table, "linear", self.image_border, self.image_fill)
-            else:
-                r = E.affine_apply(five, table, "nearest", "constant", 0.0, vector=k in self.normal_keys)
-            out[k] = r if t.dim() == 5 else r.squeeze(1)
-        return out
+        return stages.resample_batch(batch, self.normal_keys, self.image_border, self.image_fill,
+                                     lambda five, *mode, **kw: E.affine_apply(five, table, *mode, **kw))
 
 
 # ---- dataset_config.spatial ---------------------------------------------------------------------------------------------------------
@@ -329,10 +278,7 @@ def check_rotation(owner, kw):
     deg = float(kw.get("max_degrees", 30.0))
     if not 0.0 < deg <= 180.0:
         raise ValueError(f"{owner}.rotation.max_degrees: {kw.get('max_degrees')!r} is outside (0, 180]")
-    p = float(kw.get("p", 0.5))
-    if not 0.0 <= p <= 1.0:
-        raise ValueError(f"{owner}.rotation.p: {kw.get('p')!r} is not a probability")
-    return {"axes": axes, "max_degrees": deg, "p": p}
+    return {"axes": axes, "max_degrees": deg, "p": stages.probability(f"{owner}.rotation", "p", kw.get("p", 0.5))}
 
 
 def check_scale(owner, kw):
@@ -351,56 +297,18 @@ def check_scale(owner, kw):
         raise ValueError(f"{owner}.scale.range: {r!r} (two numbers, 0.5 <= lo <= hi <= 2)") from None
     if not 0.5 <= lo <= hi <= 2.0:
         raise ValueError(f"{owner}.scale.range: {list(r)} (0.5 <= lo <= hi <= 2)")
-    p = float(kw.get("p", 0.5))
-    if not 0.0 <= p <= 1.0:
-        raise ValueError(f"{owner}.scale.p: {kw.get('p')!r} is not a probability")
-    return {"range": (lo, hi), "p": p}
+    return {"range": (lo, hi), "p": stages.probability(f"{owner}.scale", "p", kw.get("p", 0.5))}
 
 
 def parse_spatial(dataset_config, patch_size, tasks):
     """`dataset_config.spatial` -> None (absent / false) or {"rotation": block | None, "scale": block | None, "normal_keys": tuple,
     "image_border": "constant" | "clamp", "where": "device" | "host"}.  Everything that would otherwise fail at some later step
     fails here, with the key named."""
-    g = (dataset_config or {}).get("spatial", None)
-    if g is None or g is False:
+    g = stages.block(dataset_config, "spatial", ("rotation", "scale", "normal_keys", "image_border", "where"), "device", None)
+    if g is None:
         return None
-    if g is True:
-        g = {}
-    if not isinstance(g, dict):
-        raise ValueError(f"dataset_config.spatial: expected a mapping (rotation, scale, normal_keys, image_border, where), got {g!r}")
-    known = ("rotation", "scale", "normal_keys", "image_border", "where")
-    unknown = set(g) - set(known)
-    if unknown:
-        raise ValueError(f"dataset_config.spatial: unknown key(s) {sorted(unknown)} (known: {', '.join(known)})")
-    where = str(g.get("where", "device")).lower()
-    if where not in ("device", "host"):
-        raise ValueError(f"dataset_config.spatial.where: {g.get('where')!r} (\"device\" or \"host\")")
-    patch = tuple(int(v) for v in patch_size)
-    if len(patch) != 3:
-        raise ValueError(f"dataset_config.spatial: needs a 3-D patch, patch_size is {list(patch)}")
-    border = str(g.get("image_border", "constant")).lower()
-    if border not in BORDER:
-        raise ValueError(f"dataset_config.spatial.image_border: {g.get('image_border')!r} (\"constant\" or \"clamp\")")
-    out = {"rotation": check_rotation("dataset_config.spatial", g.get("rotation", None)),
-           "scale": check_scale("dataset_config.spatial", g.get("scale", None)), "image_border": border, "where": where}
-    nk = g.get("normal_keys", ("normals",))
-    if isinstance(nk, str):
-        nk = (nk,)
-    out["normal_keys"] = tuple(str(k) for k in nk)
-    for k in out["normal_keys"]:
-        if k in (tasks or {}) and int(tasks[k].get("channels", 0)) != 3:
-            raise ValueError(f"dataset_config.spatial.normal_keys: task {k!r} has channels = {tasks[k].get('channels')}, "
-                             "a normals target has 3")
-    return out
-
-
-def check_host_spatial(cfg, ingest, dilate):
-    """`where: host` resamples scaled float items inside `__getitem__`: refused where an earlier stage runs on the device"""
-    if cfg is None or cfg["where"] != "host":
-        return
-    if ingest is not None and ingest.get("where") == "device":
-        raise ValueError("dataset_config.spatial.where: \"host\" cannot follow dataset_config.ingest.where: \"device\" (the items are "
-                         "the store's integers); take spatial.where: \"device\"")
-    if dilate is not None and dilate.get("where") == "device":
-        raise ValueError("dataset_config.spatial.where: \"host\" cannot precede dataset_config.dilate.where: \"device\" (the ball is "
-                         "not scale-invariant: dilation comes first); take spatial.where: \"device\" or dilate.where: \"host\"")
+    stages.patch3d("dataset_config.spatial", patch_size)
+    return {"rotation": check_rotation("dataset_config.spatial", g.get("rotation", None)),
+            "scale": check_scale("dataset_config.spatial", g.get("scale", None)),
+            "image_border": stages.image_border("dataset_config.spatial", g), "where": g["where"],
+            "normal_keys": stages.normal_keys("dataset_config.spatial", g, tasks)}

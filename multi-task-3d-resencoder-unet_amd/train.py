@@ -38,6 +38,7 @@ from torch.utils.data import DataLoader, SubsetRandomSampler
 from .builders.build_network_from_config import NetworkFromConfig
 from .configuration.config_manager import ConfigManager
 from .dataloading.dataset import SyntheticPatchDataset, ZarrSegmentationDataset3D
+from .dataloading.stages import DevicePipeline
 from .engine.ddp import GradSync, broadcast_parameters
 from .engine.streamed_step import StreamedOptimizerStep
 from .training.losses.losses import LOSS_FN_MAP
@@ -98,14 +99,9 @@ class DeviceFeeder:
     `batch["image"].to(device)`, train.py:199-203) the 33.5 MB of a cfg2 batch sit between two steps: 0.7 ms of a 17 ms step with
     the device idle (`scripts/step_timeline.py` on a `--through-trainer` trace: first kernel 707 us after the previous step's last)."""
 
-    def __init__(self, loader, device, augmenter=None, geometry=None, dilate=None, ingest=None, spatial=None, elastic=None):
+    def __init__(self, loader, device, pipeline=None):
         self.loader, self.device = loader, device
-        self.ingest = ingest                # `DeviceIngest`: raw batches are copied in the store's dtype and scaled here, first
-        self.dilate = dilate                # `DeviceDilate`: the label targets, in place, before geometry (the host order)
-        self.augmenter = augmenter          # `DeviceAugmenter`: applied on the copy stream, under the running step like the copies
-        self.geometry = geometry            # `DeviceGeometry`: the whole staged dict, before the image augmenter
-        self.spatial = spatial              # `DeviceSpatial`: the whole staged dict, after geometry (the host order)
-        self.elastic = elastic              # `DeviceElastic`: the whole staged dict, after spatial (the host order)
+        self.pipeline = pipeline if pipeline is not None else DevicePipeline()      # applied on the copy stream, under the running step
         self.stream = torch.cuda.Stream(device)
         ring = getattr(loader, "collate_fn", None)
         self.ring = ring if isinstance(ring, PinnedRingCollate) else None
@@ -119,24 +115,10 @@ class DeviceFeeder:
         except StopIteration:
             return None
         with torch.cuda.stream(self.stream):
-            if self.ingest is not None:     # integers over the link, float32 (B, C, Z, Y, X) from one HIP pass per tensor
-                dev = {k: v.to(self.device, non_blocking=True) for k, v in batch.items()}
-            else:
-                dev = {k: v.to(self.device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
+            dev = self.pipeline.to_device(batch, self.device)
             if self.ring is not None:
                 self.ring.copied()          # (records on the copy stream: the pinned slot is free once THESE copies are done)
-            if self.ingest is not None:
-                dev = self.ingest(dev)
-            if self.dilate is not None:
-                dev = self.dilate(dev)
-            if self.geometry is not None:
-                dev = self.geometry(dev)
-            if self.spatial is not None:
-                dev = self.spatial(dev)
-            if self.elastic is not None:
-                dev = self.elastic(dev)
-            if self.augmenter is not None:
-                dev["image"] = self.augmenter(dev["image"])
+            dev = self.pipeline(dev)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return dev, ev
@@ -171,6 +153,13 @@ class BaseTrainer:
         # tr_config.val_preview: checked here for the same reason
         self.val_preview_config = parse_val_preview(self.mgr.tr_configs.get("val_preview"), self.mgr.tasks, self.mgr.model_name)
         self.last_val_preview = None
+
+    # the device stages of `train()`'s pipeline, under the names they have always had here (None: that stage is off)
+    device_ingest = property(lambda self: self.pipeline.ingest)
+    device_dilate = property(lambda self: self.pipeline.dilate)
+    device_geometry = property(lambda self: self.pipeline.geometry)
+    device_spatial = property(lambda self: self.pipeline.spatial)
+    device_elastic = property(lambda self: self.pipeline.elastic)
 
     # ---- hooks ----------------------------------------------------------------------------------
     def _build_model(self):
@@ -341,56 +330,10 @@ class BaseTrainer:
         stepper = (StreamedOptimizerStep(optimizer, engine_model)
                    if isinstance(engine_model, NetworkFromConfig) and os.environ.get("RX_STREAMED_STEP", "0") == "1" else None)
 
-        # dataset_config.augment: "device" -- the dataset hands out raw patches and the stack runs as HIP kernels on the batch:
-        # behind the feeder's copies for the batches it stages, here for every other batch (RX_DEVICE_FEEDER=0, and validation:
-        # the reference augments validation items too, both loaders share the dataset)
-        augmenter = None
-        if getattr(dataset, "device_augment", False):
-            from .dataloading.augment_device import DeviceAugmenter
-            augmenter = DeviceAugmenter(rank=self.rank)
-        # dataset_config.geometric with where: device -- flips / 90-degree rotations of image AND targets (normals with their
-        # component rule) as one HIP pass per tensor, in the same two places and before the intensity stack
-        geometry = None
-        geo_cfg = getattr(dataset, "geometric", None)
-        if geo_cfg is not None and geo_cfg["where"] == "device":
-            from .dataloading.geometry_device import DeviceGeometry
-            geometry = DeviceGeometry(flip=geo_cfg["flip"], rot90=geo_cfg["rot90"], normal_keys=geo_cfg["normal_keys"], rank=self.rank)
-        self.device_geometry = geometry
-        # dataset_config.spatial with where: device -- rotation / scaling of image AND targets (normals turned by the vector rule)
-        # as one HIP resampling pass per tensor, in the same two places, after geometry and before the intensity stack
-        spatial = None
-        spa_cfg = getattr(dataset, "device_spatial", None)
-        if spa_cfg is not None:
-            from .dataloading.spatial_device import DeviceSpatial
-            spatial = DeviceSpatial(rotation=spa_cfg["rotation"], scale=spa_cfg["scale"], normal_keys=spa_cfg["normal_keys"],
-                                    image_border=spa_cfg["image_border"], rank=self.rank)
-        self.device_spatial = spatial
-        # dataset_config.elastic with where: device -- a B-spline deformation of image AND targets (normals as covectors) as one
-        # HIP resampling pass per tensor, in the same two places, after spatial and before the intensity stack
-        elastic = None
-        ela_cfg = getattr(dataset, "device_elastic", None)
-        if ela_cfg is not None:
-            from .dataloading.elastic_device import DeviceElastic
-            elastic = DeviceElastic(spacing=ela_cfg["spacing"], magnitude=ela_cfg["magnitude"], p=ela_cfg["p"],
-                                    normal_keys=ela_cfg["normal_keys"], image_border=ela_cfg["image_border"], rank=self.rank)
-        self.device_elastic = elastic
-        # tr_setup.dilate_label with dataset_config.dilate.where: device -- the dataset hands out raw labels and the ball dilation
-        # runs as a HIP pass on the targets, in the same two places and before geometry (the host order; the stages commute)
-        dilate = None
-        dil_cfg = getattr(dataset, "device_dilate", None)
-        if dil_cfg is not None:
-            from .dataloading.dilate_device import DeviceDilate
-            dilate = DeviceDilate(dil_cfg["keys"], dil_cfg["radius"])
-        self.device_dilate = dilate
-        # dataset_config.ingest.where: device -- the dataset hands out what the store holds (uint8 / uint16 / float32, normals
-        # channels-last); the float32 conversion, the scaling and the transpose run as one HIP pass per tensor, in the same two
-        # places and first, so that dilation, geometry and the intensity stack see exactly the tensors they see today
-        ingest = None
-        ing_rules = getattr(dataset, "device_ingest", None)
-        if ing_rules is not None:
-            from .dataloading.ingest_device import DeviceIngest
-            ingest = DeviceIngest(ing_rules)
-        self.device_ingest = ingest
+        # the stages the dataset leaves to the device (`where: device`, augment: "device"), in their one order: behind the feeder's
+        # copies for the batches it stages, in `forward_loss` for every other batch (RX_DEVICE_FEEDER=0, and validation: the
+        # reference augments validation items too, both loaders share the dataset)
+        pipeline = self.pipeline = DevicePipeline.from_dataset(dataset, self.rank)
 
         # tr_config.val_metrics: counts and sums accumulate on the device over the validation loop
         val_metrics = ValidationMetrics(self.mgr.tasks, self.val_metrics_config) if self.val_metrics_config is not None else None
@@ -418,21 +361,9 @@ class BaseTrainer:
 
         def forward_loss(batch, train_mode):
             staged = batch["image"].is_cuda          # a DeviceFeeder batch: already on the device, its pinned slot already released
-            if ingest is not None and not staged:    # each tensor in its own dtype; from here on the batch is what `where: host` gives
-                batch = ingest({k: v.to(device, non_blocking=True) for k, v in batch.items()})
-            if (dilate is not None or geometry is not None or spatial is not None or elastic is not None) and not staged:      # (after ingest: fresh device tensors already)
-                batch = {k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items()}
-                if dilate is not None:      # (the copies above are fresh device tensors: dilating them in place touches nothing else)
-                    batch = dilate(batch)
-                if geometry is not None:
-                    batch = geometry(batch)
-                if spatial is not None:
-                    batch = spatial(batch)
-                if elastic is not None:
-                    batch = elastic(batch)
+            if pipeline and not staged:              # (no stage on: the batch is copied below, exactly as the reference copies it)
+                batch = pipeline(pipeline.to_device(batch, device))
             x = batch["image"].to(device, dtype=torch.float32, non_blocking=True)
-            if augmenter is not None and not staged:
-                x = augmenter(x)
             targets = {k: v.to(device, dtype=torch.float32, non_blocking=True) for k, v in batch.items() if k != "image"}
             ring = getattr(train_loader, "collate_fn", None)
             if train_mode and not staged and isinstance(ring, PinnedRingCollate):
@@ -461,8 +392,7 @@ class BaseTrainer:
             steps, patches = 0, 0
             torch.cuda.synchronize(device)
             t0 = time.perf_counter()
-            feeder = (DeviceFeeder(train_loader, device, augmenter=augmenter, geometry=geometry, dilate=dilate, ingest=ingest, spatial=spatial,
-                                   elastic=elastic)
+            feeder = (DeviceFeeder(train_loader, device, pipeline)
                       if device.type == "cuda" and os.environ.get("RX_DEVICE_FEEDER", "1") != "0" else train_loader)
             for i, batch in enumerate(feeder):
                 if i >= self.mgr.max_steps_per_epoch:

@@ -185,6 +185,7 @@ def test_feeder_batches_are_the_host_dataset_items(tmp_path):
     from types import SimpleNamespace
     from torch.utils.data import DataLoader
     from mt3d_amd.dataloading.dataset import ZarrSegmentationDataset3D
+    from mt3d_amd.dataloading.stages import DevicePipeline
     from mt3d_amd.train import DeviceFeeder
     paths = _write_volume(str(tmp_path))
     tasks = {"sheet": {"channels": 1}, "normals": {"channels": 3}}
@@ -211,7 +212,7 @@ def test_feeder_batches_are_the_host_dataset_items(tmp_path):
     loader = DataLoader(torch.utils.data.Subset(dev_ds, list(range(n))), batch_size=2, shuffle=False, num_workers=0)
     stage = D.DeviceDilate(dev_ds.device_dilate["keys"], dev_ds.device_dilate["radius"])
     seen = 0
-    for b, batch in enumerate(DeviceFeeder(loader, device, dilate=stage)):
+    for b, batch in enumerate(DeviceFeeder(loader, device, DevicePipeline(dilate=stage))):
         torch.cuda.synchronize()
         for j in range(batch["image"].shape[0]):
             w = want[2 * b + j]

@@ -426,6 +426,7 @@ def test_parse_elastic():
 
 def test_zarr_dataset_refuses_host_elastic_behind_device_stages(tmp_path):
     from mt3d_amd.dataloading.dataset import ZarrSegmentationDataset3D
+    from mt3d_amd.dataloading.stages import check_stage_order
 
     def mgr(dilate_label=False, **dataset_config):
         return SimpleNamespace(model_name="m", tasks=TASKS, train_patch_size=(16, 16, 16), min_labeled_ratio=0.1, min_bbox_percent=0.9,
@@ -437,9 +438,9 @@ def test_zarr_dataset_refuses_host_elastic_behind_device_stages(tmp_path):
     with pytest.raises(ValueError, match=r"dataset_config\.elastic\.where.*dilate"):
         ZarrSegmentationDataset3D(mgr(dilate_label=True, elastic=host, dilate={"where": "device"}))
     with pytest.raises(ValueError, match=r"dataset_config\.elastic\.where.*ingest"):
-        M.check_host_elastic({"where": "host"}, {"where": "device"}, None)
-    M.check_host_elastic({"where": "device"}, {"where": "device"}, {"where": "device"})
-    M.check_host_elastic(None, {"where": "device"}, {"where": "device"})
+        check_stage_order(False, None, None, {"where": "device"}, None, {"where": "host"})
+    check_stage_order(False, None, {"where": "device"}, {"where": "device"}, None, {"where": "device"})
+    check_stage_order(False, None, {"where": "device"}, {"where": "device"}, None, None)
     assert ZarrSegmentationDataset3D(mgr(elastic=BLOCK, ingest={"where": "device"})).device_elastic["where"] == "device"
     ds = ZarrSegmentationDataset3D(mgr(dilate_label=True, elastic=host, dilate={"where": "host"}))
     assert ds.device_elastic is None and ds.elastic["where"] == "host"

@@ -228,6 +228,7 @@ def test_feeder_batches_are_the_collated_host_items(tmp_path):
     from types import SimpleNamespace
     from torch.utils.data import DataLoader, default_collate
     from mt3d_amd.dataloading.dataset import ZarrSegmentationDataset3D
+    from mt3d_amd.dataloading.stages import DevicePipeline
     from mt3d_amd.train import DeviceFeeder, PinnedRingCollate
     paths = _write_volume(str(tmp_path))
     tasks = {"sheet": {"channels": 1}, "normals": {"channels": 3}}
@@ -248,7 +249,7 @@ def test_feeder_batches_are_the_collated_host_items(tmp_path):
         loader = DataLoader(torch.utils.data.Subset(dev_ds, list(range(2 * len(want)))), batch_size=2, shuffle=False, num_workers=0,
                             **({"collate_fn": collate} if collate is not None else {}))
         seen = 0
-        for b, batch in enumerate(DeviceFeeder(loader, device, ingest=stage)):
+        for b, batch in enumerate(DeviceFeeder(loader, device, DevicePipeline(ingest=stage))):
             torch.cuda.synchronize()
             assert batch["image"].shape == (2, 1, 16, 16, 16) and batch["normals"].shape == (2, 3, 16, 16, 16)
             for k in ("image", "sheet", "normals"):
