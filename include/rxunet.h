@@ -678,6 +678,33 @@ int rx_cc_sizes(const int32_t* labels, int nvol, long voxels, int32_t* sizes, vo
 int rx_cc_filter(const uint8_t* values, const int32_t* labels, const int32_t* sizes, int min_voxels, int nvol, long voxels, uint8_t* out,
                  void* stream);
 
+/* ---- triangle mesh of a uint8 volume by surface nets (host side postprocess/isosurface.py, whose surface_nets_numpy and counts_numpy
+ *      are the statements).  `values` is a contiguous (z, y, x) block, padded with 0 on every side by the kernels themselves; inside is
+ *      value > level.  Cells form a (z+1, y+1, x+1) grid, cell (k, j, i) with corner 0 at voxel (k-1, j-1, i-1); a cell ROW is (k, j),
+ *      `rows` = (z+1) * (y+1) of them, and a row's bits are ceil((x+1) / 64) 64-bit words.  No allocation, copy or synchronisation; no
+ *      output depends on the order anything ran in.  RX_EINVAL before anything is launched: null pointers, an extent of 0 or of
+ *      2^24 - 2 or more (a position is an exact float32 integer plus a fraction), more than RX_ISO_MAX_CELLS = 2^31 - 2 cells, more than
+ *      2^24 - 1 bands of 4 cell planes x 8 cell rows (ceil((z+1) / 4) * ceil((y+1) / 8): one workgroup each), a level
+ *      outside 0 .. 254, a cell-plane window outside the grid, a misaligned pointer.
+ *      rx_iso_classify: bits[row][word] = the active flags (corners not all inside, not all outside) of the row's cells, bit l of word w
+ *        cell 64 w + l; row_counts[row] = {active cells, quads the row's cells own} (int32 pairs).  Cell planes outside [k_lo, k_hi)
+ *        get zeros: a slab of a larger volume leaves out the planes whose voxels it does not hold (the whole volume: 0, z + 1).
+ *      rx_iso_scan: row_offsets[row] = {sum of the active cells, sum of the quads} of the rows before it (int64 pairs, 16-byte
+ *        aligned), totals[0..1] = the two sums over all rows.  Three launches.
+ *      rx_iso_emit: for every active cell of planes >= k_emit, in ascending linear cell index, vertices[3 * (id - v_skip)] = its
+ *        (x, y, z) with z_base added to the plane (float32, the statement's bits), id = row_offsets[row][0] + its rank in the row;
+ *        for every quad those cells own, in (cell, axis z / y / x) order, triangles[6 * (slot - q_skip)] = its two triangles with
+ *        vertex_base added to every id.  v_skip / q_skip: row_offsets[k_emit * (y+1)], which the caller has read; a slot outside
+ *        0 .. n_vertices - 1 / n_quads - 1 is not written. */
+#define RX_ISO_MAX_EXTENT 16777213
+#define RX_ISO_MAX_CELLS 2147483646L
+int rx_iso_classify(const uint8_t* values, int level, int z, int y, int x, int k_lo, int k_hi, uint64_t* bits, int32_t* row_counts,
+                    void* stream);
+int rx_iso_scan(const int32_t* row_counts, long rows, int64_t* row_offsets, int64_t* totals, void* stream);
+int rx_iso_emit(const uint8_t* values, int level, int z, int y, int x, int z_base, const uint64_t* bits, const int64_t* row_offsets,
+                int k_emit, int64_t v_skip, int64_t q_skip, int64_t vertex_base, int64_t n_vertices, int64_t n_quads, float* vertices,
+                int64_t* triangles, void* stream);
+
 /* ---- validation preview on the device: one panel of the debug GIF (host side training/visualization/preview.py, whose
  *      panel_numpy and minmax_numpy are the statements).  `src` is ONE sample's contiguous (c, z, h, w) block of `dtype` (rx_dtype),
  *      aligned to its element (a base that is not 16-byte aligned is fine).  c == 3 draws channels 0, 1, 2 into bytes 0, 1, 2 of

@@ -81,7 +81,7 @@ class ConfigManager:
             raise ValueError(f"inference_config.{e}") from None
         if self.infer_tile == "auto" and self.infer_max_device_gb is None:
             raise ValueError("inference_config.tile: \"auto\" chooses the tile from max_device_gb, which is not set")
-        # post-processing of the written store (postprocess.ComponentFilter); absent: None, and nothing is read or written differently
+        # post-processing of the written store (postprocess.ComponentFilter, postprocess.SurfaceMesher); absent: None, and nothing is read or written differently
         from ..postprocess.components import parse_config
         self.infer_postprocess = parse_config(ic.get("postprocess", None), self.infer_targets, self.infer_patch_size)
         if verbose:

@@ -2,7 +2,7 @@
 missing -- there is no fallback path."""
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_long, c_size_t, c_void_p
 
 import torch
 
@@ -27,6 +27,7 @@ RX_AFFINE_LINEAR, RX_AFFINE_NEAREST = 0, 1
 RX_AFFINE_CONSTANT, RX_AFFINE_CLAMP = 0, 1
 RX_EDT_NONE, RX_EDT_MAX_EXTENT = 1 << 30, 1024
 RX_CC_MAX_VOXELS = 2**31 - 2
+RX_ISO_MAX_EXTENT, RX_ISO_MAX_CELLS = 2**24 - 3, 2**31 - 2
 
 
 class RxError(RuntimeError):
@@ -190,6 +191,10 @@ _SIGNATURES = {
     "rx_cc_label": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rx_cc_sizes": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "rx_cc_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "rx_iso_classify": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rx_iso_scan": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
+    "rx_iso_emit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64,
+                            c_int64, c_void_p, c_void_p, c_void_p]),
     "rx_preview_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int,
                                  c_void_p, c_void_p]),
     "rx_mesh_slice_keys": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -785,6 +785,13 @@ def main(argv=None):
         for task in pp["tasks"]:
             print(task, ComponentFilter(pp["level"], pp["connectivity"], pp["min_voxels"], pp["write_labels"],
                                         None if gb is None else int(gb * 2**30)).run(store, task), flush=True)
+    mesh = (mgr.infer_postprocess or {}).get("mesh")
+    if mesh:      # after the filter: `source: filtered` reads what it has just written
+        from .postprocess import SurfaceMesher
+        gb = mesh["max_device_gb"]
+        for task in mesh["tasks"]:
+            print(task, SurfaceMesher(mesh["level"], mesh["format"], None if gb is None else int(gb * 2**30)).run(store, task, mesh["source"]),
+                  flush=True)
     return store
 
 

@@ -172,17 +172,24 @@ def _check_options(level, connectivity, min_voxels):
 
 def parse_config(block, targets, patch_size=None):
     """`inference_config.postprocess` -> None when absent, else {"components": {tasks, level, connectivity, min_voxels, write_labels,
-    max_device_gb}}.  Unknown keys and bad values raise ValueError naming the key; `targets` is {task: {"channels": c, ...}}."""
+    max_device_gb}} and / or {"mesh": {tasks, source, level, format, max_device_gb}} (isosurface.parse_mesh_config), whichever the
+    block holds.  Unknown keys and bad values raise ValueError naming the key; `targets` is {task: {"channels": c, ...}}."""
     if block is None:
         return None
     if not isinstance(block, dict):
         raise ValueError(f"inference_config.postprocess: expected a mapping, got {block!r}")
     for k in block:
-        if k != "components":
-            raise ValueError(f"inference_config.postprocess.{k}: unknown key (components)")
-    if "components" not in block:
-        return None
-    c = block["components"]
+        if k not in ("components", "mesh"):
+            raise ValueError(f"inference_config.postprocess.{k}: unknown key (components, mesh)")
+    out = _parse_components(block["components"], targets, patch_size) if "components" in block else {}
+    if "mesh" in block:
+        from .isosurface import parse_mesh_config
+        out["mesh"] = parse_mesh_config(block["mesh"], targets, patch_size, out["components"]["tasks"] if "components" in out else None)
+    return out or None
+
+
+def _parse_components(c, targets, patch_size):
+    """the `components` block -> {"components": {...}}"""
     if not isinstance(c, dict):
         raise ValueError(f"{KEY}: expected a mapping, got {c!r}")
     known = ("tasks", "min_voxels") + tuple(_DEFAULTS)
