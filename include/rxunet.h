@@ -461,8 +461,10 @@ typedef struct {        /* one sample's transform, 48 bytes */
 int rx_geom_apply(const float* in, float* out, int batch, int c, int z, int y, int x, const rx_geom_sample* host_table,
                   int vector, void* stream);
 
-/* ---- test-time augmentation of streaming inference: the two entry points above with one rx_geom_sample per patch slot (`ops`:
- *      `batch` records in HOST memory, handed to the kernels by value; no device table, copy or synchronisation).  Both use the
+/* ---- test-time augmentation of streaming inference: rx_sw_gather / rx_sw_accumulate with a table of one rx_geom_sample per patch
+ *      slot (`ops`: `batch` records in HOST memory, handed to the kernels by value; no device table, copy or synchronisation).  One
+ *      family: each _geom entry point runs the host path and the kernel body of its plain twin, with the table as the one thing
+ *      added, so "with identity records, bit for bit" below holds by construction.  Both use the
  *      gather form of rx_geom_apply on the PATCH: out[o] = in[i(o)], i[src_axis[d]] = flip[d] ? n_d - 1 - o_d : o_d.
  *      rx_sw_gather_geom: output voxel o of slot b is slab voxel origin_b + i(o) (z modulo the ring), scaled and standardised as
  *      rx_sw_gather does; image channels are never permuted or negated.  With identity records it is rx_sw_gather, bit for bit.

@@ -4,7 +4,8 @@
 // `src` a signed permutation of the (z, y, x) axes, `ch` a signed permutation of the three components (identity for tensors that
 // are not vector fields).  The behaviour is the reference's training/transforms/geometric/geometry.py (RandomFlipWithNormals,
 // RandomRotate90WithNormals); the ops are drawn and composed on the host (dataloading/geometry_device.py) and arrive as one
-// `rx_geom_sample` per sample.  The host turns each into a base offset and three signed element strides, so the device computes
+// `rx_geom_sample` per sample.  The host checks each and turns it into a base offset and three signed element strides
+// (rx_geom_core.h, shared with the test-time-augmentation entry points of rx_infer.hip), so the device computes
 //   src(o) = base + oz * sz + oy * sy + ox * sx
 // and the records ride in the KERNEL ARGUMENTS (RX_GEOM_CHUNK samples per launch): no device table, no copy, no allocation.
 // Two access patterns, picked per sample; a workgroup belongs to one sample, so the choice is a scalar branch:
@@ -18,27 +19,21 @@
 // Negation flips the sign bit (an XOR on the bits: 0.0 becomes -0.0, as numpy's unary minus and `*= -1` give); there is no
 // floating-point arithmetic in this file.  Every output voxel is written once by one thread.
 #include "rx_common.h"
+#include "rx_geom_core.h"
 
 #define RX_GEOM_BLOCK 256
 #define RX_GEOM_CHUNK 16      // samples per launch: 16 x 36 bytes of kernel arguments
 #define RX_GEOM_TILE 64
 #define RX_GEOM_LDS_ROW 65
 
-struct GeomDev {            // one sample, as the kernels index with it (element units of ONE channel volume)
-  int32_t base, sz, sy, sx;
-  int32_t ch[3];
-  uint32_t neg;             // bit c: output channel c has its sign bit flipped
-  int32_t feeds;            // the output axis input x feeds: 2 = x stays innermost (rows), 0 or 1 = x moves (tiles)
-};
-
 struct GeomArgs {
-  GeomDev s[RX_GEOM_CHUNK];
+  RxGeomView s[RX_GEOM_CHUNK];   // feeds == 2: the row kernel's sample; 0 or 1: the tile kernel's
   int C, Z, Y, X, XQ;       // XQ: quads of 4 voxels per row
   int vol;                  // Z * Y * X (checked < 2^31 on the host)
   int vector;
 };
 
-__device__ inline void geom_channel(const GeomDev& s, int vector, int c, int& cin, uint32_t& sign) {
+__device__ inline void geom_channel(const RxGeomView& s, int vector, int c, int& cin, uint32_t& sign) {
   cin = c, sign = 0u;
   if (vector) {
     cin = c == 0 ? s.ch[0] : c == 1 ? s.ch[1] : s.ch[2];
@@ -51,7 +46,7 @@ template <bool VEC>
 __global__ __launch_bounds__(RX_GEOM_BLOCK) void geom_rows_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                                   const GeomArgs a) {
   const int bc = blockIdx.y, b = bc / a.C, c = bc - b * a.C;
-  const GeomDev& s = a.s[b];
+  const RxGeomView& s = a.s[b];
   if (s.feeds != 2) return;      // the tile kernel's sample
   int cin;
   uint32_t sign;
@@ -88,7 +83,7 @@ __global__ __launch_bounds__(RX_GEOM_BLOCK) void geom_tile_kernel(const uint32_t
                                                                   const GeomArgs a) {
   __shared__ uint32_t tile[RX_GEOM_TILE * RX_GEOM_LDS_ROW];
   const int bc = blockIdx.z, b = bc / a.C, c = bc - b * a.C;
-  const GeomDev& s = a.s[b];
+  const RxGeomView& s = a.s[b];
   if (s.feeds == 2) return;      // the row kernel's sample
   // input x feeds output axis k (z or y, source stride +/-1); the other one of the two is the third axis (e)
   const bool k_is_z = s.feeds == 0;
@@ -130,15 +125,6 @@ __global__ __launch_bounds__(RX_GEOM_BLOCK) void geom_tile_kernel(const uint32_t
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-static bool geom_is_perm(const int32_t* p) {
-  unsigned seen = 0;
-  for (int i = 0; i < 3; ++i) {
-    if (p[i] < 0 || p[i] > 2) return false;
-    seen |= 1u << p[i];
-  }
-  return seen == 7u;
-}
-
 extern "C" int rx_geom_apply(const float* in, float* out, int batch, int c, int z, int y, int x, const rx_geom_sample* host_table,
                              int vector, void* stream) {
   if (!in || !out) RX_FAIL(RX_EINVAL, "rx_geom_apply: null tensor pointer");
@@ -151,16 +137,12 @@ extern "C" int rx_geom_apply(const float* in, float* out, int batch, int c, int 
   if ((long)z * y * x > 0x7fffffffL || z > 65535 || y > 65535 || c > 65535 / RX_GEOM_CHUNK)
     RX_FAIL(RX_EINVAL, "rx_geom_apply: %d x %d x %d x %d per sample is beyond the 32-bit index arithmetic (z * y * x < 2^31, z, y <= 65535, c <= %d)",
             c, z, y, x, 65535 / RX_GEOM_CHUNK);
-  const int ext[3] = {z, y, x};
-  const int stride[3] = {y * x, x, 1};
-  for (int i = 0; i < batch; ++i) {
-    const rx_geom_sample& s = host_table[i];
-    if (!geom_is_perm(s.src_axis)) RX_FAIL(RX_EINVAL, "rx_geom_apply: sample %d: src_axis (%d, %d, %d) is not a permutation of 0..2", i, s.src_axis[0], s.src_axis[1], s.src_axis[2]);
-    if (!geom_is_perm(s.ch_src)) RX_FAIL(RX_EINVAL, "rx_geom_apply: sample %d: ch_src (%d, %d, %d) is not a permutation of 0..2", i, s.ch_src[0], s.ch_src[1], s.ch_src[2]);
-    for (int d = 0; d < 3; ++d)
-      if (ext[s.src_axis[d]] != ext[d])
-        RX_FAIL(RX_EINVAL, "rx_geom_apply: sample %d: output axis %d reads input axis %d, which would change the shape (%d x %d x %d)", i, d, s.src_axis[d], z, y, x);
-  }
+  for (int i = 0; i < batch; ++i)
+    if (const int verdict = rx_geom_check(host_table, z, y, x, i)) {
+      char text[160];
+      rx_geom_refusal(text, sizeof(text), verdict, host_table, z, y, x, i, "sample", "shape");
+      RX_FAIL(RX_EINVAL, "rx_geom_apply: %s", text);
+    }
   const bool vec = (x & 3) == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
   const long vol = (long)z * y * x;
   hipStream_t st = (hipStream_t)stream;
@@ -171,23 +153,8 @@ extern "C" int rx_geom_apply(const float* in, float* out, int batch, int c, int 
     a.C = c, a.Z = z, a.Y = y, a.X = x, a.XQ = (x + 3) / 4, a.vol = (int)vol, a.vector = vector ? 1 : 0;
     bool rows = false, tiles = false;
     for (int i = 0; i < nb; ++i) {
-      const rx_geom_sample& s = host_table[b0 + i];
-      GeomDev& d = a.s[i];
-      int32_t sd[3];
-      d.base = 0;
-      for (int ax = 0; ax < 3; ++ax) {
-        const int st_in = stride[s.src_axis[ax]];
-        sd[ax] = s.flip[ax] ? -st_in : st_in;
-        if (s.flip[ax]) d.base += (ext[ax] - 1) * st_in;
-      }
-      d.sz = sd[0], d.sy = sd[1], d.sx = sd[2];
-      d.neg = 0;
-      for (int k = 0; k < 3; ++k) {
-        d.ch[k] = s.ch_src[k];
-        if (s.ch_neg[k]) d.neg |= 1u << k;
-      }
-      d.feeds = s.src_axis[0] == 2 ? 0 : s.src_axis[1] == 2 ? 1 : 2;
-      if (d.feeds == 2) rows = true;
+      a.s[i] = rx_geom_lower(host_table[b0 + i], z, y, x);
+      if (a.s[i].feeds == 2) rows = true;
       else tiles = true;
     }
     const float* in_b = in + (long)b0 * c * vol;

@@ -6,18 +6,24 @@
 //                     ("scale") and optionally the per-patch standardisation ("zscore")
 //   rx_sw_accumulate  one task's logits (B, c, pz, py, px) -> activation -> sum += w * p and wsum += w on the ring accumulators
 //   rx_sw_finalize    finished rows -> blended fp32 + uint8 / uint16 final (+ the weight sum), accumulators reset for reuse
-// and, for test-time augmentation (one flip / 90-degree rotation record, `rx_geom_sample`, per patch slot; kernels of their own, the
-// three above are not touched by them):
+// Gather and accumulate each take an optional table of records for test-time augmentation (one flip / 90-degree rotation record,
+// `rx_geom_sample`, per patch slot; checked and lowered by rx_geom_core.h):
 //   rx_sw_gather_geom      rx_sw_gather of the TRANSFORMED patch: output voxel o of slot b reads slab voxel origin_b + i(o)
 //   rx_sw_accumulate_geom  rx_sw_accumulate of the TRANSFORMED prediction: destination voxel l of slot b adds the activated logit
 //                          at i(l), a 3-vector task with the record's component permutation and signs
-// both with the gather form of rx_geom_apply, out[o] = in[i(o)], i[src_axis[d]] = flip[d] ? n_d - 1 - o_d : o_d.
+// both with the gather form of rx_geom_apply, out[o] = in[i(o)], i[src_axis[d]] = flip[d] ? n_d - 1 - o_d : o_d.  Each pair is ONE
+// host path (sw_gather_impl, sw_accumulate_impl) and ONE kernel body with a template flag GEOM: without a table (GEOM = false) the
+// table is not among the kernel's arguments and nothing that reads it is compiled in; with identity records both forms load the
+// same values and run the same arithmetic on them, so they agree bit for bit.
 // For empty-patch skipping, rx_sw_occupancy counts per patch the raw slab voxels above a threshold (integer atomics: exact).
 // The entry points above are deterministic without atomics.  rx_sw_accumulate runs one thread per 4 destination voxels of the batch's bounding box, each adding
 // the batch's patches in patch order -- the same additions, in the same order, as one launch per patch, with every destination
 // read and written once per batch instead of once per covering patch (patches of one batch overlap by design).
 // Floating-point contraction is off in this file: every product and sum rounds like the numpy / torch statement it restates.
+#include <type_traits>
+
 #include "rx_common.h"
+#include "rx_geom_core.h"
 
 #pragma clang fp contract(off)
 
@@ -43,11 +49,66 @@ static int sw_patches(const int32_t* origins, int batch, int R, int Y, int X, in
   return RX_OK;
 }
 
+// the records of a call with a table: every one passes rx_geom_check over the patch extents
+static int sw_records(const rx_geom_sample* ops, int batch, int pz, int py, int px, const char* who) {
+  if (!ops) RX_FAIL(RX_EINVAL, "%s: null record table", who);
+  for (int b = 0; b < batch; ++b)
+    if (const int verdict = rx_geom_check(ops, pz, py, px, b)) {
+      char text[160];
+      rx_geom_refusal(text, sizeof(text), verdict, ops, pz, py, px, b, "slot", "patch shape");
+      RX_FAIL(RX_EINVAL, "%s: %s", who, text);
+    }
+  return RX_OK;
+}
+
+// the per-slot table among a kernel's arguments: V with records (GEOM), nothing without
+struct SwNone {};
+template <bool GEOM, typename V>
+using SwTable = std::conditional_t<GEOM, V, SwNone>;
+
+// f(the slab as a pointer to its element type): the launches that are templates on SwElem<decltype(pointer)>
+template <typename P>
+using SwElem = std::remove_cv_t<std::remove_pointer_t<P>>;
+template <typename F>
+static void sw_typed(int in_dtype, const void* slab, F&& f) {
+  if (in_dtype == RX_SW_U8) f((const uint8_t*)slab);
+  else if (in_dtype == RX_SW_U16) f((const uint16_t*)slab);
+  else f((const float*)slab);
+}
+
+// a quad of 4 consecutive floats: one 16-byte access (VEC), or its first n voxels one by one, the others reading as 0
+template <bool VEC>
+__device__ inline void sw_load_quad(const float* p, int n, float (&a)[4]) {
+  if (VEC) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = t[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = i < n ? p[i] : 0.f;
+  }
+}
+template <bool VEC>
+__device__ inline void sw_store_quad(float* p, int n, const float (&a)[4]) {
+  if (VEC) {
+    *reinterpret_cast<f32x4*>(p) = f32x4{a[0], a[1], a[2], a[3]};
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < n) p[i] = a[i];
+  }
+}
+
 // ---- gather ---------------------------------------------------------------------------------------------------------
 struct GatherGeom {
   int cin, R, Y, X, pz, py, px, pxq;   // pxq: quads of 4 outputs per patch row
   float div;                           // 0: fp32 input as is; otherwise the divisor 255 / 65535
   long total;                          // B * cin * pz * py * pxq
+};
+// GEOM: slot b, source axis a (z, y, x of the slab patch) takes the output coordinate of axis from[b][a], mirrored where flip[b][a]
+// (the slot's RxGeomInverse)
+struct SwViews {
+  uint8_t from[RX_SW_MAXB][3], flip[RX_SW_MAXB][3];
 };
 
 template <typename T>
@@ -55,9 +116,11 @@ __device__ inline float sw_scale(T v, float div) {
   return div == 0.f ? (float)v : (float)v / div;   // true division: bit-exact against numpy's float32 `img /= 255.0`
 }
 
-template <typename T>
+__device__ inline int sw_pick(int axis, int oz, int oy, int ox) { return axis == 0 ? oz : axis == 1 ? oy : ox; }
+
+template <typename T, bool GEOM>
 __global__ __launch_bounds__(RX_SW_BLOCK) void sw_gather_kernel(const T* __restrict__ slab, float* __restrict__ out, GatherGeom g,
-                                                                SwPatches p) {
+                                                                SwPatches p, SwTable<GEOM, SwViews> v) {
   const long q = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x;
   if (q >= g.total) return;
   long r = q;
@@ -69,18 +132,40 @@ __global__ __launch_bounds__(RX_SW_BLOCK) void sw_gather_kernel(const T* __restr
   r /= g.pz;
   const int ci = (int)(r % g.cin);
   const int b = (int)(r / g.cin);
-  const int zr = (p.oz[b] + lz) % g.R;
-  const T* src = slab + (((long)ci * g.R + zr) * g.Y + p.oy[b] + ly) * g.X + p.ox[b];
   float* dst = out + (((long)(b * g.cin + ci) * g.pz + lz) * g.py + ly) * g.px;
   const int x0 = xq * 4;
-  if ((g.px & 3) == 0) {
-    // patch origins put the source row at any alignment: four coalesced scalar loads, one 16-byte store
-    f32x4 v;
+  const bool quad = (g.px & 3) == 0;      // whole quads: one 16-byte store
+  if constexpr (GEOM) {
+    const int fz = v.from[b][0], fy = v.from[b][1], fx = v.from[b][2];
+    const int mz = v.flip[b][0], my = v.flip[b][1], mx = v.flip[b][2];
+    const T* src = slab + (long)ci * g.R * g.Y * g.X;
+    float val[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = sw_scale(src[x0 + i], g.div);
-    *reinterpret_cast<f32x4*>(dst + x0) = v;
+    for (int i = 0; i < 4; ++i) {
+      const int lx = x0 + i;
+      if (lx >= g.px) continue;
+      // the three source coordinates: z is taken modulo the ring, so one linear stride along output x is not enough
+      int sz = sw_pick(fz, lz, ly, lx), sy = sw_pick(fy, lz, ly, lx), sx = sw_pick(fx, lz, ly, lx);
+      if (mz) sz = g.pz - 1 - sz;
+      if (my) sy = g.py - 1 - sy;
+      if (mx) sx = g.px - 1 - sx;
+      const int zr = (p.oz[b] + sz) % g.R;
+      val[i] = sw_scale(src[((long)zr * g.Y + p.oy[b] + sy) * g.X + p.ox[b] + sx], g.div);
+    }
+    if (quad) sw_store_quad<true>(dst + x0, 4, val);
+    else sw_store_quad<false>(dst + x0, g.px - x0, val);
   } else {
-    for (int i = 0; i < 4 && x0 + i < g.px; ++i) dst[x0 + i] = sw_scale(src[x0 + i], g.div);
+    const int zr = (p.oz[b] + lz) % g.R;
+    const T* src = slab + (((long)ci * g.R + zr) * g.Y + p.oy[b] + ly) * g.X + p.ox[b];
+    if (quad) {
+      // patch origins put the source row at any alignment: four coalesced scalar loads, one 16-byte store
+      float val[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) val[i] = sw_scale(src[x0 + i], g.div);
+      sw_store_quad<true>(dst + x0, 4, val);
+    } else {
+      for (int i = 0; i < 4 && x0 + i < g.px; ++i) dst[x0 + i] = sw_scale(src[x0 + i], g.div);
+    }
   }
 }
 
@@ -151,156 +236,59 @@ extern "C" size_t rx_sw_gather_workspace(int batch, int cin, int pz, int py, int
   return (size_t)batch * sw_stat_chunks((long)cin * pz * py * px) * 2 * sizeof(double);
 }
 
-extern "C" int rx_sw_gather(int in_dtype, const void* slab, int cin, int ring, int y, int x, int batch, const int32_t* origins,
-                            int pz, int py, int px, int norm, float* out, void* ws, size_t ws_bytes, void* stream) {
-  if (!slab || !out || cin < 1 || ring < 1 || y < 1 || x < 1) RX_FAIL(RX_EINVAL, "rx_sw_gather: bad arguments");
-  if (in_dtype < RX_SW_U8 || in_dtype > RX_SW_F32) RX_FAIL(RX_EINVAL, "rx_sw_gather: unknown input dtype %d", in_dtype);
-  if (norm != RX_SW_SCALE && norm != RX_SW_ZSCORE) RX_FAIL(RX_EINVAL, "rx_sw_gather: unknown normalization %d", norm);
-  if ((uintptr_t)out & 15) RX_FAIL(RX_EINVAL, "rx_sw_gather: output must be 16-byte aligned");
+// `geom`: the call has a record table (`ops`, refused when null); `who`: the entry point that was called, for its messages
+static int sw_gather_impl(int in_dtype, const void* slab, int cin, int ring, int y, int x, int batch, const int32_t* origins, int pz,
+                          int py, int px, int norm, float* out, void* ws, size_t ws_bytes, void* stream, bool geom,
+                          const rx_geom_sample* ops, const char* who) {
+  if (!slab || !out || cin < 1 || ring < 1 || y < 1 || x < 1) RX_FAIL(RX_EINVAL, "%s: bad arguments", who);
+  if (in_dtype < RX_SW_U8 || in_dtype > RX_SW_F32) RX_FAIL(RX_EINVAL, "%s: unknown input dtype %d", who, in_dtype);
+  if (norm != RX_SW_SCALE && norm != RX_SW_ZSCORE) RX_FAIL(RX_EINVAL, "%s: unknown normalization %d", who, norm);
+  if ((uintptr_t)out & 15) RX_FAIL(RX_EINVAL, "%s: output must be 16-byte aligned", who);
   SwPatches p;
-  if (int rc = sw_patches(origins, batch, ring, y, x, pz, py, px, p, "rx_sw_gather")) return rc;
+  if (int rc = sw_patches(origins, batch, ring, y, x, pz, py, px, p, who)) return rc;
+  SwViews v;
+  memset(&v, 0, sizeof(v));
+  if (geom) {
+    if (int rc = sw_records(ops, batch, pz, py, px, who)) return rc;
+    for (int b = 0; b < batch; ++b) {
+      const RxGeomInverse r = rx_geom_inverse(ops[b]);
+      for (int a = 0; a < 3; ++a) v.from[b][a] = r.from[a], v.flip[b][a] = r.flip[a];
+    }
+  }
   const long n = (long)cin * pz * py * px;
   if (norm == RX_SW_ZSCORE && (!ws || ws_bytes < rx_sw_gather_workspace(batch, cin, pz, py, px)))
-    RX_FAIL(RX_EWORKSPACE, "rx_sw_gather: zscore needs rx_sw_gather_workspace() bytes of workspace");
+    RX_FAIL(RX_EWORKSPACE, "%s: zscore needs rx_sw_gather_workspace() bytes of workspace", who);
   hipStream_t st = (hipStream_t)stream;
   GatherGeom g;
   g.cin = cin, g.R = ring, g.Y = y, g.X = x, g.pz = pz, g.py = py, g.px = px, g.pxq = (px + 3) / 4;
   g.div = in_dtype == RX_SW_U8 ? 255.f : in_dtype == RX_SW_U16 ? 65535.f : 0.f;
   g.total = (long)batch * cin * pz * py * g.pxq;
   const dim3 grid((unsigned)((g.total + RX_SW_BLOCK - 1) / RX_SW_BLOCK));
-  if (in_dtype == RX_SW_U8)
-    hipLaunchKernelGGL(sw_gather_kernel<uint8_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint8_t*)slab, out, g, p);
-  else if (in_dtype == RX_SW_U16)
-    hipLaunchKernelGGL(sw_gather_kernel<uint16_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint16_t*)slab, out, g, p);
-  else
-    hipLaunchKernelGGL(sw_gather_kernel<float>, grid, dim3(RX_SW_BLOCK), 0, st, (const float*)slab, out, g, p);
-  if (norm == RX_SW_ZSCORE) {
+  sw_typed(in_dtype, slab, [&](auto* s) {
+    using T = SwElem<decltype(s)>;
+    if (geom) hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_gather_kernel<T, true>), grid, dim3(RX_SW_BLOCK), 0, st, s, out, g, p, v);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_gather_kernel<T, false>), grid, dim3(RX_SW_BLOCK), 0, st, s, out, g, p, SwNone{});
+  });
+  if (norm == RX_SW_ZSCORE) {      // of the patch as gathered: a transformed patch holds the same multiset of values
     const int chunks = sw_stat_chunks(n);
     hipLaunchKernelGGL(sw_stat_partial_kernel, dim3(chunks, batch), dim3(RX_SW_BLOCK), 0, st, (const float*)out, n, (double*)ws);
     long gx = (n / 4 + RX_SW_BLOCK - 1) / RX_SW_BLOCK;
     gx = gx < 1 ? 1 : gx > 1024 ? 1024 : gx;
     hipLaunchKernelGGL(sw_standardize_kernel, dim3((unsigned)gx, batch), dim3(RX_SW_BLOCK), 0, st, out, n, (const double*)ws, chunks);
   }
-  RX_CHECK_LAUNCH("rx_sw_gather");
+  RX_CHECK_LAUNCH(who);
   return RX_OK;
 }
 
-// ---- gather of a transformed patch (test-time augmentation) -------------------------------------------------------------------
-// slot b, source axis a (z, y, x of the slab patch) takes the output coordinate of axis from[b][a], mirrored where flip[b][a]:
-// the record's i[src_axis[d]] = flip[d] ? n_d - 1 - o_d : o_d, turned round per source axis on the host
-struct SwViews {
-  uint8_t from[RX_SW_MAXB][3], flip[RX_SW_MAXB][3];
-};
-
-static bool sw_is_perm(const int32_t* p) {
-  unsigned seen = 0;
-  for (int i = 0; i < 3; ++i) {
-    if (p[i] < 0 || p[i] > 2) return false;
-    seen |= 1u << p[i];
-  }
-  return seen == 7u;
-}
-
-// the records of a call: permutations, and none that would change the patch shape
-static int sw_check_ops(const rx_geom_sample* ops, int batch, int pz, int py, int px, const char* who) {
-  if (!ops) RX_FAIL(RX_EINVAL, "%s: null record table", who);
-  const int ext[3] = {pz, py, px};
-  for (int b = 0; b < batch; ++b) {
-    const rx_geom_sample& s = ops[b];
-    if (!sw_is_perm(s.src_axis))
-      RX_FAIL(RX_EINVAL, "%s: slot %d: src_axis (%d, %d, %d) is not a permutation of 0..2", who, b, s.src_axis[0], s.src_axis[1], s.src_axis[2]);
-    if (!sw_is_perm(s.ch_src))
-      RX_FAIL(RX_EINVAL, "%s: slot %d: ch_src (%d, %d, %d) is not a permutation of 0..2", who, b, s.ch_src[0], s.ch_src[1], s.ch_src[2]);
-    for (int d = 0; d < 3; ++d)
-      if (ext[s.src_axis[d]] != ext[d])
-        RX_FAIL(RX_EINVAL, "%s: slot %d: output axis %d reads input axis %d, which would change the patch shape (%d x %d x %d)", who,
-                b, d, s.src_axis[d], pz, py, px);
-  }
-  return RX_OK;
-}
-
-__device__ inline int sw_pick(int axis, int oz, int oy, int ox) { return axis == 0 ? oz : axis == 1 ? oy : ox; }
-
-template <typename T>
-__global__ __launch_bounds__(RX_SW_BLOCK) void sw_gather_geom_kernel(const T* __restrict__ slab, float* __restrict__ out, GatherGeom g,
-                                                                     SwPatches p, SwViews v) {
-  const long q = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x;
-  if (q >= g.total) return;
-  long r = q;
-  const int xq = (int)(r % g.pxq);
-  r /= g.pxq;
-  const int ly = (int)(r % g.py);
-  r /= g.py;
-  const int lz = (int)(r % g.pz);
-  r /= g.pz;
-  const int ci = (int)(r % g.cin);
-  const int b = (int)(r / g.cin);
-  const int fz = v.from[b][0], fy = v.from[b][1], fx = v.from[b][2];
-  const int mz = v.flip[b][0], my = v.flip[b][1], mx = v.flip[b][2];
-  const T* src = slab + (long)ci * g.R * g.Y * g.X;
-  float* dst = out + (((long)(b * g.cin + ci) * g.pz + lz) * g.py + ly) * g.px;
-  const int x0 = xq * 4;
-  float val[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int lx = x0 + i;
-    if (lx >= g.px) continue;
-    // the three source coordinates: z is taken modulo the ring, so one linear stride along output x is not enough
-    int sz = sw_pick(fz, lz, ly, lx), sy = sw_pick(fy, lz, ly, lx), sx = sw_pick(fx, lz, ly, lx);
-    if (mz) sz = g.pz - 1 - sz;
-    if (my) sy = g.py - 1 - sy;
-    if (mx) sx = g.px - 1 - sx;
-    const int zr = (p.oz[b] + sz) % g.R;
-    val[i] = sw_scale(src[((long)zr * g.Y + p.oy[b] + sy) * g.X + p.ox[b] + sx], g.div);
-  }
-  if ((g.px & 3) == 0) {
-    *reinterpret_cast<f32x4*>(dst + x0) = f32x4{val[0], val[1], val[2], val[3]};
-  } else {
-    for (int i = 0; i < 4 && x0 + i < g.px; ++i) dst[x0 + i] = val[i];
-  }
+extern "C" int rx_sw_gather(int in_dtype, const void* slab, int cin, int ring, int y, int x, int batch, const int32_t* origins,
+                            int pz, int py, int px, int norm, float* out, void* ws, size_t ws_bytes, void* stream) {
+  return sw_gather_impl(in_dtype, slab, cin, ring, y, x, batch, origins, pz, py, px, norm, out, ws, ws_bytes, stream, false, nullptr, "rx_sw_gather");
 }
 
 extern "C" int rx_sw_gather_geom(int in_dtype, const void* slab, int cin, int ring, int y, int x, int batch, const int32_t* origins,
                                  const rx_geom_sample* ops, int pz, int py, int px, int norm, float* out, void* ws, size_t ws_bytes,
                                  void* stream) {
-  if (!slab || !out || cin < 1 || ring < 1 || y < 1 || x < 1) RX_FAIL(RX_EINVAL, "rx_sw_gather_geom: bad arguments");
-  if (in_dtype < RX_SW_U8 || in_dtype > RX_SW_F32) RX_FAIL(RX_EINVAL, "rx_sw_gather_geom: unknown input dtype %d", in_dtype);
-  if (norm != RX_SW_SCALE && norm != RX_SW_ZSCORE) RX_FAIL(RX_EINVAL, "rx_sw_gather_geom: unknown normalization %d", norm);
-  if ((uintptr_t)out & 15) RX_FAIL(RX_EINVAL, "rx_sw_gather_geom: output must be 16-byte aligned");
-  SwPatches p;
-  if (int rc = sw_patches(origins, batch, ring, y, x, pz, py, px, p, "rx_sw_gather_geom")) return rc;
-  if (int rc = sw_check_ops(ops, batch, pz, py, px, "rx_sw_gather_geom")) return rc;
-  const long n = (long)cin * pz * py * px;
-  if (norm == RX_SW_ZSCORE && (!ws || ws_bytes < rx_sw_gather_workspace(batch, cin, pz, py, px)))
-    RX_FAIL(RX_EWORKSPACE, "rx_sw_gather_geom: zscore needs rx_sw_gather_workspace() bytes of workspace");
-  SwViews v;
-  memset(&v, 0, sizeof(v));
-  for (int b = 0; b < batch; ++b)
-    for (int d = 0; d < 3; ++d) {
-      const int a = ops[b].src_axis[d];
-      v.from[b][a] = (uint8_t)d, v.flip[b][a] = ops[b].flip[d] ? 1 : 0;
-    }
-  hipStream_t st = (hipStream_t)stream;
-  GatherGeom g;
-  g.cin = cin, g.R = ring, g.Y = y, g.X = x, g.pz = pz, g.py = py, g.px = px, g.pxq = (px + 3) / 4;
-  g.div = in_dtype == RX_SW_U8 ? 255.f : in_dtype == RX_SW_U16 ? 65535.f : 0.f;
-  g.total = (long)batch * cin * pz * py * g.pxq;
-  const dim3 grid((unsigned)((g.total + RX_SW_BLOCK - 1) / RX_SW_BLOCK));
-  if (in_dtype == RX_SW_U8)
-    hipLaunchKernelGGL(sw_gather_geom_kernel<uint8_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint8_t*)slab, out, g, p, v);
-  else if (in_dtype == RX_SW_U16)
-    hipLaunchKernelGGL(sw_gather_geom_kernel<uint16_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint16_t*)slab, out, g, p, v);
-  else
-    hipLaunchKernelGGL(sw_gather_geom_kernel<float>, grid, dim3(RX_SW_BLOCK), 0, st, (const float*)slab, out, g, p, v);
-  if (norm == RX_SW_ZSCORE) {      // the statistics of the transformed patch: the same multiset of values as the patch itself
-    const int chunks = sw_stat_chunks(n);
-    hipLaunchKernelGGL(sw_stat_partial_kernel, dim3(chunks, batch), dim3(RX_SW_BLOCK), 0, st, (const float*)out, n, (double*)ws);
-    long gx = (n / 4 + RX_SW_BLOCK - 1) / RX_SW_BLOCK;
-    gx = gx < 1 ? 1 : gx > 1024 ? 1024 : gx;
-    hipLaunchKernelGGL(sw_standardize_kernel, dim3((unsigned)gx, batch), dim3(RX_SW_BLOCK), 0, st, out, n, (const double*)ws, chunks);
-  }
-  RX_CHECK_LAUNCH("rx_sw_gather_geom");
-  return RX_OK;
+  return sw_gather_impl(in_dtype, slab, cin, ring, y, x, batch, origins, pz, py, px, norm, out, ws, ws_bytes, stream, true, ops, "rx_sw_gather_geom");
 }
 
 // ---- accumulate -----------------------------------------------------------------------------------------------------
@@ -311,6 +299,13 @@ struct AccGeom {
   int bx1;                  // exclusive x end of the box
   long total;               // box rows * bny * bnq
 };
+// GEOM: slot b's destination local voxel (lz, ly, lx) reads the logit at base + lz * sz + ly * sy + lx * sx of one channel volume;
+// destination channel ch of a `vector` task takes the ACTIVATED view-frame channel ch[ch], its sign bit flipped where bit ch of neg is
+// set.  The weight stays in the destination frame.
+struct SwAccViews {
+  RxGeomView s[RX_SW_MAXB];
+  int vector;
+};
 
 __device__ inline float sw_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 
@@ -320,10 +315,25 @@ __device__ inline int sw_local(const AccGeom& g, const SwPatches& p, int b, int 
   return (lz >= 0 && lz < g.pz && ly >= 0 && ly < g.py && lx >= 0 && lx < g.px) ? (lz * g.py + ly) * g.px + lx : -1;
 }
 
-template <bool VEC>
+// channel ch of one patch's logits `lb` (c channel volumes of pvol) at offset l, activated over the channels of that voxel
+__device__ inline float sw_activate(const float* __restrict__ lb, long pvol, int c, int act, int ch, int l) {
+  float pr = lb[ch * pvol + l];
+  if (act == RX_ACT_SIGMOID) {
+    pr = sw_sigmoid(pr);
+  } else if (act == RX_ACT_SOFTMAX) {   // torch.softmax over the channels: exp(x - max) / sum exp(x - max)
+    float mx = lb[l];
+    for (int k = 1; k < c; ++k) mx = fmaxf(mx, lb[k * pvol + l]);
+    float den = 0.f;
+    for (int k = 0; k < c; ++k) den = den + expf(lb[k * pvol + l] - mx);
+    pr = expf(pr - mx) / den;
+  }
+  return pr;
+}
+
+template <bool VEC, bool GEOM>
 __global__ __launch_bounds__(RX_SW_BLOCK) void sw_accumulate_kernel(const float* __restrict__ logits, const float* __restrict__ w,
                                                                     float* __restrict__ sum, float* __restrict__ wsum, AccGeom g,
-                                                                    SwPatches p) {
+                                                                    SwPatches p, SwTable<GEOM, SwAccViews> v) {
   const long q = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x;
   if (q >= g.total) return;
   const int xq = (int)(q % g.bnq);
@@ -335,266 +345,116 @@ __global__ __launch_bounds__(RX_SW_BLOCK) void sw_accumulate_kernel(const float*
   const long pvol = (long)g.pz * g.py * g.px;
   // quads that straddle the box edge: only voxels inside [bx0, bx1) are read and written on the scalar path; on the vector path
   // the whole quad is inside the row (X % 4 == 0) and voxels no patch covers are written back unchanged
+  const int nx = g.bx1 - x0;
+  float a[4];
   if (wsum) {
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (VEC) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wsum + base);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = v[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (x0 + i < g.bx1) a[i] = wsum[base + i];
-    }
+    sw_load_quad<VEC>(wsum + base, nx, a);
     for (int b = 0; b < g.npatch; ++b)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int l = sw_local(g, p, b, z, y, x0 + i);
         if (l >= 0) a[i] = a[i] + w[l];
       }
-    if (VEC) {
-      *reinterpret_cast<f32x4*>(wsum + base) = f32x4{a[0], a[1], a[2], a[3]};
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (x0 + i < g.bx1) wsum[base + i] = a[i];
-    }
+    sw_store_quad<VEC>(wsum + base, nx, a);
   }
   for (int ch = 0; ch < g.c; ++ch) {
     float* sp = sum + ch * cstride + base;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (VEC) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(sp);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = v[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (x0 + i < g.bx1) a[i] = sp[i];
-    }
+    sw_load_quad<VEC>(sp, nx, a);
     for (int b = 0; b < g.npatch; ++b) {
       const float* lb = logits + (long)b * g.c * pvol;
+      // the logit of a destination voxel: without records at the weight's offset, channel ch, as it is
+      int chs = ch, row = 0, sx = 0;
+      uint32_t sign = 0u;
+      if constexpr (GEOM) {
+        const RxGeomView& s = v.s[b];
+        if (v.vector) {
+          chs = ch == 0 ? s.ch[0] : ch == 1 ? s.ch[1] : s.ch[2];
+          sign = ((s.neg >> ch) & 1u) << 31;
+        }
+        row = s.base + (z - p.oz[b]) * s.sz + (y - p.oy[b]) * s.sy, sx = s.sx;      // offset of destination x = ox[b], step along x
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int l = sw_local(g, p, b, z, y, x0 + i);
         if (l < 0) continue;
-        float pr = lb[ch * pvol + l];
-        if (g.act == RX_ACT_SIGMOID) {
-          pr = sw_sigmoid(pr);
-        } else if (g.act == RX_ACT_SOFTMAX) {   // torch.softmax over the channels: exp(x - max) / sum exp(x - max)
-          float mx = lb[l];
-          for (int k = 1; k < g.c; ++k) mx = fmaxf(mx, lb[k * pvol + l]);
-          float den = 0.f;
-          for (int k = 0; k < g.c; ++k) den = den + expf(lb[k * pvol + l] - mx);
-          pr = expf(pr - mx) / den;
-        }
+        int li = l;
+        if constexpr (GEOM) li = row + (x0 + i - p.ox[b]) * sx;
+        float pr = sw_activate(lb, pvol, g.c, g.act, chs, li);
+        if constexpr (GEOM) pr = __uint_as_float(__float_as_uint(pr) ^ sign);   // IEEE negation: 0.0 becomes -0.0
         a[i] = a[i] + w[l] * pr;
       }
     }
-    if (VEC) {
-      *reinterpret_cast<f32x4*>(sp) = f32x4{a[0], a[1], a[2], a[3]};
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (x0 + i < g.bx1) sp[i] = a[i];
-    }
+    sw_store_quad<VEC>(sp, nx, a);
   }
+}
+
+// the least and the greatest origin per axis of the first `valid` patches
+struct SwBox {
+  int z0, z1, y0, y1, x0, x1;
+};
+static SwBox sw_bbox(const SwPatches& p, int valid) {
+  SwBox k = {p.oz[0], p.oz[0], p.oy[0], p.oy[0], p.ox[0], p.ox[0]};
+  for (int b = 1; b < valid; ++b) {
+    k.z0 = p.oz[b] < k.z0 ? p.oz[b] : k.z0, k.z1 = p.oz[b] > k.z1 ? p.oz[b] : k.z1;
+    k.y0 = p.oy[b] < k.y0 ? p.oy[b] : k.y0, k.y1 = p.oy[b] > k.y1 ? p.oy[b] : k.y1;
+    k.x0 = p.ox[b] < k.x0 ? p.ox[b] : k.x0, k.x1 = p.ox[b] > k.x1 ? p.ox[b] : k.x1;
+  }
+  return k;
+}
+
+// `geom`, `who`: as sw_gather_impl.  All `batch` records are checked, the first `valid` are lowered.
+static int sw_accumulate_impl(const float* logits, int batch, int valid, int c, int pz, int py, int px, const int32_t* origins, int act,
+                              const float* weight, float* sum, float* wsum, int ring, int y, int x, void* stream, bool geom,
+                              const rx_geom_sample* ops, int vector, const char* who) {
+  if (!logits || !weight || !sum || c < 1 || ring < 1 || y < 1 || x < 1 || valid < 0 || valid > batch)
+    RX_FAIL(RX_EINVAL, "%s: bad arguments", who);
+  if (act != RX_ACT_NONE && act != RX_ACT_SIGMOID && act != RX_ACT_SOFTMAX) RX_FAIL(RX_EINVAL, "%s: unknown activation %d", who, act);
+  if (geom && vector && c != 3) RX_FAIL(RX_EINVAL, "%s: a vector task has 3 channels, not %d", who, c);
+  SwPatches p;
+  if (int rc = sw_patches(origins, batch, ring, y, x, pz, py, px, p, who)) return rc;
+  if (geom) {
+    if (int rc = sw_records(ops, batch, pz, py, px, who)) return rc;
+    if ((long)c * pz * py * px > 0x7fffffffL) RX_FAIL(RX_EINVAL, "%s: c * pz * py * px must stay below 2^31", who);
+  }
+  if (valid == 0) return RX_OK;
+  const SwBox k = sw_bbox(p, valid);
+  // every row of the box must own a ring row of its own: rows [z0, z1 + pz) are live together
+  if (k.z1 + pz - k.z0 > ring) RX_FAIL(RX_EINVAL, "%s: patches span %d rows, the ring holds %d", who, k.z1 + pz - k.z0, ring);
+  const bool vec = (x & 3) == 0 && ((uintptr_t)sum & 15) == 0 && (!wsum || ((uintptr_t)wsum & 15) == 0);
+  AccGeom g;
+  g.c = c, g.pz = pz, g.py = py, g.px = px, g.R = ring, g.Y = y, g.X = x, g.act = act, g.npatch = valid;
+  g.bz0 = k.z0, g.by0 = k.y0, g.bx0 = vec ? (k.x0 & ~3) : k.x0, g.bx1 = k.x1 + px;
+  g.bny = k.y1 + py - k.y0, g.bnq = (g.bx1 - g.bx0 + 3) / 4;
+  g.total = (long)(k.z1 + pz - k.z0) * g.bny * g.bnq;
+  const dim3 grid((unsigned)((g.total + RX_SW_BLOCK - 1) / RX_SW_BLOCK));
+  hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto kernel, const auto& table) {
+    hipLaunchKernelGGL(kernel, grid, dim3(RX_SW_BLOCK), 0, st, logits, weight, sum, wsum, g, p, table);
+  };
+  if (geom) {
+    SwAccViews v;
+    memset(&v, 0, sizeof(v));
+    for (int b = 0; b < valid; ++b) v.s[b] = rx_geom_lower(ops[b], pz, py, px);
+    v.vector = vector ? 1 : 0;
+    if (vec) launch(sw_accumulate_kernel<true, true>, v);
+    else launch(sw_accumulate_kernel<false, true>, v);
+  } else {
+    if (vec) launch(sw_accumulate_kernel<true, false>, SwNone{});
+    else launch(sw_accumulate_kernel<false, false>, SwNone{});
+  }
+  RX_CHECK_LAUNCH(who);
+  return RX_OK;
 }
 
 extern "C" int rx_sw_accumulate(const float* logits, int batch, int valid, int c, int pz, int py, int px, const int32_t* origins,
                                 int act, const float* weight, float* sum, float* wsum, int ring, int y, int x, void* stream) {
-  if (!logits || !weight || !sum || c < 1 || ring < 1 || y < 1 || x < 1 || valid < 0 || valid > batch)
-    RX_FAIL(RX_EINVAL, "rx_sw_accumulate: bad arguments");
-  if (act != RX_ACT_NONE && act != RX_ACT_SIGMOID && act != RX_ACT_SOFTMAX) RX_FAIL(RX_EINVAL, "rx_sw_accumulate: unknown activation %d", act);
-  SwPatches p;
-  if (int rc = sw_patches(origins, batch, ring, y, x, pz, py, px, p, "rx_sw_accumulate")) return rc;
-  if (valid == 0) return RX_OK;
-  AccGeom g;
-  g.c = c, g.pz = pz, g.py = py, g.px = px, g.R = ring, g.Y = y, g.X = x, g.act = act, g.npatch = valid;
-  int z0 = p.oz[0], z1 = p.oz[0], y0 = p.oy[0], y1 = p.oy[0], x0 = p.ox[0], x1 = p.ox[0];
-  for (int b = 1; b < valid; ++b) {
-    z0 = p.oz[b] < z0 ? p.oz[b] : z0, z1 = p.oz[b] > z1 ? p.oz[b] : z1;
-    y0 = p.oy[b] < y0 ? p.oy[b] : y0, y1 = p.oy[b] > y1 ? p.oy[b] : y1;
-    x0 = p.ox[b] < x0 ? p.ox[b] : x0, x1 = p.ox[b] > x1 ? p.ox[b] : x1;
-  }
-  // every row of the box must own a ring row of its own: rows [z0, z1 + pz) are live together
-  if (z1 + pz - z0 > ring) RX_FAIL(RX_EINVAL, "rx_sw_accumulate: patches span %d rows, the ring holds %d", z1 + pz - z0, ring);
-  const bool vec = (x & 3) == 0 && ((uintptr_t)sum & 15) == 0 && (!wsum || ((uintptr_t)wsum & 15) == 0);
-  g.bz0 = z0, g.by0 = y0, g.bx0 = vec ? (x0 & ~3) : x0, g.bx1 = x1 + px;
-  g.bny = y1 + py - y0, g.bnq = (g.bx1 - g.bx0 + 3) / 4;
-  g.total = (long)(z1 + pz - z0) * g.bny * g.bnq;
-  const dim3 grid((unsigned)((g.total + RX_SW_BLOCK - 1) / RX_SW_BLOCK));
-  hipStream_t st = (hipStream_t)stream;
-  if (vec)
-    hipLaunchKernelGGL(sw_accumulate_kernel<true>, grid, dim3(RX_SW_BLOCK), 0, st, logits, weight, sum, wsum, g, p);
-  else
-    hipLaunchKernelGGL(sw_accumulate_kernel<false>, grid, dim3(RX_SW_BLOCK), 0, st, logits, weight, sum, wsum, g, p);
-  RX_CHECK_LAUNCH("rx_sw_accumulate");
-  return RX_OK;
-}
-
-// ---- accumulate of a transformed prediction (test-time augmentation) ----------------------------------------------------------
-// slot b: destination local voxel (lz, ly, lx) reads the logit at base + lz * sz + ly * sy + lx * sx of one channel volume (the
-// record as a base and signed strides, as rx_geom_apply turns it); destination channel ch of a vector task takes the ACTIVATED
-// view-frame channel ch[ch], its sign bit flipped where bit ch of neg is set.  The weight stays in the destination frame.
-struct SwAccView {
-  int32_t base, sz, sy, sx;
-  uint8_t ch[3], neg;
-};
-struct SwAccViews {
-  SwAccView s[RX_SW_MAXB];
-};
-
-// weight index (lz*py + ly)*px + lx of voxel (z, y, x) in slot b, or -1 outside it; `li` receives the logit offset
-__device__ inline int sw_local_geom(const AccGeom& g, const SwPatches& p, const SwAccView& s, int b, int z, int y, int x, int& li) {
-  const int lz = z - p.oz[b], ly = y - p.oy[b], lx = x - p.ox[b];
-  if (!(lz >= 0 && lz < g.pz && ly >= 0 && ly < g.py && lx >= 0 && lx < g.px)) return -1;
-  li = s.base + lz * s.sz + ly * s.sy + lx * s.sx;
-  return (lz * g.py + ly) * g.px + lx;
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(RX_SW_BLOCK) void sw_accumulate_geom_kernel(const float* __restrict__ logits, const float* __restrict__ w,
-                                                                         float* __restrict__ sum, float* __restrict__ wsum, AccGeom g,
-                                                                         SwPatches p, SwAccViews v, int vector) {
-  const long q = (long)blockIdx.x * RX_SW_BLOCK + threadIdx.x;
-  if (q >= g.total) return;
-  const int xq = (int)(q % g.bnq);
-  const int yy = (int)((q / g.bnq) % g.bny);
-  const int z = g.bz0 + (int)(q / ((long)g.bnq * g.bny));
-  const int y = g.by0 + yy, x0 = g.bx0 + 4 * xq;
-  const long plane = (long)g.Y * g.X, cstride = (long)g.R * plane;
-  const long base = (long)(z % g.R) * plane + (long)y * g.X + x0;
-  const long pvol = (long)g.pz * g.py * g.px;
-  if (wsum) {
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (VEC) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(wsum + base);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = t[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (x0 + i < g.bx1) a[i] = wsum[base + i];
-    }
-    for (int b = 0; b < g.npatch; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int l = sw_local(g, p, b, z, y, x0 + i);
-        if (l >= 0) a[i] = a[i] + w[l];
-      }
-    if (VEC) {
-      *reinterpret_cast<f32x4*>(wsum + base) = f32x4{a[0], a[1], a[2], a[3]};
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (x0 + i < g.bx1) wsum[base + i] = a[i];
-    }
-  }
-  for (int ch = 0; ch < g.c; ++ch) {
-    float* sp = sum + ch * cstride + base;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (VEC) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(sp);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = t[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (x0 + i < g.bx1) a[i] = sp[i];
-    }
-    for (int b = 0; b < g.npatch; ++b) {
-      const SwAccView& s = v.s[b];
-      const float* lb = logits + (long)b * g.c * pvol;
-      int chs = ch;
-      uint32_t sign = 0u;
-      if (vector) {
-        chs = ch == 0 ? s.ch[0] : ch == 1 ? s.ch[1] : s.ch[2];
-        sign = (uint32_t)((s.neg >> ch) & 1) << 31;
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int li = 0;
-        const int l = sw_local_geom(g, p, s, b, z, y, x0 + i, li);
-        if (l < 0) continue;
-        float pr = lb[chs * pvol + li];
-        if (g.act == RX_ACT_SIGMOID) {
-          pr = sw_sigmoid(pr);
-        } else if (g.act == RX_ACT_SOFTMAX) {   // over the view-frame channels of the source voxel
-          float mx = lb[li];
-          for (int k = 1; k < g.c; ++k) mx = fmaxf(mx, lb[k * pvol + li]);
-          float den = 0.f;
-          for (int k = 0; k < g.c; ++k) den = den + expf(lb[k * pvol + li] - mx);
-          pr = expf(pr - mx) / den;
-        }
-        pr = __uint_as_float(__float_as_uint(pr) ^ sign);   // IEEE negation: 0.0 becomes -0.0
-        a[i] = a[i] + w[l] * pr;
-      }
-    }
-    if (VEC) {
-      *reinterpret_cast<f32x4*>(sp) = f32x4{a[0], a[1], a[2], a[3]};
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (x0 + i < g.bx1) sp[i] = a[i];
-    }
-  }
+  return sw_accumulate_impl(logits, batch, valid, c, pz, py, px, origins, act, weight, sum, wsum, ring, y, x, stream, false, nullptr, 0, "rx_sw_accumulate");
 }
 
 extern "C" int rx_sw_accumulate_geom(const float* logits, int batch, int valid, int c, int pz, int py, int px, const int32_t* origins,
                                      const rx_geom_sample* ops, int vector, int act, const float* weight, float* sum, float* wsum,
                                      int ring, int y, int x, void* stream) {
-  if (!logits || !weight || !sum || c < 1 || ring < 1 || y < 1 || x < 1 || valid < 0 || valid > batch)
-    RX_FAIL(RX_EINVAL, "rx_sw_accumulate_geom: bad arguments");
-  if (act != RX_ACT_NONE && act != RX_ACT_SIGMOID && act != RX_ACT_SOFTMAX)
-    RX_FAIL(RX_EINVAL, "rx_sw_accumulate_geom: unknown activation %d", act);
-  if (vector && c != 3) RX_FAIL(RX_EINVAL, "rx_sw_accumulate_geom: a vector task has 3 channels, not %d", c);
-  SwPatches p;
-  if (int rc = sw_patches(origins, batch, ring, y, x, pz, py, px, p, "rx_sw_accumulate_geom")) return rc;
-  if (int rc = sw_check_ops(ops, batch, pz, py, px, "rx_sw_accumulate_geom")) return rc;
-  if ((long)c * pz * py * px > 0x7fffffffL) RX_FAIL(RX_EINVAL, "rx_sw_accumulate_geom: c * pz * py * px must stay below 2^31");
-  if (valid == 0) return RX_OK;
-  AccGeom g;
-  g.c = c, g.pz = pz, g.py = py, g.px = px, g.R = ring, g.Y = y, g.X = x, g.act = act, g.npatch = valid;
-  int z0 = p.oz[0], z1 = p.oz[0], y0 = p.oy[0], y1 = p.oy[0], x0 = p.ox[0], x1 = p.ox[0];
-  for (int b = 1; b < valid; ++b) {
-    z0 = p.oz[b] < z0 ? p.oz[b] : z0, z1 = p.oz[b] > z1 ? p.oz[b] : z1;
-    y0 = p.oy[b] < y0 ? p.oy[b] : y0, y1 = p.oy[b] > y1 ? p.oy[b] : y1;
-    x0 = p.ox[b] < x0 ? p.ox[b] : x0, x1 = p.ox[b] > x1 ? p.ox[b] : x1;
-  }
-  if (z1 + pz - z0 > ring) RX_FAIL(RX_EINVAL, "rx_sw_accumulate_geom: patches span %d rows, the ring holds %d", z1 + pz - z0, ring);
-  SwAccViews v;
-  memset(&v, 0, sizeof(v));
-  const int ext[3] = {pz, py, px};
-  const int stride[3] = {py * px, px, 1};
-  for (int b = 0; b < valid; ++b) {
-    const rx_geom_sample& s = ops[b];
-    SwAccView& d = v.s[b];
-    int32_t sd[3];
-    for (int ax = 0; ax < 3; ++ax) {
-      const int st_in = stride[s.src_axis[ax]];
-      sd[ax] = s.flip[ax] ? -st_in : st_in;
-      if (s.flip[ax]) d.base += (ext[ax] - 1) * st_in;
-    }
-    d.sz = sd[0], d.sy = sd[1], d.sx = sd[2];
-    for (int k = 0; k < 3; ++k) {
-      d.ch[k] = (uint8_t)s.ch_src[k];
-      if (s.ch_neg[k]) d.neg |= (uint8_t)(1u << k);
-    }
-  }
-  const bool vec = (x & 3) == 0 && ((uintptr_t)sum & 15) == 0 && (!wsum || ((uintptr_t)wsum & 15) == 0);
-  g.bz0 = z0, g.by0 = y0, g.bx0 = vec ? (x0 & ~3) : x0, g.bx1 = x1 + px;
-  g.bny = y1 + py - y0, g.bnq = (g.bx1 - g.bx0 + 3) / 4;
-  g.total = (long)(z1 + pz - z0) * g.bny * g.bnq;
-  const dim3 grid((unsigned)((g.total + RX_SW_BLOCK - 1) / RX_SW_BLOCK));
-  hipStream_t st = (hipStream_t)stream;
-  const int vflag = vector ? 1 : 0;
-  if (vec)
-    hipLaunchKernelGGL(sw_accumulate_geom_kernel<true>, grid, dim3(RX_SW_BLOCK), 0, st, logits, weight, sum, wsum, g, p, v, vflag);
-  else
-    hipLaunchKernelGGL(sw_accumulate_geom_kernel<false>, grid, dim3(RX_SW_BLOCK), 0, st, logits, weight, sum, wsum, g, p, v, vflag);
-  RX_CHECK_LAUNCH("rx_sw_accumulate_geom");
-  return RX_OK;
+  return sw_accumulate_impl(logits, batch, valid, c, pz, py, px, origins, act, weight, sum, wsum, ring, y, x, stream, true, ops, vector, "rx_sw_accumulate_geom");
 }
 
 // ---- finalize -------------------------------------------------------------------------------------------------------
@@ -622,14 +482,8 @@ __global__ __launch_bounds__(RX_SW_BLOCK) void sw_finalize_kernel(float* __restr
   const long src = (long)((g.z0 + row) % g.R) * g.plane + v0, dst = (long)row * g.plane + v0;
   const long cs = (long)g.R * g.plane, os = (long)g.rows * g.plane;
   const int nv = g.plane - v0 < 4 ? (int)(g.plane - v0) : 4;
-  float wv[4] = {0.f, 0.f, 0.f, 0.f};
-  if (VEC) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(wsum + src);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wv[i] = t[i];
-  } else {
-    for (int i = 0; i < nv; ++i) wv[i] = wsum[src + i];
-  }
+  float wv[4];
+  sw_load_quad<VEC>(wsum + src, nv, wv);
   float mag[4] = {1.f, 1.f, 1.f, 1.f};
   if (g.blend == RX_SW_BLEND_UNIT) {   // sqrt(s0^2 + s1^2 + s2^2) + 1e-8, the oracle's order of operations
     for (int i = 0; i < nv; ++i) {
@@ -638,15 +492,9 @@ __global__ __launch_bounds__(RX_SW_BLOCK) void sw_finalize_kernel(float* __restr
     }
   }
   for (int ch = 0; ch < g.c; ++ch) {
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    float s[4];
     float* sp = sum + ch * cs + src;
-    if (VEC) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(sp);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) s[i] = t[i];
-    } else {
-      for (int i = 0; i < nv; ++i) s[i] = sp[i];
-    }
+    sw_load_quad<VEC>(sp, nv, s);
     float o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -683,10 +531,7 @@ __global__ __launch_bounds__(RX_SW_BLOCK) void sw_finalize_kernel(float* __restr
       else for (int i = 0; i < nv; ++i) fp[i] = (uint8_t)u[i];
     }
   }
-  if (wsum_out) {
-    if (VEC) *reinterpret_cast<f32x4*>(wsum_out + dst) = f32x4{wv[0], wv[1], wv[2], wv[3]};
-    else for (int i = 0; i < nv; ++i) wsum_out[dst + i] = wv[i];
-  }
+  if (wsum_out) sw_store_quad<VEC>(wsum_out + dst, nv, wv);
   if (g.reset == 2) {
     if (VEC) *reinterpret_cast<f32x4*>(wsum + src) = f32x4{0.f, 0.f, 0.f, 0.f};
     else for (int i = 0; i < nv; ++i) wsum[src + i] = 0.f;
@@ -842,12 +687,9 @@ extern "C" int rx_sw_occupancy(int in_dtype, const void* slab, int cin, int ring
     for (int i = 0; i < n; ++i) p.oz[i] = origins[3 * (i0 + i)], p.oy[i] = origins[3 * (i0 + i) + 1], p.ox[i] = origins[3 * (i0 + i) + 2];
     const dim3 grid((unsigned)chunks, (unsigned)n);
     unsigned long long* out = (unsigned long long*)counts + i0;
-    if (in_dtype == RX_SW_U8)
-      hipLaunchKernelGGL(sw_occupancy_kernel<uint8_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint8_t*)slab, g, p, out);
-    else if (in_dtype == RX_SW_U16)
-      hipLaunchKernelGGL(sw_occupancy_kernel<uint16_t>, grid, dim3(RX_SW_BLOCK), 0, st, (const uint16_t*)slab, g, p, out);
-    else
-      hipLaunchKernelGGL(sw_occupancy_kernel<float>, grid, dim3(RX_SW_BLOCK), 0, st, (const float*)slab, g, p, out);
+    sw_typed(in_dtype, slab, [&](auto* s) {
+      hipLaunchKernelGGL(sw_occupancy_kernel<SwElem<decltype(s)>>, grid, dim3(RX_SW_BLOCK), 0, st, s, g, p, out);
+    });
   }
   RX_CHECK_LAUNCH("rx_sw_occupancy");
   return RX_OK;

@@ -275,6 +275,22 @@ def test_device_geometry_draws_without_a_device():
         ops.geom_apply(torch.zeros(1, 1, 4, 4, 4), [G.GeomOp.identity()], False)
 
 
+def test_record_check_and_lowering_host_program(tmp_path):
+    """csrc/rx_geom_core.h is what rx_geom_apply, rx_sw_gather_geom and rx_sw_accumulate_geom check and lower a record with.  A
+    stand-alone C++ program (csrc/tools/geom_core_check.cpp) runs it over all 48 (src_axis, flip) records and three shapes against the
+    definition in include/rxunet.h, voxel by voxel, and over the malformed kinds, compiled with -fsanitize=address,undefined."""
+    import subprocess
+    csrc = os.path.join(ROOT, "multi-task-3d-resencoder-unet_amd", "csrc")
+    exe = str(tmp_path / "geom_core_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(csrc, "tools", "geom_core_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and not r.stderr, r.stdout[-1000:] + r.stderr[-3000:]
+    shapes = [(4, 4, 4), (3, 5, 5), (3, 4, 5)]
+    keep = [sum(op.preserves(s) for op in all_axis_ops()) for s in shapes]
+    assert keep == [48, 16, 8] and r.stdout.strip() == "accepted 48 16 8 of 48, 0 expectations failed"
+
+
 def test_rx_geom_apply_is_declared_and_exported():
     import ctypes
     import __graft_entry__

@@ -223,8 +223,49 @@ def test_accumulate_geom_overlapping_patches(X, act, vector, weights, pick):
     assert np.array_equal(s2.cpu().numpy().view(np.uint32), before.view(np.uint32))
 
 
+def test_refusals_name_the_entry_point_called_and_every_record_is_checked():
+    """the plain and the record forms share one host path each: a refusal still starts with the name of the entry point that was
+    called, and rx_sw_accumulate_geom still refuses a bad record in a slot at or beyond `valid`"""
+    L, lib = _lib()
+    G = _geo()
+    cin, R, Y, X, pz, py, px = 1, 8, 16, 20, 8, 8, 12
+    sp = L.stream_ptr()
+    slab = torch.zeros((cin, R, Y, X), dtype=torch.uint8, device="cuda")
+    out = torch.full((2, cin, pz, py, px), -7.0, dtype=torch.float32, device="cuda")
+    logits = torch.ones((2, 1, pz, py, px), dtype=torch.float32, device="cuda")
+    w = torch.ones((pz, py, px), dtype=torch.float32, device="cuda")
+    acc = torch.full((1, R, Y, X), -7.0, dtype=torch.float32, device="cuda")
+    wsum = torch.full((R, Y, X), -7.0, dtype=torch.float32, device="cuda")
+    ok = _rows([G.GeomOp(), G.flip_op(2)])
+    here, away = _org([(0, 0, 0), (0, 8, 8)]), _org([(0, 0, 0), (0, Y - py + 1, 0)])      # the second origin leaves the slab in y
+
+    def accumulate_geom(org, rows, valid=2):
+        return lib.rx_sw_accumulate_geom(logits.data_ptr(), 2, valid, 1, pz, py, px, org, rows, 0, 0, w.data_ptr(), acc.data_ptr(),
+                                         wsum.data_ptr(), R, Y, X, sp)
+    calls = {
+        "rx_sw_gather": lambda: lib.rx_sw_gather(0, slab.data_ptr(), cin, R, Y, X, 2, away, pz, py, px, 0, out.data_ptr(), None, 0, sp),
+        "rx_sw_gather_geom": lambda: lib.rx_sw_gather_geom(0, slab.data_ptr(), cin, R, Y, X, 2, away, ok, pz, py, px, 0, out.data_ptr(),
+                                                           None, 0, sp),
+        "rx_sw_accumulate": lambda: lib.rx_sw_accumulate(logits.data_ptr(), 2, 2, 1, pz, py, px, away, 0, w.data_ptr(), acc.data_ptr(),
+                                                         wsum.data_ptr(), R, Y, X, sp),
+        "rx_sw_accumulate_geom": lambda: accumulate_geom(away, ok),
+    }
+    for name, call in calls.items():
+        assert call() != 0, name
+        assert lib.rx_last_error().decode().startswith(name + ": patch 1 at "), (name, lib.rx_last_error())
+    bad = (ctypes.c_int32 * 24)(*(list(G.GeomOp().row()) + [0, 0, 2, 0, 0, 0, 0, 1, 2, 0, 0, 0]))      # slot 1: src_axis is no permutation
+    for valid in (1, 0):                                                    # slot 1 is at `valid`, then beyond it
+        assert accumulate_geom(here, bad, valid) != 0, valid
+        assert lib.rx_last_error().decode().startswith("rx_sw_accumulate_geom: slot 1: src_axis (0, 0, 2) "), lib.rx_last_error()
+    torch.cuda.synchronize()
+    assert (out == -7.0).all().item() and (acc == -7.0).all().item() and (wsum == -7.0).all().item()      # nothing was launched
+    assert accumulate_geom(here, ok, 1) == 0
+    torch.cuda.synchronize()
+    assert (acc[0, :pz, :py, :px] == -6.0).all().item() and (acc == -7.0).sum().item() == R * Y * X - pz * py * px
+
+
 # ---- end to end -----------------------------------------------------------------------------------------------------------------
-TASKS = {"sheet": {"channels": 1, "activation": "sigmoid"}, "normals": {"channels": 3, "activation": "none"}}
+TASKS ={"sheet": {"channels": 1, "activation": "sigmoid"}, "normals": {"channels": 3, "activation": "none"}}
 PATCH = (16, 16, 16)
 
 
