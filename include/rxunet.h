@@ -707,6 +707,49 @@ int rx_iso_emit(const uint8_t* values, int level, int z, int y, int x, int z_bas
                 int k_emit, int64_t v_skip, int64_t q_skip, int64_t vertex_base, int64_t n_vertices, int64_t n_quads, float* vertices,
                 int64_t* triangles, void* stream);
 
+/* ---- refinement of an indexed triangle mesh: canonical vertex adjacency, Taubin smoothing passes, area-weighted vertex normals (host
+ *      side postprocess/refine.py, whose adjacency_numpy, smooth_numpy and vertex_normals_numpy are the statements).  `vertices`:
+ *      float32 (x, y, z) triples; `triangles`: int64 id triples; at most RX_MESH_MAX_VERTICES vertices and RX_MESH_MAX_TRIANGLES
+ *      triangles, because ids, triangle indices and a vertex's corner count are held as int32.  A triangle with an id outside
+ *      [0, n_vertices) takes part in nothing and sets bit 0 of `flag` (caller-zeroed).  Every vertex owns the corner SLOTS
+ *      [face_offsets[v], face_offsets[v + 1]); slot s holds its triangle in faces[s] and the corner's two edge partners in raw[2 s],
+ *      raw[2 s + 1].  Every output has an explicit capacity outside which nothing is stored, and every list entry read back is
+ *      checked against its range before it is followed.  No float atomics; no allocation, copy or synchronisation.  RX_EINVAL
+ *      before anything is launched: null or misaligned pointers, sizes outside the limits, a non-finite factor, a negative clamp.
+ *      rx_mesh_count: counts[v] = the triangle corners at v (zeroed first; integer atomics).
+ *      rx_mesh_scan: offsets[i] = counts[0] + .. + counts[i - 1] for i = 0 .. n (n + 1 int64 values).  Up to three launches.
+ *      rx_mesh_fill: every corner takes the next slot of its vertex at `cursor` (n_vertices int32, zeroed first) and fills it;
+ *        `capacity`: the slots of `faces` (raw holds 2 * capacity).  Which slot a corner gets depends on arrival.
+ *      rx_mesh_canonical: per vertex, faces and raw of its slots sorted ascending; the distinct partners other than the vertex
+ *        itself moved to the front of its raw slots, degrees[v] their number; boundary[v] = some partner appeared exactly once.
+ *        After it, nothing depends on the order anything ran in.
+ *      rx_mesh_compact: neighbours[offsets[v] + r] = raw[2 * face_offsets[v] + r] for r < offsets[v + 1] - offsets[v], where
+ *        offsets = rx_mesh_scan(degrees); `capacity`: the entries of `neighbours`.
+ *      rx_mesh_check_vertices: bit 0 of `flag` is set when a coordinate is not finite.
+ *      rx_mesh_smooth_pass: out[v] = p + factor * (m - p), m = (sum of the neighbours' positions in list order) / float(degree), p
+ *        = positions[v]; with `origin`, each component then clamped to origin[v] -+ clamp.  A vertex of degree 0, or with
+ *        boundary[v] != 0 (`boundary` may be null: nothing is pinned), keeps p.  `out` is another buffer than `positions`.
+ *      rx_mesh_face_vectors: face_vectors[t] = cross(pb - pa, pc - pa) of triangle t = (a, b, c); (0, 0, 0) for a dropped one.
+ *      rx_mesh_vertex_normals: normals[v] = the sum of face_vectors over the vertex's slots in order, divided by its length
+ *        sqrt(x*x + y*y + z*z); (0, 0, 0) where that is 0.  `capacity`: the entries of `faces`. */
+#define RX_MESH_MAX_VERTICES 2147483646L
+#define RX_MESH_MAX_TRIANGLES 715827882L
+int rx_mesh_count(const int64_t* triangles, int64_t n_triangles, int64_t n_vertices, int32_t* counts, int32_t* flag, void* stream);
+int rx_mesh_scan(const int32_t* counts, int64_t n, int64_t* offsets, void* stream);
+int rx_mesh_fill(const int64_t* triangles, int64_t n_triangles, int64_t n_vertices, const int64_t* face_offsets, int32_t* cursor,
+                 int64_t capacity, int32_t* faces, int32_t* raw, void* stream);
+int rx_mesh_canonical(int64_t n_vertices, const int64_t* face_offsets, int64_t capacity, int32_t* faces, int32_t* raw, int32_t* degrees,
+                      uint8_t* boundary, void* stream);
+int rx_mesh_compact(int64_t n_vertices, const int64_t* face_offsets, const int32_t* raw, int64_t raw_capacity, const int64_t* offsets,
+                    int64_t capacity, int32_t* neighbours, void* stream);
+int rx_mesh_check_vertices(const float* vertices, int64_t n_vertices, int32_t* flag, void* stream);
+int rx_mesh_smooth_pass(const float* positions, const float* origin, int64_t n_vertices, const int64_t* offsets, const int32_t* neighbours,
+                        int64_t n_neighbours, const uint8_t* boundary, float factor, float clamp, float* out, void* stream);
+int rx_mesh_face_vectors(const float* vertices, int64_t n_vertices, const int64_t* triangles, int64_t n_triangles, float* face_vectors,
+                         void* stream);
+int rx_mesh_vertex_normals(int64_t n_vertices, const int64_t* face_offsets, const int32_t* faces, int64_t capacity, const float* face_vectors,
+                           int64_t n_triangles, float* normals, void* stream);
+
 /* ---- validation preview on the device: one panel of the debug GIF (host side training/visualization/preview.py, whose
  *      panel_numpy and minmax_numpy are the statements).  `src` is ONE sample's contiguous (c, z, h, w) block of `dtype` (rx_dtype),
  *      aligned to its element (a base that is not 16-byte aligned is fine).  c == 3 draws channels 0, 1, 2 into bytes 0, 1, 2 of

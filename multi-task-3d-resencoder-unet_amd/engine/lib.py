@@ -28,6 +28,7 @@ RX_AFFINE_CONSTANT, RX_AFFINE_CLAMP = 0, 1
 RX_EDT_NONE, RX_EDT_MAX_EXTENT = 1 << 30, 1024
 RX_CC_MAX_VOXELS = 2**31 - 2
 RX_ISO_MAX_EXTENT, RX_ISO_MAX_CELLS = 2**24 - 3, 2**31 - 2
+RX_MESH_MAX_VERTICES, RX_MESH_MAX_TRIANGLES = 2**31 - 2, (2**31 - 2) // 3
 
 
 class RxError(RuntimeError):
@@ -195,6 +196,15 @@ _SIGNATURES = {
     "rx_iso_scan": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "rx_iso_emit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64,
                             c_int64, c_void_p, c_void_p, c_void_p]),
+    "rx_mesh_count": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "rx_mesh_scan": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rx_mesh_fill": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "rx_mesh_canonical": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rx_mesh_compact": (c_int, [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rx_mesh_check_vertices": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rx_mesh_smooth_pass": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    "rx_mesh_face_vectors": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rx_mesh_vertex_normals": (c_int, [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "rx_preview_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int,
                                  c_void_p, c_void_p]),
     "rx_mesh_slice_keys": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -1,6 +1,10 @@
 """Post-processing on the device: connected components of a thresholded uint8 volume, their sizes, and the size filter
 (csrc/rx_components.hip; postprocess/components.py holds the numpy statements and the out-of-core driver), and the triangle mesh of
-a uint8 volume by surface nets (csrc/rx_isosurface.hip; postprocess/isosurface.py)."""
+a uint8 volume by surface nets (csrc/rx_isosurface.hip; postprocess/isosurface.py), and the refinement of such a mesh: canonical
+adjacency, Taubin smoothing, vertex normals (csrc/rx_meshrefine.hip; postprocess/refine.py)."""
+from ctypes import c_void_p
+from typing import NamedTuple
+
 import torch
 
 from .. import lib as _l
@@ -8,6 +12,7 @@ from ..lib import check, load, stream_ptr
 from .core import _ptr, device_batch, result_tensor, timed_bytes
 
 _CONNECTIVITY = (6, 18, 26)
+_F32_MAX = 3.4028234663852886e38      # a factor or a clamp must be finite as a float32
 
 
 def _volumes(fn, t, what, dtypes, statement):
@@ -162,4 +167,158 @@ def cc_filter(values, labels, sizes, min_voxels, out=None):
     timed_bytes("cc_filter", v.numel() * (1 + 4 + 1),
                 lambda: check(load().rx_cc_filter(_ptr(v), _ptr(lab), _ptr(sizes), min_voxels, n * c, voxels, _ptr(out), stream_ptr()),
                               "rx_cc_filter"))
+    return out
+
+
+# ---- mesh refinement (csrc/rx_meshrefine.hip; postprocess/refine.py) ----------------------------------------------------------------------------
+class MeshAdjacency(NamedTuple):
+    """what `mesh_adjacency` returns.  The first three are postprocess.adjacency_numpy's, with the ids as int32; the last two are the
+    triangles of the corners at each vertex, ascending (postprocess.refine.corner_faces_numpy), which the normals gather over."""
+    offsets: torch.Tensor          # int64 (V + 1,)
+    neighbours: torch.Tensor       # int32 (E,)
+    boundary: torch.Tensor         # uint8 (V,)
+    face_offsets: torch.Tensor     # int64 (V + 1,)
+    faces: torch.Tensor            # int32 (3 T,)
+
+
+def _mesh_triangles(fn, n_vertices, triangles):
+    if isinstance(n_vertices, bool) or not isinstance(n_vertices, int) or not 0 <= n_vertices <= _l.RX_MESH_MAX_VERTICES:
+        raise _l.RxError(f"{fn}: n_vertices {n_vertices!r} (an integer 0 .. 2^31 - 2: ids are held as int32)")
+    t = triangles
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _l.RxError(f"{fn}: `triangles` must be a device tensor (the host statement is postprocess.adjacency_numpy)")
+    if t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 3:
+        raise _l.RxError(f"{fn}: `triangles` must be an int64 (T, 3) tensor, got {t.dtype} {tuple(t.shape)}")
+    if t.shape[0] > _l.RX_MESH_MAX_TRIANGLES:
+        raise _l.RxError(f"{fn}: `triangles`: {t.shape[0]} of them (at most (2^31 - 2) / 3: a vertex's corners are counted in int32)")
+    if t.shape[0] and n_vertices == 0:
+        raise _l.RxError(f"{fn}: `triangles` name vertices of a mesh that has none")
+    return t.contiguous()
+
+
+def _mesh_vertices(fn, vertices):
+    v = vertices
+    if not isinstance(v, torch.Tensor) or not v.is_cuda:
+        raise _l.RxError(f"{fn}: `vertices` must be a device tensor (the host statement is postprocess.refine_numpy)")
+    if v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3:
+        raise _l.RxError(f"{fn}: `vertices` must be a float32 (V, 3) tensor, got {v.dtype} {tuple(v.shape)}")
+    return v.contiguous()
+
+
+def _mesh_finite(fn, v):
+    """one launch and one small device-to-host read: refuses `vertices` that hold a NaN or an infinity"""
+    flag = torch.zeros(1, dtype=torch.int32, device=v.device)
+    check(load().rx_mesh_check_vertices(_ptr(v), v.shape[0], _ptr(flag), stream_ptr()), "rx_mesh_check_vertices")
+    if flag.item():
+        raise _l.RxError(f"{fn}: `vertices` hold a NaN or an infinity")
+
+
+def _mesh_adjacency_of(fn, adjacency, n_vertices, t):
+    """`adjacency` (None: built here) checked against the mesh's sizes"""
+    if adjacency is None:
+        return mesh_adjacency(n_vertices, t)
+    a = adjacency
+    want = ((n_vertices + 1,), torch.int64), (None, torch.int32), ((n_vertices,), torch.uint8), ((n_vertices + 1,), torch.int64), ((3 * t.shape[0],), torch.int32)
+    if not isinstance(a, MeshAdjacency) or any(not isinstance(x, torch.Tensor) or x.device != t.device or x.dtype != d or not x.is_contiguous()
+                                               or x.dim() != 1 or (s is not None and tuple(x.shape) != s) for x, (s, d) in zip(a, want)):
+        raise _l.RxError(f"{fn}: `adjacency` must be what mesh_adjacency({n_vertices}, triangles) returned for this mesh")
+    return a
+
+
+def mesh_adjacency(n_vertices, triangles):
+    """the canonical vertex adjacency of an int64 (T, 3) device tensor of triangles over `n_vertices` vertices -> MeshAdjacency
+    (postprocess.adjacency_numpy and corner_faces_numpy are the statements).  Count (integer atomics), scan, fill at a cursor,
+    canonicalise per vertex, scan, compact: after the canonicalising pass nothing of the arrival order is left, so two runs give
+    the same bytes.  One small device-to-host read (the id check's flag and the number of neighbours, which sizes the result).  No
+    launch where `n_vertices` or T is 0."""
+    fn = "mesh_adjacency"
+    t = _mesh_triangles(fn, n_vertices, triangles)
+    V, T, dev = n_vertices, t.shape[0], t.device
+    if V == 0 or T == 0:
+        z = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+        return MeshAdjacency(z, torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(V, dtype=torch.uint8, device=dev), z.clone(),
+                             torch.zeros(0, dtype=torch.int32, device=dev))
+    so, st = load(), stream_ptr()
+    counts = torch.empty(V, dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    foff = torch.empty(V + 1, dtype=torch.int64, device=dev)
+    faces = torch.empty(3 * T, dtype=torch.int32, device=dev)
+    raw = torch.empty(6 * T, dtype=torch.int32, device=dev)
+    boundary = torch.empty(V, dtype=torch.uint8, device=dev)
+    offsets = torch.empty(V + 1, dtype=torch.int64, device=dev)
+    timed_bytes("mesh_count", T * 24 + 3 * T * 4, lambda: check(so.rx_mesh_count(_ptr(t), T, V, _ptr(counts), _ptr(flag), st), "rx_mesh_count"))
+    timed_bytes("mesh_scan", V * 12, lambda: check(so.rx_mesh_scan(_ptr(counts), V, _ptr(foff), st), "rx_mesh_scan"))
+    # `counts` is free again: it serves as the fill cursor, then holds the degrees
+    timed_bytes("mesh_fill", T * 24 + 3 * T * (16 + 4 + 12),
+                lambda: check(so.rx_mesh_fill(_ptr(t), T, V, _ptr(foff), _ptr(counts), 3 * T, _ptr(faces), _ptr(raw), st), "rx_mesh_fill"))
+    timed_bytes("mesh_canonical", 2 * 3 * T * 12 + V * (8 + 4 + 1),
+                lambda: check(so.rx_mesh_canonical(V, _ptr(foff), 3 * T, _ptr(faces), _ptr(raw), _ptr(counts), _ptr(boundary), st), "rx_mesh_canonical"))
+    timed_bytes("mesh_scan", V * 12, lambda: check(so.rx_mesh_scan(_ptr(counts), V, _ptr(offsets), st), "rx_mesh_scan"))
+    bad, E = torch.cat([flag.to(torch.int64), offsets[V:]]).tolist()      # the one device-to-host read
+    if bad:
+        raise _l.RxError(f"{fn}: `triangles` name a vertex outside 0 .. {V - 1}")
+    nbr = torch.empty(E, dtype=torch.int32, device=dev)
+    timed_bytes("mesh_compact", V * 24 + E * 8,
+                lambda: check(so.rx_mesh_compact(V, _ptr(foff), _ptr(raw), 3 * T, _ptr(offsets), E, _ptr(nbr), st), "rx_mesh_compact"))
+    return MeshAdjacency(offsets, nbr, boundary, foff, faces)
+
+
+def mesh_smooth(vertices, triangles, iterations, lam=0.5, mu=-0.53, clamp=None, pin_boundary=True, adjacency=None):
+    """Taubin smoothing of a float32 (V, 3) device tensor of vertices over int64 (T, 3) triangles -> a new float32 (V, 3) tensor, bit
+    for bit postprocess.smooth_numpy: every iteration is one pass with factor `lam`, then one with `mu` (None: `lam` passes only);
+    `clamp` keeps every component within that distance of the input; `pin_boundary` keeps boundary vertices where they are.  One
+    launch per pass over two ping-pong buffers; a vertex gathers its neighbours in list order; no atomics.  `adjacency`: what
+    `mesh_adjacency` returned for this mesh (None: built here).  One small device-to-host read for the finiteness check."""
+    fn = "mesh_smooth"
+    v = _mesh_vertices(fn, vertices)
+    t = _mesh_triangles(fn, v.shape[0], triangles)
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 0:
+        raise _l.RxError(f"{fn}: `iterations` {iterations!r} (an integer >= 0)")
+    for name, x in (("lam", lam), ("mu", mu)):
+        if (x is not None or name == "lam") and (isinstance(x, bool) or not isinstance(x, (int, float))
+                                                 or not abs(x) <= _F32_MAX):
+            raise _l.RxError(f"{fn}: `{name}` {x!r} (a finite number)")
+    if clamp is not None and (isinstance(clamp, bool) or not isinstance(clamp, (int, float)) or not 0 <= clamp <= _F32_MAX):
+        raise _l.RxError(f"{fn}: `clamp` {clamp!r} (a finite number >= 0, or None)")
+    V = v.shape[0]
+    if V == 0:
+        return v.clone()
+    _mesh_finite(fn, v)
+    if t.shape[0] == 0 or iterations == 0:
+        return v.clone()
+    a = _mesh_adjacency_of(fn, adjacency, V, t)
+    factors = [lam] if mu is None else [lam, mu]
+    bufs = [torch.empty_like(v), torch.empty_like(v)]
+    so, st, E, src = load(), stream_ptr(), a.neighbours.shape[0], v
+    origin = _ptr(v) if clamp is not None else c_void_p(0)
+    pin = _ptr(a.boundary) if pin_boundary else c_void_p(0)
+    for i in range(iterations * len(factors)):
+        dst, f = bufs[i % 2], factors[i % len(factors)]
+        timed_bytes("mesh_smooth_pass", V * (12 + 12 + 16 + 1) + E * (4 + 12) + (V * 12 if clamp is not None else 0),
+                    lambda: check(so.rx_mesh_smooth_pass(_ptr(src), origin, V, _ptr(a.offsets), _ptr(a.neighbours), E, pin, f,
+                                                         0.0 if clamp is None else clamp, _ptr(dst), st), "rx_mesh_smooth_pass"))
+        src = dst
+    return src
+
+
+def mesh_vertex_normals(vertices, triangles, adjacency=None):
+    """area-weighted vertex normals of a float32 (V, 3) / int64 (T, 3) device mesh -> float32 (V, 3), bit for bit
+    postprocess.vertex_normals_numpy: the face vectors cross(pb - pa, pc - pa) are stored by one pass, then every vertex sums those of
+    its corners over its sorted triangle list and normalises.  No float atomics.  `adjacency` as in `mesh_smooth`."""
+    fn = "mesh_vertex_normals"
+    v = _mesh_vertices(fn, vertices)
+    t = _mesh_triangles(fn, v.shape[0], triangles)
+    V, T = v.shape[0], t.shape[0]
+    if V == 0 or T == 0:
+        return torch.zeros_like(v)
+    _mesh_finite(fn, v)
+    a = _mesh_adjacency_of(fn, adjacency, V, t)
+    so, st = load(), stream_ptr()
+    fvec = torch.empty((T, 3), dtype=torch.float32, device=v.device)
+    out = torch.empty_like(v)
+    timed_bytes("mesh_face_vectors", T * (24 + 36 + 12),
+                lambda: check(so.rx_mesh_face_vectors(_ptr(v), V, _ptr(t), T, _ptr(fvec), st), "rx_mesh_face_vectors"))
+    timed_bytes("mesh_vertex_normals", V * (16 + 12) + 3 * T * (4 + 12),
+                lambda: check(so.rx_mesh_vertex_normals(V, _ptr(a.face_offsets), _ptr(a.faces), a.faces.shape[0], _ptr(fvec), T, _ptr(out), st),
+                              "rx_mesh_vertex_normals"))
     return out

@@ -792,6 +792,14 @@ def main(argv=None):
         for task in mesh["tasks"]:
             print(task, SurfaceMesher(mesh["level"], mesh["format"], None if gb is None else int(gb * 2**30)).run(store, task, mesh["source"]),
                   flush=True)
+    refine = (mgr.infer_postprocess or {}).get("refine")
+    if refine:      # after the mesher: it reads the file that has just been written
+        from .postprocess import MeshRefiner
+        gb = refine["max_device_gb"]
+        for task in refine["tasks"]:
+            print(task, MeshRefiner(refine["iterations"], refine["lam"], refine["mu"], refine["clamp"], refine["pin_boundary"], refine["normals"],
+                                    max_device_bytes=None if gb is None else int(gb * 2**30)).run(
+                                        os.path.join(store, f"{task}_{mesh['source']}.{mesh['format']}")), flush=True)
     return store
 
 

@@ -172,19 +172,22 @@ def _check_options(level, connectivity, min_voxels):
 
 def parse_config(block, targets, patch_size=None):
     """`inference_config.postprocess` -> None when absent, else {"components": {tasks, level, connectivity, min_voxels, write_labels,
-    max_device_gb}} and / or {"mesh": {tasks, source, level, format, max_device_gb}} (isosurface.parse_mesh_config), whichever the
-    block holds.  Unknown keys and bad values raise ValueError naming the key; `targets` is {task: {"channels": c, ...}}."""
+    max_device_gb}} and / or {"mesh": {tasks, source, level, format, max_device_gb}} (isosurface.parse_mesh_config) and / or
+    {"refine": {...}} (refine.parse_refine_config), whichever the block holds.  Unknown keys and bad values raise ValueError naming the key; `targets` is {task: {"channels": c, ...}}."""
     if block is None:
         return None
     if not isinstance(block, dict):
         raise ValueError(f"inference_config.postprocess: expected a mapping, got {block!r}")
     for k in block:
-        if k not in ("components", "mesh"):
-            raise ValueError(f"inference_config.postprocess.{k}: unknown key (components, mesh)")
+        if k not in ("components", "mesh", "refine"):
+            raise ValueError(f"inference_config.postprocess.{k}: unknown key (components, mesh, refine)")
     out = _parse_components(block["components"], targets, patch_size) if "components" in block else {}
     if "mesh" in block:
         from .isosurface import parse_mesh_config
         out["mesh"] = parse_mesh_config(block["mesh"], targets, patch_size, out["components"]["tasks"] if "components" in out else None)
+    if "refine" in block:      # a sibling of `mesh`, whose parsed dict stays as it is
+        from .refine import parse_refine_config
+        out["refine"] = parse_refine_config(block["refine"], out["mesh"]["tasks"] if "mesh" in out else None)
     return out or None
 
 

@@ -1,0 +1,116 @@
+"""The small meshes of the mesh-refinement tests, shared by the CPU tests (the statements' invariants), the GPU tests (ops.mesh_* against
+the statements) and, restated in C++, csrc/tools/meshrefine_host_check.cpp.  Each is chosen for a way the kernels can go wrong.
+
+The kernels run a thread per vertex or per triangle in workgroups of 256 and scan 1024 values per workgroup, so the vertex counts
+cross a wave (63, 64, 65), a workgroup (257) and two scan groups (2100); a vertex's lists live in global memory and are heap-sorted
+in place, so the fans go far past anything a thread could keep in registers or LDS."""
+import numpy as np
+
+import isosurface_cases as I
+
+F32 = np.float32
+SCAN_GROUP = 1024      # csrc/rx_meshrefine.hip: RX_MR_SCAN_GROUP
+COUNTS = (1, 63, 64, 65, 257, 2 * SCAN_GROUP + 52)
+FANS = (3, 8, 9, 300, 3000)
+GRID = (5, 7)      # rows, columns
+BALL = I.BALL
+
+
+def _positions(n, seed):
+    return np.random.default_rng(seed).uniform(-100, 100, (n, 3)).astype(F32)
+
+
+def grid_patch(ny=GRID[0], nx=GRID[1], z=3.0):
+    """an open ny x nx patch of unit squares in the plane z, each split along the same diagonal: border vertices are boundary, interior
+    ones have six neighbours placed symmetrically around them, so their neighbour sums and means are exact"""
+    j, i = np.indices((ny, nx))
+    v = np.stack([i.ravel(), j.ravel(), np.full(ny * nx, z)], 1).astype(F32)
+    a = (j[:-1, :-1] * nx + i[:-1, :-1]).ravel()
+    b, c, d = a + 1, a + nx, a + nx + 1
+    t = np.stack([np.stack([a, b, d], 1), np.stack([a, d, c], 1)], 1).reshape(-1, 3).astype(np.int64)
+    return v, t
+
+
+def grid_interior(ny=GRID[0], nx=GRID[1]):
+    j, i = np.indices((ny, nx))
+    return ((j > 0) & (j < ny - 1) & (i > 0) & (i < nx - 1)).ravel()
+
+
+def fan(degree, seed=0):
+    """a closed fan around vertex 0: `degree` neighbours and `degree` triangles at one vertex"""
+    i = np.arange(degree)
+    t = np.stack([np.zeros(degree, np.int64), 1 + i, 1 + (i + 1) % degree], 1).astype(np.int64)
+    return _positions(degree + 1, seed + degree), t
+
+
+def soup(n_vertices, seed=0):
+    """random triangles over `n_vertices` vertices: repeated ids, repeated triangles and unused vertices all happen"""
+    rng = np.random.default_rng(seed + n_vertices)
+    t = rng.integers(0, n_vertices, (2 if n_vertices == 1 else 2 * n_vertices, 3)).astype(np.int64)
+    return _positions(n_vertices, seed + 1), t
+
+
+def awkward():
+    """vertex 3 isolated; vertex 4 only in a degenerate triangle; (5, 5, 6) repeats an id; (0, 1, 2) appears twice and two more
+    triangles use its edge (0, 1), which so has multiplicity 4; three triangles on the edge (7, 8); the last id, V - 1 = 12, in use"""
+    t = np.array([[0, 1, 2], [0, 1, 2], [4, 4, 4], [5, 5, 6], [7, 8, 9], [7, 8, 10], [8, 7, 11], [12, 0, 9], [1, 0, 6], [0, 1, 9]], np.int64)
+    return _positions(13, 5), t
+
+
+def ball_mesh():
+    """the closed 2-manifold of isosurface_cases' graded ball, through the surface-nets statement"""
+    import mt3d_amd.postprocess as pp
+    return pp.surface_nets_numpy(I.ball(BALL["shape"], BALL["R"], BALL["centre"]), 127)
+
+
+def closed_meshes():
+    """the surface-nets meshes of a few volumes of tests/isosurface_cases.py: closed, not always manifold, degrees from 3 to 12 and more"""
+    import mt3d_amd.postprocess as pp
+    out = [("ball", ball_mesh())]
+    for shape, kind in (((9, 10, 12), "random50"), ((9, 10, 12), "checkerboard"), ((33, 17, 70), "slab"), ((5, 1, 3), "full")):
+        out.append((f"{'x'.join(map(str, shape))}-{kind}", pp.surface_nets_numpy(dict(I.volumes(shape, 127))[kind], 127)))
+    return out
+
+
+def shuffled(vertices, triangles, seed=11):
+    """the same mesh with its triangles in another order and the ids rotated within each"""
+    rng = np.random.default_rng(seed)
+    t = triangles[rng.permutation(len(triangles))]
+    r = rng.integers(0, 3, len(t))
+    return vertices, np.take_along_axis(t, (np.arange(3)[None, :] + r[:, None]) % 3, 1)
+
+
+_CASES = None
+
+
+def cases():
+    """[(id, vertices float32 (V, 3), triangles int64 (T, 3))]: every case, then every case once more shuffled.  Built once."""
+    global _CASES
+    if _CASES is None:
+        base = closed_meshes() + [("grid", grid_patch()), ("awkward", awkward())]
+        base += [(f"soup{n}", soup(n)) for n in COUNTS] + [(f"fan{d}", fan(d)) for d in FANS]
+        base.append(("no-triangles", (_positions(5, 9), np.zeros((0, 3), np.int64))))
+        _CASES = [(name, v, t) for name, (v, t) in base] + [(name + "-shuffled",) + shuffled(v, t) for name, (v, t) in base]
+    return _CASES
+
+
+def adjacency_sets(n_vertices, triangles):
+    """a plain Python restatement: (list of neighbour sets, boundary flags)"""
+    nbr, uses = [set() for _ in range(n_vertices)], {}
+    for tri in triangles.tolist():
+        for k in range(3):
+            a, b = tri[k], tri[(k + 1) % 3]
+            if a != b:
+                nbr[a].add(b)
+                nbr[b].add(a)
+                uses[(min(a, b), max(a, b))] = uses.get((min(a, b), max(a, b)), 0) + 1
+    boundary = np.zeros(n_vertices, np.uint8)
+    for (a, b), n in uses.items():
+        if n == 1:
+            boundary[a] = boundary[b] = 1
+    return nbr, boundary
+
+
+def enclosed_volume(vertices, triangles):
+    p = vertices[triangles].astype(np.float64)
+    return float(np.einsum("ij,ij->i", p[:, 0], np.cross(p[:, 1], p[:, 2])).sum() / 6)
