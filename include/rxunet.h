@@ -750,6 +750,53 @@ int rx_mesh_face_vectors(const float* vertices, int64_t n_vertices, const int64_
 int rx_mesh_vertex_normals(int64_t n_vertices, const int64_t* face_offsets, const int32_t* faces, int64_t capacity, const float* face_vectors,
                            int64_t n_triangles, float* normals, void* stream);
 
+/* ---- mesh decimation by vertex clustering on a uniform grid (host side postprocess/decimate.py, whose decimate_numpy is the
+ *      statement).  Sizes as in the refinement group above; n_vertices, n_clusters and n_triangles are at least 1 (the caller
+ *      handles empty meshes).  Counts, cursors, flags and list entries are int32, offsets are what rx_mesh_scan returns.  Every
+ *      call refuses with a status and a message before anything is launched: null or misaligned pointers, sizes outside the
+ *      limits, a cell that is not finite and > 0, a table capacity that is not a power of two above n_vertices.  No float
+ *      atomics; nothing is stored beyond a stated capacity; after the calls nothing depends on the order anything ran in.
+ *      rx_mesh_cluster_keys: keys[v] = ((k0 + 2^20) << 42) | ((k1 + 2^20) << 21) | (k2 + 2^20), k = floor(p / cell) per component;
+ *        bit 0 of `flag` is set, and the key is -1, where some |k| >= 2^20.
+ *      rx_mesh_cluster_assign: open-addressing table of `capacity` slots (table_keys int64, table_min int32, both cleared here),
+ *        claimed by 64-bit compare-and-swap with linear probing, at most `capacity` probes (bit 1 of `flag` on exhaustion);
+ *        slot_of[v] = the slot of v's key, table_min[slot] = the smallest id with that key, first[v] = v is that id.
+ *      rx_mesh_cluster_number: cluster_of[v] = rank[smallest id of v's slot], rank = rx_mesh_scan(first): the clusters numbered
+ *        by ascending smallest member; rank[n_vertices] is their number.
+ *      rx_mesh_cluster_count / _fill: the member counts (zeroed first), and the members of cluster c in
+ *        members[member_offsets[c] .. member_offsets[c + 1]) in arrival order (`cursor`: n_clusters int32, zeroed first).
+ *      rx_mesh_cluster_mean: per cluster its member list sorted ascending in place, then representatives[c] = (the sum of the
+ *        members' positions in that order, from 0) / float(n).
+ *      rx_mesh_cluster_nearest: best[c] = the minimum over members of (bits of d) << 32 | id, d = dx*dx + dy*dy + dz*dz to the cell
+ *        centre (float(k) + 0.5f) * cell; representatives[c] = the position of that id.
+ *      rx_mesh_cluster_remap: a triangle whose corners lie in three different clusters sets used[c] = 1 for each and adds 1 to
+ *        counts[its smallest cluster] (both zeroed first); bit 2 of `flag`: an id outside [0, n_vertices).
+ *      rx_mesh_cluster_unique: those triangles stored as (middle, largest, triangle) at entry_offsets = rx_mesh_scan(counts) of
+ *        their smallest cluster (`capacity` entries of three int32), each list sorted in place, keep[t] = 1 for the first entry
+ *        of every (middle, largest) run, 0 for every other triangle.
+ *      rx_mesh_cluster_emit: out_triangles[keep_offsets[t]] = used_offsets[cluster of each corner] for kept t, and
+ *        out_vertices[used_offsets[c]] = representatives[c] for used c, with the offsets rx_mesh_scan(keep) and rx_mesh_scan(used). */
+int rx_mesh_cluster_keys(const float* vertices, int64_t n_vertices, float cell, int64_t* keys, int32_t* flag, void* stream);
+int rx_mesh_cluster_assign(const int64_t* keys, int64_t n_vertices, int64_t capacity, int64_t* table_keys, int32_t* table_min, int32_t* slot_of,
+                           int32_t* first, int32_t* flag, void* stream);
+int rx_mesh_cluster_number(int64_t n_vertices, const int32_t* slot_of, int64_t capacity, const int32_t* table_min, const int64_t* rank,
+                           int64_t* cluster_of, void* stream);
+int rx_mesh_cluster_count(const int64_t* cluster_of, int64_t n_vertices, int64_t n_clusters, int32_t* counts, void* stream);
+int rx_mesh_cluster_fill(const int64_t* cluster_of, int64_t n_vertices, int64_t n_clusters, const int64_t* member_offsets, int32_t* cursor,
+                         int64_t capacity, int32_t* members, void* stream);
+int rx_mesh_cluster_mean(const float* vertices, int64_t n_vertices, int64_t n_clusters, const int64_t* member_offsets, int32_t* members,
+                         int64_t capacity, float* representatives, void* stream);
+int rx_mesh_cluster_nearest(const float* vertices, const int64_t* keys, int64_t n_vertices, float cell, const int64_t* cluster_of,
+                            int64_t n_clusters, uint64_t* best, float* representatives, void* stream);
+int rx_mesh_cluster_remap(const int64_t* triangles, int64_t n_triangles, int64_t n_vertices, const int64_t* cluster_of, int64_t n_clusters,
+                          int32_t* counts, int32_t* used, int32_t* flag, void* stream);
+int rx_mesh_cluster_unique(const int64_t* triangles, int64_t n_triangles, int64_t n_vertices, const int64_t* cluster_of, int64_t n_clusters,
+                           const int64_t* entry_offsets, int32_t* cursor, int64_t capacity, int32_t* entries, int32_t* keep, void* stream);
+int rx_mesh_cluster_emit(const int64_t* triangles, int64_t n_triangles, int64_t n_vertices, const int64_t* cluster_of, int64_t n_clusters,
+                         const int32_t* keep, const int64_t* keep_offsets, const int32_t* used, const int64_t* used_offsets,
+                         const float* representatives, int64_t vertex_capacity, float* out_vertices, int64_t triangle_capacity,
+                         int64_t* out_triangles, void* stream);
+
 /* ---- validation preview on the device: one panel of the debug GIF (host side training/visualization/preview.py, whose
  *      panel_numpy and minmax_numpy are the statements).  `src` is ONE sample's contiguous (c, z, h, w) block of `dtype` (rx_dtype),
  *      aligned to its element (a base that is not 16-byte aligned is fine).  c == 3 draws channels 0, 1, 2 into bytes 0, 1, 2 of

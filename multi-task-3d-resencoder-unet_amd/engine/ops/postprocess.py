@@ -1,7 +1,8 @@
 """Post-processing on the device: connected components of a thresholded uint8 volume, their sizes, and the size filter
 (csrc/rx_components.hip; postprocess/components.py holds the numpy statements and the out-of-core driver), and the triangle mesh of
 a uint8 volume by surface nets (csrc/rx_isosurface.hip; postprocess/isosurface.py), and the refinement of such a mesh: canonical
-adjacency, Taubin smoothing, vertex normals (csrc/rx_meshrefine.hip; postprocess/refine.py)."""
+adjacency, Taubin smoothing, vertex normals (csrc/rx_meshrefine.hip; postprocess/refine.py), and its decimation by vertex clustering
+(csrc/rx_meshdecimate.hip; postprocess/decimate.py)."""
 from ctypes import c_void_p
 from typing import NamedTuple
 
@@ -322,3 +323,92 @@ def mesh_vertex_normals(vertices, triangles, adjacency=None):
                 lambda: check(so.rx_mesh_vertex_normals(V, _ptr(a.face_offsets), _ptr(a.faces), a.faces.shape[0], _ptr(fvec), T, _ptr(out), st),
                               "rx_mesh_vertex_normals"))
     return out
+
+
+# ---- mesh decimation (csrc/rx_meshdecimate.hip; postprocess/decimate.py) ------------------------------------------------------------------------
+_REPRESENTATIVES = ("mean", "nearest")
+
+
+def _table_capacity(n_vertices):
+    """the smallest power of two that is at least 2 V + 2 (the library wants one above V, and takes at most 2^31)"""
+    return min(1 << (2 * n_vertices + 1).bit_length(), 2**31)
+
+
+def mesh_decimate(vertices, triangles, cell, representative="mean"):
+    """vertex clustering of a float32 (V, 3) / int64 (T, 3) device mesh on a grid of `cell`-sized cubes -> (vertices float32 (V', 3),
+    triangles int64 (T', 3), cluster_of int64 (V,)), bit for bit postprocess.decimate_numpy: the vertices of a cube become one
+    representative ("mean": the sequential float32 mean of the members in ascending id; "nearest": the member nearest the cube's
+    centre, lowest id on ties), a triangle with two corners in one cluster is dropped, and of the triangles with the same unordered
+    cluster triple the lowest index stays.  Keys, a hash table claimed by 64-bit compare-and-swap with an integer minimum per slot,
+    scans, lists filled at a cursor and heap-sorted in place: no float atomics, and every number is derived from keys and smallest
+    member ids, so two runs give the same bytes.  Two small device-to-host reads (the number of clusters; the output sizes).  No
+    launch where V is 0; none of the triangle passes where T is 0."""
+    fn = "mesh_decimate"
+    v = _mesh_vertices(fn, vertices)
+    t = _mesh_triangles(fn, v.shape[0], triangles)
+    if isinstance(cell, bool) or not isinstance(cell, (int, float)) or not 0 < cell <= _F32_MAX or torch.tensor(float(cell), dtype=torch.float32).item() <= 0:
+        raise _l.RxError(f"{fn}: `cell` {cell!r} (a finite float32 > 0)")
+    if representative not in _REPRESENTATIVES:
+        raise _l.RxError(f"{fn}: `representative` {representative!r} (one of {', '.join(_REPRESENTATIVES)})")
+    V, T, dev = v.shape[0], t.shape[0], v.device
+    empty = lambda: (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int64, device=dev))      # noqa: E731
+    if V == 0:
+        return empty() + (torch.zeros(0, dtype=torch.int64, device=dev),)
+    _mesh_finite(fn, v)
+    so, st = load(), stream_ptr()
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)      # noqa: E731
+    i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)      # noqa: E731
+    cap = _table_capacity(V)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    keys, table_keys, table_min, slot_of, first, rank, cluster_of = i64(V), i64(cap), i32(cap), i32(V), i32(V), i64(V + 1), i64(V)
+    timed_bytes("mesh_cluster_keys", V * (12 + 8), lambda: check(so.rx_mesh_cluster_keys(_ptr(v), V, cell, _ptr(keys), _ptr(flag), st), "rx_mesh_cluster_keys"))
+    timed_bytes("mesh_cluster_assign", cap * 12 + V * (8 + 12 + 4 + 4),
+                lambda: check(so.rx_mesh_cluster_assign(_ptr(keys), V, cap, _ptr(table_keys), _ptr(table_min), _ptr(slot_of), _ptr(first), _ptr(flag), st),
+                              "rx_mesh_cluster_assign"))
+    timed_bytes("mesh_scan", V * 12, lambda: check(so.rx_mesh_scan(_ptr(first), V, _ptr(rank), st), "rx_mesh_scan"))
+    timed_bytes("mesh_cluster_number", V * (4 + 4 + 8 + 8),
+                lambda: check(so.rx_mesh_cluster_number(V, _ptr(slot_of), cap, _ptr(table_min), _ptr(rank), _ptr(cluster_of), st), "rx_mesh_cluster_number"))
+    bad, C = torch.cat([flag.to(torch.int64), rank[V:]]).tolist()      # the first device-to-host read
+    if bad & 1:
+        raise _l.RxError(f"{fn}: `cell` {cell!r} puts a vertex in a grid cell with an index of 2^20 or more; choose a larger cell")
+    if bad:
+        raise _l.RxError(f"{fn}: the hash table of {cap} slots ran out of probes (flag {bad}): not a state this call can reach")
+    del table_keys, table_min, slot_of, first, rank
+    counts, reps = i32(C), torch.empty((C, 3), dtype=torch.float32, device=dev)
+    if representative == "mean":
+        moff, members = i64(C + 1), i32(V)
+        timed_bytes("mesh_cluster_count", V * 12, lambda: check(so.rx_mesh_cluster_count(_ptr(cluster_of), V, C, _ptr(counts), st), "rx_mesh_cluster_count"))
+        timed_bytes("mesh_scan", C * 12, lambda: check(so.rx_mesh_scan(_ptr(counts), C, _ptr(moff), st), "rx_mesh_scan"))
+        # `counts` is free again: it serves as the fill cursor
+        timed_bytes("mesh_cluster_fill", V * (8 + 16 + 4 + 4),
+                    lambda: check(so.rx_mesh_cluster_fill(_ptr(cluster_of), V, C, _ptr(moff), _ptr(counts), V, _ptr(members), st), "rx_mesh_cluster_fill"))
+        timed_bytes("mesh_cluster_mean", C * (16 + 12) + 2 * V * 4 + V * 12,
+                    lambda: check(so.rx_mesh_cluster_mean(_ptr(v), V, C, _ptr(moff), _ptr(members), V, _ptr(reps), st), "rx_mesh_cluster_mean"))
+        del moff, members
+    else:
+        best = i64(C)
+        timed_bytes("mesh_cluster_nearest", V * (12 + 8 + 8 + 8) + C * (8 + 12 + 12),
+                    lambda: check(so.rx_mesh_cluster_nearest(_ptr(v), _ptr(keys), V, cell, _ptr(cluster_of), C, _ptr(best), _ptr(reps), st),
+                                  "rx_mesh_cluster_nearest"))
+        del best
+    del keys
+    if T == 0:
+        return empty() + (cluster_of,)
+    used, toff, uoff, entries, keep, koff = i32(C), i64(C + 1), i64(C + 1), i32(3 * T), i32(T), i64(T + 1)
+    timed_bytes("mesh_cluster_remap", T * (24 + 24 + 4 + 12),
+                lambda: check(so.rx_mesh_cluster_remap(_ptr(t), T, V, _ptr(cluster_of), C, _ptr(counts), _ptr(used), _ptr(flag), st), "rx_mesh_cluster_remap"))
+    timed_bytes("mesh_scan", C * 12, lambda: check(so.rx_mesh_scan(_ptr(counts), C, _ptr(toff), st), "rx_mesh_scan"))
+    timed_bytes("mesh_scan", C * 12, lambda: check(so.rx_mesh_scan(_ptr(used), C, _ptr(uoff), st), "rx_mesh_scan"))
+    timed_bytes("mesh_cluster_unique", T * (24 + 24 + 16 + 4 + 3 * 12 + 4),
+                lambda: check(so.rx_mesh_cluster_unique(_ptr(t), T, V, _ptr(cluster_of), C, _ptr(toff), _ptr(counts), T, _ptr(entries), _ptr(keep), st),
+                              "rx_mesh_cluster_unique"))
+    timed_bytes("mesh_scan", T * 12, lambda: check(so.rx_mesh_scan(_ptr(keep), T, _ptr(koff), st), "rx_mesh_scan"))
+    bad, nv, nt = torch.cat([flag.to(torch.int64), uoff[C:], koff[T:]]).tolist()      # the second read: the sizes of the result
+    if bad:
+        raise _l.RxError(f"{fn}: `triangles` name a vertex outside 0 .. {V - 1}")
+    out_v, out_t = torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nt, 3), dtype=torch.int64, device=dev)
+    if nt:
+        timed_bytes("mesh_cluster_emit", T * (4 + 8) + nt * (24 + 24 + 24 + 24) + C * (4 + 8) + nv * 24,
+                    lambda: check(so.rx_mesh_cluster_emit(_ptr(t), T, V, _ptr(cluster_of), C, _ptr(keep), _ptr(koff), _ptr(used), _ptr(uoff), _ptr(reps),
+                                                          nv, _ptr(out_v), nt, _ptr(out_t), st), "rx_mesh_cluster_emit"))
+    return out_v, out_t, cluster_of

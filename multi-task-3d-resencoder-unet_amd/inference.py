@@ -800,6 +800,15 @@ def main(argv=None):
             print(task, MeshRefiner(refine["iterations"], refine["lam"], refine["mu"], refine["clamp"], refine["pin_boundary"], refine["normals"],
                                     max_device_bytes=None if gb is None else int(gb * 2**30)).run(
                                         os.path.join(store, f"{task}_{mesh['source']}.{mesh['format']}")), flush=True)
+    decimate = (mgr.infer_postprocess or {}).get("decimate")
+    if decimate:      # last: it reads the refined file where the task is refined as well, the mesher's otherwise
+        from .postprocess import MeshDecimator
+        gb = decimate["max_device_gb"]
+        for task in decimate["tasks"]:
+            stem = f"{task}_{mesh['source']}" + ("_refined" if refine and task in refine["tasks"] else "")
+            print(task, MeshDecimator(decimate["cell"], decimate["representative"], decimate["normals"],
+                                      max_device_bytes=None if gb is None else int(gb * 2**30)).run(
+                                          os.path.join(store, f"{stem}.{mesh['format']}")), flush=True)
     return store
 
 
