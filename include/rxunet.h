@@ -797,6 +797,42 @@ int rx_mesh_cluster_emit(const int64_t* triangles, int64_t n_triangles, int64_t 
                          const float* representatives, int64_t vertex_capacity, float* out_vertices, int64_t triangle_capacity,
                          int64_t* out_triangles, void* stream);
 
+/* ---- mesh orientation against a sampled vector field (host side postprocess/orient.py, whose sample_points_numpy, unit_numpy,
+ *      face_cos_numpy and side_numpy are the statements).  Sizes as in the refinement group above; n_points, n_vertices and
+ *      n_triangles are at least 1 (the caller handles empty meshes).  Every float32 operation is one rounding, nothing is
+ *      contracted into an fma, and there is no atomic that chooses anything: two runs give the same bytes.  Every call refuses
+ *      with a status and a message before anything is launched: null or misaligned pointers, sizes outside the limits, an unknown
+ *      rule, channels outside 1 .. 8, `unit` with another channel count than 3, a slab that does not lie inside z_total, a
+ *      min_cos outside [0, 1).  No allocation, copy or synchronisation.
+ *      rx_mesh_sample: `volume` is (channels, z_depth, y, x) contiguous, of float32 (RX_MESH_SAMPLE_COPY), uint8 (_U8) or uint16
+ *        (_U16, _NORMAL_U16) values, planes [z_base, z_base + z_depth) of a volume of z_total planes; `points` float32
+ *        (n_points, 3) as (x, y, z) in voxel coordinates.  out[v] (float32, `channels` values) = the trilinear sample with clamped
+ *        borders: per axis i = floor(p), f = p - i, corners i and i + 1 clamped; every corner decoded first (copy: unchanged;
+ *        u8: v / 255; u16: v / 65535; normal_u16: (v / 65535) * 2 - 1); lerp(u, w, f) = u + f * (w - u) along x, then y, then z.
+ *        unit != 0: the three values are then divided by their length sqrt(x*x + y*y + z*z), (0, 0, 0) where that is not > 0.
+ *        A point whose two clamped z indices are not both inside the slab is left untouched in `out`, so successive slab launches
+ *        fill one buffer.  No load leaves the slab, whatever the coordinates hold.
+ *      rx_mesh_face_cos: per triangle (a, b, c): g = cross(pb - pa, pc - pa), m = (n_a + n_b) + n_c of `vectors`,
+ *        cos[t] = (g.m) / sqrt((g.g) * (m.m)), each dot three products summed left to right; side[t] = 1 where cos > min_cos,
+ *        -1 where cos < -min_cos, else 0 (a NaN included); keep[t] = side[t] == want (want 0: every triangle); used[v] = 1 for
+ *        the corners of a kept triangle (zeroed first; a plain store of a constant).  Bit 2 of `flag`: an id outside
+ *        [0, n_vertices); such a triangle is not followed, its cos is NaN and it is not kept.
+ *      rx_mesh_select_mark: used[v] = 1 for the corners of the triangles with keep[t] != 0 (zeroed first); `flag` as above.
+ *      The compaction of the kept triangles and the used vertices is rx_mesh_scan over `keep` and `used`, then
+ *      rx_mesh_cluster_emit with cluster_of[v] = v and n_clusters = n_vertices. */
+#define RX_MESH_SAMPLE_COPY 0
+#define RX_MESH_SAMPLE_U8 1
+#define RX_MESH_SAMPLE_U16 2
+#define RX_MESH_SAMPLE_NORMAL_U16 3
+#define RX_MESH_SAMPLE_MAX_CHANNELS 8
+#define RX_MESH_SAMPLE_MAX_EXTENT 16777214
+int rx_mesh_sample(const void* volume, int rule, int channels, int z_base, int z_depth, int z_total, int y, int x, const float* points,
+                   int64_t n_points, int unit, float* out, void* stream);
+int rx_mesh_face_cos(const float* vertices, const float* vectors, int64_t n_vertices, const int64_t* triangles, int64_t n_triangles,
+                     float min_cos, int want, float* cos, int8_t* side, int32_t* keep, int32_t* used, int32_t* flag, void* stream);
+int rx_mesh_select_mark(const int64_t* triangles, int64_t n_triangles, int64_t n_vertices, const int32_t* keep, int32_t* used, int32_t* flag,
+                        void* stream);
+
 /* ---- validation preview on the device: one panel of the debug GIF (host side training/visualization/preview.py, whose
  *      panel_numpy and minmax_numpy are the statements).  `src` is ONE sample's contiguous (c, z, h, w) block of `dtype` (rx_dtype),
  *      aligned to its element (a base that is not 16-byte aligned is fine).  c == 3 draws channels 0, 1, 2 into bytes 0, 1, 2 of

@@ -29,6 +29,8 @@ RX_EDT_NONE, RX_EDT_MAX_EXTENT = 1 << 30, 1024
 RX_CC_MAX_VOXELS = 2**31 - 2
 RX_ISO_MAX_EXTENT, RX_ISO_MAX_CELLS = 2**24 - 3, 2**31 - 2
 RX_MESH_MAX_VERTICES, RX_MESH_MAX_TRIANGLES = 2**31 - 2, (2**31 - 2) // 3
+RX_MESH_SAMPLE_COPY, RX_MESH_SAMPLE_U8, RX_MESH_SAMPLE_U16, RX_MESH_SAMPLE_NORMAL_U16 = 0, 1, 2, 3
+RX_MESH_SAMPLE_MAX_CHANNELS, RX_MESH_SAMPLE_MAX_EXTENT = 8, 2**24 - 2
 
 
 class RxError(RuntimeError):
@@ -216,6 +218,10 @@ _SIGNATURES = {
     "rx_mesh_cluster_unique": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "rx_mesh_cluster_emit": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_void_p, c_int64, c_void_p, c_void_p]),
+    "rx_mesh_sample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "rx_mesh_face_cos": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "rx_mesh_select_mark": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rx_preview_panel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int,
                                  c_void_p, c_void_p]),
     "rx_mesh_slice_keys": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

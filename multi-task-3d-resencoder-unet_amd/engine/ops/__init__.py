@@ -29,6 +29,6 @@ from .network import (avgpool_bwd, avgpool_fwd, channel_sum, conv3d_bwd_data, co
 from .pipeline import (affine_apply, affine_table, aug_filter_zy, aug_philox_u32, aug_pointwise, augment_batch,      # noqa: F401
                        box_stats, elastic_apply, elastic_nodes, elastic_tables, geom_apply, geom_table, ingest, label_dilate)
 from .postprocess import (MeshAdjacency, cc_filter, cc_label, cc_sizes, iso_counts, iso_mesh, mesh_adjacency,      # noqa: F401
-                          mesh_decimate, mesh_smooth, mesh_vertex_normals)
+                          mesh_decimate, mesh_face_cos, mesh_sample, mesh_select, mesh_smooth, mesh_vertex_normals)
 from .validation import (class_counts, edt_sq, mask_edges, normal_stats, preview_frames, preview_panel, seg_counts,      # noqa: F401
                          surface_hist, surface_scratch)

@@ -1,8 +1,9 @@
 """Post-processing on the device: connected components of a thresholded uint8 volume, their sizes, and the size filter
 (csrc/rx_components.hip; postprocess/components.py holds the numpy statements and the out-of-core driver), and the triangle mesh of
 a uint8 volume by surface nets (csrc/rx_isosurface.hip; postprocess/isosurface.py), and the refinement of such a mesh: canonical
-adjacency, Taubin smoothing, vertex normals (csrc/rx_meshrefine.hip; postprocess/refine.py), and its decimation by vertex clustering
-(csrc/rx_meshdecimate.hip; postprocess/decimate.py)."""
+adjacency, Taubin smoothing, vertex normals (csrc/rx_meshrefine.hip; postprocess/refine.py), its decimation by vertex clustering
+(csrc/rx_meshdecimate.hip; postprocess/decimate.py), and its orientation against a sampled vector field: trilinear sampling at the
+vertices, the per-triangle cosine and side, the selection of one face (csrc/rx_meshsample.hip; postprocess/orient.py)."""
 from ctypes import c_void_p
 from typing import NamedTuple
 
@@ -10,7 +11,7 @@ import torch
 
 from .. import lib as _l
 from ..lib import check, load, stream_ptr
-from .core import _ptr, device_batch, result_tensor, timed_bytes
+from .core import _U16, _ptr, device_batch, result_tensor, timed_bytes
 
 _CONNECTIVITY = (6, 18, 26)
 _F32_MAX = 3.4028234663852886e38      # a factor or a clamp must be finite as a float32
@@ -412,3 +413,153 @@ def mesh_decimate(vertices, triangles, cell, representative="mean"):
                     lambda: check(so.rx_mesh_cluster_emit(_ptr(t), T, V, _ptr(cluster_of), C, _ptr(keep), _ptr(koff), _ptr(used), _ptr(uoff), _ptr(reps),
                                                           nv, _ptr(out_v), nt, _ptr(out_t), st), "rx_mesh_cluster_emit"))
     return out_v, out_t, cluster_of
+
+
+# ---- mesh orientation (csrc/rx_meshsample.hip; postprocess/orient.py) ---------------------------------------------------------------------------
+_SAMPLE_RULES = {"copy": (_l.RX_MESH_SAMPLE_COPY, (torch.float32,)), "u8": (_l.RX_MESH_SAMPLE_U8, (torch.uint8,)),
+                 "u16": (_l.RX_MESH_SAMPLE_U16, (_U16, torch.int16)), "normal_u16": (_l.RX_MESH_SAMPLE_NORMAL_U16, (_U16, torch.int16))}
+_SIDES = {"both": 0, "front": 1, "back": -1}
+
+
+def _plain_int(x):
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+def mesh_sample(volume, points, rule, z_base=0, z_total=None, unit=False, out=None):
+    """a (C, Zs, Y, X) device volume, C in 1 .. 8, sampled trilinearly with clamped borders at float32 (V, 3) device `points` given as
+    (x, y, z) in voxel coordinates -> float32 (V, C), bit for bit postprocess.sample_points_numpy.  `rule` decodes a stored value:
+    "copy" (a float32 volume), "u8" (uint8, v / 255), "u16" (uint16, v / 65535), "normal_u16" (uint16, (v / 65535) * 2 - 1); a
+    uint16 volume may be held as int16, whose bits are read as uint16.  `volume` holds planes [z_base, z_base + Zs) of a volume of
+    `z_total` planes (default: z_base + Zs); a point whose two clamped z planes are not both among them is left untouched in `out`
+    (a new `out` starts as zeros), so successive slab calls fill one buffer.  `unit` (C = 3): the three values are divided by
+    their length, (0, 0, 0) where it is 0 (postprocess.unit_numpy).  One launch, a thread per point, no atomics; one small
+    device-to-host read for the finiteness check.  No launch where V is 0."""
+    fn = "mesh_sample"
+    if rule not in _SAMPLE_RULES:
+        raise _l.RxError(f"{fn}: rule {rule!r} (one of {', '.join(_SAMPLE_RULES)})")
+    code, dtypes = _SAMPLE_RULES[rule]
+    if not isinstance(volume, torch.Tensor) or not volume.is_cuda:
+        raise _l.RxError(f"{fn}: `volume` must be a device tensor (the host statement is postprocess.sample_points_numpy)")
+    if volume.dtype not in dtypes:
+        raise _l.RxError(f"{fn}: rule {rule!r} decodes a {str(dtypes[0]).replace('torch.', '')} volume, got {volume.dtype}")
+    if volume.dim() != 4 or volume.numel() == 0:
+        raise _l.RxError(f"{fn}: `volume` must be a non-empty (C, Z, Y, X) tensor, got {tuple(volume.shape)}")
+    C, Zs, Y, X = volume.shape
+    if not 1 <= C <= _l.RX_MESH_SAMPLE_MAX_CHANNELS:
+        raise _l.RxError(f"{fn}: `volume` has {C} channels (1 .. {_l.RX_MESH_SAMPLE_MAX_CHANNELS})")
+    p = points
+    if not isinstance(p, torch.Tensor) or not p.is_cuda:
+        raise _l.RxError(f"{fn}: `points` must be a device tensor (the host statement is postprocess.sample_points_numpy)")
+    if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 3:
+        raise _l.RxError(f"{fn}: `points` must be a float32 (V, 3) tensor, got {p.dtype} {tuple(p.shape)}")
+    if p.shape[0] > _l.RX_MESH_MAX_VERTICES:
+        raise _l.RxError(f"{fn}: `points`: {p.shape[0]} of them (at most 2^31 - 2)")
+    if z_total is None and _plain_int(z_base):
+        z_total = z_base + Zs
+    if not _plain_int(z_base) or not _plain_int(z_total) or z_base < 0 or z_base + Zs > z_total:
+        raise _l.RxError(f"{fn}: a slab of planes {z_base!r} .. {z_base!r} + {Zs} does not lie inside z_total {z_total!r}")
+    if max(z_total, Y, X) > _l.RX_MESH_SAMPLE_MAX_EXTENT:
+        raise _l.RxError(f"{fn}: an extent above 2^24 - 2 in {(z_total, Y, X)}: an index must be an exact float32")
+    if not isinstance(unit, bool) or (unit and C != 3):
+        raise _l.RxError(f"{fn}: `unit` {unit!r} with {C} channels (true or false; true needs 3 channels)")
+    vol, p = volume.contiguous(), p.contiguous()
+    V = p.shape[0]
+    out = result_tensor(fn, "out", out, (V, C), torch.float32, p.device, alloc=torch.zeros)
+    if V == 0:
+        return out
+    flag = torch.zeros(1, dtype=torch.int32, device=p.device)
+    check(load().rx_mesh_check_vertices(_ptr(p), V, _ptr(flag), stream_ptr()), "rx_mesh_check_vertices")
+    if flag.item():
+        raise _l.RxError(f"{fn}: `points` hold a NaN or an infinity")
+    timed_bytes("mesh_sample", V * (12 + 4 * C + 8 * C * vol.element_size()),
+                lambda: check(load().rx_mesh_sample(_ptr(vol), code, C, z_base, Zs, z_total, Y, X, _ptr(p), V, int(unit), _ptr(out), stream_ptr()),
+                              "rx_mesh_sample"))
+    return out
+
+
+def mesh_face_cos(vertices, triangles, vectors, min_cos, side):
+    """per triangle of a float32 (V, 3) / int64 (T, 3) device mesh the cosine between its face vector and the sum of the float32
+    (V, 3) `vectors` at its corners, and its classification -> (cos float32 (T,), side int8 (T,), used int32 (V,)), bit for bit
+    postprocess.face_cos_numpy and side_numpy: side is 1 (front) where cos > min_cos, -1 (back) where cos < -min_cos, else 0 (rim;
+    a NaN, which a degenerate triangle or a zero vector sum gives, included).  `side`: "front", "back" or "both" -- used[v] = 1 for
+    the corners of the triangles of that side ("both": of every triangle), a plain store of a constant.  One launch, a thread per
+    triangle, no atomics; one small device-to-host read (the id check's flag).  No launch where T is 0."""
+    fn = "mesh_face_cos"
+    v = _mesh_vertices(fn, vertices)
+    t = _mesh_triangles(fn, v.shape[0], triangles)
+    n = vectors
+    if not isinstance(n, torch.Tensor) or not n.is_cuda:
+        raise _l.RxError(f"{fn}: `vectors` must be a device tensor (the host statement is postprocess.face_cos_numpy)")
+    if n.dtype != torch.float32 or tuple(n.shape) != tuple(v.shape):
+        raise _l.RxError(f"{fn}: `vectors` must be a float32 {tuple(v.shape)} tensor, got {n.dtype} {tuple(n.shape)}")
+    if isinstance(min_cos, bool) or not isinstance(min_cos, (int, float)) or not 0 <= min_cos < 1:
+        raise _l.RxError(f"{fn}: `min_cos` {min_cos!r} (a number in [0, 1))")
+    if not isinstance(side, str) or side not in _SIDES:
+        raise _l.RxError(f"{fn}: `side` {side!r} (one of {', '.join(_SIDES)})")
+    V, T, dev = v.shape[0], t.shape[0], v.device
+    cos, sd = torch.empty(T, dtype=torch.float32, device=dev), torch.empty(T, dtype=torch.int8, device=dev)
+    used = torch.zeros(V, dtype=torch.int32, device=dev)
+    if T == 0:
+        return cos, sd, used
+    _mesh_finite(fn, v)
+    keep, flag = torch.empty(T, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    n = n.contiguous()
+    timed_bytes("mesh_face_cos", T * (24 + 36 + 36 + 4 + 1 + 4 + 12),
+                lambda: check(load().rx_mesh_face_cos(_ptr(v), _ptr(n), V, _ptr(t), T, float(min_cos), _SIDES[side], _ptr(cos), _ptr(sd), _ptr(keep),
+                                                      _ptr(used), _ptr(flag), stream_ptr()), "rx_mesh_face_cos"))
+    if flag.item():
+        raise _l.RxError(f"{fn}: `triangles` name a vertex outside 0 .. {V - 1}")
+    return cos, sd, used
+
+
+def mesh_select(vertices, triangles, keep, attrs=(), used=None):
+    """the triangles of a float32 (V, 3) / int64 (T, 3) device mesh where the bool or int32 (T,) device tensor `keep` is not 0, in
+    input order, over the vertices some kept triangle names, in ascending id, renumbered to match -> (vertices, triangles, attrs,
+    row_of), bit for bit postprocess.select_numpy: `attrs` are float32 (V, 3) per-vertex tensors carried along, `row_of` int64 (V,)
+    the output row of every input vertex, -1 for a dropped one.  `used`: what `mesh_face_cos` returned for the same selection
+    (None: marked here, one launch).  Scans of the keep and the used flags (rx_mesh_scan), then the emit pass of the decimation
+    under the identity map: no atomic chooses a slot, so two runs give the same bytes.  One small device-to-host read (the id
+    check's flag and the output sizes).  No launch where V or T is 0."""
+    fn = "mesh_select"
+    v = _mesh_vertices(fn, vertices)
+    t = _mesh_triangles(fn, v.shape[0], triangles)
+    V, T, dev = v.shape[0], t.shape[0], v.device
+    if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype not in (torch.bool, torch.int32) or tuple(keep.shape) != (T,):
+        raise _l.RxError(f"{fn}: `keep` must be a bool or int32 device tensor of shape {(T,)}")
+    attrs = tuple(attrs)
+    for a in attrs:
+        if not isinstance(a, torch.Tensor) or a.device != dev or a.dtype != torch.float32 or tuple(a.shape) != (V, 3):
+            raise _l.RxError(f"{fn}: every attribute must be a float32 {(V, 3)} tensor on {dev}")
+    if used is not None and (not isinstance(used, torch.Tensor) or used.device != dev or used.dtype != torch.int32 or tuple(used.shape) != (V,)
+                             or not used.is_contiguous()):
+        raise _l.RxError(f"{fn}: `used` must be what mesh_face_cos returned for this mesh: a contiguous int32 {(V,)} tensor on {dev}")
+    if V == 0 or T == 0:
+        return (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int64, device=dev),
+                tuple(torch.zeros((0, 3), dtype=torch.float32, device=dev) for _ in attrs), torch.full((V,), -1, dtype=torch.int64, device=dev))
+    so, st = load(), stream_ptr()
+    keep = (keep != 0).to(torch.int32).contiguous()
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    if used is None:
+        used = torch.empty(V, dtype=torch.int32, device=dev)
+        timed_bytes("mesh_select_mark", T * (4 + 24 + 12),
+                    lambda: check(so.rx_mesh_select_mark(_ptr(t), T, V, _ptr(keep), _ptr(used), _ptr(flag), st), "rx_mesh_select_mark"))
+    koff, uoff = torch.empty(T + 1, dtype=torch.int64, device=dev), torch.empty(V + 1, dtype=torch.int64, device=dev)
+    timed_bytes("mesh_scan", T * 12, lambda: check(so.rx_mesh_scan(_ptr(keep), T, _ptr(koff), st), "rx_mesh_scan"))
+    timed_bytes("mesh_scan", V * 12, lambda: check(so.rx_mesh_scan(_ptr(used), V, _ptr(uoff), st), "rx_mesh_scan"))
+    bad, nv, nt = torch.cat([flag.to(torch.int64), uoff[V:], koff[T:]]).tolist()      # the one device-to-host read
+    if bad:
+        raise _l.RxError(f"{fn}: `triangles` name a vertex outside 0 .. {V - 1}")
+    identity = torch.arange(V, dtype=torch.int64, device=dev)
+    out_v, out_t = torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nt, 3), dtype=torch.int64, device=dev)
+    out_a = tuple(torch.empty((nv, 3), dtype=torch.float32, device=dev) for _ in attrs)
+    if nt:
+        timed_bytes("mesh_cluster_emit", T * (4 + 8) + nt * (24 + 24 + 24 + 24) + V * (4 + 8) + nv * 24,
+                    lambda: check(so.rx_mesh_cluster_emit(_ptr(t), T, V, _ptr(identity), V, _ptr(keep), _ptr(koff), _ptr(used), _ptr(uoff), _ptr(v),
+                                                          nv, _ptr(out_v), nt, _ptr(out_t), st), "rx_mesh_cluster_emit"))
+        for a, o in zip(attrs, out_a):      # the vertex half of the emit pass alone
+            a = a.contiguous()
+            timed_bytes("mesh_cluster_emit", V * (4 + 8) + nv * 24,
+                        lambda: check(so.rx_mesh_cluster_emit(_ptr(t), T, V, _ptr(identity), V, _ptr(keep), _ptr(koff), _ptr(used), _ptr(uoff), _ptr(a),
+                                                              nv, _ptr(o), 0, c_void_p(0), st), "rx_mesh_cluster_emit"))
+    row_of = torch.where(used != 0, uoff[:V], torch.full_like(uoff[:V], -1))
+    return out_v, out_t, out_a, row_of

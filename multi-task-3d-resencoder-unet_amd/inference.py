@@ -809,6 +809,16 @@ def main(argv=None):
             print(task, MeshDecimator(decimate["cell"], decimate["representative"], decimate["normals"],
                                       max_device_bytes=None if gb is None else int(gb * 2**30)).run(
                                           os.path.join(store, f"{stem}.{mesh['format']}")), flush=True)
+    orient = (mgr.infer_postprocess or {}).get("orient")
+    if orient:      # last: it reads the newest mesh file of the chain -- decimated, else refined, else the mesher's
+        from .postprocess import MeshOrienter
+        gb = orient["max_device_gb"]
+        for task in orient["tasks"]:
+            stem = (f"{task}_{mesh['source']}" + ("_refined" if refine and task in refine["tasks"] else "")
+                    + ("_decimated" if decimate and task in decimate["tasks"] else ""))
+            print(task, MeshOrienter(orient["side"], orient["min_cos"], orient["normals"],
+                                     max_device_bytes=None if gb is None else int(gb * 2**30)).run(
+                                         os.path.join(store, f"{stem}.{mesh['format']}"), store, f"{orient['normals_task']}_final"), flush=True)
     return store
 
 

@@ -173,14 +173,15 @@ def _check_options(level, connectivity, min_voxels):
 def parse_config(block, targets, patch_size=None):
     """`inference_config.postprocess` -> None when absent, else {"components": {tasks, level, connectivity, min_voxels, write_labels,
     max_device_gb}} and / or {"mesh": {tasks, source, level, format, max_device_gb}} (isosurface.parse_mesh_config) and / or
-    {"refine": {...}} (refine.parse_refine_config) and / or {"decimate": {...}} (decimate.parse_decimate_config), whichever the block holds.  Unknown keys and bad values raise ValueError naming the key; `targets` is {task: {"channels": c, ...}}."""
+    {"refine": {...}} (refine.parse_refine_config) and / or {"decimate": {...}} (decimate.parse_decimate_config) and / or
+    {"orient": {...}} (orient.parse_orient_config), whichever the block holds.  Unknown keys and bad values raise ValueError naming the key; `targets` is {task: {"channels": c, ...}}."""
     if block is None:
         return None
     if not isinstance(block, dict):
         raise ValueError(f"inference_config.postprocess: expected a mapping, got {block!r}")
     for k in block:
-        if k not in ("components", "mesh", "refine", "decimate"):
-            raise ValueError(f"inference_config.postprocess.{k}: unknown key (components, mesh, refine, decimate)")
+        if k not in ("components", "mesh", "refine", "decimate", "orient"):
+            raise ValueError(f"inference_config.postprocess.{k}: unknown key (components, mesh, refine, decimate), or orient")
     out = _parse_components(block["components"], targets, patch_size) if "components" in block else {}
     if "mesh" in block:
         from .isosurface import parse_mesh_config
@@ -191,6 +192,9 @@ def parse_config(block, targets, patch_size=None):
     if "decimate" in block:      # another sibling: it reads the refiner's file where there is one, else the mesher's
         from .decimate import parse_decimate_config
         out["decimate"] = parse_decimate_config(block["decimate"], out["mesh"]["tasks"] if "mesh" in out else None)
+    if "orient" in block:      # the last sibling: it reads the newest mesh file of the chain and the store of the normals task
+        from .orient import parse_orient_config
+        out["orient"] = parse_orient_config(block["orient"], out["mesh"]["tasks"] if "mesh" in out else None, targets)
     return out or None
 
 
