@@ -27,31 +27,24 @@
 //                        clusters' representatives at the scan of the referenced flags.
 #include "rx_common.h"
 #include "rx_meshdecimate_core.h"
+#include "rx_mesh_host.h"
 
 #pragma clang fp contract(off)
 
-#define RX_MD_BLOCK 256
-
-static inline unsigned md_blocks(long long n) { return (unsigned)((n + RX_MD_BLOCK - 1) / RX_MD_BLOCK); }      // n <= 2^31 - 2
-
-#define MD_THREAD(i, n)                                                        \
-  const long long i = (long long)blockIdx.x * RX_MD_BLOCK + threadIdx.x;       \
-  if (i >= (n)) return
-
 // ---- clusters ---------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_keys_kernel(const float* __restrict__ pos, long long V, float cell, long long* __restrict__ keys,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_keys_kernel(const float* __restrict__ pos, long long V, float cell, long long* __restrict__ keys,
                                                               int* __restrict__ flag) {
-  MD_THREAD(v, V);
+  RX_MESH_THREAD(v, V);
   const float p[3] = {pos[3 * v], pos[3 * v + 1], pos[3 * v + 2]};
   int64_t key = MD_EMPTY;
   if (!md_key(p, cell, &key)) atomicOr(flag, 1);
   keys[v] = key;
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_insert_kernel(const long long* __restrict__ keys, long long V, long long capacity,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_insert_kernel(const long long* __restrict__ keys, long long V, long long capacity,
                                                                 long long* table_keys, unsigned* table_min, int* __restrict__ slot_of,
                                                                 int* __restrict__ flag) {
-  MD_THREAD(v, V);
+  RX_MESH_THREAD(v, V);
   const long long key = keys[v];
   int32_t slot = -1;
   if (key >= 0) {      // a vertex outside the key range has no key
@@ -61,32 +54,32 @@ __global__ __launch_bounds__(RX_MD_BLOCK) void md_insert_kernel(const long long*
   slot_of[v] = slot;
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_first_kernel(long long V, const int* __restrict__ slot_of, long long capacity,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_first_kernel(long long V, const int* __restrict__ slot_of, long long capacity,
                                                                const unsigned* __restrict__ table_min, int* __restrict__ first) {
-  MD_THREAD(v, V);
+  RX_MESH_THREAD(v, V);
   first[v] = md_smallest(slot_of[v], capacity, table_min, V) == (int32_t)v;
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_number_kernel(long long V, const int* __restrict__ slot_of, long long capacity,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_number_kernel(long long V, const int* __restrict__ slot_of, long long capacity,
                                                                 const unsigned* __restrict__ table_min, const long long* __restrict__ rank,
                                                                 long long* __restrict__ cluster_of) {
-  MD_THREAD(v, V);
+  RX_MESH_THREAD(v, V);
   const int32_t m = md_smallest(slot_of[v], capacity, table_min, V);
   cluster_of[v] = m < 0 ? -1 : rank[m];
 }
 
 // ---- representatives --------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_count_kernel(const long long* __restrict__ cluster_of, long long V, long long C,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_count_kernel(const long long* __restrict__ cluster_of, long long V, long long C,
                                                                int* __restrict__ counts) {
-  MD_THREAD(v, V);
+  RX_MESH_THREAD(v, V);
   const long long c = cluster_of[v];
   if ((unsigned long long)c < (unsigned long long)C) atomicAdd(&counts[c], 1);
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_fill_kernel(const long long* __restrict__ cluster_of, long long V, long long C,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_fill_kernel(const long long* __restrict__ cluster_of, long long V, long long C,
                                                               const long long* __restrict__ moff, int* __restrict__ cursor, long long capacity,
                                                               int* __restrict__ members) {
-  MD_THREAD(v, V);
+  RX_MESH_THREAD(v, V);
   const long long c = cluster_of[v];
   if ((unsigned long long)c >= (unsigned long long)C) return;
   const long long b = moff[c], e = moff[c + 1];
@@ -94,10 +87,10 @@ __global__ __launch_bounds__(RX_MD_BLOCK) void md_fill_kernel(const long long* _
   if (at >= 0 && at < e && at < capacity) members[at] = (int)v;      // at >= e: more members than were counted -- not this mesh's scan
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_mean_kernel(const float* __restrict__ pos, long long V, long long C,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_mean_kernel(const float* __restrict__ pos, long long V, long long C,
                                                               const long long* __restrict__ moff, int* members, long long capacity,
                                                               float* __restrict__ reps) {
-  MD_THREAD(c, C);
+  RX_MESH_THREAD(c, C);
   long long b = moff[c], e = moff[c + 1];
   if (b < 0 || e > capacity || e < b) b = e = 0;      // not a scan of this mesh: the cluster gets nothing
   float r[3] = {0.0f, 0.0f, 0.0f};
@@ -105,29 +98,29 @@ __global__ __launch_bounds__(RX_MD_BLOCK) void md_mean_kernel(const float* __res
   reps[3 * c] = r[0], reps[3 * c + 1] = r[1], reps[3 * c + 2] = r[2];
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_nearest_kernel(const float* __restrict__ pos, const long long* __restrict__ keys, long long V,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_nearest_kernel(const float* __restrict__ pos, const long long* __restrict__ keys, long long V,
                                                                  float cell, const long long* __restrict__ cluster_of, long long C,
                                                                  unsigned long long* __restrict__ best) {
-  MD_THREAD(v, V);
+  RX_MESH_THREAD(v, V);
   const long long c = cluster_of[v];
   if ((unsigned long long)c >= (unsigned long long)C || keys[v] < 0) return;
   const float p[3] = {pos[3 * v], pos[3 * v + 1], pos[3 * v + 2]};
   atomicMin(&best[c], (unsigned long long)md_nearest_pack(p, keys[v], cell, (int32_t)v));
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_pick_kernel(const float* __restrict__ pos, long long V, long long C,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_pick_kernel(const float* __restrict__ pos, long long V, long long C,
                                                               const unsigned long long* __restrict__ best, float* __restrict__ reps) {
-  MD_THREAD(c, C);
+  RX_MESH_THREAD(c, C);
   const unsigned long long m = best[c] & 0xffffffffULL;
   const bool ok = best[c] != ~0ULL && m < (unsigned long long)V;
   for (int k = 0; k < 3; ++k) reps[3 * c + k] = ok ? pos[3 * m + k] : 0.0f;
 }
 
 // ---- triangles --------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_remap_kernel(const long long* __restrict__ tri, long long T, long long V,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_remap_kernel(const long long* __restrict__ tri, long long T, long long V,
                                                                const long long* __restrict__ cluster_of, long long C, int* __restrict__ counts,
                                                                int* __restrict__ used, int* __restrict__ flag) {
-  MD_THREAD(t, T);
+  RX_MESH_THREAD(t, T);
   const int64_t id[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
   if (!mr_triangle_ok(id, V)) {
     atomicOr(flag, 4);
@@ -140,11 +133,11 @@ __global__ __launch_bounds__(RX_MD_BLOCK) void md_remap_kernel(const long long* 
   atomicAdd(&counts[lo], 1);
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_attach_kernel(const long long* __restrict__ tri, long long T, long long V,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_attach_kernel(const long long* __restrict__ tri, long long T, long long V,
                                                                 const long long* __restrict__ cluster_of, long long C,
                                                                 const long long* __restrict__ toff, int* __restrict__ cursor, long long capacity,
                                                                 int* __restrict__ entries) {
-  MD_THREAD(t, T);
+  RX_MESH_THREAD(t, T);
   const int64_t id[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
   int64_t c[3];
   int32_t lo, mid, hi;
@@ -155,20 +148,20 @@ __global__ __launch_bounds__(RX_MD_BLOCK) void md_attach_kernel(const long long*
   entries[3 * at] = mid, entries[3 * at + 1] = hi, entries[3 * at + 2] = (int)t;
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_unique_kernel(long long C, const long long* __restrict__ toff, long long capacity, int* entries,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_unique_kernel(long long C, const long long* __restrict__ toff, long long capacity, int* entries,
                                                                 long long T, int* __restrict__ keep) {
-  MD_THREAD(c, C);
+  RX_MESH_THREAD(c, C);
   const long long b = toff[c], e = toff[c + 1];
   if (b < 0 || e > capacity || e <= b) return;
   md_unique(entries + 3 * b, e - b, T, keep);
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_emit_triangles_kernel(const long long* __restrict__ tri, long long T, long long V,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_emit_triangles_kernel(const long long* __restrict__ tri, long long T, long long V,
                                                                         const long long* __restrict__ cluster_of, long long C,
                                                                         const int* __restrict__ keep, const long long* __restrict__ koff,
                                                                         const long long* __restrict__ uoff, long long capacity,
                                                                         long long* __restrict__ out) {
-  MD_THREAD(t, T);
+  RX_MESH_THREAD(t, T);
   if (!keep[t]) return;
   const long long at = koff[t];
   if (at < 0 || at >= capacity) return;
@@ -179,9 +172,9 @@ __global__ __launch_bounds__(RX_MD_BLOCK) void md_emit_triangles_kernel(const lo
   }
 }
 
-__global__ __launch_bounds__(RX_MD_BLOCK) void md_emit_vertices_kernel(long long C, const int* __restrict__ used, const long long* __restrict__ uoff,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void md_emit_vertices_kernel(long long C, const int* __restrict__ used, const long long* __restrict__ uoff,
                                                                        const float* __restrict__ reps, long long capacity, float* __restrict__ out) {
-  MD_THREAD(c, C);
+  RX_MESH_THREAD(c, C);
   if (!used[c]) return;
   const long long at = uoff[c];
   if (at < 0 || at >= capacity) return;
@@ -189,21 +182,6 @@ __global__ __launch_bounds__(RX_MD_BLOCK) void md_emit_vertices_kernel(long long
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------------
-#define MD_ALIGNED(p, a) ((((uintptr_t)(p)) & ((a) - 1)) == 0)
-#define MD_LAUNCH(fn, kernel, n, st, ...)                                                                  \
-  do {                                                                                                     \
-    hipLaunchKernelGGL(kernel, dim3(md_blocks(n)), dim3(RX_MD_BLOCK), 0, (hipStream_t)(st), __VA_ARGS__);  \
-    RX_CHECK_LAUNCH(fn);                                                                                   \
-  } while (0)
-
-static inline int md_count_ok(const char* fn, const char* what, int64_t n, int64_t lo, int64_t hi) {
-  if (n < lo || n > hi) RX_FAIL(RX_EINVAL, "%s: %lld %s (%lld .. %lld)", fn, (long long)n, what, (long long)lo, (long long)hi);
-  return RX_OK;
-}
-#define MD_VERTICES(fn, V) if (int rc = md_count_ok(fn, "vertices", V, 1, RX_MESH_MAX_VERTICES)) return rc
-#define MD_CLUSTERS(fn, C, V) if (int rc = md_count_ok(fn, "clusters", C, 1, V)) return rc
-#define MD_TRIANGLES(fn, T) if (int rc = md_count_ok(fn, "triangles", T, 1, RX_MESH_MAX_TRIANGLES)) return rc
-
 static inline int md_cell_ok(const char* fn, float cell) {
   if (!(cell > 0.0f && cell <= 3.402823466e38f)) RX_FAIL(RX_EINVAL, "%s: cell must be finite and > 0", fn);
   return RX_OK;
@@ -213,10 +191,10 @@ extern "C" int rx_mesh_cluster_keys(const float* vertices, int64_t n_vertices, f
   const char* fn = "rx_mesh_cluster_keys";
   if (!vertices) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!keys || !flag) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
+  RX_MESH_VERTICES(fn, n_vertices);
   if (int rc = md_cell_ok(fn, cell)) return rc;
-  if (!MD_ALIGNED(vertices, 4) || !MD_ALIGNED(keys, 8) || !MD_ALIGNED(flag, 4)) RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
-  MD_LAUNCH(fn, md_keys_kernel, n_vertices, stream, vertices, (long long)n_vertices, cell, (long long*)keys, flag);
+  if (!RX_MESH_ALIGNED(vertices, 4) || !RX_MESH_ALIGNED(keys, 8) || !RX_MESH_ALIGNED(flag, 4)) RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
+  RX_MESH_LAUNCH(fn, md_keys_kernel, n_vertices, stream, vertices, (long long)n_vertices, cell, (long long*)keys, flag);
   return RX_OK;
 }
 
@@ -225,19 +203,19 @@ extern "C" int rx_mesh_cluster_assign(const int64_t* keys, int64_t n_vertices, i
   const char* fn = "rx_mesh_cluster_assign";
   if (!keys) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!table_keys || !table_min || !slot_of || !first || !flag) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
+  RX_MESH_VERTICES(fn, n_vertices);
   if (capacity <= n_vertices || capacity > (1LL << 31) || (capacity & (capacity - 1)) != 0)
     RX_FAIL(RX_EINVAL, "%s: table capacity %lld (a power of two above the %lld vertices, at most 2^31)", fn, (long long)capacity, (long long)n_vertices);
-  if (!MD_ALIGNED(keys, 8) || !MD_ALIGNED(table_keys, 8) || !MD_ALIGNED(table_min, 4) || !MD_ALIGNED(slot_of, 4) || !MD_ALIGNED(first, 4) ||
-      !MD_ALIGNED(flag, 4))
+  if (!RX_MESH_ALIGNED(keys, 8) || !RX_MESH_ALIGNED(table_keys, 8) || !RX_MESH_ALIGNED(table_min, 4) || !RX_MESH_ALIGNED(slot_of, 4) || !RX_MESH_ALIGNED(first, 4) ||
+      !RX_MESH_ALIGNED(flag, 4))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(table_keys, 0xff, (size_t)capacity * 8, st) != hipSuccess ||      // MD_EMPTY
       hipMemsetAsync(table_min, 0xff, (size_t)capacity * 4, st) != hipSuccess)         // MD_NO_MIN
     RX_FAIL(RX_ELAUNCH, "%s: clearing the table failed", fn);
-  MD_LAUNCH(fn, md_insert_kernel, n_vertices, st, (const long long*)keys, (long long)n_vertices, (long long)capacity, (long long*)table_keys,
+  RX_MESH_LAUNCH(fn, md_insert_kernel, n_vertices, st, (const long long*)keys, (long long)n_vertices, (long long)capacity, (long long*)table_keys,
             (unsigned*)table_min, slot_of, flag);
-  MD_LAUNCH(fn, md_first_kernel, n_vertices, st, (long long)n_vertices, (const int*)slot_of, (long long)capacity, (const unsigned*)table_min, first);
+  RX_MESH_LAUNCH(fn, md_first_kernel, n_vertices, st, (long long)n_vertices, (const int*)slot_of, (long long)capacity, (const unsigned*)table_min, first);
   return RX_OK;
 }
 
@@ -246,11 +224,11 @@ extern "C" int rx_mesh_cluster_number(int64_t n_vertices, const int32_t* slot_of
   const char* fn = "rx_mesh_cluster_number";
   if (!slot_of || !table_min || !rank) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!cluster_of) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
+  RX_MESH_VERTICES(fn, n_vertices);
   if (capacity <= n_vertices || capacity > (1LL << 31)) RX_FAIL(RX_EINVAL, "%s: table capacity %lld", fn, (long long)capacity);
-  if (!MD_ALIGNED(slot_of, 4) || !MD_ALIGNED(table_min, 4) || !MD_ALIGNED(rank, 8) || !MD_ALIGNED(cluster_of, 8))
+  if (!RX_MESH_ALIGNED(slot_of, 4) || !RX_MESH_ALIGNED(table_min, 4) || !RX_MESH_ALIGNED(rank, 8) || !RX_MESH_ALIGNED(cluster_of, 8))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
-  MD_LAUNCH(fn, md_number_kernel, n_vertices, stream, (long long)n_vertices, slot_of, (long long)capacity, (const unsigned*)table_min, (const long long*)rank,
+  RX_MESH_LAUNCH(fn, md_number_kernel, n_vertices, stream, (long long)n_vertices, slot_of, (long long)capacity, (const unsigned*)table_min, (const long long*)rank,
             (long long*)cluster_of);
   return RX_OK;
 }
@@ -259,12 +237,12 @@ extern "C" int rx_mesh_cluster_count(const int64_t* cluster_of, int64_t n_vertic
   const char* fn = "rx_mesh_cluster_count";
   if (!cluster_of) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!counts) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
-  MD_CLUSTERS(fn, n_clusters, n_vertices);
-  if (!MD_ALIGNED(cluster_of, 8) || !MD_ALIGNED(counts, 4)) RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
+  RX_MESH_VERTICES(fn, n_vertices);
+  RX_MESH_CLUSTERS(fn, n_clusters, n_vertices);
+  if (!RX_MESH_ALIGNED(cluster_of, 8) || !RX_MESH_ALIGNED(counts, 4)) RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(counts, 0, (size_t)n_clusters * 4, st) != hipSuccess) RX_FAIL(RX_ELAUNCH, "%s: clearing the counts failed", fn);
-  MD_LAUNCH(fn, md_count_kernel, n_vertices, st, (const long long*)cluster_of, (long long)n_vertices, (long long)n_clusters, counts);
+  RX_MESH_LAUNCH(fn, md_count_kernel, n_vertices, st, (const long long*)cluster_of, (long long)n_vertices, (long long)n_clusters, counts);
   return RX_OK;
 }
 
@@ -273,14 +251,14 @@ extern "C" int rx_mesh_cluster_fill(const int64_t* cluster_of, int64_t n_vertice
   const char* fn = "rx_mesh_cluster_fill";
   if (!cluster_of || !member_offsets) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!cursor || !members) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
-  MD_CLUSTERS(fn, n_clusters, n_vertices);
+  RX_MESH_VERTICES(fn, n_vertices);
+  RX_MESH_CLUSTERS(fn, n_clusters, n_vertices);
   if (capacity < 0 || capacity > RX_MESH_MAX_VERTICES) RX_FAIL(RX_EINVAL, "%s: capacity %lld (0 .. 2^31 - 2 members)", fn, (long long)capacity);
-  if (!MD_ALIGNED(cluster_of, 8) || !MD_ALIGNED(member_offsets, 8) || !MD_ALIGNED(cursor, 4) || !MD_ALIGNED(members, 4))
+  if (!RX_MESH_ALIGNED(cluster_of, 8) || !RX_MESH_ALIGNED(member_offsets, 8) || !RX_MESH_ALIGNED(cursor, 4) || !RX_MESH_ALIGNED(members, 4))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(cursor, 0, (size_t)n_clusters * 4, st) != hipSuccess) RX_FAIL(RX_ELAUNCH, "%s: clearing the cursors failed", fn);
-  MD_LAUNCH(fn, md_fill_kernel, n_vertices, st, (const long long*)cluster_of, (long long)n_vertices, (long long)n_clusters,
+  RX_MESH_LAUNCH(fn, md_fill_kernel, n_vertices, st, (const long long*)cluster_of, (long long)n_vertices, (long long)n_clusters,
             (const long long*)member_offsets, cursor, (long long)capacity, members);
   return RX_OK;
 }
@@ -290,12 +268,12 @@ extern "C" int rx_mesh_cluster_mean(const float* vertices, int64_t n_vertices, i
   const char* fn = "rx_mesh_cluster_mean";
   if (!vertices || !member_offsets || !members) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!representatives) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
-  MD_CLUSTERS(fn, n_clusters, n_vertices);
+  RX_MESH_VERTICES(fn, n_vertices);
+  RX_MESH_CLUSTERS(fn, n_clusters, n_vertices);
   if (capacity < 0 || capacity > RX_MESH_MAX_VERTICES) RX_FAIL(RX_EINVAL, "%s: capacity %lld (0 .. 2^31 - 2 members)", fn, (long long)capacity);
-  if (!MD_ALIGNED(vertices, 4) || !MD_ALIGNED(member_offsets, 8) || !MD_ALIGNED(members, 4) || !MD_ALIGNED(representatives, 4))
+  if (!RX_MESH_ALIGNED(vertices, 4) || !RX_MESH_ALIGNED(member_offsets, 8) || !RX_MESH_ALIGNED(members, 4) || !RX_MESH_ALIGNED(representatives, 4))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
-  MD_LAUNCH(fn, md_mean_kernel, n_clusters, stream, vertices, (long long)n_vertices, (long long)n_clusters, (const long long*)member_offsets, members,
+  RX_MESH_LAUNCH(fn, md_mean_kernel, n_clusters, stream, vertices, (long long)n_vertices, (long long)n_clusters, (const long long*)member_offsets, members,
             (long long)capacity, representatives);
   return RX_OK;
 }
@@ -305,16 +283,16 @@ extern "C" int rx_mesh_cluster_nearest(const float* vertices, const int64_t* key
   const char* fn = "rx_mesh_cluster_nearest";
   if (!vertices || !keys || !cluster_of) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!best || !representatives) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
-  MD_CLUSTERS(fn, n_clusters, n_vertices);
+  RX_MESH_VERTICES(fn, n_vertices);
+  RX_MESH_CLUSTERS(fn, n_clusters, n_vertices);
   if (int rc = md_cell_ok(fn, cell)) return rc;
-  if (!MD_ALIGNED(vertices, 4) || !MD_ALIGNED(keys, 8) || !MD_ALIGNED(cluster_of, 8) || !MD_ALIGNED(best, 8) || !MD_ALIGNED(representatives, 4))
+  if (!RX_MESH_ALIGNED(vertices, 4) || !RX_MESH_ALIGNED(keys, 8) || !RX_MESH_ALIGNED(cluster_of, 8) || !RX_MESH_ALIGNED(best, 8) || !RX_MESH_ALIGNED(representatives, 4))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(best, 0xff, (size_t)n_clusters * 8, st) != hipSuccess) RX_FAIL(RX_ELAUNCH, "%s: clearing the minima failed", fn);
-  MD_LAUNCH(fn, md_nearest_kernel, n_vertices, st, vertices, (const long long*)keys, (long long)n_vertices, cell, (const long long*)cluster_of,
+  RX_MESH_LAUNCH(fn, md_nearest_kernel, n_vertices, st, vertices, (const long long*)keys, (long long)n_vertices, cell, (const long long*)cluster_of,
             (long long)n_clusters, (unsigned long long*)best);
-  MD_LAUNCH(fn, md_pick_kernel, n_clusters, st, vertices, (long long)n_vertices, (long long)n_clusters, (const unsigned long long*)best,
+  RX_MESH_LAUNCH(fn, md_pick_kernel, n_clusters, st, vertices, (long long)n_vertices, (long long)n_clusters, (const unsigned long long*)best,
             representatives);
   return RX_OK;
 }
@@ -324,15 +302,15 @@ extern "C" int rx_mesh_cluster_remap(const int64_t* triangles, int64_t n_triangl
   const char* fn = "rx_mesh_cluster_remap";
   if (!triangles || !cluster_of) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!counts || !used || !flag) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
-  MD_CLUSTERS(fn, n_clusters, n_vertices);
-  MD_TRIANGLES(fn, n_triangles);
-  if (!MD_ALIGNED(triangles, 8) || !MD_ALIGNED(cluster_of, 8) || !MD_ALIGNED(counts, 4) || !MD_ALIGNED(used, 4) || !MD_ALIGNED(flag, 4))
+  RX_MESH_VERTICES(fn, n_vertices);
+  RX_MESH_CLUSTERS(fn, n_clusters, n_vertices);
+  RX_MESH_TRIANGLES(fn, n_triangles);
+  if (!RX_MESH_ALIGNED(triangles, 8) || !RX_MESH_ALIGNED(cluster_of, 8) || !RX_MESH_ALIGNED(counts, 4) || !RX_MESH_ALIGNED(used, 4) || !RX_MESH_ALIGNED(flag, 4))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(counts, 0, (size_t)n_clusters * 4, st) != hipSuccess || hipMemsetAsync(used, 0, (size_t)n_clusters * 4, st) != hipSuccess)
     RX_FAIL(RX_ELAUNCH, "%s: clearing the counts failed", fn);
-  MD_LAUNCH(fn, md_remap_kernel, n_triangles, st, (const long long*)triangles, (long long)n_triangles, (long long)n_vertices,
+  RX_MESH_LAUNCH(fn, md_remap_kernel, n_triangles, st, (const long long*)triangles, (long long)n_triangles, (long long)n_vertices,
             (const long long*)cluster_of, (long long)n_clusters, counts, used, flag);
   return RX_OK;
 }
@@ -342,20 +320,20 @@ extern "C" int rx_mesh_cluster_unique(const int64_t* triangles, int64_t n_triang
   const char* fn = "rx_mesh_cluster_unique";
   if (!triangles || !cluster_of || !entry_offsets) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!cursor || !keep || (capacity > 0 && !entries)) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
-  MD_CLUSTERS(fn, n_clusters, n_vertices);
-  MD_TRIANGLES(fn, n_triangles);
+  RX_MESH_VERTICES(fn, n_vertices);
+  RX_MESH_CLUSTERS(fn, n_clusters, n_vertices);
+  RX_MESH_TRIANGLES(fn, n_triangles);
   if (capacity < 0 || capacity > RX_MESH_MAX_TRIANGLES) RX_FAIL(RX_EINVAL, "%s: capacity %lld (0 .. (2^31 - 2) / 3 entries)", fn, (long long)capacity);
-  if (!MD_ALIGNED(triangles, 8) || !MD_ALIGNED(cluster_of, 8) || !MD_ALIGNED(entry_offsets, 8) || !MD_ALIGNED(cursor, 4) || !MD_ALIGNED(entries, 4) ||
-      !MD_ALIGNED(keep, 4))
+  if (!RX_MESH_ALIGNED(triangles, 8) || !RX_MESH_ALIGNED(cluster_of, 8) || !RX_MESH_ALIGNED(entry_offsets, 8) || !RX_MESH_ALIGNED(cursor, 4) || !RX_MESH_ALIGNED(entries, 4) ||
+      !RX_MESH_ALIGNED(keep, 4))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(cursor, 0, (size_t)n_clusters * 4, st) != hipSuccess || hipMemsetAsync(keep, 0, (size_t)n_triangles * 4, st) != hipSuccess)
     RX_FAIL(RX_ELAUNCH, "%s: clearing the cursors failed", fn);
   if (capacity == 0) return RX_OK;      // no triangle survives
-  MD_LAUNCH(fn, md_attach_kernel, n_triangles, st, (const long long*)triangles, (long long)n_triangles, (long long)n_vertices,
+  RX_MESH_LAUNCH(fn, md_attach_kernel, n_triangles, st, (const long long*)triangles, (long long)n_triangles, (long long)n_vertices,
             (const long long*)cluster_of, (long long)n_clusters, (const long long*)entry_offsets, cursor, (long long)capacity, entries);
-  MD_LAUNCH(fn, md_unique_kernel, n_clusters, st, (long long)n_clusters, (const long long*)entry_offsets, (long long)capacity, entries,
+  RX_MESH_LAUNCH(fn, md_unique_kernel, n_clusters, st, (long long)n_clusters, (const long long*)entry_offsets, (long long)capacity, entries,
             (long long)n_triangles, keep);
   return RX_OK;
 }
@@ -367,20 +345,20 @@ extern "C" int rx_mesh_cluster_emit(const int64_t* triangles, int64_t n_triangle
   const char* fn = "rx_mesh_cluster_emit";
   if (!triangles || !cluster_of || !keep || !keep_offsets || !used || !used_offsets || !representatives) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if ((vertex_capacity > 0 && !out_vertices) || (triangle_capacity > 0 && !out_triangles)) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  MD_VERTICES(fn, n_vertices);
-  MD_CLUSTERS(fn, n_clusters, n_vertices);
-  MD_TRIANGLES(fn, n_triangles);
+  RX_MESH_VERTICES(fn, n_vertices);
+  RX_MESH_CLUSTERS(fn, n_clusters, n_vertices);
+  RX_MESH_TRIANGLES(fn, n_triangles);
   if (vertex_capacity < 0 || triangle_capacity < 0) RX_FAIL(RX_EINVAL, "%s: negative capacity", fn);
-  if (!MD_ALIGNED(triangles, 8) || !MD_ALIGNED(cluster_of, 8) || !MD_ALIGNED(keep, 4) || !MD_ALIGNED(keep_offsets, 8) || !MD_ALIGNED(used, 4) ||
-      !MD_ALIGNED(used_offsets, 8) || !MD_ALIGNED(representatives, 4) || !MD_ALIGNED(out_vertices, 4) || !MD_ALIGNED(out_triangles, 8))
+  if (!RX_MESH_ALIGNED(triangles, 8) || !RX_MESH_ALIGNED(cluster_of, 8) || !RX_MESH_ALIGNED(keep, 4) || !RX_MESH_ALIGNED(keep_offsets, 8) || !RX_MESH_ALIGNED(used, 4) ||
+      !RX_MESH_ALIGNED(used_offsets, 8) || !RX_MESH_ALIGNED(representatives, 4) || !RX_MESH_ALIGNED(out_vertices, 4) || !RX_MESH_ALIGNED(out_triangles, 8))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (triangle_capacity > 0)
-    MD_LAUNCH(fn, md_emit_triangles_kernel, n_triangles, st, (const long long*)triangles, (long long)n_triangles, (long long)n_vertices,
+    RX_MESH_LAUNCH(fn, md_emit_triangles_kernel, n_triangles, st, (const long long*)triangles, (long long)n_triangles, (long long)n_vertices,
               (const long long*)cluster_of, (long long)n_clusters, keep, (const long long*)keep_offsets, (const long long*)used_offsets,
               (long long)triangle_capacity, (long long*)out_triangles);
   if (vertex_capacity > 0)
-    MD_LAUNCH(fn, md_emit_vertices_kernel, n_clusters, st, (long long)n_clusters, used, (const long long*)used_offsets, representatives,
+    RX_MESH_LAUNCH(fn, md_emit_vertices_kernel, n_clusters, st, (long long)n_clusters, used, (const long long*)used_offsets, representatives,
               (long long)vertex_capacity, out_vertices);
   return RX_OK;
 }

@@ -5,56 +5,49 @@
 // thread writes its own vertex or triangle, and `used` receives plain stores of the constant 1.  The prefix sums and the emit pass
 // that follow are rx_mesh_scan (rx_meshrefine.hip) and rx_mesh_cluster_emit (rx_meshdecimate.hip) under the identity map.
 //
-//   ms_sample_kernel     a thread per vertex, all C channels: the clamped indices once, per channel the four x-pairs, the decode
+//   msp_sample_kernel     a thread per vertex, all C channels: the clamped indices once, per channel the four x-pairs, the decode
 //                        and the seven lerps; with `unit` the three values are normalised before the store.  A vertex whose two
 //                        z planes are not both in the slab is left alone, so successive slab launches fill one (V, C) buffer.
 //                        These are gathers: the mesher numbers vertices in ascending cell index, so the threads of a wave read
 //                        neighbouring lines; per vertex 12 bytes in, 4 C out and 8 C values of the volume, mostly from cache.
-//   ms_face_cos_kernel   a thread per triangle: cos, side, the keep flag (side == want, or every triangle where want is 0), and
+//   msp_face_cos_kernel   a thread per triangle: cos, side, the keep flag (side == want, or every triangle where want is 0), and
 //                        used[v] = 1 for the corners of a kept triangle.
-//   ms_mark_kernel       a thread per triangle: used[v] = 1 for the corners of a triangle whose keep flag is set.
+//   msp_mark_kernel       a thread per triangle: used[v] = 1 for the corners of a triangle whose keep flag is set.
 #include "rx_common.h"
 #include "rx_meshsample_core.h"
+#include "rx_mesh_host.h"
 
 #pragma clang fp contract(off)
 
-#define RX_MS_BLOCK 256
-
-static inline unsigned ms_blocks(long long n) { return (unsigned)((n + RX_MS_BLOCK - 1) / RX_MS_BLOCK); }      // n <= 2^31 - 2
-
-#define MS_THREAD(i, n)                                                        \
-  const long long i = (long long)blockIdx.x * RX_MS_BLOCK + threadIdx.x;       \
-  if (i >= (n)) return
-
 template <int RULE, typename T>
-__global__ __launch_bounds__(RX_MS_BLOCK) void ms_sample_kernel(const T* __restrict__ vol, int C, int z_base, int z_depth, int z_total, int Y, int X,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void msp_sample_kernel(const T* __restrict__ vol, int C, int z_base, int z_depth, int z_total, int Y, int X,
                                                                 const float* __restrict__ points, long long V, int unit, float* __restrict__ out) {
-  MS_THREAD(v, V);
+  RX_MESH_THREAD(v, V);
   const float p[3] = {points[3 * v], points[3 * v + 1], points[3 * v + 2]};
-  ms_sample_point<RULE, T>(vol, C, z_base, z_depth, z_total, Y, X, p, unit != 0, out + v * C);
+  msp_sample_point<RULE, T>(vol, C, z_base, z_depth, z_total, Y, X, p, unit != 0, out + v * C);
 }
 
-__global__ __launch_bounds__(RX_MS_BLOCK) void ms_face_cos_kernel(const float* __restrict__ pos, const float* __restrict__ vec, long long V,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void msp_face_cos_kernel(const float* __restrict__ pos, const float* __restrict__ vec, long long V,
                                                                   const long long* __restrict__ tri, long long T, float min_cos, int want,
                                                                   float* __restrict__ cos_out, signed char* __restrict__ side_out,
                                                                   int* __restrict__ keep, int* __restrict__ used, int* __restrict__ flag) {
-  MS_THREAD(t, T);
+  RX_MESH_THREAD(t, T);
   const int64_t id[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
   if (!mr_triangle_ok(id, V)) {      // never followed: the triangle is rim, and the caller refuses the mesh
     atomicOr(flag, 4);
     cos_out[t] = nanf(""), side_out[t] = 0, keep[t] = 0;
     return;
   }
-  const float c = ms_face_cos(pos + 3 * id[0], pos + 3 * id[1], pos + 3 * id[2], vec + 3 * id[0], vec + 3 * id[1], vec + 3 * id[2]);
-  const int s = ms_side(c, min_cos);
+  const float c = msp_face_cos(pos + 3 * id[0], pos + 3 * id[1], pos + 3 * id[2], vec + 3 * id[0], vec + 3 * id[1], vec + 3 * id[2]);
+  const int s = msp_side(c, min_cos);
   const int k = want == 0 || s == want;
   cos_out[t] = c, side_out[t] = (signed char)s, keep[t] = k;
   if (k) used[id[0]] = 1, used[id[1]] = 1, used[id[2]] = 1;      // every writer stores the same value
 }
 
-__global__ __launch_bounds__(RX_MS_BLOCK) void ms_mark_kernel(const long long* __restrict__ tri, long long T, long long V, const int* __restrict__ keep,
+__global__ __launch_bounds__(RX_MESH_BLOCK) void msp_mark_kernel(const long long* __restrict__ tri, long long T, long long V, const int* __restrict__ keep,
                                                               int* __restrict__ used, int* __restrict__ flag) {
-  MS_THREAD(t, T);
+  RX_MESH_THREAD(t, T);
   if (!keep[t]) return;
   const int64_t id[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
   if (!mr_triangle_ok(id, V)) {
@@ -65,38 +58,31 @@ __global__ __launch_bounds__(RX_MS_BLOCK) void ms_mark_kernel(const long long* _
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------------
-#define MS_ALIGNED(p, a) ((((uintptr_t)(p)) & ((a) - 1)) == 0)
-#define MS_LAUNCH(fn, kernel, n, st, ...)                                                                  \
-  do {                                                                                                     \
-    hipLaunchKernelGGL(kernel, dim3(ms_blocks(n)), dim3(RX_MS_BLOCK), 0, (hipStream_t)(st), __VA_ARGS__);  \
-    RX_CHECK_LAUNCH(fn);                                                                                   \
-  } while (0)
-
 extern "C" int rx_mesh_sample(const void* volume, int rule, int channels, int z_base, int z_depth, int z_total, int y, int x, const float* points,
                               int64_t n_points, int unit, float* out, void* stream) {
   const char* fn = "rx_mesh_sample";
   if (!volume || !points) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!out) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  if (rule < RX_MS_COPY || rule > RX_MS_NORMAL_U16) RX_FAIL(RX_EINVAL, "%s: rule %d (0 copy, 1 u8, 2 u16, 3 normal_u16)", fn, rule);
-  if (channels < 1 || channels > RX_MS_MAX_CHANNELS) RX_FAIL(RX_EINVAL, "%s: %d channels (1 .. %d)", fn, channels, RX_MS_MAX_CHANNELS);
+  if (rule < RX_MSP_COPY || rule > RX_MSP_NORMAL_U16) RX_FAIL(RX_EINVAL, "%s: rule %d (0 copy, 1 u8, 2 u16, 3 normal_u16)", fn, rule);
+  if (channels < 1 || channels > RX_MSP_MAX_CHANNELS) RX_FAIL(RX_EINVAL, "%s: %d channels (1 .. %d)", fn, channels, RX_MSP_MAX_CHANNELS);
   if (unit != 0 && channels != 3) RX_FAIL(RX_EINVAL, "%s: unit needs 3 channels, got %d", fn, channels);
-  if (y < 1 || x < 1 || z_total < 1 || y > RX_MS_MAX_EXTENT || x > RX_MS_MAX_EXTENT || z_total > RX_MS_MAX_EXTENT)
+  if (y < 1 || x < 1 || z_total < 1 || y > RX_MSP_MAX_EXTENT || x > RX_MSP_MAX_EXTENT || z_total > RX_MSP_MAX_EXTENT)
     RX_FAIL(RX_EINVAL, "%s: extents %d x %d x %d (1 .. 2^24 - 2 each)", fn, z_total, y, x);
   if (z_base < 0 || z_depth < 1 || z_depth > z_total - z_base)
     RX_FAIL(RX_EINVAL, "%s: slab planes %d .. %d + %d do not lie inside the %d planes of the volume", fn, z_base, z_base, z_depth, z_total);
-  if (n_points < 1 || n_points > RX_MESH_MAX_VERTICES) RX_FAIL(RX_EINVAL, "%s: %lld points (1 .. 2^31 - 2)", fn, (long long)n_points);
-  const int width = rule == RX_MS_COPY ? 4 : (rule == RX_MS_U8 ? 1 : 2);
-  if (!MS_ALIGNED(volume, width) || !MS_ALIGNED(points, 4) || !MS_ALIGNED(out, 4)) RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
-#define MS_SAMPLE(RULE, T)                                                                                                                  \
-  MS_LAUNCH(fn, (ms_sample_kernel<RULE, T>), n_points, stream, (const T*)volume, channels, z_base, z_depth, z_total, y, x, points, \
+  if (int rc = rx_mesh_range_ok(fn, n_points, 1, RX_MESH_MAX_VERTICES, "points (1 .. 2^31 - 2)")) return rc;
+  const int width = rule == RX_MSP_COPY ? 4 : (rule == RX_MSP_U8 ? 1 : 2);
+  if (!RX_MESH_ALIGNED(volume, width) || !RX_MESH_ALIGNED(points, 4) || !RX_MESH_ALIGNED(out, 4)) RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
+#define MSP_SAMPLE(RULE, T)                                                                                                                  \
+  RX_MESH_LAUNCH(fn, (msp_sample_kernel<RULE, T>), n_points, stream, (const T*)volume, channels, z_base, z_depth, z_total, y, x, points, \
             (long long)n_points, unit, out)
   switch (rule) {
-    case RX_MS_COPY: MS_SAMPLE(RX_MS_COPY, float); break;
-    case RX_MS_U8: MS_SAMPLE(RX_MS_U8, uint8_t); break;
-    case RX_MS_U16: MS_SAMPLE(RX_MS_U16, uint16_t); break;
-    default: MS_SAMPLE(RX_MS_NORMAL_U16, uint16_t); break;
+    case RX_MSP_COPY: MSP_SAMPLE(RX_MSP_COPY, float); break;
+    case RX_MSP_U8: MSP_SAMPLE(RX_MSP_U8, uint8_t); break;
+    case RX_MSP_U16: MSP_SAMPLE(RX_MSP_U16, uint16_t); break;
+    default: MSP_SAMPLE(RX_MSP_NORMAL_U16, uint16_t); break;
   }
-#undef MS_SAMPLE
+#undef MSP_SAMPLE
   return RX_OK;
 }
 
@@ -105,16 +91,16 @@ extern "C" int rx_mesh_face_cos(const float* vertices, const float* vectors, int
   const char* fn = "rx_mesh_face_cos";
   if (!vertices || !vectors || !triangles) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!cos || !side || !keep || !used || !flag) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  if (n_vertices < 1 || n_vertices > RX_MESH_MAX_VERTICES) RX_FAIL(RX_EINVAL, "%s: %lld vertices (1 .. 2^31 - 2)", fn, (long long)n_vertices);
-  if (n_triangles < 1 || n_triangles > RX_MESH_MAX_TRIANGLES) RX_FAIL(RX_EINVAL, "%s: %lld triangles (1 .. (2^31 - 2) / 3)", fn, (long long)n_triangles);
+  if (int rc = rx_mesh_range_ok(fn, n_vertices, 1, RX_MESH_MAX_VERTICES, "vertices (1 .. 2^31 - 2)")) return rc;
+  if (int rc = rx_mesh_range_ok(fn, n_triangles, 1, RX_MESH_MAX_TRIANGLES, "triangles (1 .. (2^31 - 2) / 3)")) return rc;
   if (!(min_cos >= 0.0f && min_cos < 1.0f)) RX_FAIL(RX_EINVAL, "%s: min_cos must lie in [0, 1)", fn);
   if (want < -1 || want > 1) RX_FAIL(RX_EINVAL, "%s: want %d (1 front, -1 back, 0 every triangle)", fn, want);
-  if (!MS_ALIGNED(vertices, 4) || !MS_ALIGNED(vectors, 4) || !MS_ALIGNED(triangles, 8) || !MS_ALIGNED(cos, 4) || !MS_ALIGNED(keep, 4) ||
-      !MS_ALIGNED(used, 4) || !MS_ALIGNED(flag, 4))
+  if (!RX_MESH_ALIGNED(vertices, 4) || !RX_MESH_ALIGNED(vectors, 4) || !RX_MESH_ALIGNED(triangles, 8) || !RX_MESH_ALIGNED(cos, 4) || !RX_MESH_ALIGNED(keep, 4) ||
+      !RX_MESH_ALIGNED(used, 4) || !RX_MESH_ALIGNED(flag, 4))
     RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(used, 0, (size_t)n_vertices * 4, st) != hipSuccess) RX_FAIL(RX_ELAUNCH, "%s: clearing the used flags failed", fn);
-  MS_LAUNCH(fn, ms_face_cos_kernel, n_triangles, st, vertices, vectors, (long long)n_vertices, (const long long*)triangles, (long long)n_triangles,
+  RX_MESH_LAUNCH(fn, msp_face_cos_kernel, n_triangles, st, vertices, vectors, (long long)n_vertices, (const long long*)triangles, (long long)n_triangles,
             min_cos, want, cos, (signed char*)side, keep, used, flag);
   return RX_OK;
 }
@@ -124,11 +110,11 @@ extern "C" int rx_mesh_select_mark(const int64_t* triangles, int64_t n_triangles
   const char* fn = "rx_mesh_select_mark";
   if (!triangles || !keep) RX_FAIL(RX_EINVAL, "%s: null input pointer", fn);
   if (!used || !flag) RX_FAIL(RX_EINVAL, "%s: null output pointer", fn);
-  if (n_vertices < 1 || n_vertices > RX_MESH_MAX_VERTICES) RX_FAIL(RX_EINVAL, "%s: %lld vertices (1 .. 2^31 - 2)", fn, (long long)n_vertices);
-  if (n_triangles < 1 || n_triangles > RX_MESH_MAX_TRIANGLES) RX_FAIL(RX_EINVAL, "%s: %lld triangles (1 .. (2^31 - 2) / 3)", fn, (long long)n_triangles);
-  if (!MS_ALIGNED(triangles, 8) || !MS_ALIGNED(keep, 4) || !MS_ALIGNED(used, 4) || !MS_ALIGNED(flag, 4)) RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
+  if (int rc = rx_mesh_range_ok(fn, n_vertices, 1, RX_MESH_MAX_VERTICES, "vertices (1 .. 2^31 - 2)")) return rc;
+  if (int rc = rx_mesh_range_ok(fn, n_triangles, 1, RX_MESH_MAX_TRIANGLES, "triangles (1 .. (2^31 - 2) / 3)")) return rc;
+  if (!RX_MESH_ALIGNED(triangles, 8) || !RX_MESH_ALIGNED(keep, 4) || !RX_MESH_ALIGNED(used, 4) || !RX_MESH_ALIGNED(flag, 4)) RX_FAIL(RX_EINVAL, "%s: misaligned pointer", fn);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(used, 0, (size_t)n_vertices * 4, st) != hipSuccess) RX_FAIL(RX_ELAUNCH, "%s: clearing the used flags failed", fn);
-  MS_LAUNCH(fn, ms_mark_kernel, n_triangles, st, (const long long*)triangles, (long long)n_triangles, (long long)n_vertices, keep, used, flag);
+  RX_MESH_LAUNCH(fn, msp_mark_kernel, n_triangles, st, (const long long*)triangles, (long long)n_triangles, (long long)n_vertices, keep, used, flag);
   return RX_OK;
 }

@@ -16,15 +16,11 @@
 #include <vector>
 
 #include "../rx_components_core.h"
+#include "check_util.h"
 
 struct Shape { int z, y, x; };
 static const Shape SHAPES[] = {{1, 1, 1}, {1, 1, 70}, {1, 70, 1}, {5, 1, 3}, {9, 10, 12}, {33, 17, 70}, {3, 130, 5}, {130, 3, 5}, {2, 3, 257}, {40, 40, 130}};
 
-static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-static uint32_t rnd() {
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return (uint32_t)(g_rng >> 33);
-}
 
 struct TileForest {      // a tile's forest: what the kernel keeps in LDS
   std::vector<int> p;
@@ -40,11 +36,6 @@ struct VolForest {      // the label volume: label = parent + 1
   void set_parent(int i, int v) { l.at(i) = v + 1; }
 };
 
-static void order(std::vector<long>& idx, int how) {      // 0 raster, 1 reverse, 2 shuffled
-  if (how == 1) std::reverse(idx.begin(), idx.end());
-  if (how == 2)
-    for (size_t i = idx.size(); i > 1; --i) std::swap(idx[i - 1], idx[rnd() % i]);
-}
 
 static std::vector<int> label_core(const std::vector<uint8_t>& m, Shape s, int conn, int how) {
   const int Z = s.z, Y = s.y, X = s.x, steps = cc_max_steps(conn);

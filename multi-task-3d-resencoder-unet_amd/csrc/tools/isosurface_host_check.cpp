@@ -18,22 +18,13 @@
 #include <vector>
 
 #include "../rx_isosurface_core.h"
+#include "check_util.h"
 
 struct Shape { int z, y, x; };
 static const Shape SHAPES[] = {{1, 1, 1}, {1, 1, 70}, {1, 70, 1}, {5, 1, 3}, {9, 10, 12}, {33, 17, 70}, {3, 130, 5}, {130, 3, 5}, {2, 3, 257}, {40, 40, 130}};
 static const int LEVELS[] = {0, 127, 254};
 
-static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-static uint32_t rnd() {
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return (uint32_t)(g_rng >> 33);
-}
 
-static void order(std::vector<long>& idx, int how) {      // 0 raster, 1 reverse, 2 shuffled
-  if (how == 1) std::reverse(idx.begin(), idx.end());
-  if (how == 2)
-    for (size_t i = idx.size(); i > 1; --i) std::swap(idx[i - 1], idx[rnd() % i]);
-}
 
 struct Mesh {
   std::vector<float> v;        // 3 per vertex: x, y, z
@@ -219,7 +210,7 @@ int main() {
           const Mesh got = mesh_core(v, level, how);
           ++ncases;
           const bool same = got.t == want.t && got.v.size() == want.v.size() &&
-                            (got.v.empty() || memcmp(got.v.data(), want.v.data(), got.v.size() * sizeof(float)) == 0);
+                            same_bits(got.v, want.v);
           if (!same) {
             ++bad;
             printf("DIFFER %dx%dx%d %s level %d order %d: %zu / %zu vertices, %zu / %zu triangles\n", s.z, s.y, s.x, c.name.c_str(), level, how,

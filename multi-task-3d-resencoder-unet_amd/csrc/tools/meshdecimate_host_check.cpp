@@ -24,13 +24,8 @@
 #include <vector>
 
 #include "../rx_meshdecimate_core.h"
+#include "check_util.h"
 
-static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-static uint32_t rnd() {
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return (uint32_t)(g_rng >> 33);
-}
-static float rndf() { return (float)(rnd() % 20001) / 100.0f - 100.0f; }
 
 struct Mesh {
   std::string name;
@@ -45,16 +40,14 @@ struct Result {
   std::vector<float> v;
   std::vector<int64_t> t, cluster_of;
   bool operator==(const Result& o) const {
-    return v.size() == o.v.size() && (v.empty() || memcmp(v.data(), o.v.data(), v.size() * sizeof(float)) == 0) && t == o.t && cluster_of == o.cluster_of;
+    return same_bits(v, o.v) && t == o.t && cluster_of == o.cluster_of;
   }
 };
 
 static std::vector<int64_t> order(int64_t n, int how) {      // 0 raster, 1 reverse, 2 shuffled
   std::vector<int64_t> idx;
   for (int64_t i = 0; i < n; ++i) idx.push_back(i);
-  if (how == 1) std::reverse(idx.begin(), idx.end());
-  if (how == 2)
-    for (size_t i = idx.size(); i > 1; --i) std::swap(idx[i - 1], idx[rnd() % i]);
+  order(idx, how);
   return idx;
 }
 

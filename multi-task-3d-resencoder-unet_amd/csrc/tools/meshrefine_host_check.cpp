@@ -22,13 +22,8 @@
 #include <vector>
 
 #include "../rx_meshrefine_core.h"
+#include "check_util.h"
 
-static uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-static uint32_t rnd() {
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return (uint32_t)(g_rng >> 33);
-}
-static float rndf() { return (float)(rnd() % 20001) / 100.0f - 100.0f; }
 
 struct Mesh {
   std::string name;
@@ -47,11 +42,6 @@ struct Adjacency {
   }
 };
 
-static void order(std::vector<int64_t>& idx, int how) {      // 0 raster, 1 reverse, 2 shuffled
-  if (how == 1) std::reverse(idx.begin(), idx.end());
-  if (how == 2)
-    for (size_t i = idx.size(); i > 1; --i) std::swap(idx[i - 1], idx[rnd() % i]);
-}
 
 // ---- the passes, through the core header --------------------------------------------------------------------------------------------------
 static Adjacency adjacency_core(const Mesh& m, int how) {
@@ -251,9 +241,6 @@ static Mesh shuffled(const Mesh& m) {
   return s;
 }
 
-static bool same_bits(const std::vector<float>& a, const std::vector<float>& b) {
-  return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(float)) == 0);
-}
 
 int main() {
   long runs = 0, bad = 0;

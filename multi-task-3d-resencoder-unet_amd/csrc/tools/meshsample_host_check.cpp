@@ -14,27 +14,22 @@
 #include <vector>
 
 #include "../rx_meshsample_core.h"
+#include "check_util.h"
 
-static uint64_t g_state = 0x9e3779b97f4a7c15ULL;
-static uint32_t rnd() {
-  g_state = g_state * 6364136223846793005ULL + 1442695040888963407ULL;
-  return (uint32_t)(g_state >> 33);
-}
 static float uniform(float lo, float hi) { return lo + (hi - lo) * (float)(rnd() % 65536) / 65536.0f; }
 
-static bool same_bits(float a, float b) { return std::memcmp(&a, &b, 4) == 0; }
 
 // ---- the restatement ----------------------------------------------------------------------------------------------------------------------------
 template <typename T>
 static float ref_decode(int rule, T v) {
   volatile float f = (float)v;
-  if (rule == RX_MS_COPY) return f;
-  if (rule == RX_MS_U8) {
+  if (rule == RX_MSP_COPY) return f;
+  if (rule == RX_MSP_U8) {
     volatile float q = f / 255.0f;
     return q;
   }
   volatile float q = f / 65535.0f;
-  if (rule == RX_MS_U16) return q;
+  if (rule == RX_MSP_U16) return q;
   volatile float d = q * 2.0f;
   volatile float r = d - 1.0f;
   return r;
@@ -142,10 +137,10 @@ template <int RULE, typename T>
 static void run_volume(int C, int Z, int Y, int X, bool wild) {
   std::vector<T> vol((size_t)C * Z * Y * X);
   for (auto& v : vol) {
-    if (RULE == RX_MS_COPY) v = (T)uniform(-4.0f, 4.0f);
-    else v = (T)(rnd() % (RULE == RX_MS_U8 ? 256 : 65536));
+    if (RULE == RX_MSP_COPY) v = (T)uniform(-4.0f, 4.0f);
+    else v = (T)(rnd() % (RULE == RX_MSP_U8 ? 256 : 65536));
   }
-  if (RULE == RX_MS_COPY) {      // -0.0 and two denormals
+  if (RULE == RX_MSP_COPY) {      // -0.0 and two denormals
     const uint32_t bits[3] = {0x80000000u, 1u, 0x8000085eu};
     for (int k = 0; k < 3 && k < (int)vol.size(); ++k) std::memcpy(&vol[(size_t)k * (vol.size() / 3)], &bits[k], 4);
   }
@@ -155,7 +150,7 @@ static void run_volume(int C, int Z, int Y, int X, bool wild) {
   for (long v = 0; v < V; ++v) ref_sample<T>(RULE, vol, C, Z, Y, X, &pts[3 * v], &want[(size_t)v * C]);
   // resident
   for (long v = 0; v < V; ++v)
-    if (!ms_sample_point<RULE, T>(vol.data(), C, 0, Z, Z, Y, X, &pts[3 * v], false, &got[(size_t)v * C])) ++g_differ;
+    if (!msp_sample_point<RULE, T>(vol.data(), C, 0, Z, Z, Y, X, &pts[3 * v], false, &got[(size_t)v * C])) ++g_differ;
   ++g_runs;
   for (size_t i = 0; i < want.size(); ++i)
     if (!same_bits(want[i], got[i])) { ++g_differ; break; }
@@ -168,7 +163,7 @@ static void run_volume(int C, int Z, int Y, int X, bool wild) {
       std::vector<T> slab((size_t)C * planes * Y * X);
       for (int c = 0; c < C; ++c)
         std::memcpy(&slab[(size_t)c * planes * Y * X], &vol[((size_t)c * Z + a) * Y * X], (size_t)planes * Y * X * sizeof(T));
-      for (long v = 0; v < V; ++v) times[v] += ms_sample_point<RULE, T>(slab.data(), C, a, planes, Z, Y, X, &pts[3 * v], false, &fill[(size_t)v * C]);
+      for (long v = 0; v < V; ++v) times[v] += msp_sample_point<RULE, T>(slab.data(), C, a, planes, Z, Y, X, &pts[3 * v], false, &fill[(size_t)v * C]);
     }
     ++g_runs;
     bool bad = false;
@@ -181,7 +176,7 @@ static void run_volume(int C, int Z, int Y, int X, bool wild) {
     for (long v = 0; v < V; ++v) {
       float u[3] = {want[3 * v], want[3 * v + 1], want[3 * v + 2]}, o[3] = {-77.0f, -77.0f, -77.0f};
       ref_unit(u);
-      ms_sample_point<RULE, T>(vol.data(), C, 0, Z, Z, Y, X, &pts[3 * v], true, o);
+      msp_sample_point<RULE, T>(vol.data(), C, 0, Z, Z, Y, X, &pts[3 * v], true, o);
       if (!same_bits(u[0], o[0]) || !same_bits(u[1], o[1]) || !same_bits(u[2], o[2])) { ++g_differ; break; }
     }
   }
@@ -211,10 +206,10 @@ static void run_faces() {
       if (t % 11 == 0) id[0] = id[1] = id[2] = 7 * (rnd() % 9);      // zero vectors at all corners, and degenerate
       if (t % 13 == 0) id[0] = 0, id[1] = 7, id[2] = 14;             // zero vectors, a proper triangle: m = 0
       const float want = ref_face_cos(&pos[3 * id[0]], &pos[3 * id[1]], &pos[3 * id[2]], &vec[3 * id[0]], &vec[3 * id[1]], &vec[3 * id[2]]);
-      const float got = ms_face_cos(&pos[3 * id[0]], &pos[3 * id[1]], &pos[3 * id[2]], &vec[3 * id[0]], &vec[3 * id[1]], &vec[3 * id[2]]);
+      const float got = msp_face_cos(&pos[3 * id[0]], &pos[3 * id[1]], &pos[3 * id[2]], &vec[3 * id[0]], &vec[3 * id[1]], &vec[3 * id[2]]);
       const int side = want > min_cos ? 1 : (want < -min_cos ? -1 : 0);
-      bad = bad || !(same_bits(want, got) || (std::isnan(want) && std::isnan(got))) || side != ms_side(got, min_cos);
-      if ((t % 9 == 0 || t % 13 == 0) && !(std::isnan(got) && ms_side(got, min_cos) == 0)) bad = true;      // the rim rule
+      bad = bad || !(same_bits(want, got) || (std::isnan(want) && std::isnan(got))) || side != msp_side(got, min_cos);
+      if ((t % 9 == 0 || t % 13 == 0) && !(std::isnan(got) && msp_side(got, min_cos) == 0)) bad = true;      // the rim rule
       ++seen[side + 1];
     }
     if (bad || !seen[0] || !seen[1] || !seen[2]) ++g_differ;
@@ -222,16 +217,16 @@ static void run_faces() {
   // the unit rule at its edges
   ++g_runs;
   float z[3] = {0.0f, -0.0f, 0.0f}, tiny[3] = {1e-30f, 0.0f, 0.0f}, v[3] = {3.0f, 0.0f, 4.0f};
-  ms_unit(z), ms_unit(tiny), ms_unit(v);
+  msp_unit(z), msp_unit(tiny), msp_unit(v);
   const float zero = 0.0f;
   if (!same_bits(z[0], zero) || !same_bits(z[1], zero) || !same_bits(tiny[0], zero) || v[0] != 3.0f / 5.0f || v[2] != 4.0f / 5.0f) ++g_differ;
 }
 
 int main() {
-  run_rule<RX_MS_COPY, float>();
-  run_rule<RX_MS_U8, uint8_t>();
-  run_rule<RX_MS_U16, uint16_t>();
-  run_rule<RX_MS_NORMAL_U16, uint16_t>();
+  run_rule<RX_MSP_COPY, float>();
+  run_rule<RX_MSP_U8, uint8_t>();
+  run_rule<RX_MSP_U16, uint16_t>();
+  run_rule<RX_MSP_NORMAL_U16, uint16_t>();
   run_faces();
   std::printf("%ld runs, %ld differ from the direct restatement\n", g_runs, g_differ);
   return g_differ ? 1 : 0;

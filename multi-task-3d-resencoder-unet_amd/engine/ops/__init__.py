@@ -18,7 +18,8 @@ from .infer import (SW_ACT, SW_BLEND, SW_CAST, SW_NORM, sw_accumulate, sw_finali
                     sw_gather_workspace, sw_occupancy)
 from .losses import (bce_dice_loss_bwd, bce_dice_loss_fwd, cross_entropy_loss_bwd, cross_entropy_loss_fwd,      # noqa: F401
                      elem_loss_bwd, elem_loss_fwd, masked_cosine_loss_bwd, masked_cosine_loss_fwd)
-from .mesh import mesh_slice_labels, mesh_slice_normals      # noqa: F401
+from .mesh import (MeshAdjacency, mesh_adjacency, mesh_decimate, mesh_face_cos, mesh_sample, mesh_select,      # noqa: F401
+                   mesh_slice_labels, mesh_slice_normals, mesh_smooth, mesh_vertex_normals)
 from .network import (avgpool_bwd, avgpool_fwd, channel_sum, conv3d_bwd_data, conv3d_bwd_data_instats,      # noqa: F401
                       conv3d_bwd_weight, conv3d_fwd, conv3d_fwd_stats, convT3d_bwd_data, convT3d_bwd_weight, convT3d_fwd,
                       head_bwd, head_fwd, instnorm_act_bwd, instnorm_act_bwd_apply, instnorm_act_bwd_head,
@@ -28,7 +29,6 @@ from .network import (avgpool_bwd, avgpool_fwd, channel_sum, conv3d_bwd_data, co
                       stem_conv_bwd_weight, stem_conv_fwd, stem_conv_fwd_stats)
 from .pipeline import (affine_apply, affine_table, aug_filter_zy, aug_philox_u32, aug_pointwise, augment_batch,      # noqa: F401
                        box_stats, elastic_apply, elastic_nodes, elastic_tables, geom_apply, geom_table, ingest, label_dilate)
-from .postprocess import (MeshAdjacency, cc_filter, cc_label, cc_sizes, iso_counts, iso_mesh, mesh_adjacency,      # noqa: F401
-                          mesh_decimate, mesh_face_cos, mesh_sample, mesh_select, mesh_smooth, mesh_vertex_normals)
+from .postprocess import cc_filter, cc_label, cc_sizes, iso_counts, iso_mesh      # noqa: F401
 from .validation import (class_counts, edt_sq, mask_edges, normal_stats, preview_frames, preview_panel, seg_counts,      # noqa: F401
                          surface_hist, surface_scratch)

@@ -753,6 +753,17 @@ def load_model(mgr, device="cuda"):
     return model
 
 
+def _mesh_chain():
+    """the mesh stages after the mesher, in the order they run: (config key, (block, max_device_bytes) -> driver, (block, store) ->
+    what `run` takes beside the mesh file)"""
+    from .postprocess import MeshDecimator, MeshOrienter, MeshRefiner
+    return (("refine", lambda c, b: MeshRefiner(c["iterations"], c["lam"], c["mu"], c["clamp"], c["pin_boundary"], c["normals"], max_device_bytes=b),
+             lambda c, store: ()),
+            ("decimate", lambda c, b: MeshDecimator(c["cell"], c["representative"], c["normals"], max_device_bytes=b), lambda c, store: ()),
+            ("orient", lambda c, b: MeshOrienter(c["side"], c["min_cos"], c["normals"], max_device_bytes=b),
+             lambda c, store: (store, f"{c['normals_task']}_final")))
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Streaming sliding-window inference of the multi-task 3-D ResEnc U-Net (HIP engine).")
@@ -792,33 +803,16 @@ def main(argv=None):
         for task in mesh["tasks"]:
             print(task, SurfaceMesher(mesh["level"], mesh["format"], None if gb is None else int(gb * 2**30)).run(store, task, mesh["source"]),
                   flush=True)
-    refine = (mgr.infer_postprocess or {}).get("refine")
-    if refine:      # after the mesher: it reads the file that has just been written
-        from .postprocess import MeshRefiner
-        gb = refine["max_device_gb"]
-        for task in refine["tasks"]:
-            print(task, MeshRefiner(refine["iterations"], refine["lam"], refine["mu"], refine["clamp"], refine["pin_boundary"], refine["normals"],
-                                    max_device_bytes=None if gb is None else int(gb * 2**30)).run(
-                                        os.path.join(store, f"{task}_{mesh['source']}.{mesh['format']}")), flush=True)
-    decimate = (mgr.infer_postprocess or {}).get("decimate")
-    if decimate:      # last: it reads the refined file where the task is refined as well, the mesher's otherwise
-        from .postprocess import MeshDecimator
-        gb = decimate["max_device_gb"]
-        for task in decimate["tasks"]:
-            stem = f"{task}_{mesh['source']}" + ("_refined" if refine and task in refine["tasks"] else "")
-            print(task, MeshDecimator(decimate["cell"], decimate["representative"], decimate["normals"],
-                                      max_device_bytes=None if gb is None else int(gb * 2**30)).run(
-                                          os.path.join(store, f"{stem}.{mesh['format']}")), flush=True)
-    orient = (mgr.infer_postprocess or {}).get("orient")
-    if orient:      # last: it reads the newest mesh file of the chain -- decimated, else refined, else the mesher's
-        from .postprocess import MeshOrienter
-        gb = orient["max_device_gb"]
-        for task in orient["tasks"]:
-            stem = (f"{task}_{mesh['source']}" + ("_refined" if refine and task in refine["tasks"] else "")
-                    + ("_decimated" if decimate and task in decimate["tasks"] else ""))
-            print(task, MeshOrienter(orient["side"], orient["min_cos"], orient["normals"],
-                                     max_device_bytes=None if gb is None else int(gb * 2**30)).run(
-                                         os.path.join(store, f"{stem}.{mesh['format']}"), store, f"{orient['normals_task']}_final"), flush=True)
+    newest = {task: os.path.join(store, f"{task}_{mesh['source']}.{mesh['format']}") for task in mesh["tasks"]} if mesh else {}
+    for key, make, more in _mesh_chain():      # every stage reads the newest mesh file of its task: the stage's before it, else the mesher's
+        c = (mgr.infer_postprocess or {}).get(key)
+        if not c:
+            continue
+        gb = c["max_device_gb"]
+        for task in c["tasks"]:
+            stage = make(c, None if gb is None else int(gb * 2**30))
+            print(task, stage.run(newest[task], *more(c, store)), flush=True)
+            newest[task] = f"{os.path.splitext(newest[task])[0]}_{stage.suffix}.{mesh['format']}"
     return store
 
 

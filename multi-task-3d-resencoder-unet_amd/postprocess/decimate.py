@@ -7,12 +7,11 @@ representative and drops the triangles that collapse.  It is linear in the mesh,
 result is a property of the mesh alone: every number below is derived from cell keys and smallest member ids, every float32
 operation is one rounding in the order written here, and the kernels reproduce that -- results compare with array_equal, floats by
 their bits.  The statement uses numpy only."""
-import os
-
 import numpy as np
 
-from .isosurface import FORMATS
-from .refine import F32, _check_mesh, _gather_sum, read_mesh, vertex_normals_numpy, write_refined
+from .mesh_io import F32, _check_mesh, gather_sum
+from .refine import vertex_normals_numpy
+from .stage import MeshStage, parse_stage_block
 
 KEY = "inference_config.postprocess.decimate"
 REPRESENTATIVES = ("mean", "nearest")
@@ -113,7 +112,7 @@ def decimate_numpy(vertices, triangles, cell, representative="mean"):
     n = np.bincount(cluster_of, minlength=C)
     offsets = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
     if representative == "mean":
-        rep = (_gather_sum(p, offsets, members, np.arange(C)) / n.astype(F32)[:, None]).astype(F32)
+        rep = (gather_sum(p, offsets, members, np.arange(C)) / n.astype(F32)[:, None]).astype(F32)
     else:
         with np.errstate(over="ignore"):
             centre = (k.astype(F32) + F32(0.5)) * c
@@ -135,64 +134,38 @@ def decimate_numpy(vertices, triangles, cell, representative="mean"):
 
 
 # ---- the config block -------------------------------------------------------------------------------------------------------------------------
-_DEFAULTS = {"representative": "mean", "normals": True, "max_device_gb": None}
+_DEFAULTS = {"representative": "mean", "normals": True}
 
 
 def parse_decimate_config(m, mesh_tasks):
     """`inference_config.postprocess.decimate` -> {tasks, cell, representative, normals, max_device_gb}.  Unknown keys and bad values
     raise ValueError naming the key; `mesh_tasks`: the tasks the `mesh` block of the same config writes a mesh of (None: no such
     block) -- every task decimated must be one of them.  `cell` has no default: it is in the mesh's units (voxels)."""
-    if not isinstance(m, dict):
-        raise ValueError(f"{KEY}: expected a mapping, got {m!r}")
-    known = ("tasks", "cell") + tuple(_DEFAULTS)
-    for k in m:
-        if k not in known:
-            raise ValueError(f"{KEY}.{k}: unknown key ({', '.join(known)})")
-    tasks = m.get("tasks")
-    if isinstance(tasks, str):
-        tasks = [tasks]
-    if not isinstance(tasks, (list, tuple)) or not tasks:
-        raise ValueError(f"{KEY}.tasks: {tasks!r} (a list of task names)")
-    for t in tasks:
-        if mesh_tasks is None or t not in mesh_tasks:
-            raise ValueError(f"{KEY}.tasks: task {t!r} is not listed under inference_config.postprocess.mesh, so no mesh of it is written")
-    if "cell" not in m:
-        raise ValueError(f"{KEY}.cell: missing (the edge of a grid cell, in voxels)")
-    cell = float(_cell(f"{KEY}.cell:", m["cell"]))
-    o = {k: m.get(k, d) for k, d in _DEFAULTS.items()}
+    o = parse_stage_block(KEY, m, mesh_tasks, _DEFAULTS, required={"cell": "the edge of a grid cell, in voxels"})
+    cell = float(_cell(f"{KEY}.cell:", o["cell"]))
     _representative(f"{KEY}.representative:", o["representative"])
     if not isinstance(o["normals"], bool):
         raise ValueError(f"{KEY}.normals: {o['normals']!r} (true or false)")
-    gb = o["max_device_gb"]
-    if gb is not None and (isinstance(gb, bool) or not isinstance(gb, (int, float)) or not gb > 0):
-        raise ValueError(f"{KEY}.max_device_gb: {gb!r} (a positive number)")
-    return dict(tasks=tuple(tasks), cell=cell, representative=o["representative"], normals=o["normals"],
-                max_device_gb=None if gb is None else float(gb))
+    return dict(o, cell=cell)
 
 
 # ---- the driver -------------------------------------------------------------------------------------------------------------------------------
-class MeshDecimator:
-    """Reads an OBJ or a PLY mesh as `write_obj` / `write_ply` / `write_refined` write them (normals in the file are not used),
-    decimates it (`decimate_numpy` is the statement), takes the normals of the decimated mesh (`vertex_normals_numpy`) and writes
-    `<stem>_decimated.<ext>` next to it (or `out`) through `write_refined`.  An existing file is refused.  `fmt`: "obj" or "ply";
-    None keeps the input's.  `normals=False` writes positions only.
+class MeshDecimator(MeshStage):
+    """The stage (stage.py: MeshStage) that decimates a mesh (`decimate_numpy` is the statement), takes the normals of the decimated
+    mesh (`vertex_normals_numpy`) and writes `<stem>_decimated.<ext>`.  `normals=False` writes positions only.
 
     The whole mesh is resident on the device: `scratch_bytes(V, T)` = 156 V + 72 T + 96 bytes (BYTES_PER_VERTEX, BYTES_PER_TRIANGLE,
     inputs and outputs included), and a mesh that needs more than `max_device_bytes` (default: half of the free device memory) raises
     MemoryError.  There is no out-of-core path.  `decimator`: None runs the HIP kernels; a callable
     (vertices, triangles, cell, representative) -> (vertices, triangles, cluster_of), such as `decimate_numpy`, replaces them and
     the normals are then taken on the host, which is how the driver runs there."""
+    suffix = "decimated"
 
     def __init__(self, cell, representative="mean", normals=True, fmt=None, max_device_bytes=None, decimator=None):
         self.cell = float(_cell("MeshDecimator: cell", cell))
         self.representative = _representative("MeshDecimator: representative", representative)
-        if fmt is not None and fmt not in FORMATS:
-            raise ValueError(f"MeshDecimator: fmt {fmt!r} (one of {', '.join(FORMATS)}, or None for the input's)")
-        if max_device_bytes is not None and int(max_device_bytes) < 1:
-            raise ValueError(f"MeshDecimator: max_device_bytes {max_device_bytes}")
-        self.normals, self.fmt = bool(normals), fmt
-        self.max_device_bytes = None if max_device_bytes is None else int(max_device_bytes)
-        self.decimator = decimator
+        super().__init__(fmt, max_device_bytes)
+        self.normals, self.decimator = bool(normals), decimator
 
     scratch_bytes = staticmethod(scratch_bytes)
 
@@ -203,29 +176,15 @@ class MeshDecimator:
             return v, t, cluster_of, vertex_normals_numpy(v, t) if self.normals else None
         import torch
         from ..engine import ops
-        need, budget = scratch_bytes(len(vertices), len(triangles)), self.max_device_bytes
-        if budget is None:
-            budget = torch.cuda.mem_get_info()[0] // 2
-        if need > budget:
-            raise MemoryError(f"MeshDecimator: a mesh of {len(vertices)} vertices and {len(triangles)} triangles needs {need} bytes on the "
-                              f"device, the budget is {budget} (the whole mesh is resident; there is no out-of-core path)")
+        self._budget(scratch_bytes(len(vertices), len(triangles)), f"a mesh of {len(vertices)} vertices and {len(triangles)} triangles")
         v, t, cluster_of = ops.mesh_decimate(torch.from_numpy(vertices).cuda(), torch.from_numpy(triangles).cuda(), self.cell, self.representative)
         n = ops.mesh_vertex_normals(v, t) if self.normals else None
         return v.cpu().numpy(), t.cpu().numpy(), cluster_of.cpu().numpy(), None if n is None else n.cpu().numpy()
 
-    def run(self, path, out=None):
-        path = str(path)
-        vertices, triangles, _ = read_mesh(path)
-        stem, ext = os.path.splitext(path)
-        fmt = self.fmt or ext[1:].lower()
-        out = f"{stem}_decimated.{fmt}" if out is None else str(out)
-        if os.path.exists(out):
-            raise FileExistsError(f"{out} already exists")
-        vertices, triangles = _check_mesh("MeshDecimator", vertices, triangles)
+    def _work(self, vertices, triangles):
         v, t, cluster_of, n = self.decimate(vertices, triangles)
-        write_refined(out, fmt, v, t, n)
         # the largest float32 |representative - p| over the components of the input vertices whose cluster is in the output
         rows = cluster_rows(cluster_of, triangles)[cluster_of] if len(cluster_of) else np.zeros(0, np.int64)
         moved = float(np.abs(v[rows[rows >= 0]] - vertices[rows >= 0]).max()) if (rows >= 0).any() else 0.0
-        return dict(vertices=len(v), triangles=len(t), input_vertices=len(vertices), input_triangles=len(triangles),
-                    clusters=int(cluster_of.max()) + 1 if len(cluster_of) else 0, cell=self.cell, max_displacement=moved)
+        return v, t, n, dict(vertices=len(v), triangles=len(t), input_vertices=len(vertices), input_triangles=len(triangles),
+                             clusters=int(cluster_of.max()) + 1 if len(cluster_of) else 0, cell=self.cell, max_displacement=moved)

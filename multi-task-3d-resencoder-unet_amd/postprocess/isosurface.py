@@ -1,5 +1,5 @@
-"""Triangle mesh of a prediction volume by surface nets: the numpy statement of csrc/rx_isosurface.hip, the OBJ / PLY writers, the
-config block and the out-of-core `SurfaceMesher` driver.
+"""Triangle mesh of a prediction volume by surface nets: the numpy statement of csrc/rx_isosurface.hip, the config block and the
+out-of-core `SurfaceMesher` driver (the OBJ / PLY writers: mesh_io.py).
 
 Surface nets (dual contouring without gradients) need no case table.  The volume is padded with one voxel of 0 on every side; a voxel
 is inside when `value > level`; every cell of the (Z+1, Y+1, X+1) grid whose eight corners are not all inside or all outside holds one
@@ -11,17 +11,15 @@ Vertices are (x, y, z) in voxel coordinates of the unpadded volume -- column 2 i
 slice index z and columns 0, 1 are what it rounds to the pixel (w, h) of that slice -- so `read_obj` of a written mesh and
 `MeshTargetBuilder` paint the surface back where the volume has it.  The statements use numpy only."""
 import os
-import struct
 
 import numpy as np
 
-F32 = np.float32
-INT32_MAX = 2**31 - 1
+from .mesh_io import F32, FORMATS, _MeshFile
+
 MAX_EXTENT = 2**24 - 3      # an extent of 2^24 - 2 or more is refused: a position is an exact float32 integer plus a fraction
 MAX_CELLS = 2**31 - 2
 MAX_BANDS = 2**24 - 1      # the kernels give a band of 4 cell planes x 8 cell rows to a workgroup of 256 threads
 KEY = "inference_config.postprocess.mesh"
-FORMATS = ("obj", "ply")
 # device memory of a slab beyond its outputs: the voxel bytes, the active bits (one 64-bit word per 64 cells of a cell row) and,
 # per cell row, its two counts (2 x int32) and its two scanned offsets (2 x int64: 3 quads per cell are more than int32 holds)
 BYTES_PER_VOXEL = 1
@@ -157,85 +155,6 @@ def surface_nets_numpy(values, level, z_base=0):
         keys.append(np.repeat(key * 2, 2) + np.tile([0, 1], key.size))
     tris, keys = np.concatenate(tris), np.concatenate(keys)
     return vertices, np.ascontiguousarray(tris[np.argsort(keys, kind="stable")].astype(np.int64))
-
-
-# ---- writers -------------------------------------------------------------------------------------------------------------------------------
-class _MeshFile:
-    """an OBJ or PLY file written piecewise: `add(vertices, triangles)` any number of times (triangle ids are global), `close()`.
-    Everything goes to `<path>.partial`; `close` assembles the file and renames it, `abort` removes what was written.  OBJ: `v`
-    lines then `f` lines, 1-based.  PLY: binary little-endian, float vertices, int faces."""
-
-    def __init__(self, path, fmt):
-        if fmt not in FORMATS:
-            raise ValueError(f"{KEY}.format: {fmt!r} (one of {', '.join(FORMATS)})")
-        if os.path.exists(path):
-            raise FileExistsError(f"{path} already exists")
-        self.path, self.fmt, self.nv, self.nt = path, fmt, 0, 0
-        self.parts = [path + ".partial", path + ".partial.faces"]
-        self.v, self.f = (open(p, "wb") for p in self.parts)
-
-    def add(self, vertices, triangles):
-        vertices, triangles = np.ascontiguousarray(vertices, F32).reshape(-1, 3), np.asarray(triangles, np.int64).reshape(-1, 3)
-        self.nv += len(vertices)
-        self.nt += len(triangles)
-        if self.fmt == "obj":
-            # nine significant digits read back to the same float32
-            self.v.write("".join("v %.9g %.9g %.9g\n" % (x, y, z) for x, y, z in vertices.tolist()).encode())
-            self.f.write("".join("f %d %d %d\n" % (a + 1, b + 1, c + 1) for a, b, c in triangles.tolist()).encode())
-        else:
-            if len(triangles) and (triangles.max() > INT32_MAX):
-                raise ValueError(f"write_ply: vertex id {int(triangles.max())} does not fit the int faces of a PLY file")
-            self.v.write(vertices.astype("<f4").tobytes())
-            rec = np.empty(len(triangles), dtype=[("n", "u1"), ("i", "<i4", (3,))])
-            rec["n"], rec["i"] = 3, triangles
-            self.f.write(rec.tobytes())
-
-    def close(self):
-        self.v.close()
-        self.f.close()
-        with open(self.parts[0] + ".head", "wb") as out:
-            if self.fmt == "ply":
-                out.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {self.nv}\nproperty float x\nproperty float y\n"
-                           f"property float z\nelement face {self.nt}\nproperty list uchar int vertex_indices\nend_header\n").encode())
-            for p in self.parts:
-                with open(p, "rb") as src:
-                    while True:
-                        block = src.read(1 << 24)
-                        if not block:
-                            break
-                        out.write(block)
-        os.remove(self.parts[1])
-        os.replace(self.parts[0] + ".head", self.parts[0])
-        os.rename(self.parts[0], self.path)
-
-    def abort(self):
-        for f in (self.v, self.f):
-            f.close()
-        for p in self.parts + [self.parts[0] + ".head"]:
-            if os.path.exists(p):
-                os.remove(p)
-
-
-def _write(path, fmt, vertices, triangles):
-    f = _MeshFile(str(path), fmt)
-    try:
-        f.add(vertices, triangles)
-        f.close()
-    except BaseException:
-        f.abort()
-        raise
-
-
-def write_obj(path, vertices, triangles):
-    """`v x y z` and 1-based `f a b c` lines; tasks.normals.mesh_targets.read_obj reads the same arrays back.  Written to
-    `<path>.partial` and renamed; an existing `path` is refused."""
-    _write(path, "obj", vertices, triangles)
-
-
-def write_ply(path, vertices, triangles):
-    """binary little-endian PLY: float x, y, z vertices, `uchar int` face lists.  Written to `<path>.partial` and renamed; an existing
-    `path` is refused."""
-    _write(path, "ply", vertices, triangles)
 
 
 # ---- the config block ----------------------------------------------------------------------------------------------------------------------

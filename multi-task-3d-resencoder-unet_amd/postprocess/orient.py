@@ -14,8 +14,9 @@ import os
 
 import numpy as np
 
-from .isosurface import FORMATS
-from .refine import F32, _check_mesh, read_mesh, vertex_normals_numpy, write_refined
+from .mesh_io import F32, _check_mesh
+from .refine import vertex_normals_numpy
+from .stage import MeshStage, parse_stage_block
 
 KEY = "inference_config.postprocess.orient"
 RULES = {"copy": np.float32, "u8": np.uint8, "u16": np.uint16, "normal_u16": np.uint16}      # rule -> the dtype it decodes
@@ -183,7 +184,7 @@ def select_numpy(vertices, triangles, keep_mask, *attrs):
 
 
 # ---- the config block -------------------------------------------------------------------------------------------------------------------------
-_DEFAULTS = {"normals_task": "normals", "side": "front", "min_cos": 0.2, "normals": "predicted", "max_device_gb": None}
+_DEFAULTS = {"normals_task": "normals", "side": "front", "min_cos": 0.2, "normals": "predicted"}
 
 
 def _side(name, side):
@@ -210,21 +211,7 @@ def parse_orient_config(m, mesh_tasks, targets):
     such block) -- every task oriented must be one of them; `targets`: {task: {"channels": c, ...}} -- `normals_task` must be one
     whose output rule is the 3-channel unit field stored as uint16."""
     from ..inference_schedule import task_output_rule
-    if not isinstance(m, dict):
-        raise ValueError(f"{KEY}: expected a mapping, got {m!r}")
-    known = ("tasks",) + tuple(_DEFAULTS)
-    for k in m:
-        if k not in known:
-            raise ValueError(f"{KEY}.{k}: unknown key ({', '.join(known)})")
-    tasks = m.get("tasks")
-    if isinstance(tasks, str):
-        tasks = [tasks]
-    if not isinstance(tasks, (list, tuple)) or not tasks:
-        raise ValueError(f"{KEY}.tasks: {tasks!r} (a list of task names)")
-    for t in tasks:
-        if mesh_tasks is None or t not in mesh_tasks:
-            raise ValueError(f"{KEY}.tasks: task {t!r} is not listed under inference_config.postprocess.mesh, so no mesh of it is written")
-    o = {k: m.get(k, d) for k, d in _DEFAULTS.items()}
+    o = parse_stage_block(KEY, m, mesh_tasks, _DEFAULTS)
     nt = o["normals_task"]
     if not isinstance(nt, str) or nt not in targets:
         raise ValueError(f"{KEY}.normals_task: {nt!r} is not an inference target (one of {', '.join(targets)})")
@@ -233,28 +220,21 @@ def parse_orient_config(m, mesh_tasks, targets):
         raise ValueError(f"{KEY}.normals_task: target {nt!r} with {targets[nt].get('channels', 1)} channels is not written as a 3-channel unit "
                          f"field in uint16 (a target named `normals` with 3 channels is)")
     _side(f"{KEY}.side:", o["side"])
-    min_cos = _min_cos(f"{KEY}.min_cos:", o["min_cos"])
     _normals(f"{KEY}.normals:", o["normals"])
-    gb = o["max_device_gb"]
-    if gb is not None and (isinstance(gb, bool) or not isinstance(gb, (int, float)) or not gb > 0):
-        raise ValueError(f"{KEY}.max_device_gb: {gb!r} (a positive number)")
-    return dict(tasks=tuple(tasks), normals_task=nt, side=o["side"], min_cos=min_cos, normals=o["normals"],
-                max_device_gb=None if gb is None else float(gb))
+    return dict(o, min_cos=_min_cos(f"{KEY}.min_cos:", o["min_cos"]))
 
 
 # ---- the driver -------------------------------------------------------------------------------------------------------------------------------
 _WANT = {"both": 0, "front": 1, "back": -1}
 
 
-class MeshOrienter:
-    """Reads an OBJ or a PLY mesh as `write_obj` / `write_ply` / `write_refined` write them (normals in the file are not used) and
-    the (3, Z, Y, X) uint16 array `<store>/<normals_name>` (zarr_lite), samples the array at the vertices under the rule
-    `normal_u16` (`sample_points_numpy`), makes the samples unit (`unit_numpy`), classifies the triangles (`face_cos_numpy`,
-    `side_numpy` with `min_cos`) and writes `<stem>_<side>.<ext>` next to the mesh (or `out`) through `write_refined`: the
+class MeshOrienter(MeshStage):
+    """The stage (stage.py: MeshStage) that reads, beside the mesh, the (3, Z, Y, X) uint16 array `<store>/<normals_name>`
+    (zarr_lite), samples the array at the vertices under the rule `normal_u16` (`sample_points_numpy`), makes the samples unit
+    (`unit_numpy`), classifies the triangles (`face_cos_numpy`, `side_numpy` with `min_cos`) and writes `<stem>_<side>.<ext>`: the
     triangles of that side and the vertices they name (`select_numpy`).  `side="both"` keeps every triangle, the rim included, and
     is named `_oriented`.  `normals="predicted"` writes the unit samples, the sheet normal, with the same sense on both faces;
-    `normals="mesh"` writes `vertex_normals_numpy` of the output mesh.  An existing file is refused.  `fmt`: "obj" or "ply"; None
-    keeps the input's.
+    `normals="mesh"` writes `vertex_normals_numpy` of the output mesh.
 
     Device memory is `scratch_bytes(V, T, 3, planes, Y, X)`.  If the whole array fits `max_device_bytes` (default: half of the
     free device memory; on the host: no limit) beside the mesh it is resident.  Otherwise it goes in z-slabs of full planes
@@ -268,17 +248,16 @@ class MeshOrienter:
         self.side = _side("MeshOrienter: side", side)
         self.min_cos = _min_cos("MeshOrienter: min_cos", min_cos)
         self.normals = _normals("MeshOrienter: normals", normals)
-        if fmt is not None and fmt not in FORMATS:
-            raise ValueError(f"MeshOrienter: fmt {fmt!r} (one of {', '.join(FORMATS)}, or None for the input's)")
-        if max_device_bytes is not None and int(max_device_bytes) < 1:
-            raise ValueError(f"MeshOrienter: max_device_bytes {max_device_bytes}")
+        super().__init__(fmt, max_device_bytes)
         if where not in ("device", "host"):
             raise ValueError(f"MeshOrienter: where {where!r} (device or host)")
-        self.fmt, self.where = fmt, where
-        self.max_device_bytes = None if max_device_bytes is None else int(max_device_bytes)
-        self.last_slabs = None
+        self.where, self.last_slabs = where, None
 
     scratch_bytes = staticmethod(scratch_bytes)
+
+    @property
+    def suffix(self):
+        return "oriented" if self.side == "both" else self.side
 
     def plan(self, V, T, shape, itemsize=2):
         """-> (slabs [(z_base, planes)], number of device buffers) for a (C, Z, Y, X) array beside a mesh of V vertices and T triangles"""
@@ -321,15 +300,10 @@ class MeshOrienter:
         return out
 
     def run(self, mesh_path, store, normals_name="normals_final", out=None):
+        return super().run(mesh_path, out, store=store, normals_name=normals_name)
+
+    def _work(self, vertices, triangles, store, normals_name):
         from ..dataloading import zarr_lite
-        path = str(mesh_path)
-        vertices, triangles, _ = read_mesh(path)
-        stem, ext = os.path.splitext(path)
-        fmt = self.fmt or ext[1:].lower()
-        out = f"{stem}_{'oriented' if self.side == 'both' else self.side}.{fmt}" if out is None else str(out)
-        if os.path.exists(out):
-            raise FileExistsError(f"{out} already exists")
-        vertices, triangles = _check_mesh("MeshOrienter", vertices, triangles)
         src_path = os.path.join(str(store), normals_name)
         try:
             src = zarr_lite.open(src_path)
@@ -364,8 +338,7 @@ class MeshOrienter:
                 on = ops.mesh_vertex_normals(ov, ot)
             unit, cos, side = dunit.cpu().numpy(), dcos.cpu().numpy(), dside.cpu().numpy()
             v, t, n = ov.cpu().numpy(), ot.cpu().numpy(), on.cpu().numpy()
-        write_refined(out, fmt, v, t, n)
         ok = ~np.isnan(cos)
-        return dict(vertices=len(v), triangles=len(t), input_vertices=V, input_triangles=T, front=int((side == 1).sum()),
-                    back=int((side == -1).sum()), rim=int((side == 0).sum()), zero_normals=int((unit == 0).all(1).sum()),
-                    mean_abs_cos=float(np.abs(cos[ok]).astype(np.float64).mean()) if ok.any() else 0.0)
+        return v, t, n, dict(vertices=len(v), triangles=len(t), input_vertices=V, input_triangles=T, front=int((side == 1).sum()),
+                             back=int((side == -1).sum()), rim=int((side == 0).sum()), zero_normals=int((unit == 0).all(1).sum()),
+                             mean_abs_cos=float(np.abs(cos[ok]).astype(np.float64).mean()) if ok.any() else 0.0)

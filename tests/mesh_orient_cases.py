@@ -14,6 +14,7 @@ same kinds in C++.  Each is chosen for a way the kernels can go wrong:
 import numpy as np
 
 import isosurface_cases as I
+from mesh_cases import ball_mesh      # noqa: F401 -- also reached as O.ball_mesh
 
 F32 = np.float32
 RULES = {"copy": np.float32, "u8": np.uint8, "u16": np.uint16, "normal_u16": np.uint16}
@@ -119,14 +120,6 @@ def sheet_mesh():
     if "sheet" not in _MESHES:
         _MESHES["sheet"] = pp.surface_nets_numpy(sheet_volume(), 127)
     return _MESHES["sheet"]
-
-
-def ball_mesh():
-    import mt3d_amd.postprocess as pp
-    if "ball" not in _MESHES:
-        B = I.BALL
-        _MESHES["ball"] = pp.surface_nets_numpy(I.ball(B["shape"], B["R"], B["centre"]), 127)
-    return _MESHES["ball"]
 
 
 def rim_mesh():

@@ -7,47 +7,18 @@ in place, so the fans go far past anything a thread could keep in registers or L
 import numpy as np
 
 import isosurface_cases as I
+from mesh_cases import BALL, GRID, ball_mesh, fan, grid_patch, shuffled, soup      # noqa: F401 -- the generic builders, reached as R.NAME
+from mesh_cases import positions as _positions
 
 F32 = np.float32
 SCAN_GROUP = 1024      # csrc/rx_meshrefine.hip: RX_MR_SCAN_GROUP
 COUNTS = (1, 63, 64, 65, 257, 2 * SCAN_GROUP + 52)
 FANS = (3, 8, 9, 300, 3000)
-GRID = (5, 7)      # rows, columns
-BALL = I.BALL
-
-
-def _positions(n, seed):
-    return np.random.default_rng(seed).uniform(-100, 100, (n, 3)).astype(F32)
-
-
-def grid_patch(ny=GRID[0], nx=GRID[1], z=3.0):
-    """an open ny x nx patch of unit squares in the plane z, each split along the same diagonal: border vertices are boundary, interior
-    ones have six neighbours placed symmetrically around them, so their neighbour sums and means are exact"""
-    j, i = np.indices((ny, nx))
-    v = np.stack([i.ravel(), j.ravel(), np.full(ny * nx, z)], 1).astype(F32)
-    a = (j[:-1, :-1] * nx + i[:-1, :-1]).ravel()
-    b, c, d = a + 1, a + nx, a + nx + 1
-    t = np.stack([np.stack([a, b, d], 1), np.stack([a, d, c], 1)], 1).reshape(-1, 3).astype(np.int64)
-    return v, t
 
 
 def grid_interior(ny=GRID[0], nx=GRID[1]):
     j, i = np.indices((ny, nx))
     return ((j > 0) & (j < ny - 1) & (i > 0) & (i < nx - 1)).ravel()
-
-
-def fan(degree, seed=0):
-    """a closed fan around vertex 0: `degree` neighbours and `degree` triangles at one vertex"""
-    i = np.arange(degree)
-    t = np.stack([np.zeros(degree, np.int64), 1 + i, 1 + (i + 1) % degree], 1).astype(np.int64)
-    return _positions(degree + 1, seed + degree), t
-
-
-def soup(n_vertices, seed=0):
-    """random triangles over `n_vertices` vertices: repeated ids, repeated triangles and unused vertices all happen"""
-    rng = np.random.default_rng(seed + n_vertices)
-    t = rng.integers(0, n_vertices, (2 if n_vertices == 1 else 2 * n_vertices, 3)).astype(np.int64)
-    return _positions(n_vertices, seed + 1), t
 
 
 def awkward():
@@ -57,12 +28,6 @@ def awkward():
     return _positions(13, 5), t
 
 
-def ball_mesh():
-    """the closed 2-manifold of isosurface_cases' graded ball, through the surface-nets statement"""
-    import mt3d_amd.postprocess as pp
-    return pp.surface_nets_numpy(I.ball(BALL["shape"], BALL["R"], BALL["centre"]), 127)
-
-
 def closed_meshes():
     """the surface-nets meshes of a few volumes of tests/isosurface_cases.py: closed, not always manifold, degrees from 3 to 12 and more"""
     import mt3d_amd.postprocess as pp
@@ -70,14 +35,6 @@ def closed_meshes():
     for shape, kind in (((9, 10, 12), "random50"), ((9, 10, 12), "checkerboard"), ((33, 17, 70), "slab"), ((5, 1, 3), "full")):
         out.append((f"{'x'.join(map(str, shape))}-{kind}", pp.surface_nets_numpy(dict(I.volumes(shape, 127))[kind], 127)))
     return out
-
-
-def shuffled(vertices, triangles, seed=11):
-    """the same mesh with its triangles in another order and the ids rotated within each"""
-    rng = np.random.default_rng(seed)
-    t = triangles[rng.permutation(len(triangles))]
-    r = rng.integers(0, 3, len(t))
-    return vertices, np.take_along_axis(t, (np.arange(3)[None, :] + r[:, None]) % 3, 1)
 
 
 _CASES = None

@@ -110,7 +110,7 @@ def test_smallest_table_capacity_gives_the_same_result(representative):
     """the hash table at the smallest capacity the library accepts (the power of two just above V: long probe chains where every
     vertex is its own cluster) and at the default of the ops layer"""
     L, ops, pp = _mods()
-    from mt3d_amd.engine.ops.postprocess import _table_capacity
+    from mt3d_amd.engine.ops.mesh import _table_capacity
     for name in ("big-grid-fine", "big-grid-c2", "ball-c0.75", "soup257-c3.5", "fan3000-c50"):
         _, v, t, cell = D.case(name)
         wv, wt, wc = _statement(pp, name, representative)
